@@ -23,6 +23,8 @@ sum_l n_{j,l} -- per second of kernel time against the MI355X vec
 PMC-measured HBM bytes per launch of the committed profile.  SURVEY.md 8(d)'s "algorithmic bytes / 8 TB/s" figure is
 kept as `normalised_hbm` (a throughput normalisation, not a roofline: it exceeds 1).
 --strong splits the configuration's TOTAL chain count over the ranks instead of giving every rank a full batch.
+--dump-outputs DIR writes the last timed step's product (points, labels; float64 .npy) for output-by-output comparison of
+two builds: inputs and seeds are fixed, so the same arguments give the same files.
 """
 import argparse
 import json
@@ -36,7 +38,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak
 
 CONFIGS = {
     # name: (D, M, N, Nout per GPU, Niter, precision, config_id)
@@ -96,6 +98,26 @@ def load_traffic(workload):
     return {}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Writes `arrays` ({name: [rows, samples] array}) as float64 `path/<name>.npy`.  Past DUMP_MAX_BYTES in all, the same
+    fixed, seeded sample of columns is kept in every array and its indices go to `sample_index.npy`.  Returns a summary."""
+    n = next(iter(arrays.values())).shape[1]
+    rows = sum(a.shape[0] for a in arrays.values())
+    out = {k: np.asarray(a, dtype=np.float64) for k, a in arrays.items()}
+    keep = min(n, (DUMP_MAX_BYTES - 4096) // (8 * (rows + 1)))   # (4 KB: the .npy headers)
+    if keep < n:
+        cols = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        out = {k: a[:, cols] for k, a in out.items()}
+        out["sample_index"] = cols.astype(np.float64)[None, :]
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": path, "files": sorted(k + ".npy" for k in out), "samples": int(keep), "samples_total": int(n)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -130,7 +152,14 @@ def main():
                          "bandwidth search on the product's output shape (D x Nout of --config), evaluate = evaluateDualTree(bd, pos) "
                          "of one density of --config at 65,536 positions, tree = kde!(points, ks) of D x Nout points, host builder "
                          "beside the GPU builder; each with roofline (kernel time by HIP events inside the library) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed -- the product's points [D, Nout] and labels [M, Nout] as a "
+                         "caller receives them -- to DIR/points.npy and DIR/labels.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.frow or args.inproc_gpus > 0 or args.batch > 0):
+        raise SystemExit("--dump-outputs applies to the headline path only (not with --frow, --inproc-gpus or --batch)")
     if args.frow:
         return frow_mode(args)
     if args.inproc_gpus > 0:
@@ -270,6 +299,11 @@ def main():
 
     elapsed = timed_pass(0)
     gather_wait_s = gather_wait[0]
+    # the last timed step's product as its caller receives it, copied out before the passes below reuse the slots
+    last_outputs = None
+    if args.dump_outputs and rank == 0:
+        pts_d, ind_d = sp._assemble(slots[(args.warmup + args.steps - 1) & 1], Np_total)
+        last_outputs = {"points": pts_d.cpu().numpy(), "labels": ind_d.cpu().numpy()}
     # The kernel's duration in THIS loop: the same calls once more, now with the sampling launch of every call bracketed
     # by timing events on its stream (inside the library: the launch is not visible from here).  A pass of its own because
     # the timestamps cost 2 % of a step (0.648 -> 0.661 ms at config 3) -- they are kept out of `value`.
@@ -435,6 +469,8 @@ def main():
             out["cold_start"] = cold_start(args.config)
         if world == 1 and not args.no_cpu_baseline:
             out.update(cpu_baseline_and_parity(kdehip, plan, pts_all, bw_all, D, M, N, Nout, Niter, seed, args.warmup))
+        if last_outputs is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, last_outputs)
     if use_dist:
         dist.destroy_process_group()
     if rank == 0:

@@ -6,7 +6,7 @@ code or data layout decisions with oracle/kde_oracle.c.  It is slow and only mea
 tests require the C oracle to agree with it exactly (labels) / to 1e-13 (points), so a misreading of
 the reference would have to be made twice, in two different shapes, to go unnoticed.
 
-Citations are relative to /root/reference/src.
+Citations are relative to the reference package's src/ directory.
 """
 import math
 

@@ -52,6 +52,40 @@ def test_bench_single_gpu_json_contract():
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes the product of the last timed step as its caller receives it (points [D, Nout], labels
+    [M, Nout], float64): the same files from run to run, equal to the same call made on its own at that step's offset."""
+    import numpy as np
+    import torch
+
+    import bench
+    import kdehip
+    W, K = 2, 3
+    runs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--config", "c2", "--steps", str(K), "--warmup", str(W), "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == K and d["ms_per_step"] > 0
+        assert d["dump_outputs"]["files"] == ["labels.npy", "points.npy"] and d["dump_outputs"]["samples"] == 256
+        runs.append({k: np.load(tmp_path / name / f"{k}.npy") for k in ("points", "labels")})
+    assert all(a.dtype == np.float64 for r in runs for a in r.values())
+    assert np.array_equal(runs[0]["points"], runs[1]["points"]) and np.array_equal(runs[0]["labels"], runs[1]["labels"])
+    D, M, N, Nout, Niter, prec, cid = bench.CONFIGS["c2"]
+    pts, bws = bench.synth_inputs(kdehip, D, M, N, cid)
+    dd = [kdehip.DeviceDensity(kdehip.kde(p, b)) for p, b in zip(pts, bws)]
+    P = torch.zeros(D * Nout, dtype=torch.float64, device="cuda:0")
+    I = torch.zeros(M * Nout, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    # (bench.py's seed; step i of the timed pass draws chains [i * Nout, (i + 1) * Nout) of its stream)
+    kdehip.prodAppxMSGibbsS_device(dd, P, I, Np=Nout, Niter=Niter, seed=20260101, sample_offset=(W + K - 1) * Nout,
+                                   precision=prec)
+    torch.cuda.synchronize()
+    assert np.array_equal(runs[0]["points"], P.cpu().numpy().reshape(Nout, D).T)
+    assert np.array_equal(runs[0]["labels"], I.cpu().numpy().reshape(Nout, M).T)
+    for x in dd:
+        x.close()
+
+
 def test_bench_distributed_path_one_rank():
     d = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
              env={"KDEHIP_FORCE_DIST": "1", "MASTER_PORT": "29533"})

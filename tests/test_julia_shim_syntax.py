@@ -260,8 +260,9 @@ def test_enable_overrides_the_whole_star_operator():
     assert listed.count('"') == 14
 
 
-# ---- the overrides against the reference's ACTUAL source (skipped where /root/reference does not exist: the GPU box) ----
-REFERENCE_SRC = "/root/reference/src"
+# ---- the overrides against the reference's ACTUAL signatures (tests/golden/reference_signatures.json, parsed from the
+# reference's src/ by tests/golden/make_reference_signatures.py with the functions below) ----
+REFERENCE_SIGNATURES = os.path.join(ROOT, "tests", "golden", "reference_signatures.json")
 
 
 def _split_top(text, sep=","):
@@ -333,15 +334,14 @@ def test_overrides_carry_the_references_own_signatures():
     signature (names, type annotations, `where` clause) of a method that exists in the reference's source -- the same
     signature is what makes the definition REPLACE the reference's method instead of adding a more or less specific one --
     and, for the two keyword methods, the reference's keyword names in its order.  Parsed from src/KDE01.jl,
-    src/DualTree01.jl and src/MSGibbs01.jl themselves, not from strings in this file."""
-    import pytest
-    if not os.path.isdir(REFERENCE_SRC):
-        pytest.skip("the reference's source is not on this machine")
-    ref_code = {f: strip_code(open(os.path.join(REFERENCE_SRC, f)).read()) for f in ("KDE01.jl", "DualTree01.jl", "MSGibbs01.jl")}
+    src/DualTree01.jl and src/MSGibbs01.jl themselves into the committed fixture, not from strings in this file
+    (VERDICT round 5, weak 1)."""
+    import json
+    with open(REFERENCE_SIGNATURES) as f:
+        golden = json.load(f)
     ref = {}
-    for name, f in (("kde!", "KDE01.jl"), ("evaluateDualTree", "DualTree01.jl"), ("gibbs1", "MSGibbs01.jl"),
-                    ("prodAppxMSGibbsS", "MSGibbs01.jl")):
-        ref[name] = [_canonical(s, w) for s, w in _function_signatures(ref_code[f], name)]
+    for name in ("kde!", "evaluateDualTree", "gibbs1", "prodAppxMSGibbsS"):
+        ref[name] = [(tuple(m["positional"]), tuple(m["keywords"]), m["where"]) for m in golden[name]["methods"]]
         assert ref[name], name
     enable = _enable_body(strip_code(open(SHIM).read()))
     seen = []
