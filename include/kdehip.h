@@ -346,6 +346,59 @@ typedef struct kdehip_batch_item {
 } kdehip_batch_item;
 int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int precision, void *stream);
 
+/* ---- (2f) drawing from a density: sample, rand, resample ---------------------------------------------------------
+ * `sample(p, Npts)` (reference src/KDE01.jl:164-183):  w = the leaf weights in ORIGINAL point order (getWeights);
+ * C = cumsum(w), a sequential left-to-right fp64 sum, then C = C ./ C[end]; the label of a uniform u is the first i with
+ * C[i] > u (strict: a zero-weight point is never drawn); the point is x = P[:, i] + sqrt(V[:, i]) .* n with P the leaf means
+ * (the centers getPoints reads, in every density kde! builds) and V the leaf variances (`bandwidth`), in original order --
+ * the multiply and the add are separate roundings (no fused multiply-add), sqrt and the divide are correctly rounded.
+ * ind = the 1-based original index of the drawn point (the reference's convention, = the product's permutation+1).
+ * Random numbers: sample s of a call has the global index g = sample_offset + s and draws u = the uniform and n[d] = the
+ * normal d < D that kdehip_philox_fill_uniform(seed, g, 1, K = 1) / kdehip_philox_fill_normal(seed, g, 1, R = D) return
+ * (philox.hpp: philox_uniform(seed, g, 1), philox_normal(seed, g, d)) -- the reference's rand / randn are replaced by the
+ * Philox stream, so every result is reproducible on the host, and a call with sample_offset continues an earlier one.
+ * (The device's log / sin / cos may differ from the host libm in the last bits of a normal; labels never depend on them.)
+ * Output order: draw order, pts D x Npts column-major (as the product's).  The reference sorts its uniforms and returns
+ * the samples grouped by ascending label; the distribution is the same.
+ * Given labels (`sample(p, Npts, ind)`, src/KDE01.jl:185-189): ind_in holds Npts 1-based labels and the call consumes only
+ * the normals.  The host entry refuses an out-of-range label (KDEHIP_ERR_ARG); the device entries never read out of
+ * bounds: an out-of-range label gives a NaN point and ind = 0.
+ * Arguments: Npts = 0 does nothing; Npts < 0, weights that are negative or not finite, or whose total is not positive
+ * (and finite) are KDEHIP_ERR_ARG; D above KDEHIP_MAX_DIMS is KDEHIP_ERR_UNSUPPORTED.  The host entry checks all of this
+ * before it touches a device.
+ * Device handles: the first sample call on a handle builds its table (C in original order and the inverse permutation, one
+ * wavefront per density, about N dependent fp64 adds) on the calling thread's stream and blocks until it is complete --
+ * that call validates the weights and can return KDEHIP_ERR_ARG.  Later calls only enqueue: the table is complete in
+ * memory before any call can use it, from any thread or stream.  Concurrent first calls on one handle build it once.
+ * kdehip_density_free releases the table (also for the handles of a kdehip_mul_device_batch block). */
+
+/* Host density, host buffers, blocking, on hipStreamPerThread.  ind_in: NULL = draw the labels. */
+int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset, const int64_t *ind_in,
+                  double *pts, int64_t *ind, int device);
+/* A resident density; device pointers (d_ind_in may be NULL); enqueue only on `stream` (hipStream_t, NULL = the null
+ * stream) once the handle's table exists (the first call builds it, see above). */
+int kdehip_sample_device(kdehip_device_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
+                         const int64_t *d_ind_in, double *d_pts, int64_t *d_ind, void *stream);
+/* Many draws in one call: items of any densities (mixed D and N) on one device.  One table-build launch for the handles
+ * that have no table yet (blocking, as above), then one draw launch per distinct D on `stream`.  Every item's result is bit
+ * for bit that of kdehip_sample_device with the same arguments. */
+typedef struct kdehip_sample_item {
+  kdehip_device_density *density;
+  int64_t Npts;
+  uint64_t seed;
+  int64_t sample_offset;
+  const int64_t *d_ind_in;  /* device, Npts 1-based labels, or NULL = draw */
+  double *d_pts;            /* device, double[D*Npts] */
+  int64_t *d_ind;           /* device, int64[Npts]    */
+} kdehip_sample_item;
+int kdehip_sample_device_batch(int n, const kdehip_sample_item *items, void *stream);
+/* `resample(p, Np, :lcv)` (src/BallTreeDensity01.jl:312-334): sample(p, Np) into a pooled device buffer, then
+ * kdehip_density_from_device_points -- the result is bit for bit kdehip_make_density_auto on the same points.  Np <= 0 means
+ * Npts(p) (the reference's default calls an undefined getNpts; Npts(p) is its evident intent).  Needs Np >= 2.  Blocking, on
+ * the calling thread's stream; bw_out (D standard deviations) and nevals are optional. */
+int kdehip_resample_device(kdehip_device_density **out, kdehip_device_density *p, int64_t Np, uint64_t seed, double *bw_out,
+                           int32_t *nevals);
+
 /* ---- diagnostics (not part of the drop-in surface; bench.py and the tests use them) -----------------------------
  * While enabled, every kdehip_prod_philox_device call brackets its sampling launch with a pair of timing events on the
  * caller's stream; kdehip_profile_sampler_read waits for the device's calls in flight and returns the sum of those

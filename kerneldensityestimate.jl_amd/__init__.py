@@ -1,7 +1,8 @@
 """kdehip -- MI355X-native multiscale-Gibbs KDE products (hot path of KernelDensityEstimate.jl).
 
 This package is the Python host mirror of the reference's interface for that path
-(`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`)
+(`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`,
+`sample/rand/resample`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
 """
@@ -12,6 +13,7 @@ from .bandwidth import auto_bandwidth, evaluateDualTree, kde_auto  # noqa: F401
 from .product import (DeviceDensity, GbGlb, MultiProductPlan, ProductBatch, ProductPlan, gibbs1, makeEmptyGbGlb, mul, mul_device, mul_device_batch,  # noqa: F401
                       nlevels, philox_streams, prodAppxMSGibbsS, prodAppxMSGibbsS_batch, prodAppxMSGibbsS_device,
                       prodAppxMSGibbsS_resident)
+from .sample import rand, resample, sample, sample_device_batch  # noqa: F401
 
 
 def device_count() -> int:

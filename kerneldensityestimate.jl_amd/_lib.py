@@ -44,6 +44,12 @@ class CMulItem(C.Structure):
     _fields_ = [("Ndens", C.c_int32), ("addEntropy", C.c_int32), ("trees", C.POINTER(C.c_void_p)), ("seed", C.c_uint64)]
 
 
+class CSampleItem(C.Structure):
+    """struct kdehip_sample_item"""
+    _fields_ = [("density", C.c_void_p), ("Npts", C.c_int64), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
+                ("d_ind_in", C.c_void_p), ("d_pts", C.c_void_p), ("d_ind", C.c_void_p)]
+
+
 class CProductInfo(C.Structure):
     """struct kdehip_product_info_t"""
     _fields_ = [
@@ -125,6 +131,11 @@ SIGNATURES = {
     "kdehip_density_download": (C.c_int, [C.c_void_p, f64p, f64p, f64p, i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p,
                                           f64p, f64p]),
     "kdehip_prod_philox_batch": (C.c_int, [C.c_int, C.POINTER(CBatchItem), C.c_int, C.c_void_p]),
+    "kdehip_sample": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int]),
+    "kdehip_sample_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "kdehip_sample_device_batch": (C.c_int, [C.c_int, C.POINTER(CSampleItem), C.c_void_p]),
+    "kdehip_resample_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_uint64, f64p, i32p]),
     "kdehip_make_density_auto": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p, i64p, i64p,
                                            i64p, i64p, f64p, f64p, f64p, f64p]),
     "kdehip_make_density": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, C.c_int64, f64p, f64p, f64p, f64p,

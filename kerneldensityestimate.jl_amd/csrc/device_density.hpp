@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <mutex>
 #include <vector>
 
 #include "kdehip_internal.hpp"
@@ -110,6 +111,14 @@ struct kdehip_device_density {
   } m;
   double bw[KDEHIP_MAX_DIMS] = {};  // its LOOCV bandwidth (standard deviations)
   kdehip::SharedBlock *shared = nullptr;  // set: d_blob / mirror above are null, the arrays live in the batch's blocks
+  // The table sample.hip draws from, built by the first sample call (include/kdehip.h section 2f): ONE device block of its
+  // own -- also for a density in a shared batch block -- [C (fp64, original order) | inverse permutation (int32: original
+  // index -> leaf) | status].  `cdf_ready` is published (release) once the build has completed on the device.
+  std::mutex cdf_mu;
+  std::atomic<bool> cdf_ready{false};
+  int cdf_rc = 0;         // KDEHIP_OK, or KDEHIP_ERR_ARG for weights / a permutation the table cannot be built from
+  void *d_cdf = nullptr;
+  size_t cdf_bytes = 0;
 };
 
 namespace kdehip {

@@ -163,6 +163,7 @@ extern "C" void kdehip_clear_cache(void) {
   using namespace kdehip;
   g_peer_epoch.fetch_add(1, std::memory_order_relaxed);  // verdicts cached per raw pointer do not survive a cache reset
   kdehip::drain_pending();  // product.hip: plans of enqueue-only device products still waiting for their work
+  kdehip::drain_sample_pending();  // sample.hip: descriptor blocks of batched draws
   int cur = 0;
   const bool have_cur = hipGetDevice(&cur) == hipSuccess;
   int n = 0;

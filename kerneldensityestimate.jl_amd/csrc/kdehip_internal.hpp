@@ -309,6 +309,7 @@ hipError_t cached_malloc(void **out, size_t bytes);
 void cached_free(void *p, size_t bytes);
 hipError_t cached_host_malloc(void **out, size_t bytes);
 void drain_pending();  // (product.hip) releases the plans of enqueue-only device products once their work is over
+void drain_sample_pending();  // (sample.hip) the same for the descriptor blocks of kdehip_sample_device_batch
 void cached_host_free(void *p, size_t bytes);
 
 // Makes `device` the thread's current HIP device for the lifetime of the guard and restores the caller's

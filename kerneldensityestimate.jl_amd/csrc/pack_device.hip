@@ -893,6 +893,7 @@ extern "C" void kdehip_density_free(kdehip_device_density *h) {
     (void)hipDeviceSynchronize();  // products enqueued on caller streams may still read the block
     if (h->d_blob) cached_free(h->d_blob, h->blob_bytes);
     if (h->mirror) cached_host_free(h->mirror, h->mirror_bytes);
+    if (h->d_cdf) cached_free(h->d_cdf, h->cdf_bytes);  // (sample.hip's table: the handle's own, also in a shared block)
     if (last) {
       if (sb->d_blob) cached_free(sb->d_blob, sb->blob_bytes);
       if (sb->mirror) cached_host_free(sb->mirror, sb->mirror_bytes);

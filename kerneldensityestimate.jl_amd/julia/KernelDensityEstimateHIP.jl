@@ -409,6 +409,46 @@ function evaluateDualTree(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, lvF
 end
 
 """
+    hip_sample(bd, Npts[, ind]; seed=nothing, sample_offset=0, device=0) -> (points, ind)
+
+`sample(npd, Npts)` / `sample(npd, Npts, ind)` (src/KDE01.jl:164-189) on the GPU (`kdehip_sample`): labels by weight
+(first i with cumsum(w)[i] / cumsum(w)[end] > u), points `getPoints(bd)[:, i] + getBW(bd)[:, i] .* n`, ind 1-based.  The
+random numbers come from the library's Philox stream (include/kdehip.h section 2f), and the samples are in draw order
+where the reference groups them by ascending label: same distribution, not the same matrix.  Not installed by `enable!()`.
+"""
+function hip_sample(bd::BallTreeDensity, Npts::Int, ind::Union{Nothing,Vector{Int}}=nothing;
+                    seed::Union{Nothing,UInt64}=nothing, sample_offset::Int=0, device::Int=0)
+  D = Ndim(bd)
+  pts = zeros(D, Npts)
+  out = zeros(Int, Npts)
+  s = seed === nothing ? rand(UInt64) : seed
+  cd = Ref(CDensity(bd))
+  lab = ind === nothing ? C_NULL : Vector{Int64}(ind)
+  GC.@preserve bd lab begin
+    check(ccall((:kdehip_sample, libkdehip), Cint,
+                (Ref{CDensity}, Int64, UInt64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Cint),
+                cd, Npts, s, sample_offset, lab, pts, out, device))
+  end
+  return pts, out
+end
+
+"`rand(p, N=1)` (src/KDE01.jl:196-198): the points of `hip_sample(p, N)`."
+hip_rand(p::BallTreeDensity, N::Int=1; seed::Union{Nothing,UInt64}=nothing) = hip_sample(p, N; seed=seed)[1]
+
+"""
+    hip_resample(p, Np=-1, ksType=:lcv; seed=nothing)
+
+`resample(p, Np, :lcv)` (src/BallTreeDensity01.jl:312-334): `kde!(hip_sample(p, Np)[1])`; Np <= 0 means Npts(p) (the
+reference's default calls an undefined `getNpts`).
+"""
+function hip_resample(p::BallTreeDensity, Np::Int=-1, ksType::Symbol=:lcv; seed::Union{Nothing,UInt64}=nothing)
+  ksType == :lcv || error("hip_resample: only ksType = :lcv")
+  n = Np <= 0 ? Npts(p) : Np
+  pts, = hip_sample(p, n; seed=seed)
+  return kde!(pts)
+end
+
+"""
     kde!(points)
 
 `kde!(points)` (src/KDE01.jl:3-27) in ONE library call (`kdehip_make_density_auto`): the per-dimension LOOCV bandwidth is

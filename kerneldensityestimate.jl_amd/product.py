@@ -259,6 +259,29 @@ class DeviceDensity:
     def __mul__(self, other):
         return mul_device([self, other])
 
+    def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None):
+        """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):
+        d_pts float64[D*Npts] (column-major D x Npts), d_ind int64[Npts] (1-based original indices), `ind` an optional
+        device int64[Npts] of given labels.  The first call on the density builds its table and blocks; later calls only
+        enqueue on `stream` (kdehip_sample_device)."""
+        _lib.check(_lib.lib.kdehip_sample_device(self._h, int(Npts), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset),
+                                                 ProductPlan._addr(ind), ProductPlan._addr(d_pts), ProductPlan._addr(d_ind),
+                                                 ProductPlan._addr(stream)))
+
+    def resample(self, Np=None, *, seed=None) -> "DeviceDensity":
+        """`resample(p, Np, :lcv)` (reference src/BallTreeDensity01.jl:312-334) without leaving the device: Np samples
+        (None = Npts(p)), then `kde!(points)` on the device matrix (kdehip_resample_device)."""
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        h = C.c_void_p()
+        bw = np.empty(self.dims)
+        ne = C.c_int32(0)
+        _lib.check(_lib.lib.kdehip_resample_device(C.byref(h), self._h, 0 if Np is None else int(Np),
+                                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(bw, f64p), C.byref(ne)))
+        out = DeviceDensity(device=self.device, _handle=h)
+        out.bw, out.nevals = bw, int(ne.value)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib.kdehip_density_free(self._h)

@@ -1,0 +1,114 @@
+"""Drawing from a density: `sample`, `rand`, `resample` (reference src/KDE01.jl:155-199, src/BallTreeDensity01.jl:312-334)
+over kdehip_sample / kdehip_sample_device / kdehip_sample_device_batch / kdehip_resample_device (include/kdehip.h
+section 2f; kernels in csrc/sample.hip).
+
+Labels are 1-based original point indices (the reference's, and the product's `ind`).  Random numbers come from the
+device Philox stream: sample s of a call draws the uniform and the D normals `philox_streams(seed, sample_offset + s, 1,
+1, D)` returns, so a result is reproducible on the host and `sample_offset` continues an earlier call.  Samples come in
+draw order; the reference returns them grouped by ascending label (same distribution).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from ._lib import f64p, i64p, ptr
+from .density import BallTreeDensity, getBW, getPoints, kde
+
+
+def _seed(seed):
+    if seed is None:
+        seed = int.from_bytes(os.urandom(8), "little")
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _labels(ind, Npts):
+    a = np.ascontiguousarray(np.asarray(ind, dtype=np.int64).ravel())
+    if a.size != Npts:
+        raise ValueError("ind must hold Npts labels")
+    return a
+
+
+def sample(p, Npts, ind=None, *, seed=None, sample_offset=0, device=0):
+    """`sample(p, Npts)` / `sample(p, Npts, ind)` (reference src/KDE01.jl:164-189): returns (points (D, Npts),
+    ind (Npts,) 1-based).  `p`: a BallTreeDensity (host arrays, kdehip_sample on `device`) or a DeviceDensity (its own
+    device; results come back as host arrays).  `ind`: given 1-based labels -- only the normals are drawn."""
+    from .product import DeviceDensity
+    Npts = int(Npts)  # (Npts < 0 is refused by the library: KdeHipError ERR_ARG)
+    n = max(Npts, 0)
+    s = _seed(seed)
+    if isinstance(p, DeviceDensity):
+        import torch
+        D = p.dims
+        dev = torch.device("cuda", p.device)
+        P = torch.empty(D * max(n, 1), dtype=torch.float64, device=dev)
+        I = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        T = None if ind is None else torch.from_numpy(_labels(ind, n)).to(dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            p.sample_device(P, I, Npts, seed=s, sample_offset=sample_offset, ind=T, stream=st.cuda_stream)
+            st.synchronize()
+        return P.cpu().numpy()[:D * n].reshape(n, D).T.copy(), I.cpu().numpy()[:n].copy()
+    if not isinstance(p, BallTreeDensity):
+        raise TypeError("sample: p must be a BallTreeDensity or a DeviceDensity")
+    D = p.bt.dims
+    pts = np.empty(D * n)
+    out = np.empty(n, dtype=np.int64)
+    lab = None if ind is None else _labels(ind, n)
+    _lib.check(_lib.lib.kdehip_sample(C.byref(p._cstruct()), Npts, C.c_uint64(s), int(sample_offset),
+                                      None if lab is None else ptr(lab, i64p), ptr(pts, f64p), ptr(out, i64p), int(device)))
+    return pts.reshape(n, D).T.copy(), out
+
+
+def rand(p, N=1, *, seed=None):
+    """`rand(p, N=1)` (reference src/KDE01.jl:196-198): the points of `sample(p, N)`, (D, N)."""
+    return sample(p, N, seed=seed)[0]
+
+
+def resample(p, Np=None, ksType="lcv", *, seed=None):
+    """`resample(p, Np, ksType)` (reference src/BallTreeDensity01.jl:312-334).  Np None / <= 0 means Npts(p) (the
+    reference's default calls an undefined `getNpts`; Npts(p) is its evident intent).
+    ksType "lcv": `kde!(sample(p, Np)[0])` -- a DeviceDensity stays on the device (kdehip_resample_device) and gives a
+    DeviceDensity, a BallTreeDensity gives a BallTreeDensity.
+    ksType "discrete" (BallTreeDensity only): labels drawn by weight, the points themselves without noise, then
+    `kde(points, getBW(p)[:, 0])`.  The reference's branch calls undefined functions; this is its evident intent (a
+    zero-bandwidth copy of p sampled by weight, the kernel size of p's first point)."""
+    from .product import DeviceDensity
+    if ksType not in ("lcv", "discrete"):
+        raise ValueError("resample: ksType must be 'lcv' or 'discrete'")
+    if isinstance(p, DeviceDensity):
+        if ksType != "lcv":
+            raise ValueError("resample: ksType 'discrete' needs the host arrays of a BallTreeDensity")
+        return p.resample(Np, seed=seed)
+    N = p.bt.num_points
+    Np = N if Np is None or int(Np) <= 0 else int(Np)
+    if ksType == "discrete":
+        _, lab = sample(p, Np, seed=seed)
+        return kde(getPoints(p)[:, lab - 1], getBW(p)[:, 0])
+    pts, _ = sample(p, Np, seed=seed)
+    return kde(pts)
+
+
+def sample_device_batch(items, stream=None):
+    """Many draws in ONE call (kdehip_sample_device_batch): `items` = dicts with `density` (DeviceDensity), `Npts`,
+    `d_pts` (float64[D*Npts]), `d_ind` (int64[Npts]) device arrays (torch tensors or addresses) and optionally `seed`
+    (default 0), `sample_offset` (0), `ind` (device int64[Npts] of 1-based labels).  One table build for the densities
+    that have none yet, one draw launch per dimension count; every item gets what `DeviceDensity.sample_device` gives it.
+    Enqueues on `stream` and returns."""
+    from .product import ProductPlan
+    items = list(items)
+    n = len(items)
+    arr = (_lib.CSampleItem * max(1, n))()
+    for k, it in enumerate(items):
+        a = arr[k]
+        a.density = it["density"]._h
+        a.Npts = int(it["Npts"])
+        a.seed = int(it.get("seed", 0)) & (2 ** 64 - 1)
+        a.sample_offset = int(it.get("sample_offset", 0))
+        a.d_ind_in = ProductPlan._addr(it.get("ind"))
+        a.d_pts = ProductPlan._addr(it["d_pts"])
+        a.d_ind = ProductPlan._addr(it["d_ind"])
+    _lib.check(_lib.lib.kdehip_sample_device_batch(n, arr, ProductPlan._addr(stream)))

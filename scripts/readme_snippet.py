@@ -15,3 +15,8 @@ print([m.num_points for m in msgs], msgs[0].bw)
 a = kdehip.kde(np.vstack([np.random.randn(300), np.random.uniform(-3.1, 3.1, 300)]), [0.3])
 pts, idx = kdehip.prodAppxMSGibbsS(None, [a, a], None, None, Niter=3, Np=100, seed=1, manifold=["euclid", "circular"])
 print(pts.shape, float(np.abs(pts[1]).max()) < np.pi)
+# drawing from a density: sample / rand / resample (labels 1-based, Philox stream keyed by seed and sample index)
+x, ind = kdehip.sample(p, 1000, seed=3)          # (3, 1000) points and their labels
+r = kdehip.rand(q, 5, seed=4)                    # (3, 5)
+m = msgs[0].resample(seed=5)                     # resample(p, Npts(p), :lcv) without leaving HBM
+print(x.shape, int(ind.min()) >= 1, r.shape, m.num_points)
