@@ -149,18 +149,6 @@ __device__ __forceinline__ float lane_read(float v, int src) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
-// ---- phase stamps (diagnostic build only, -DKDEHIP_STAMPS; never part of the product library) ----
-#ifdef KDEHIP_STAMPS
-static __device__ unsigned long long g_stamp_acc[16];
-#define KSTAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime()
-#define KSTAMP_ARGS , stamp_acc, stamp_on
-#define KSTAMP_ADD(slot, t0, t1) do { if (stamp_on) stamp_acc[slot] += (t1) - (t0); } while (0)
-#else
-#define KSTAMP(var) do {} while (0)
-#define KSTAMP_ARGS
-#define KSTAMP_ADD(slot, t0, t1) do {} while (0)
-#endif
-
 template <typename P> constexpr bool kIsLdsPointer = false;
 template <typename T> constexpr bool kIsLdsPointer<const __attribute__((address_space(3))) T *> = true;
 template <typename T> constexpr bool kIsLdsPointer<const volatile __attribute__((address_space(3))) T *> = true;
@@ -337,26 +325,12 @@ struct EvalFast {
       }
     }
     const V w = row.w;
-#ifndef KDEHIP_X_PREFIXPROD
     // sum_d d2[d] / c[d] as ONE fraction num / prod, by pairwise addition of fractions n_a/e_a + n_b/e_b =
-    // (n_a e_b + n_b e_a) / (e_a e_b) over a balanced tree: 3 (D - 1) instructions (round 4; D = 6: 15, where the
-    // prefix/suffix products below take 19 -- c3 -1.5 %, c4 -1.3 %, c5 -1.4 %, profiles/r04_experiments.md)
+    // (n_a e_b + n_b e_a) / (e_a e_b) over a balanced tree: 3 (D - 1) instructions (D = 6: 15).  Replaced the
+    // prefix/suffix products of rounds 1-3 (D = 6: 19) in round 4: c3 -1.5 %, c4 -1.3 %, c5 -1.4 %,
+    // profiles/r04_experiments.md
     V num, prod;
     fraction_sum<V, 0, D>(d2, c, num, prod);
-#else
-    // (rounds 1-3) pre[d]*suf[d] = prod_{k != d} c[k]; P = prod_k c[k]
-    V pre[D], suf[D];
-    pre[0] = V(1);
-#pragma unroll
-    for (int d = 1; d < D; ++d) pre[d] = pre[d - 1] * c[d - 1];
-    suf[D - 1] = V(1);
-#pragma unroll
-    for (int d = D - 2; d >= 0; --d) suf[d] = suf[d + 1] * c[d + 1];
-    const V prod = pre[D - 1] * c[D - 1];
-    V num = V(0);
-#pragma unroll
-    for (int d = 0; d < D; ++d) num = Num<V>::fma(d2[d], pre[d] * suf[d], num);
-#endif
     const V r = Num<V>::rsqrt(prod);
     const V q = num * r * r;  // = sum_d delta_d^2 / c_d
     front = w * r;
@@ -464,14 +438,9 @@ struct EvalGeneric {
 // adoption) run at high priority, the rows -- throughput work -- at low, so that a wavefront in a dependent chain is
 // served at once while its partner streams rows: oldest-first arbitration alone lets the OLDER wavefront's rows hold up the
 // younger one's chain.  Config 3, 2048 chains: 0.6047 -> 0.5840 ms (interleaved A/B, profiles/r04_experiments.md); config 5
-// -1 %; config 4 and 16-chain workgroups unchanged.  (-DKDEHIP_X_NO_SETPRIO: A/B builds without it.)
-#ifndef KDEHIP_X_NO_SETPRIO
+// -1 %; config 4 and 16-chain workgroups unchanged (all against the same builds without s_setprio).
 #define KDEHIP_PRIO_ROWS() __builtin_amdgcn_s_setprio(0)
 #define KDEHIP_PRIO_CHAIN() __builtin_amdgcn_s_setprio(3)
-#else
-#define KDEHIP_PRIO_ROWS() do {} while (0)
-#define KDEHIP_PRIO_CHAIN() do {} while (0)
-#endif
 
 // ---- one categorical label draw over a frontier -------------------------------------------------
 // Evaluates every node of the frontier with `ev`, and returns the tile position (row*64 + lane) of
@@ -617,22 +586,14 @@ __device__ __forceinline__ void count_fallback(const void *fb, int lane) {
 
 template <typename T, typename P, typename Eval, typename DS>
 __device__ __forceinline__ int select_from_scan(T incl, T S, P rows, const DS &ds, int lane, const Eval &ev,
-                                                double u, T thr, bool final, const void *fb
-#ifdef KDEHIP_STAMPS
-                                                , unsigned long long *stamp_acc, bool stamp_on
-#endif
-);
+                                                double u, T thr, bool final, const void *fb);
 
 // Selection from the lane sums S: wavefront scan, winning lane, then pass 2 over the winning lane's
 // block read through `rows` (row 0, field 0, lane 0 of the whole tile; LDS or global).
 template <typename T, typename P, typename Eval, typename DS>
 __device__ __forceinline__ int select_label(T S, P rows, const DS &ds, int lane, const Eval &ev, double u,
-                                            T thr, bool final, const void *fb
-#ifdef KDEHIP_STAMPS
-                                            , unsigned long long *stamp_acc, bool stamp_on
-#endif
-) {
-  return select_from_scan<T, P>(wave_inclusive_scan(S), S, rows, ds, lane, ev, u, thr, final, fb KSTAMP_ARGS);
+                                            T thr, bool final, const void *fb) {
+  return select_from_scan<T, P>(wave_inclusive_scan(S), S, rows, ds, lane, ev, u, thr, final, fb);
 }
 
 // The selection proper, from the inclusive wavefront scan `incl` of the lane sums S.  Also entered
@@ -641,15 +602,10 @@ __device__ __forceinline__ int select_label(T S, P rows, const DS &ds, int lane,
 // otherwise -1 is returned and the caller repeats the evaluation with raised exponents (fp32 only).
 template <typename T, typename P, typename Eval, typename DS>
 __device__ __forceinline__ int select_from_scan(T incl, T S, P rows, const DS &ds, int lane, const Eval &ev,
-                                                double u, T thr, bool final, const void *fb
-#ifdef KDEHIP_STAMPS
-                                                , unsigned long long *stamp_acc, bool stamp_on
-#endif
-) {
+                                                double u, T thr, bool final, const void *fb) {
   using TA = TileAddr<T>;
   const int n = ds.n, B = ds.B, F = ds.F;
   const int RS = TA::stride(F);
-  KSTAMP(tp1);
   const T total = lane_read(incl, 63);
 
   if (!(total >= thr)) {  // also taken when every weight is NaN (:302 zeroes them all)
@@ -672,12 +628,7 @@ __device__ __forceinline__ int select_from_scan(T incl, T S, P rows, const DS &d
   const int last_lane = ds.last_lane;
   int lstar = hit ? (__ffsll(hit) - 1) : last_lane;
   if (lstar > last_lane) lstar = last_lane;
-  KSTAMP(tp2);
-  KSTAMP_ADD(3, tp1, tp2);
   if (B == 1) return lstar;
-#ifdef KDEHIP_X_NOPASS2  // timing ablation only (wrong labels): what the second pass costs
-  return lstar;
-#endif
 
   // pass 2: narrow inside the winning lane's block until a single node is left
   T base = lane_read(incl - S, lstar);  // exclusive prefix of the block
@@ -706,8 +657,6 @@ __device__ __forceinline__ int select_from_scan(T incl, T S, P rows, const DS &d
   const T inc3 = wave_inclusive_scan(p2);
   const unsigned long long h3 = __ballot((target <= base + inc3) && (lane < len));
   const int istar = h3 ? (__ffsll(h3) - 1) : (len - 1);
-  KSTAMP(tp3);
-  KSTAMP_ADD(4, tp2, tp3);
   return (r0 + istar) * 64 + lstar;
 }
 
@@ -818,11 +767,7 @@ __device__ __forceinline__ int draw_label_raised(P rows, const DS &ds, int lane,
     const T S = lane_sum_rows<T, P, std::decay_t<decltype(evo)>, false>(rows, ds.B, TileAddr<T>::stride(ds.F), lane, evo);
     const bool final = (k == Num<T>::kOffsetSteps);
     pos = select_from_scan<T, P>(wave_inclusive_scan(S), S, rows, ds, lane, evo, u,
-                                 final ? Num<T>::final_total() : Num<T>::tiny_total(), final, fb
-#ifdef KDEHIP_STAMPS
-                                 , nullptr, false
-#endif
-    );
+                                 final ? Num<T>::final_total() : Num<T>::tiny_total(), final, fb);
   }
   return pos;
 }
@@ -830,13 +775,9 @@ __device__ __forceinline__ int draw_label_raised(P rows, const DS &ds, int lane,
 // selection from first-pass lane sums S formed at offset 0, then the raised attempts if the sum underflowed
 template <typename T, typename P, typename Eval, typename DS>
 __device__ __forceinline__ int select_or_raise(T S, P rows, const DS &ds, int lane, const Eval &ev, double u,
-                                               const void *fb
-#ifdef KDEHIP_STAMPS
-                                               , unsigned long long *stamp_acc, bool stamp_on
-#endif
-) {
+                                               const void *fb) {
   constexpr bool kOneAttempt = (Num<T>::kOffsetSteps == 0);
-  const int pos = select_label<T, P>(S, rows, ds, lane, ev, u, Num<T>::tiny_total(), kOneAttempt, fb KSTAMP_ARGS);
+  const int pos = select_label<T, P>(S, rows, ds, lane, ev, u, Num<T>::tiny_total(), kOneAttempt, fb);
   if constexpr (kOneAttempt) return pos;
   else {
     if (__builtin_expect(pos >= 0, 1)) return pos;
@@ -868,17 +809,13 @@ __device__ __forceinline__ int seg_count(int seg) { return seg >> 16; }
 
 template <typename T, typename P, typename Eval, typename DS>
 __device__ __forceinline__ int select_or_raise_seg(T S, const SegSums<T> &seg, int seg_rows, P rows, const DS &ds,
-                                                   int lane, const Eval &ev, double u, const void *fb
-#ifdef KDEHIP_STAMPS
-                                                   , unsigned long long *stamp_acc, bool stamp_on
-#endif
-) {
+                                                   int lane, const Eval &ev, double u, const void *fb) {
   const int n = ds.n, B = ds.B;
   const int RS = TileAddr<T>::stride(ds.F);
   const T incl = wave_inclusive_scan(S);
   const T total = lane_read(incl, 63);
   // underflow (uniform fallback, fp32 raised repeats): the general path
-  if (!(total >= Num<T>::tiny_total())) return select_or_raise<T, P>(S, rows, ds, lane, ev, u, fb KSTAMP_ARGS);
+  if (!(total >= Num<T>::tiny_total())) return select_or_raise<T, P>(S, rows, ds, lane, ev, u, fb);
   const T target = static_cast<T>(u) * total;
   const unsigned long long hit = __ballot(target <= incl);
   const int last_lane = ds.last_lane;
@@ -915,26 +852,16 @@ __device__ __forceinline__ int select_or_raise_seg(T S, const SegSums<T> &seg, i
 
 template <typename T, typename P, bool PREFETCH, bool kKeptRows, typename Eval, typename DS>
 __device__ __forceinline__ int draw_label(P rows, const DS &ds, int lane, const Eval &ev, double u,
-                                          const void *fb
-#ifdef KDEHIP_STAMPS
-                                          , unsigned long long *stamp_acc, bool stamp_on
-#endif
-) {
-#if !defined(KDEHIP_STAMPS) && !defined(KDEHIP_NO_KEPT)
+                                          const void *fb) {
   // PREFETCH marks the builds with registers to spare (see kPrefetchRows); fp32 has its packed-pair first pass
   if constexpr (PREFETCH && kIsLdsPtr<P> && sizeof(T) == 8 && kKeptRows) {
     if (ds.B > 1 && ds.B <= 4) return draw_label_kept<T, P, Eval, 4>(rows, ds, lane, ev, u, fb);
     if (ds.B > 4 && ds.B <= 8) return draw_label_kept<T, P, Eval, 8>(rows, ds, lane, ev, u, fb);
-
   }
-#endif
-  KSTAMP(tp0);
   KDEHIP_PRIO_ROWS();
   const T S = lane_sum_rows<T, P, Eval, PREFETCH>(rows, ds.B, TileAddr<T>::stride(ds.F), lane, ev);
   KDEHIP_PRIO_CHAIN();
-  KSTAMP(tp1);
-  KSTAMP_ADD(2, tp0, tp1);
-  return select_or_raise<T, P>(S, rows, ds, lane, ev, u, fb KSTAMP_ARGS);
+  return select_or_raise<T, P>(S, rows, ds, lane, ev, u, fb);
 }
 
 // ---- the sampler ----------------------------------------------------------------------------------
@@ -1020,16 +947,12 @@ __device__ __forceinline__ void stage_tile(const unsigned char *__restrict__ src
       __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(src), 0, bytes, 0x00020000);
   const int pieces = bytes >> 10;
   // (the piece offset goes through readfirstlane: strength reduction otherwise keeps it in a vector register, and the
-  // scalar-offset operand of the load is then fed by a waterfall loop -- 18 instructions per 1-KiB piece instead of 6)
-#ifdef KDEHIP_X_OLDSTAGE  // (A/B only: the round-3 form)
-  for (int c = wave; c < pieces; c += WAVES)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsVoidPtr)(dst + (c << 10)), 16, lane << 4, c << 10, 0, 0);
-#else
+  // scalar-offset operand of the load is then fed by a waterfall loop -- 18 instructions per 1-KiB piece instead of 6;
+  // against that round-3 form, round 4 measured c3 0.6334 -> 0.6144 ms, profiles/r04_experiments.md)
   for (int c = wave; c < pieces; c += WAVES) {
     const int off = __builtin_amdgcn_readfirstlane(c << 10);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsVoidPtr)(dst + off), 16, lane << 4, off, 0, 0);
   }
-#endif
 }
 
 // What a workgroup works on.  A plain launch: the kernel arguments, block = blockIdx.x.  A BATCHED launch

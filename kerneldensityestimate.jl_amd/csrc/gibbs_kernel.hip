@@ -67,11 +67,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
   // pass 1 prefetches the next row's fields while it evaluates the current one; the 16-wavefront fp64
   // builds have 128 VGPRs and would spill from D = 6 on
   constexpr bool kPrefetchRows = (WAVES <= 12) || sizeof(T) == 4 || D <= 4;
-#ifdef KDEHIP_X_ALLCOPY  // (A/B only: rounds 1-3)
-  constexpr int kCopyWaves = WAVES;
-#else
   constexpr int kCopyWaves = WAVES > 4 ? 4 : WAVES;  // who issues the copies of streamed tiles and chunks (gibbs_lean.hip)
-#endif
   using Lay = LdsLayout<T, D, WAVES>;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[TBL ? Lay::kPoolOff : Lay::kBytes];
 
@@ -102,17 +98,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
   const int dl = lane < D ? lane : D - 1;  // this lane's dimension in the "lanes = dimensions" phases
 
   // variant: 0 default; 1 = read every tile from global memory (no LDS staging); 2 / 8 / 16 = 4 / 8 / 16 chains per workgroup.
-  // Diagnostic builds (-DKDEHIP_EXPERIMENTS, scripts/) add level cut-offs and ablation flags.
+  // Diagnostic builds (-DKDEHIP_EXPERIMENTS, scripts/) add level cut-offs (100 + k).  The thousands digit only pins the
+  // width of the register-resident kernel (lean_waves, kdehip_internal.hpp); this kernel reads variant % 1000.
   const int vlev = a.variant % 1000;
-#ifdef KDEHIP_EXPERIMENTS
-  const int vflags = a.variant / 1000;
-#else
-  constexpr int vflags = 0;
-#endif
-#ifdef KDEHIP_STAMPS
-  unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool stamp_on = false;
-#endif
   uint32_t any_bits = 0;  // dimensions informed by at least one density
   for (int j = 0; j < M; ++j) any_bits |= levels[j * (L + 1)].mask_bits;
 
@@ -239,19 +227,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
   // it.  Updating the selected kernel right after the draw is equivalent to the reference's deferred
   // calcIndices! (:383): within the sampleIndices! pass nothing reads the selected kernels.
   auto step = [&](int j, const LevelDesc &ds, auto hdr, T mean, T cov, double u) {
-    KSTAMP(ts0);
     auto rows = hdr + kTileHeader;
     using P = decltype(rows);
-    const int pos = (vflags & 8) ? 0 : draw(ds, hdr, mean, cov, [&](const auto &ev) {
-      return draw_label<T, P, kPrefetchRows, (WAVES <= 8)>(rows, ds, lane, ev, u, fb KSTAMP_ARGS);
+    const int pos = draw(ds, hdr, mean, cov, [&](const auto &ev) {
+      return draw_label<T, P, kPrefetchRows, (WAVES <= 8)>(rows, ds, lane, ev, u, fb);
     });
     wave_sync();
-    KSTAMP(ts1);
-    if (!(vflags & 2)) set_particle(j, ds, hdr, pos);
+    set_particle(j, ds, hdr, pos);
     wave_sync();
-    KSTAMP(ts2);
-    KSTAMP_ADD(1, ts0, ts1);  // whole draw (setup + passes + scans)
-    KSTAMP_ADD(5, ts1, ts2);  // set_particle
   };
 
   // Chunked step for tiles larger than half the LDS pool: pass 1 streams the rows through the two
@@ -294,8 +277,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
       const T S = acc.total();
       // (a raised repeat of the evaluation reads the tile from global memory: no staging, no barriers)
       if (use_seg)
-        return select_or_raise_seg<T, const T *>(S, seg, cps * rc, hdr + kTileHeader, ds, lane, ev, u, fb KSTAMP_ARGS);
-      return select_or_raise<T, const T *>(S, hdr + kTileHeader, ds, lane, ev, u, fb KSTAMP_ARGS);
+        return select_or_raise_seg<T, const T *>(S, seg, cps * rc, hdr + kTileHeader, ds, lane, ev, u, fb);
+      return select_or_raise<T, const T *>(S, hdr + kTileHeader, ds, lane, ev, u, fb);
     });
     wave_sync();
     set_particle(j, ds, hdr, pos);
@@ -378,7 +361,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
   uint32_t ubatch = 0xFFFFFFFFu;
   double u_even = 0.0, u_odd = 0.0;
   auto next_uniform = [&]() -> double {
-    if (vflags & 1) { ++c; return 0.37; }
     const uint32_t b = c >> 7;
     if (b != ubatch) {
       ubatch = b;
@@ -455,14 +437,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
         const LevelDesc ds = kNeedsNext ? ds_next : levels[j * (L + 1) + l];
         if constexpr (kNeedsNext) ds_next = levels[jn * (L + 1) + l];
         T mean = x, cov = T(0);      // sampleIndices! (:364-385): against the point just drawn
-#ifdef KDEHIP_STAMPS
-        stamp_on = (l == (vflags >> 8)) ;  // stamp only the level selected by the experiment
-#endif
-        KSTAMP(tq0);
-        if (t >= M && !(vflags & 4)) product_dim(j, ds.others_bits, mean, cov);  // sampleIndex (:404-429): leave j out
+        if (t >= M) product_dim(j, ds.others_bits, mean, cov);  // sampleIndex (:404-429): leave j out
         const double u = next_uniform();
-        KSTAMP(tq1);
-        KSTAMP_ADD(0, tq0, tq1);
         if constexpr (kMode == kStageGlobal) {
           step(j, ds, data + ds.hdr_off, mean, cov, u);
         } else if constexpr (kMode == kStageResident) {
@@ -472,10 +448,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
         } else {
           // tile t has been copied by all wavefronts once everyone passes this barrier; buffer
           // (t+1)&1 was last read in step t-1, which everyone has left -> start the next copy
-          KSTAMP(tb0);
           staging_barrier();
-          KSTAMP(tb1);
-          KSTAMP_ADD(6, tb0, tb1);
           // (the next tile's copy: at the end of the step by the older wavefronts, gibbs_lean.hip "kLateCopy"; with one
           // wavefront per SIMD at its start by everyone)
           constexpr bool kLateCopy = kCopyWaves < WAVES;
@@ -551,10 +524,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
     }
   }
 
-#ifdef KDEHIP_STAMPS
-  if (blockIdx.x == 3 && wave == 1 && lane == 0)
-    for (int k = 0; k < 8; ++k) g_stamp_acc[k] = stamp_acc[k];
-#endif
   // final labels (:612-616) and final point (:625)
   if (live && lane == 0) {
     for (int k = 0; k < M; ++k) {
@@ -656,10 +625,3 @@ int KDEHIP_CAT(launch_gibbs_d, KDEHIP_DIM)(int precision, int mode, const PlanDe
 }
 
 }  // namespace kdehip
-
-#if defined(KDEHIP_STAMPS) && KDEHIP_DIM == 6
-extern "C" int kdehip_debug_read_stamps(unsigned long long *out) {
-  (void)hipDeviceSynchronize();
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(kdehip::g_stamp_acc), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -5;
-}
-#endif

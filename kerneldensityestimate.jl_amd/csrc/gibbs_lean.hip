@@ -103,12 +103,10 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   // how the rows of an LDS tile are read: see LdsPtrSplit (fp32 reads its row pairs as single loads either way: load_pair)
   using RowPtr = std::conditional_t<(WAVES == 16 && sizeof(T) == 8), LdsPtrSplit<T>, LdsPtr<T>>;
   // the wavefronts that issue the copies of streamed tiles and chunks: the OLDEST wavefront of every SIMD (wavefronts w,
-  // w + 4, w + 8, w + 12 share a SIMD, the lowest is the oldest: scripts/micro/simd_map.hip); everyone when each SIMD has one
-#ifdef KDEHIP_X_ALLCOPY  // (A/B only: rounds 1-3, every wavefront issues its share at the start of the step)
-  constexpr int kCopyWaves = WAVES;
-#else
+  // w + 4, w + 8, w + 12 share a SIMD, the lowest is the oldest: scripts/micro/simd_map.hip); everyone when each SIMD has one.
+  // Rounds 1-3 had every wavefront issue its share at the start of the step; round 4 measured against that: c3 -2.7 %,
+  // c4 -4.4 % (profiles/r04_experiments.md section 17)
   constexpr int kCopyWaves = WAVES > 4 ? 4 : WAVES;  // (16 wavefronts: the oldest of the four on a SIMD; its half: c5 +0.8 %)
-#endif
   constexpr bool kKeptRows = (WAVES <= 8);
   // fp32 screening of the deep levels (screen_device.hpp): the fp64 instantiations of plain launches
   constexpr bool kScreen = sizeof(T) == 8 && !BATCH;
@@ -124,11 +122,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   // the rows r = k mod 4 in increasing order -- each class is one sequential sum, so the split changes no bit), two requests
   // at a time.  Per request slot: mean and variance of the draw per dimension (what the helpers build the evaluator from)
   // and the 4 x 64 class sums.  Flags are double-buffered by step parity: a wavefront may be one step ahead of another.
-#ifndef KDEHIP_X_NO_COOP
+  // (Against the repeat by the undecided wavefront alone: config 4 3.00 -> 2.88 ms, profiles/r06_experiments.md section 12.)
   constexpr bool kCoop = kScreen && SCHUNK && WAVES == 8;
-#else
-  constexpr bool kCoop = false;
-#endif
   constexpr int kXchgOff = kPoolOff + kLdsPoolBytes;
   constexpr int kXchgSlotDoubles = 32 + 4 * 64;  // [0..7] mean, [8..15] variance, [32 + 64 k + lane] class sums
   constexpr int kXchgBytes = kCoop ? 64 + WAVES * kXchgSlotDoubles * 8 : 0;
@@ -162,11 +157,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   // ---- the chain's normal deviates, once (samplePoint! consumes D per level + D at the end, :440-463) ----
   double *sNorm = reinterpret_cast<double *>(smem + kNormOff) + chain * kLeanMaxNormals;
   const int R = D * (L + 1);
-#ifdef KDEHIP_X_OLDNORMALS
-  for (int r = lane; r < R; r += 64)
-    sNorm[r] = a.rng_philox ? philox_normal(a.seed, gs, static_cast<uint32_t>(r)) : a.randN[s * a.R + r];
-#else
-  if (a.rng_philox) {  // a lane makes BOTH normals of a Philox block (one logarithm, one sine/cosine pair for two)
+  // (a lane makes BOTH normals of a Philox block: one logarithm, one sine/cosine pair for two; against one normal per
+  // lane, round 4 measured c3 0.5880 -> 0.5839 ms, profiles/r04_experiments.md)
+  if (a.rng_philox) {
     for (int b = lane; 2 * b < R; b += 64) {
       double n0, n1;
       philox_normal_pair(a.seed, gs, static_cast<uint32_t>(b), n0, n1);
@@ -176,7 +169,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   } else {
     for (int r = lane; r < R; r += 64) sNorm[r] = a.randN[s * a.R + r];
   }
-#endif
   __syncthreads();  // (exp table; the strip is only read by its own chain's wavefronts)
 
   // ---- chain state: selected kernel of every density, lanes = dimensions ----
@@ -291,7 +283,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   // unchanged 0.471 ms kernel (profiles/r06_experiments.md section 10).
   auto draw_rows_repeat = [&](const auto &ds, const T *rows, const auto &ev, double u) -> int {
     using Ev = std::decay_t<decltype(ev)>;
-#ifndef KDEHIP_X_NO_DEEP
     if constexpr (kScreen && SCHUNK && sizeof(typename Ev::Row) <= 7 * sizeof(T) && WAVES <= 8) {
       LaneAcc<T> acc;
       KDEHIP_PRIO_ROWS();
@@ -299,7 +290,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       KDEHIP_PRIO_CHAIN();
       return select_or_raise<T, const T *>(acc.total(), rows, ds, lane, ev, u, fb);
     }
-#endif
     return draw_rows(ds, rows, ev, u);
   };
 
@@ -361,7 +351,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   // one (pass, density) step on a tile readable through one pointer: leave-one-out product (sweeps) or the point
   // just drawn (sampleIndices! pass, :364-385), the draw, and the new kernel
   auto step = [&](auto jc, const auto &ds, auto hdr, bool first, T x) {
-#ifndef KDEHIP_X_NO_PRELOAD
     // Frontiers with per-node bandwidths whose tile sits in LDS for the whole level, up to KDEHIP_PRELOAD_MAXB rows per
     // lane (config 3: levels 5..8 and the first pass of 1..4): the fields of the lane's first row do not depend on the
     // chain's state, so they are requested FIRST and land while the leave-one-out product and the broadcasts run -- a
@@ -387,7 +376,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
         return;
       }
     }
-#endif
     T mean = x, cov = T(0);
     if (!first) product(jc, mean, cov);
     const double u = next_uniform();
@@ -572,12 +560,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       const float acen = fabsf(cen);
       const float t = fminf(mmax + acen, 2.0f * acen);
       float a2 = lane < D ? t * t * __builtin_amdgcn_rcpf(cf) : 0.0f;
-      // (a2 <= kScreenMaxA2 in every dimension keeps na <= 2^-11, the regime the bound is linearised for: screen_device.hpp)
-#ifndef KDEHIP_X_NO_NA_GUARD
+      // (a2 <= kScreenMaxA2 in every dimension keeps na <= 2^-11, the regime the bound is linearised for: screen_device.hpp;
+      // folded into this range ballot it costs config 3 +0.4 % against no guard, profiles/r06_experiments.md)
       const bool inr = (acen <= kScreenMaxAbsMean) && (covf <= static_cast<float>(kScreenMaxVar)) && (a2 <= kScreenMaxA2);  // (false for a NaN)
-#else
-      const bool inr = (acen <= kScreenMaxAbsMean) && (covf <= static_cast<float>(kScreenMaxVar));
-#endif
       int pos = -1;
       const T *hdrg = data + ds.hdr_off();
       if (valid != 0.0f && __ballot(lane < D && !inr) == 0ull) {

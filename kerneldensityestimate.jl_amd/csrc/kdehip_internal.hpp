@@ -349,7 +349,8 @@ int auto_bandwidth_run(int D, int64_t N, const double *points, const double *d_p
 // (kdehip_product_set_variant).  Shared by both sampler kernels.
 int chains_per_workgroup(int64_t Np, int variant);
 // The same for the register-resident sampler (gibbs_lean.hip): diagnostic builds combine a level cut-off (variant % 1000 =
-// 100 + k) with a width in the thousands digit (6: sixteen, 8: eight chains per workgroup).
+// 100 + k) with a width in the thousands digit (6: sixteen, 8: eight chains per workgroup).  Pinning this width is the
+// only meaning of the thousands digit: everything else reads variant % 1000.
 // (Rounds 3-4 also had "wavefront teams" -- one chain on 2 or 4 wavefronts of a 16-wavefront workgroup, plan variants
 // 52 / 54: bit-identical, measured slower than one wavefront per chain at every BASELINE shape in both rounds
 // (profiles/r03_experiments.md), never selected by a plan; removed in round 5.)

@@ -76,11 +76,7 @@ struct ScreenConst {
   static constexpr float kx_uni = 12 + D, kx_node = 16 + 2 * depth + D;
   static constexpr float vc_uni = D + 9, vc_node = (3 * D + 18) / 2;
 };
-#ifdef KDEHIP_X_NO_REPEAT  // (timing experiment only: every fp32 decision accepted -- NOT the fp64 labels)
-constexpr double kScreenMargin = 0.0;
-#else
 constexpr double kScreenMargin = 2.1;  // boundaries farther than this many error sums from the target are decided (2 suffices)
-#endif
 
 template <int D, bool UNI>
 struct ScreenEval {

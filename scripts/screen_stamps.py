@@ -1,4 +1,4 @@
-"""Phase stamps of a SCREENED step (diagnostic build: scripts/dev_lean.sh stamps -DKDEHIP_SCREEN_STAMPS -DKDEHIP_X_SCREEN_NOKEPT),
+"""Phase stamps of a SCREENED step (diagnostic build: scripts/dev_lean.sh stamps -DKDEHIP_SCREEN_STAMPS),
 one wavefront (workgroup 3, wavefront 5), cycles per step:  KDEHIP_LIB=.../libkdehip_stamps.so python scripts/screen_stamps.py"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
