@@ -505,6 +505,49 @@ int kdehip_make_density_auto(int64_t D, int64_t N, const double *points, double 
                              int64_t *lowest_leaf, int64_t *highest_leaf, int64_t *permutation, double *means,
                              double *bandwidth, double *bandwidthMin, double *bandwidthMax);
 
+/* ---- (5b) evalAvgLogL, and evaluation of resident densities ----------------------------------------------------
+ * `evalAvgLogL(bd, at)` (src/DualTree01.jl:450-470): L = evaluateDualTree(bd, at) -- bd at at's points, by the direct sum
+ * of kdehip_evaluate -- and W = at's weights; if some L_q == 0 has W_q != 0 the result is -Inf (whatever else is NaN),
+ * otherwise sum_q W_q log L_q with the L_q == 0 terms counted as 0.  at's points are its leaf means (the centers getPoints
+ * reads in every density kde! builds).  leave_one_out is the reference's `bd == at` (an identity test, :333): the self term
+ * is skipped and L_q is divided by (1 - w_q) (:335); it needs at == bd (KDEHIP_ERR_ARG otherwise).  at == bd without the
+ * flag is the reference's evalAvgLogL(bd, deepcopy(bd)).
+ * The other functions of the reference are compositions of this one (leave_one_out = 1 exactly where the arguments are
+ * the same object):
+ *   entropy(bd)   = -evalAvgLogL(bd, bd)                         (:505-508)
+ *   kld(p, q)     = evalAvgLogL(p, p) - evalAvgLogL(q, p)        (:477-503, method = :direct; kld(p, p) is not 0)
+ *   minkld(p, q)  = min(|kld(p, q)|, |kld(q, p)|)                (:510)
+ * Arguments: ndims must match (KDEHIP_ERR_DIM_MISMATCH); D above KDEHIP_MAX_DIMS, or an evaluated density whose leaves do
+ * not share one bandwidth vector, is KDEHIP_ERR_UNSUPPORTED (as kdehip_evaluate; `at` contributes only points and weights).
+ * Every entry checks all of its arguments before it touches a device.
+ * Arithmetic: every L_q is bit for bit what kdehip_evaluate returns for that point (same kernels' arithmetic, same split of
+ * the sum, which depends on the pair's (N, Nq) alone); W_q log L_q is summed in at's leaf order, in blocks of 256 by a fixed
+ * tree, the blocks in order.  The result is the same bits from the host entry, a single device call and any batch, run
+ * after run. */
+int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out, int device);
+/* Host densities (at may be NULL when leave_one_out is set), one pinned upload, blocking, on hipStreamPerThread. */
+typedef struct kdehip_logl_item {
+  const kdehip_device_density *bd;
+  const kdehip_device_density *at;
+  int32_t leave_one_out;
+  int32_t reserved_;
+} kdehip_logl_item;
+/* Resident densities, all on one device: d_out[i] (device, n doubles) = evalAvgLogL(items[i].bd, items[i].at).  One
+ * partial-sum launch per distinct D, one finish launch and one reduction launch for all items.  Enqueue only, on `stream`
+ * (hipStream_t, NULL = the null stream). */
+int kdehip_eval_avg_logl_device_batch(int n, const kdehip_logl_item *items, double *d_out, void *stream);
+/* The same for one pair, blocking on the calling thread's stream; the result to host memory. */
+int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                double *out);
+/* `evaluateDualTree(bd, pos)` on a resident density, enqueue only on `stream`: d_pos = D x Nq column-major device points,
+ * d_out = Nq device doubles in query order.  leave_one_out != 0: d_pos and Nq are ignored, bd is evaluated at its own
+ * points as kdehip_evaluate does, d_out holds npts values in the original point order. */
+int kdehip_evaluate_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out, double *d_out,
+                           void *stream);
+/* bd at at's points (leave-one-out when at == bd), d_out = npts(at) device doubles in at's ORIGINAL point order (through
+ * its permutation, as getPoints orders them); enqueue only on `stream`. */
+int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

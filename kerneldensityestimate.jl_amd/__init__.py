@@ -2,7 +2,7 @@
 
 This package is the Python host mirror of the reference's interface for that path
 (`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`,
-`sample/rand/resample`)
+`sample/rand/resample`, `evalAvgLogL/entropy/kld/minkld`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
 """
@@ -14,6 +14,7 @@ from .product import (DeviceDensity, GbGlb, MultiProductPlan, ProductBatch, Prod
                       nlevels, philox_streams, prodAppxMSGibbsS, prodAppxMSGibbsS_batch, prodAppxMSGibbsS_device,
                       prodAppxMSGibbsS_resident)
 from .sample import rand, resample, sample, sample_device_batch  # noqa: F401
+from .loglik import entropy, eval_avg_logl_device_batch, evalAvgLogL, kld, kld_batch, minkld  # noqa: F401
 
 
 def device_count() -> int:

@@ -50,6 +50,11 @@ class CSampleItem(C.Structure):
                 ("d_ind_in", C.c_void_p), ("d_pts", C.c_void_p), ("d_ind", C.c_void_p)]
 
 
+class CLoglItem(C.Structure):
+    """struct kdehip_logl_item"""
+    _fields_ = [("bd", C.c_void_p), ("at", C.c_void_p), ("leave_one_out", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class CProductInfo(C.Structure):
     """struct kdehip_product_info_t"""
     _fields_ = [
@@ -113,6 +118,11 @@ SIGNATURES = {
     "kdehip_philox_fill_uniform": (None, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, f64p]),
     "kdehip_philox_fill_normal": (None, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, f64p]),
     "kdehip_evaluate": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, f64p, C.c_int]),
+    "kdehip_eval_avg_logl": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int, f64p, C.c_int]),
+    "kdehip_eval_avg_logl_device_batch": (C.c_int, [C.c_int, C.POINTER(CLoglItem), C.c_void_p, C.c_void_p]),
+    "kdehip_eval_avg_logl_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p]),
+    "kdehip_evaluate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "kdehip_evaluate_device_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kdehip_auto_bandwidth": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int]),
     "kdehip_make_density_device_supported": (C.c_int, [C.c_int64, C.c_int64]),
     "kdehip_make_densities_device": (C.c_int, [C.c_int, C.c_int64, i64p] + [C.POINTER(C.c_void_p)] * 2 + [C.c_int64] +

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "device_density.hpp"
 #include "fastexp.hpp"
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
@@ -1204,3 +1205,471 @@ extern "C" int kdehip_debug_prep_stamps(unsigned long long *out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prep_stamps), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -5;
 }
 #endif
+
+// ---- evalAvgLogL, and evaluation of resident densities (include/kdehip.h section 5b) ----------------------------------
+// evalAvgLogL(bd1, bd2) (src/DualTree01.jl:450-470) = sum_q W_q log p_q with p = bd1 at bd2's points (evaluateDualTree with
+// FORCE_EVAL_DIRECT, leave-one-out when bd1 === bd2) and W = bd2's weights; a p_q == 0 with W_q != 0 makes it -Inf.  Three
+// kernels, for any number of items (pairs) of any sizes, described in device memory:
+//   logl_partial_kernel<D>  one launch per distinct D: the group sums of eval_partial_kernel, item by item -- the same fma
+//                           chain, exp_nonpos, chunking and group split (split_chunks(N, Nq, 1): it depends on the item's
+//                           (N, Nq) alone, not on the batch), so every p_q is bit for bit what kdehip_evaluate returns;
+//   logl_finish_kernel      eval_finish_kernel's sum of the groups in order, / norm, / (1 - w) for leave-one-out, the value
+//                           stored (in the query density's original order) when asked for, then W_q log p_q and the block's
+//                           share in a fixed LDS tree; a weighted zero raises the block's flag instead of adding -Inf;
+//   logl_reduce_kernel      per item, the block shares summed in block order (or -Inf if a flag is up) into one double.
+// Nothing depends on the launch or the batch: the host entry, a single device call and any batch give the same bits.
+#define KDEHIP_CHECK_RC(expr)          \
+  do {                                 \
+    const int rc_ = (expr);            \
+    if (rc_ != KDEHIP_OK) return rc_;  \
+  } while (0)
+
+namespace {
+
+constexpr int kLoglThreads = 256;  // queries per finish block
+
+struct LoglItem {
+  const double *src;    // [N][D] leaf means of the evaluated density (tree order)
+  const double *w;      // [N] its leaf weights
+  const double *bw;     // [D] its first leaf's variances (every leaf has them: checked on the host)
+  const double *qry;    // [Nq][D] query points
+  const double *qw;     // [Nq] query weights (the `at` density's leaf weights), or null: no log-likelihood
+  const int64_t *perm;  // [Nq] 1-based output position of query q, or null: query order
+  double *out;          // [Nq] p, or null
+  double *partial;      // [ngroups][Nq]
+  double *bpart;        // [nfb] the finish blocks' shares of sum W log p
+  int32_t *bzero;       // [nfb] the finish block met a p == 0 with W != 0
+  double *logl;         // the result, or null
+  double norm0;         // (2 pi)^(D/2) as gauss_norm's libm rounds it
+  int64_t N, Nq, chunks_per_group;
+  int32_t ngroups, nfb, D, loo;
+};
+
+// the item that owns global block b: the last i with first[i] <= b (first[] ascending, first[n] = the number of blocks)
+__device__ __forceinline__ int item_of_block(const int32_t *__restrict__ first, int n, int b) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// eval_partial_kernel for the items [0, n) of one D: item i owns blocks [first[i], first[i+1]) - first[0], its block k is
+// query block k % qblocks of source group k / qblocks.  The body is eval_partial_kernel's, line for line.
+template <int D>
+__global__ __launch_bounds__(kEvalThreads) void logl_partial_kernel(const LoglItem *__restrict__ items,
+                                                                    const int32_t *__restrict__ first, int n) {
+  __shared__ double sSrc[2][kEvalChunk * (D + 1)];
+  __shared__ double sExpTab[32];
+  if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
+  const int b = static_cast<int>(blockIdx.x) + first[0];
+  const int i = item_of_block(first, n, b);
+  const LoglItem pb = items[i];
+  const int64_t qblocks = (pb.Nq + kEvalThreads - 1) / kEvalThreads;
+  const int64_t kb = b - first[i];
+  const int64_t qb = kb % qblocks, grp = kb / qblocks;
+  const int64_t q = qb * kEvalThreads + threadIdx.x;
+  const int64_t c_begin = grp * pb.chunks_per_group;
+  int64_t c_end = c_begin + pb.chunks_per_group;
+  const int64_t nchunks = (pb.N + kEvalChunk - 1) / kEvalChunk;
+  if (c_end > nchunks) c_end = nchunks;
+  if (c_begin >= c_end) return;  // block-uniform
+  double nhib[D];  // -1/(2 bw_k), as kdehip_evaluate's host computes it (IEEE division)
+#pragma unroll
+  for (int k = 0; k < D; ++k) nhib[k] = -0.5 / pb.bw[k];
+  double x[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = (q < pb.Nq) ? pb.qry[q * D + k] : 0.0;
+  auto stage = [&](int64_t c, int buf) {
+    const int64_t i0 = c * kEvalChunk;
+    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
+    for (int t = threadIdx.x; t < cnt * (D + 1); t += kEvalThreads) {
+      const int i = t / (D + 1), f = t % (D + 1);
+      sSrc[buf][t] = (f < D) ? pb.src[(i0 + i) * D + f] : pb.w[i0 + i];
+    }
+  };
+  stage(c_begin, 0);
+  double total = 0.0;
+  for (int64_t c = c_begin; c < c_end; ++c) {
+    const int buf = static_cast<int>((c - c_begin) & 1);
+    __syncthreads();  // chunk c is staged; the other buffer is free again
+    if (c + 1 < c_end) stage(c + 1, buf ^ 1);
+    const int64_t i0 = c * kEvalChunk;
+    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
+    double sum = 0.0;
+    for (int i = 0; i < cnt; ++i) {
+      const double *s = sSrc[buf] + i * (D + 1);
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const double d = x[k] - s[k];
+        acc = fma(d * d, nhib[k], acc);
+      }
+      double v = s[D] * exp_nonpos(acc, sExpTab);  // acc <= 0
+      if (pb.loo && i0 + i == q) v = 0.0;  // leave-one-out: skip the self term (:141)
+      sum += v;
+    }
+    total += sum;
+  }
+  if (q < pb.Nq) pb.partial[grp * pb.Nq + q] = total;
+}
+
+// eval_finish_kernel's p, then W log p and the block's share (items [0, n), item i owns blocks [first[i], first[i+1]))
+__global__ __launch_bounds__(kLoglThreads) void logl_finish_kernel(const LoglItem *__restrict__ items,
+                                                                   const int32_t *__restrict__ first, int n) {
+  __shared__ double red[kLoglThreads];
+  const int b = static_cast<int>(blockIdx.x);
+  const int i = item_of_block(first, n, b);
+  const LoglItem it = items[i];
+  const int fb = b - first[i];
+  const int64_t q = static_cast<int64_t>(fb) * kLoglThreads + threadIdx.x;
+  double norm = it.norm0;  // gauss_norm: (2 pi)^(D/2) * prod_k sqrt(bw_k), the same roundings in the same order
+  for (int k = 0; k < it.D; ++k) norm *= __dsqrt_rn(it.bw[k]);
+  const double inv_norm = 1.0 / norm;
+  double term = 0.0;
+  int zero = 0;
+  if (q < it.Nq) {
+    double s = 0.0;
+    for (int c = 0; c < it.ngroups; ++c) s += it.partial[static_cast<int64_t>(c) * it.Nq + q];
+    double p = s * inv_norm;
+    if (it.loo) p = p / (1.0 - it.w[q]);
+    if (it.out) {
+      const int64_t o = it.perm ? it.perm[q] - 1 : q;
+      if (o >= 0 && o < it.Nq) it.out[o] = p;  // (an uploaded density's permutation is the caller's)
+    }
+    if (it.qw) {  // evalAvgLogL (:456-466): L == 0 counts as 1 when its weight is 0, and makes the result -Inf otherwise
+      const double W = it.qw[q];
+      if (p == 0.0) { zero = W != 0.0; p = 1.0; }
+      term = log(p) * W;
+    }
+  }
+  if (!it.logl) return;  // (block-uniform)
+  red[threadIdx.x] = term;
+  const int anyzero = __syncthreads_or(zero);
+  for (int off = kLoglThreads / 2; off > 0; off >>= 1) {
+    if (static_cast<int>(threadIdx.x) < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    it.bpart[fb] = red[0];
+    it.bzero[fb] = anyzero;
+  }
+}
+
+// one thread per item: the block shares in block order
+__global__ void logl_reduce_kernel(const LoglItem *__restrict__ items, int n) {
+  const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const LoglItem it = items[i];
+  if (!it.logl) return;
+  double s = 0.0;
+  int zero = 0;
+  for (int b = 0; b < it.nfb; ++b) {
+    s += it.bpart[b];
+    zero |= it.bzero[b];
+  }
+  *it.logl = zero ? -INFINITY : s;
+}
+
+template <int D>
+void launch_logl_partial(const LoglItem *d_items, const int32_t *d_first, int n, int blocks, hipStream_t st) {
+  hipLaunchKernelGGL(logl_partial_kernel<D>, dim3(static_cast<unsigned>(blocks)), dim3(kEvalThreads), 0, st, d_items,
+                     d_first, n);
+}
+int launch_logl_partial_dims(int D, const LoglItem *d_items, const int32_t *d_first, int n, int blocks, hipStream_t st) {
+  switch (D) {
+    case 1: launch_logl_partial<1>(d_items, d_first, n, blocks, st); break;
+    case 2: launch_logl_partial<2>(d_items, d_first, n, blocks, st); break;
+    case 3: launch_logl_partial<3>(d_items, d_first, n, blocks, st); break;
+    case 4: launch_logl_partial<4>(d_items, d_first, n, blocks, st); break;
+    case 5: launch_logl_partial<5>(d_items, d_first, n, blocks, st); break;
+    case 6: launch_logl_partial<6>(d_items, d_first, n, blocks, st); break;
+    case 7: launch_logl_partial<7>(d_items, d_first, n, blocks, st); break;
+    case 8: launch_logl_partial<8>(d_items, d_first, n, blocks, st); break;
+    default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  }
+  KDEHIP_CHECK(hipGetLastError());
+  return KDEHIP_OK;
+}
+
+// The blocks of one call: ONE device block [caller's data | descriptors | first[] | results | per item: partial, shares,
+// flags] and ONE pinned image of everything up to the results, which goes up in one copy.  Protocol: fill `items` (sizes,
+// D, loo, what to compute) -> alloc(prefix bytes of caller data) -> the caller writes its data into host() and points the
+// items at dev() -> enqueue(stream) -> wait() (blocking calls) or defer(stream) (enqueue-only calls).
+class LoglRun {
+ public:
+  std::vector<LoglItem> items;
+  ~LoglRun() {
+    if (armed_) (void)hipStreamSynchronize(st_);  // (an error return after launches: nothing goes back to a cache in use)
+    if (d_) cached_free(d_, dbytes_);
+    if (h_) cached_host_free(h_, hbytes_);
+  }
+  int alloc(size_t prefix) {
+    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+    const size_t n = items.size();
+    int64_t pblocks = 0, fblocks = 0;
+    for (LoglItem &it : items) {
+      const GroupSplit gs = split_chunks(it.N, it.Nq, 1);
+      it.chunks_per_group = gs.chunks_per_group;
+      it.ngroups = it.Nq > 0 ? gs.ngroups : 0;
+      it.nfb = static_cast<int32_t>((it.Nq + kLoglThreads - 1) / kLoglThreads);
+      pblocks += ((it.Nq + kEvalThreads - 1) / kEvalThreads) * it.ngroups;
+      fblocks += it.nfb;
+    }
+    if (pblocks > INT32_MAX || fblocks > INT32_MAX) return set_error(KDEHIP_ERR_UNSUPPORTED, "evaluation too large for one launch");
+    o_items_ = al(prefix);
+    o_first_ = al(o_items_ + sizeof(LoglItem) * n);
+    o_res_ = al(o_first_ + sizeof(int32_t) * 2 * (n + 1));
+    size_t o = al(o_res_ + sizeof(double) * n);
+    scratch_.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      const LoglItem &it = items[k];
+      scratch_[k] = o;
+      o = al(o + sizeof(double) * (it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
+    }
+    dbytes_ = o;
+    hbytes_ = o_res_ + sizeof(double) * n;
+    KDEHIP_CHECK(cached_malloc(&d_, dbytes_));
+    KDEHIP_CHECK(cached_host_malloc(&h_, hbytes_));
+    return KDEHIP_OK;
+  }
+  unsigned char *dev() const { return static_cast<unsigned char *>(d_); }
+  unsigned char *host() const { return static_cast<unsigned char *>(h_); }
+  double *result(size_t k) const { return reinterpret_cast<double *>(dev() + o_res_) + k; }  // (device) an item's own result slot
+  double *host_result(size_t k) const { return reinterpret_cast<double *>(host() + o_res_) + k; }
+
+  // scratch pointers, descriptors sorted by D, one upload, the launches -- all on `st`
+  int enqueue(hipStream_t st) {
+    st_ = st;
+    const size_t n = items.size();
+    for (size_t k = 0; k < n; ++k) {
+      LoglItem &it = items[k];
+      unsigned char *s = dev() + scratch_[k];
+      it.partial = reinterpret_cast<double *>(s);
+      it.bpart = it.partial + static_cast<int64_t>(it.ngroups) * it.Nq;
+      it.bzero = reinterpret_cast<int32_t *>(it.bpart + it.nfb);
+    }
+    std::stable_sort(items.begin(), items.end(), [](const LoglItem &a, const LoglItem &b) { return a.D < b.D; });
+    int32_t *pfirst = reinterpret_cast<int32_t *>(host() + o_first_), *ffirst = pfirst + (n + 1);
+    pfirst[0] = ffirst[0] = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const LoglItem &it = items[k];
+      pfirst[k + 1] = pfirst[k] + static_cast<int32_t>(((it.Nq + kEvalThreads - 1) / kEvalThreads) * it.ngroups);
+      ffirst[k + 1] = ffirst[k] + it.nfb;
+    }
+    if (n) std::memcpy(host() + o_items_, items.data(), sizeof(LoglItem) * n);
+    armed_ = true;
+    KDEHIP_CHECK(hipMemcpyAsync(d_, h_, o_res_, hipMemcpyHostToDevice, st));
+    const LoglItem *d_items = reinterpret_cast<const LoglItem *>(dev() + o_items_);
+    const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 1);
+    for (size_t a = 0; a < n;) {  // one launch per distinct D
+      size_t e = a;
+      while (e < n && items[e].D == items[a].D) ++e;
+      const int blocks = pfirst[e] - pfirst[a];
+      if (blocks > 0) {
+        const int rc = launch_logl_partial_dims(items[a].D, d_items + a, d_pfirst + a, static_cast<int>(e - a), blocks, st);
+        if (rc != KDEHIP_OK) return rc;
+      }
+      a = e;
+    }
+    if (ffirst[n] > 0)
+      hipLaunchKernelGGL(logl_finish_kernel, dim3(static_cast<unsigned>(ffirst[n])), dim3(kLoglThreads), 0, st, d_items,
+                         d_ffirst, static_cast<int>(n));
+    if (n) hipLaunchKernelGGL(logl_reduce_kernel, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, st, d_items,
+                              static_cast<int>(n));
+    KDEHIP_CHECK(hipGetLastError());
+    return KDEHIP_OK;
+  }
+  // blocking calls: the n results of the items' own slots come back to host_result()
+  int wait(bool fetch_results) {
+    const size_t n = items.size();
+    hipError_t e = hipSuccess;
+    if (fetch_results && n) e = hipMemcpyAsync(host_result(0), result(0), sizeof(double) * n, hipMemcpyDeviceToHost, st_);
+    const hipError_t se = hipStreamSynchronize(st_);
+    armed_ = false;
+    KDEHIP_CHECK(e);
+    KDEHIP_CHECK(se);
+    return KDEHIP_OK;
+  }
+  // enqueue-only calls: both blocks go back once the work on the stream is done
+  int defer(int device) {
+    const int rc = release_after(device, d_, dbytes_, h_, hbytes_, st_);
+    d_ = h_ = nullptr;
+    armed_ = false;
+    return rc;
+  }
+
+ private:
+  void *d_ = nullptr, *h_ = nullptr;
+  size_t dbytes_ = 0, hbytes_ = 0, o_items_ = 0, o_first_ = 0, o_res_ = 0;
+  std::vector<size_t> scratch_;
+  hipStream_t st_ = nullptr;
+  bool armed_ = false;
+};
+
+// evaluateDualTree reads ONE bandwidth vector (bandwidthMin[1..D], BallTreeDensity01.jl:98): a resident density qualifies when
+// its all-leaf frontier (level Lown) shares its first node's -- the flag the upload / the builders set (examine_frontiers)
+bool leaves_share_bandwidth(const kdehip_device_density *h) {
+  const Frontiers &fr = h->fr;
+  const size_t L = static_cast<size_t>(h->Lown);
+  return fr.uniform.size() > L && fr.off.size() > L + 1 && fr.uniform[L] && fr.off[L + 1] - fr.off[L] == h->N;
+}
+
+// the checks every resident entry makes; `at` may be bd
+int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at, int loo) {
+  if (!bd || !at) return set_error(KDEHIP_ERR_ARG, "null density");
+  if (loo && at != bd) return set_error(KDEHIP_ERR_ARG, "leave_one_out needs at == bd");
+  if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  if (at->D != bd->D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "evaluate -- dimensions of two BallTreeDensities must match");
+  if (at->device != bd->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
+  if (!leaves_share_bandwidth(bd))
+    return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  return KDEHIP_OK;
+}
+
+// bd at at's leaf points (tree order; out, if any, through at's permutation), W = at's leaf weights
+LoglItem pair_item(const kdehip_device_density *bd, const kdehip_device_density *at, int loo, bool logl) {
+  LoglItem it{};
+  const int64_t N = bd->N, Nq = at->N;
+  const int D = bd->D;
+  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
+  it.qry = at->means + Nq * D;
+  it.qw = logl ? at->weights + Nq : nullptr;
+  it.perm = at->perm + Nq;
+  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.N = N; it.Nq = Nq; it.D = D; it.loo = loo ? 1 : 0;
+  return it;
+}
+
+}  // namespace
+
+extern "C" int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
+                                    int device) {
+  // every check that needs no device comes first
+  if (!bd || !out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  if (leave_one_out && at && at != bd) return set_error(KDEHIP_ERR_ARG, "leave_one_out needs at == bd (or at == NULL)");
+  if (!leave_one_out && !at) return set_error(KDEHIP_ERR_ARG, "null argument");
+  if (!at) at = bd;
+  const int64_t D = bd->ndim, N = bd->npts, Nq = at->npts;
+  if (D > KDEHIP_MAX_DIMS || at->ndim > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims above KDEHIP_MAX_DIMS");
+  if (D < 1 || at->ndim < 1) return set_error(KDEHIP_ERR_ARG, "density with no dimensions");
+  if (at->ndim != D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "evaluate -- dimensions of two BallTreeDensities must match");
+  if (N < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation) return set_error(KDEHIP_ERR_ARG, "malformed density");
+  if (Nq < 0 || (Nq > 0 && (!at->means || !at->weights))) return set_error(KDEHIP_ERR_ARG, "malformed density");
+  const double *bw = bd->bandwidth + N * D;
+  for (int64_t i = 0; i < N; ++i)
+    for (int k = 0; k < D; ++k)
+      if (bd->bandwidth[(N + i) * D + k] != bw[k])
+        return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  DeviceGuard guard;
+  int rc = guard.enter(device);
+  if (rc != KDEHIP_OK) return rc;
+  hipStream_t st = hipStreamPerThread;
+  const bool self = at == bd;
+  // caller data: [bd leaf means | bd leaf weights | bd leaf bandwidth | at leaf means | at leaf weights] (at == bd: none)
+  const size_t o_w = sizeof(double) * N * D, o_bw = o_w + sizeof(double) * N, o_q = o_bw + sizeof(double) * D;
+  const size_t o_qw = o_q + (self ? 0 : sizeof(double) * Nq * D), prefix = o_qw + (self ? 0 : sizeof(double) * Nq);
+  LoglRun run;
+  LoglItem it{};
+  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.N = N; it.Nq = Nq; it.D = static_cast<int32_t>(D); it.loo = leave_one_out ? 1 : 0;
+  run.items.push_back(it);
+  KDEHIP_CHECK_RC(run.alloc(prefix));
+  unsigned char *h = run.host(), *d = run.dev();
+  std::memcpy(h, bd->means + N * D, sizeof(double) * N * D);
+  std::memcpy(h + o_w, bd->weights + N, sizeof(double) * N);
+  std::memcpy(h + o_bw, bw, sizeof(double) * D);
+  if (!self) {
+    std::memcpy(h + o_q, at->means + Nq * D, sizeof(double) * Nq * D);
+    std::memcpy(h + o_qw, at->weights + Nq, sizeof(double) * Nq);
+  }
+  LoglItem &ri = run.items[0];
+  ri.src = reinterpret_cast<const double *>(d);
+  ri.w = reinterpret_cast<const double *>(d + o_w);
+  ri.bw = reinterpret_cast<const double *>(d + o_bw);
+  ri.qry = self ? ri.src : reinterpret_cast<const double *>(d + o_q);
+  ri.qw = self ? ri.w : reinterpret_cast<const double *>(d + o_qw);
+  ri.logl = run.result(0);
+  KDEHIP_CHECK_RC(run.enqueue(st));
+  KDEHIP_CHECK_RC(run.wait(true));
+  *out = *run.host_result(0);
+  return KDEHIP_OK;
+}
+
+extern "C" int kdehip_eval_avg_logl_device_batch(int n, const kdehip_logl_item *items, double *d_out, void *stream) {
+  if (n < 0 || (n > 0 && (!items || !d_out))) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: bad item list");
+  if (n == 0) return KDEHIP_OK;
+  for (int i = 0; i < n; ++i) {
+    const int rc = check_pair(items[i].bd, items[i].at, items[i].leave_one_out);
+    if (rc != KDEHIP_OK) return rc;
+    if (items[i].bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: densities on different devices");
+  }
+  const int device = items[0].bd->device;
+  DeviceGuard guard;
+  int rc = guard.enter(device);
+  if (rc != KDEHIP_OK) return rc;
+  LoglRun run;
+  for (int i = 0; i < n; ++i) {
+    run.items.push_back(pair_item(items[i].bd, items[i].at, items[i].leave_one_out, true));
+    run.items.back().logl = d_out + i;
+  }
+  KDEHIP_CHECK_RC(run.alloc(0));
+  KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
+  return run.defer(device);
+}
+
+extern "C" int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                           double *out) {
+  if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  int rc = check_pair(bd, at, leave_one_out);
+  if (rc != KDEHIP_OK) return rc;
+  DeviceGuard guard;
+  rc = guard.enter(bd->device);
+  if (rc != KDEHIP_OK) return rc;
+  LoglRun run;
+  run.items.push_back(pair_item(bd, at, leave_one_out, true));
+  KDEHIP_CHECK_RC(run.alloc(0));
+  run.items[0].logl = run.result(0);
+  KDEHIP_CHECK_RC(run.enqueue(hipStreamPerThread));
+  KDEHIP_CHECK_RC(run.wait(true));
+  *out = *run.host_result(0);
+  return KDEHIP_OK;
+}
+
+extern "C" int kdehip_evaluate_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,
+                                      double *d_out, void *stream) {
+  if (!bd || !d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  if (leave_one_out) return kdehip_evaluate_device_at(bd, bd, d_out, stream);
+  if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
+  int rc = check_pair(bd, bd, 0);
+  if (rc != KDEHIP_OK) return rc;
+  if (Nq == 0) return KDEHIP_OK;
+  DeviceGuard guard;
+  rc = guard.enter(bd->device);
+  if (rc != KDEHIP_OK) return rc;
+  LoglRun run;
+  LoglItem it = pair_item(bd, bd, 0, false);
+  it.qry = d_pos; it.perm = nullptr; it.Nq = Nq; it.out = d_out;
+  run.items.push_back(it);
+  KDEHIP_CHECK_RC(run.alloc(0));
+  KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
+  return run.defer(bd->device);
+}
+
+extern "C" int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out,
+                                         void *stream) {
+  if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  int rc = check_pair(bd, at, at == bd);
+  if (rc != KDEHIP_OK) return rc;
+  DeviceGuard guard;
+  rc = guard.enter(bd->device);
+  if (rc != KDEHIP_OK) return rc;
+  LoglRun run;
+  LoglItem it = pair_item(bd, at, at == bd, false);
+  it.out = d_out;
+  run.items.push_back(it);
+  KDEHIP_CHECK_RC(run.alloc(0));
+  KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
+  return run.defer(bd->device);
+}

@@ -361,6 +361,7 @@ struct PendingDesc {
   hipEvent_t done = nullptr;
   void *d = nullptr, *h = nullptr;
   size_t bytes = 0;
+  size_t hbytes = 0;  // (0: the pinned block has `bytes` too)
   int device = 0;
 };
 std::mutex g_desc_mu;
@@ -369,7 +370,7 @@ std::vector<PendingDesc> g_desc;
 void release_desc(PendingDesc &p) {
   if (p.done) (void)hipEventDestroy(p.done);
   if (p.d) cached_free(p.d, p.bytes);
-  if (p.h) cached_host_free(p.h, p.bytes);
+  if (p.h) cached_host_free(p.h, p.hbytes ? p.hbytes : p.bytes);
 }
 // (the device is current) releases every finished entry of `device`; all = wait for the unfinished ones too
 void reap_desc(int device, bool all) {
@@ -391,6 +392,24 @@ void reap_desc(int device, bool all) {
 bool weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }
 
 }  // namespace
+
+int kdehip::release_after(int device, void *d, size_t dbytes, void *h, size_t hbytes, void *stream) {
+  reap_desc(device, false);
+  PendingDesc pd;
+  pd.device = device;
+  pd.d = d; pd.bytes = dbytes ? dbytes : 1;
+  pd.h = h; pd.hbytes = hbytes ? hbytes : 1;
+  hipError_t e = hipEventCreateWithFlags(&pd.done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(pd.done, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
+    release_desc(pd);
+    return set_error(KDEHIP_ERR_HIP, std::string("release_after: ") + hipGetErrorString(e));
+  }
+  std::lock_guard<std::mutex> lock(g_desc_mu);
+  g_desc.push_back(pd);
+  return KDEHIP_OK;
+}
 
 void kdehip::drain_sample_pending() {
   int n = 0;

@@ -449,6 +449,39 @@ function hip_resample(p::BallTreeDensity, Np::Int=-1, ksType::Symbol=:lcv; seed:
 end
 
 """
+    hip_evalAvgLogL(bd1, bd2; device=0)
+
+`evalAvgLogL(bd1, bd2)` (src/DualTree01.jl:450-470) on the GPU (`kdehip_eval_avg_logl`, include/kdehip.h section 5b):
+sum over bd2's points of W log L, L = bd1 at those points by the direct sum, -Inf when an L == 0 carries weight.
+Leave-one-out when `bd1 === bd2`, as the reference's `bd == locations` decides it.  Not installed by `enable!()`.
+"""
+function hip_evalAvgLogL(bd1::BallTreeDensity, bd2::BallTreeDensity; device::Int=0)
+  Ndim(bd1) == Ndim(bd2) || error("evaluate -- dimensions of two BallTreeDensities must match")
+  loo = bd1 === bd2
+  c1 = Ref(CDensity(bd1))
+  c2 = loo ? c1 : Ref(CDensity(bd2))
+  out = Ref{Float64}(0.0)
+  GC.@preserve bd1 bd2 begin
+    check(ccall((:kdehip_eval_avg_logl, libkdehip), Cint, (Ref{CDensity}, Ref{CDensity}, Cint, Ptr{Float64}, Cint),
+                c1, c2, loo ? 1 : 0, out, device))
+  end
+  return out[]
+end
+
+"`entropy(bd)` (src/DualTree01.jl:505-508) = -hip_evalAvgLogL(bd, bd)."
+hip_entropy(bd::BallTreeDensity; device::Int=0) = -hip_evalAvgLogL(bd, bd; device=device)
+
+"`kld(p1, p2; method=:direct)` (src/DualTree01.jl:477-503) = hip_evalAvgLogL(p1, p1) - hip_evalAvgLogL(p2, p1)."
+function hip_kld(p1::BallTreeDensity, p2::BallTreeDensity; method::Symbol=:direct, device::Int=0)
+  method == :direct || error("hip_kld: only method = :direct is supported")
+  return hip_evalAvgLogL(p1, p1; device=device) - hip_evalAvgLogL(p2, p1; device=device)
+end
+
+"`minkld(p, q)` (src/DualTree01.jl:510) = min(|kld(p, q)|, |kld(q, p)|)."
+hip_minkld(p::BallTreeDensity, q::BallTreeDensity; device::Int=0) =
+  min(abs(hip_kld(p, q; device=device)), abs(hip_kld(q, p; device=device)))
+
+"""
     kde!(points)
 
 `kde!(points)` (src/KDE01.jl:3-27) in ONE library call (`kdehip_make_density_auto`): the per-dimension LOOCV bandwidth is

@@ -1,0 +1,110 @@
+"""Log-likelihoods of one density at another's points: `evalAvgLogL`, `entropy`, `kld`, `minkld` (reference
+src/DualTree01.jl:450-510), and evaluation of resident densities, over kdehip_eval_avg_logl / kdehip_eval_avg_logl_device /
+kdehip_eval_avg_logl_device_batch / kdehip_evaluate_device / kdehip_evaluate_device_at (include/kdehip.h section 5b;
+kernels in csrc/evaluate.hip).
+
+Leave-one-out is decided by identity, as in the reference (`bd == locations` on a mutable struct, :333): evalAvgLogL(p, p)
+skips the self terms, evalAvgLogL(p, copy_of_p) does not -- so kld(p, p) is not 0.  Both arguments are BallTreeDensity
+(host arrays, evaluated on `device`) or both DeviceDensity (on their own device); mixing the two is a TypeError.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .density import BallTreeDensity
+
+
+def _kind(bd1, bd2):
+    from .product import DeviceDensity
+    if isinstance(bd1, BallTreeDensity) and isinstance(bd2, BallTreeDensity):
+        return "host"
+    if isinstance(bd1, DeviceDensity) and isinstance(bd2, DeviceDensity):
+        return "device"
+    raise TypeError("both densities must be BallTreeDensity, or both DeviceDensity")
+
+
+def _dims(d):
+    return d.bt.dims if isinstance(d, BallTreeDensity) else d.dims
+
+
+def evalAvgLogL(bd1, bd2, *, device=0) -> float:
+    """`evalAvgLogL(bd1, bd2)` (src/DualTree01.jl:450-470): sum over bd2's points of W log L, L = bd1 at those points
+    (leave-one-out when `bd1 is bd2`), W = bd2's weights; -inf when an L == 0 carries weight."""
+    kind = _kind(bd1, bd2)
+    if _dims(bd1) != _dims(bd2):
+        raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
+    out = C.c_double(0.0)
+    loo = 1 if bd1 is bd2 else 0
+    if kind == "host":
+        c1 = bd1._cstruct()
+        c2 = c1 if loo else bd2._cstruct()
+        _lib.check(_lib.lib.kdehip_eval_avg_logl(C.byref(c1), C.byref(c2), loo, C.byref(out), int(device)))
+    else:
+        _lib.check(_lib.lib.kdehip_eval_avg_logl_device(bd1._h, bd2._h, loo, C.byref(out)))
+    return float(out.value)
+
+
+def entropy(bd, *, device=0) -> float:
+    """`entropy(bd)` (src/DualTree01.jl:505-508) = -evalAvgLogL(bd, bd)."""
+    return -evalAvgLogL(bd, bd, device=device)
+
+
+def kld(p1, p2, method="direct", *, device=0) -> float:
+    """`kld(p1, p2; method=:direct)` (src/DualTree01.jl:477-503) = evalAvgLogL(p1, p1) - evalAvgLogL(p2, p1)."""
+    if method != "direct":
+        raise ValueError(f"kld: method {method!r} is not supported (only 'direct'; the reference's 'unscented' builds "
+                         "overlapping sigma-point blocks)")
+    _kind(p1, p2)
+    if _dims(p1) != _dims(p2):
+        raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
+    return evalAvgLogL(p1, p1, device=device) - evalAvgLogL(p2, p1, device=device)
+
+
+def minkld(p, q, *, device=0) -> float:
+    """`minkld(p, q)` (src/DualTree01.jl:510) = min(|kld(p, q)|, |kld(q, p)|)."""
+    return min(abs(kld(p, q, device=device)), abs(kld(q, p, device=device)))
+
+
+def eval_avg_logl_device_batch(pairs, d_out, stream=None):
+    """evalAvgLogL of many (bd, at) DeviceDensity pairs in ONE call (kdehip_eval_avg_logl_device_batch): d_out[i] (a
+    float64 device tensor or address of len(pairs) doubles) = evalAvgLogL(bd_i, at_i), leave-one-out where `bd_i is
+    at_i`.  Enqueues on `stream` and returns."""
+    from .product import DeviceDensity, ProductPlan
+    pairs = list(pairs)
+    n = len(pairs)
+    arr = (_lib.CLoglItem * max(1, n))()
+    for k, (bd, at) in enumerate(pairs):
+        if not (isinstance(bd, DeviceDensity) and isinstance(at, DeviceDensity)):
+            raise TypeError("eval_avg_logl_device_batch: pairs of DeviceDensity")
+        arr[k].bd, arr[k].at, arr[k].leave_one_out = bd._h, at._h, 1 if bd is at else 0
+    _lib.check(_lib.lib.kdehip_eval_avg_logl_device_batch(n, arr, ProductPlan._addr(d_out), ProductPlan._addr(stream)))
+
+
+def kld_batch(pairs):
+    """kld(p_i, q_i) for many DeviceDensity pairs: ONE batch call of 2n items (evalAvgLogL(p, p), evalAvgLogL(q, p) per
+    pair), one synchronisation; returns a numpy array of n values, each bit for bit `kld(p_i, q_i)`."""
+    from .product import DeviceDensity
+    pairs = [(p, q) for p, q in pairs]
+    n = len(pairs)
+    if n == 0:
+        return np.zeros(0)
+    for p, q in pairs:
+        if not (isinstance(p, DeviceDensity) and isinstance(q, DeviceDensity)):
+            raise TypeError("kld_batch: pairs of DeviceDensity")
+        if p.dims != q.dims:
+            raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
+    import torch
+    dev = torch.device("cuda", pairs[0][0].device)
+    items = []
+    for p, q in pairs:
+        items += [(p, p), (q, p)]
+    out = torch.empty(2 * n, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev)
+        eval_avg_logl_device_batch(items, out, stream=st.cuda_stream)
+        st.synchronize()
+    v = out.cpu().numpy()
+    return v[0::2] - v[1::2]

@@ -259,6 +259,48 @@ class DeviceDensity:
     def __mul__(self, other):
         return mul_device([self, other])
 
+    def evaluate(self, pos=None, lvFlag=False):
+        """`evaluateDualTree(bd, pos, lvFlag)` (reference src/DualTree01.jl:370-421, FORCE_EVAL_DIRECT) on the device
+        (kdehip_evaluate_device / kdehip_evaluate_device_at): every value is bit for bit what `evaluateDualTree` gives on the
+        density's host arrays.  `pos`: a (D, Nq) numpy array -- values in query order, as a numpy array --, a float64 (D, Nq)
+        torch tensor on the density's device -- a device tensor, enqueued on the current torch stream --, or a DeviceDensity
+        -- values at its points in ITS original order (getPoints order), as a numpy array.  `pos is self` or lvFlag=True:
+        leave-one-out at the density's own points, original order."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if lvFlag:
+            pos = self
+        if pos is None:
+            raise TypeError("evaluate: pos is required unless lvFlag=True")
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            if isinstance(pos, DeviceDensity):
+                if pos.dims != self.dims:
+                    raise ValueError("bd and pos must have the same dimension")
+                out = torch.empty(max(1, pos.num_points), dtype=torch.float64, device=dev)
+                _lib.check(_lib.lib.kdehip_evaluate_device_at(self._h, pos._h, ProductPlan._addr(out), ProductPlan._addr(st.cuda_stream)))
+                st.synchronize()
+                return out.cpu().numpy()[:pos.num_points].copy()
+            tensor = hasattr(pos, "data_ptr")
+            P = pos if tensor else np.asarray(pos, dtype=np.float64)
+            if P.ndim == 1:
+                P = P.reshape(1, -1)
+            if P.shape[0] != self.dims:
+                raise ValueError("bd and pos must have the same dimension")
+            Nq = int(P.shape[1])
+            # column-major D x Nq = the (Nq, D) row-major array
+            flat = P.t().contiguous().to(dev, torch.float64) if tensor else torch.from_numpy(np.ascontiguousarray(P.T)).to(dev)
+            out = torch.empty(max(1, Nq), dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib.kdehip_evaluate_device(self._h, ProductPlan._addr(flat), Nq, 0, ProductPlan._addr(out),
+                                                       ProductPlan._addr(st.cuda_stream)))
+            if tensor:
+                return out[:Nq]
+            st.synchronize()
+            return out.cpu().numpy()[:Nq].copy()
+
+    def __call__(self, pos=None, lvFlag=False):
+        return self.evaluate(pos, lvFlag)
+
     def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None):
         """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):
         d_pts float64[D*Npts] (column-major D x Npts), d_ind int64[Npts] (1-based original indices), `ind` an optional
