@@ -548,6 +548,76 @@ int kdehip_evaluate_device(const kdehip_device_density *bd, const double *d_pos,
  * its permutation, as getPoints orders them); enqueue only on `stream`. */
 int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out, void *stream);
 
+/* ---- (5c) summaries: marginal, getKDERange, getKDEMax, getKDEMean, getKDEfit, intersIntgAppxIS -------------------------
+ * The calls a belief-propagation host makes after a solve (src/KDE01.jl:143-153, src/DualTree01.jl:512-618), on densities
+ * that live in HBM (and, for getKDEMax / intersIntgAppxIS, on host densities uploaded for the call).  A density's points are
+ * its leaf means (as in 5b); "original order" is getPoints order, through the permutation.  dims are 1-based here (0-based in
+ * the Python mirror).  Only the Euclidean operators exist: the reference's addop / diffop arguments of these functions (and
+ * the circular semantics of the tree build, the bandwidth search and the evaluation they would need) are not supported.
+ *   marginal(p, dims)  = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims], getWeights(p)): size(bandwidth, 2) > 2N is false
+ *                        for the flat arrays, so the bandwidth is that of ORIGINAL point 1; getBW returns sqrt(variance) and
+ *                        kde! squares it again, so the marginal's variance is fl(sqrt(v))^2, not v.  The weights are
+ *                        normalised again as kdehip_make_density normalises them.  Repeated and reordered dims are allowed.
+ *   getKDERange(p, extend) = per dimension lo = min, hi = max over the points, dr = extend * (hi - lo), (lo - dr, hi + dr):
+ *                        D x 2 column-major (the reference's rangeV; range[d] = lo, range[D + d] = hi).  Exact.
+ *   grid(lo, hi, Ngrid) = x_k = lo + k h for k < Ngrid - 1, h = (hi - lo) / (Ngrid - 1), x_{Ngrid-1} = hi, every operation
+ *                        rounded on its own (no fused multiply-add); Ngrid >= 2.  Julia's range(lo, stop=hi, length=N) forms
+ *                        its points in double-double arithmetic: the two may differ in the last bit.
+ *   getKDEMax(p, N)    = per dimension i: the 1-D marginal over [i], its range with extend 0.1 (:562 uses the default), that
+ *                        marginal evaluated on the grid by the direct sum (FORCE_EVAL_DIRECT), and x_k of the FIRST k with the
+ *                        maximum value (findfirst(isequal(maximum(y)), y): a NaN wins).  The grid values are those of the
+ *                        marginal density -- weights w_i / S (S = the weights' total, summed in a fixed tree), variance
+ *                        fl(sqrt(v_1))^2, norm sqrt(2 pi) sqrt(variance) -- summed over p's leaves in p's tree order, in leaf
+ *                        groups that depend on (N, Ngrid) alone, with the evaluator's exp: not bit-equal to kdehip_evaluate on a
+ *                        host-built marginal (whose leaf order differs), within about 1e-13 relative of the exact value (the
+ *                        tests hold them to 1e-12).
+ *   getKDEMean(p)      = Statistics.mean(getPoints(p), dims=2): unweighted; per dimension the sequential left-to-right fp64 sum
+ *                        in original order from +0.0 (Julia's sum(A, dims=2) of a column-major matrix loops over the columns),
+ *                        then / N (current Statistics: result ./= n; older versions scaled by 1//n, which can differ in the
+ *                        last bit).  Bit for bit.
+ *   getKDEfit(p)       = fit(MvNormal, getPoints(p)): the mean above and the covariance (1/N) sum_j (x_j - mu)(x_j - mu)^T, each
+ *                        entry a sequential sum in original order (BLAS's order is not reproducible: a tolerance).
+ *   intersIntgAppxIS(p, q, N) = D = 1 or 2 (others KDEHIP_ERR_UNSUPPORTED, the reference errors); the grid of dimension d is
+ *                        grid(getKDERange(p, 0.3)[d]) (= p's marginal range), dx_d = x_1 - x_0; p and q are evaluated on it by
+ *                        the kernels of kdehip_evaluate (every value bit for bit what kdehip_evaluate returns there).  1-D:
+ *                        0 + (sum_k p_k q_k) dx_1; 2-D: row i is the points (x1_j, x2_i), j = 0..N-1, its sum_j p q in j order,
+ *                        and acc += (dx_1 row_i) dx_2 over the rows in order.  The reference's `sum` is pairwise: a tolerance.
+ * Every entry checks all of its arguments before it touches a device: NULLs, Ngrid < 2 (KDEHIP_ERR_ARG), Ngrid above 2^24
+ * (2^14 for a 2-D intersIntgAppxIS: KDEHIP_ERR_UNSUPPORTED), nsel outside 1..KDEHIP_MAX_DIMS, dims outside 1..D, the
+ * dimensions of p and q (KDEHIP_ERR_DIM_MISMATCH), D above KDEHIP_MAX_DIMS (KDEHIP_ERR_UNSUPPORTED). */
+
+/* marginal of a resident density (the dims gathered on the device, one copy down, the host builder with explicit ks and
+ * weights, the block back up).  The result keeps the host mirror: kdehip_density_download works on it (bw_out = the
+ * marginal's ks).  Blocking, on the calling thread's stream. */
+int kdehip_density_marginal_device(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
+                                   const int32_t *dims);
+/* Summaries of many resident densities (any D and N, one device) in one call, enqueue only on `stream` (hipStream_t, NULL =
+ * the null stream): one moments launch (one workgroup per item), then -- for the items that ask for the grid -- one grid
+ * launch and one argmax launch for all of them.  The grid is grid(getKDERange(p, extend)[d], Ngrid): getKDEMax is extend =
+ * 0.1.  Outputs are device pointers; NULL ones are skipped.  Every item's result is bit for bit what it gets alone. */
+typedef struct kdehip_summary_item {
+  const kdehip_device_density *density;
+  double extend;
+  int64_t Ngrid;       /* >= 2 (also when no grid output is asked for) */
+  double *d_range;     /* 2D: D x 2 column-major, (lo - dr, hi + dr) per dimension */
+  double *d_mean;      /* D */
+  double *d_cov;       /* D*D */
+  double *d_argmax;    /* D: getKDEMax */
+  double *d_values;    /* D*Ngrid: the 1-D marginal over [d] on its grid at [d*Ngrid, (d+1)*Ngrid) */
+} kdehip_summary_item;
+int kdehip_summary_device_batch(int n, const kdehip_summary_item *items, void *stream);
+/* The same for one resident density, host outputs (any may be NULL; values: D*Ngrid), blocking on the calling thread's
+ * stream.  extend: one double, or NULL for the reference's default 0.1. */
+int kdehip_density_summary(const kdehip_device_density *p, const double *extend, int64_t Ngrid, double *range, double *mean,
+                           double *cov, double *argmax, double *values);
+/* getKDEMax of a host density (uploaded for the call), out: D values, grid_values: NULL or D*Ngrid as d_values above.
+ * Blocking.  The same bits as the resident entries on the same density. */
+int kdehip_kde_max(const kdehip_density *p, int64_t Ngrid, double *out, double *grid_values, int device);
+/* intersIntgAppxIS of two host densities (uploaded for the call) / of two resident densities on one device; blocking. */
+int kdehip_inters_intg_appx_is(const kdehip_density *p, const kdehip_density *q, int64_t Ngrid, double *out, int device);
+int kdehip_inters_intg_appx_is_device(const kdehip_device_density *p, const kdehip_device_density *q, int64_t Ngrid,
+                                      double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,12 @@ class CLoglItem(C.Structure):
     _fields_ = [("bd", C.c_void_p), ("at", C.c_void_p), ("leave_one_out", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class CSummaryItem(C.Structure):
+    """struct kdehip_summary_item"""
+    _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
+                ("d_mean", C.c_void_p), ("d_cov", C.c_void_p), ("d_argmax", C.c_void_p), ("d_values", C.c_void_p)]
+
+
 class CProductInfo(C.Structure):
     """struct kdehip_product_info_t"""
     _fields_ = [
@@ -123,6 +129,12 @@ SIGNATURES = {
     "kdehip_eval_avg_logl_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p]),
     "kdehip_evaluate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "kdehip_evaluate_device_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kdehip_density_marginal_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, i32p]),
+    "kdehip_summary_device_batch": (C.c_int, [C.c_int, C.POINTER(CSummaryItem), C.c_void_p]),
+    "kdehip_density_summary": (C.c_int, [C.c_void_p, f64p, C.c_int64, f64p, f64p, f64p, f64p, f64p]),
+    "kdehip_kde_max": (C.c_int, [C.POINTER(CDensity), C.c_int64, f64p, f64p, C.c_int]),
+    "kdehip_inters_intg_appx_is": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int64, f64p, C.c_int]),
+    "kdehip_inters_intg_appx_is_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, f64p]),
     "kdehip_auto_bandwidth": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int]),
     "kdehip_make_density_device_supported": (C.c_int, [C.c_int64, C.c_int64]),
     "kdehip_make_densities_device": (C.c_int, [C.c_int, C.c_int64, i64p] + [C.POINTER(C.c_void_p)] * 2 + [C.c_int64] +

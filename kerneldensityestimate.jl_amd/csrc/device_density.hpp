@@ -122,6 +122,9 @@ struct kdehip_device_density {
 };
 
 namespace kdehip {
+// (evaluate.hip) whether every leaf of a resident density has its first leaf's variances: the one bandwidth vector the
+// direct evaluation reads
+bool leaves_share_bandwidth(const kdehip_device_density *h);
 // kdehip_prod_philox_device with everything -- preparation and sampling -- on ONE stream (product.hip): what a blocking
 // caller that waits for the product anyway uses (kdehip_mul_device).
 int prod_philox_device_blocking_stream(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,

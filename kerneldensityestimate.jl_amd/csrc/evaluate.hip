@@ -1508,13 +1508,17 @@ class LoglRun {
   bool armed_ = false;
 };
 
+}  // namespace
+
 // evaluateDualTree reads ONE bandwidth vector (bandwidthMin[1..D], BallTreeDensity01.jl:98): a resident density qualifies when
 // its all-leaf frontier (level Lown) shares its first node's -- the flag the upload / the builders set (examine_frontiers)
-bool leaves_share_bandwidth(const kdehip_device_density *h) {
+bool kdehip::leaves_share_bandwidth(const kdehip_device_density *h) {
   const Frontiers &fr = h->fr;
   const size_t L = static_cast<size_t>(h->Lown);
   return fr.uniform.size() > L && fr.off.size() > L + 1 && fr.uniform[L] && fr.off[L + 1] - fr.off[L] == h->N;
 }
+
+namespace {
 
 // the checks every resident entry makes; `at` may be bd
 int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at, int loo) {

@@ -302,6 +302,49 @@ __global__ void unpermute_points_kernel(const double *__restrict__ means, const 
   out[(perm[N + i] - 1) * D + k] = means[(N + i) * D + k];
 }
 
+// The layout of a built density's mirror head (device_density.hpp): the device block of a tree of N leaves, whose frontier
+// ids number at most (Lown + 1) * N
+BlockLayout mirror_layout(const kdehip_device_density *h) {
+  return BlockLayout(h->N, h->D, static_cast<size_t>(h->Lown + 1) * static_cast<size_t>(h->N) + 64);
+}
+
+// The reference's twelve arrays of a density the library builds, as the handle's host mirror (kdehip_density_download), in
+// one pinned block whose head is the image of the device block `bl`; h->m points into it
+hipError_t alloc_mirror(kdehip_device_density *h, const BlockLayout &bl) {
+  const size_t nd = static_cast<size_t>(2 * h->N * h->D), n2 = static_cast<size_t>(2 * h->N);
+  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
+  const size_t o_extra = bl.total;  // centers, ranges (nd each), bwmin, bwmax (nd / 2 each), left, right, lowest, highest (n2 each)
+  h->mirror_bytes = al(o_extra + sizeof(double) * (2 * nd + nd) + sizeof(int64_t) * 4 * n2);
+  const hipError_t e = cached_host_malloc(&h->mirror, h->mirror_bytes);
+  if (e != hipSuccess) { h->mirror = nullptr; return e; }
+  unsigned char *mb = static_cast<unsigned char *>(h->mirror);
+  double *means = reinterpret_cast<double *>(mb + bl.o_mean), *bandwidth = reinterpret_cast<double *>(mb + bl.o_bw);
+  double *weights = reinterpret_cast<double *>(mb + bl.o_w);
+  int64_t *perm = reinterpret_cast<int64_t *>(mb + bl.o_perm);
+  double *centers = reinterpret_cast<double *>(mb + o_extra), *ranges = centers + nd, *bwmin = ranges + nd, *bwmax = bwmin + nd / 2;
+  int64_t *left = reinterpret_cast<int64_t *>(bwmax + nd / 2), *right = left + n2, *lowest = right + n2, *highest = lowest + n2;
+  h->m = {centers, ranges, means, bandwidth, bwmin, bwmax, weights, left, right, lowest, highest, perm};
+  return hipSuccess;
+}
+
+// marginal(p, dims) (src/KDE01.jl:143-153) gathers getPoints(p)[dims, :] (nsel x N, column-major), getWeights(p) and the
+// variances of ORIGINAL point 1's leaf (getBW(p, [1]) before its sqrt) into one block: out = [pts | w | var1]
+struct MarginalDims { int32_t d[KDEHIP_MAX_DIMS]; };
+__global__ void gather_marginal_kernel(const double *__restrict__ means, const double *__restrict__ bandwidth,
+                                       const double *__restrict__ weights, const int64_t *__restrict__ perm, int64_t N, int D,
+                                       int nsel, const MarginalDims dims, double *__restrict__ out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= N * nsel) return;
+  const int64_t i = t / nsel;
+  const int s = static_cast<int>(t - i * nsel);
+  const int64_t o = perm[N + i] - 1;
+  if (o < 0 || o >= N) return;  // (an uploaded density's permutation is the caller's)
+  out[o * nsel + s] = means[(N + i) * D + dims.d[s]];
+  if (s == 0) out[N * nsel + o] = weights[N + i];
+  if (s == 0 && o == 0)
+    for (int k = 0; k < D; ++k) out[N * nsel + N + k] = bandwidth[(N + i) * D + k];
+}
+
 }  // namespace
 
 extern "C" int kdehip_density_upload(kdehip_device_density **out, const kdehip_density *host, int device) {
@@ -391,19 +434,12 @@ extern "C" int kdehip_density_from_device_points(kdehip_device_density **out, co
   // The reference's twelve arrays, kept as the handle's host mirror (kdehip_density_download), in one pinned block whose
   // head is the image of the device block (device_density.hpp).  The frontier ids of a tree of N leaves number at most
   // (Lown + 1) * N; the layout reserves that much.
-  const size_t nd = static_cast<size_t>(2 * N * D), n2 = static_cast<size_t>(2 * N);
-  const BlockLayout bl(N, D, static_cast<size_t>(h->Lown + 1) * static_cast<size_t>(N) + 64);
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  const size_t o_extra = bl.total;  // centers, ranges (nd each), bwmin, bwmax (nd / 2 each), left, right, lowest, highest (n2 each)
-  h->mirror_bytes = al(o_extra + sizeof(double) * (2 * nd + nd) + sizeof(int64_t) * 4 * n2);
-  KDEHIP_CHECK(cached_host_malloc(&h->mirror, h->mirror_bytes));
+  const BlockLayout bl = mirror_layout(h);
+  KDEHIP_CHECK(alloc_mirror(h, bl));
   unsigned char *mb = static_cast<unsigned char *>(h->mirror);
-  double *means = reinterpret_cast<double *>(mb + bl.o_mean), *bandwidth = reinterpret_cast<double *>(mb + bl.o_bw);
-  double *weights = reinterpret_cast<double *>(mb + bl.o_w);
-  int64_t *perm = reinterpret_cast<int64_t *>(mb + bl.o_perm);
-  double *centers = reinterpret_cast<double *>(mb + o_extra), *ranges = centers + nd, *bwmin = ranges + nd, *bwmax = bwmin + nd / 2;
-  int64_t *left = reinterpret_cast<int64_t *>(bwmax + nd / 2), *right = left + n2, *lowest = right + n2, *highest = lowest + n2;
-  h->m = {centers, ranges, means, bandwidth, bwmin, bwmax, weights, left, right, lowest, highest, perm};
+  double *means = h->m.means, *bandwidth = h->m.bandwidth, *weights = h->m.weights, *centers = h->m.centers;
+  double *ranges = h->m.ranges, *bwmin = h->m.bwmin, *bwmax = h->m.bwmax;
+  int64_t *perm = h->m.perm, *left = h->m.left, *right = h->m.right, *lowest = h->m.lowest, *highest = h->m.highest;
   const kdehip_density host{N, D, means, bandwidth, weights, left, right, perm};
   double bw[KDEHIP_MAX_DIMS];
   int tree_rc = KDEHIP_OK, side_rc = KDEHIP_OK;
@@ -499,6 +535,72 @@ extern "C" int kdehip_density_from_device_points(kdehip_device_density **out, co
     std::fprintf(stderr, "kdehip_density_from_device_points D=%lld N=%lld: tree built at %.0f us | block prepared at %.0f us | search over at %.0f us | variances %.0f | flags %.0f | staged %.0f | done at %.0f us\n",
                  static_cast<long long>(D), static_cast<long long>(N), us_tree, us_side, us_search, us_setbw, us_exam, us_copy, us());
   cl.s1 = cl.s2 = nullptr;  // (everything has been waited for)
+  cl.h = nullptr;
+  *out = h;
+  return KDEHIP_OK;
+}
+
+// marginal(p, dims) (src/KDE01.jl:143-153) of a resident density = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims],
+// getWeights(p)): the gather kernel above, ONE copy down, the host builder with explicit ks and weights (the path of
+// kdehip_density_from_device_points without the bandwidth search), the block back up.  The sqrt of getBW is the host's.
+extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
+                                              const int32_t *dims) {
+  if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
+  *out = nullptr;
+  if (nsel < 1 || nsel > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_ARG, "marginal: nsel outside 1..KDEHIP_MAX_DIMS");
+  if (!dims) return set_error(KDEHIP_ERR_ARG, "marginal: null dims");
+  if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
+  const int64_t N = p->N;
+  const int D = p->D;
+  int rc = check_shape(N, D);
+  if (rc != KDEHIP_OK) return rc;
+  MarginalDims md{};
+  for (int s = 0; s < nsel; ++s) {
+    if (dims[s] < 1 || dims[s] > D) return set_error(KDEHIP_ERR_ARG, "marginal: dims outside 1..ndims");
+    md.d[s] = dims[s] - 1;
+  }
+  DeviceGuard guard;
+  rc = guard.enter(p->device);
+  if (rc != KDEHIP_OK) return rc;
+  hipStream_t cs = hipStreamPerThread;
+  struct Cleanup {
+    kdehip_device_density *h = nullptr; void *d = nullptr, *pin = nullptr; size_t bytes = 0; hipStream_t st = nullptr;
+    ~Cleanup() {
+      if (st) (void)hipStreamSynchronize(st);
+      if (d) cached_free(d, bytes);
+      if (pin) cached_host_free(pin, bytes);
+      if (h && h->d_blob) cached_free(h->d_blob, h->blob_bytes);
+      if (h && h->mirror) cached_host_free(h->mirror, h->mirror_bytes);
+      delete h;
+    }
+  } cl;
+  cl.bytes = sizeof(double) * (N * nsel + N + D);
+  KDEHIP_CHECK(cached_malloc(&cl.d, cl.bytes));
+  KDEHIP_CHECK(cached_host_malloc(&cl.pin, cl.bytes));
+  cl.st = cs;
+  double *d_blk = static_cast<double *>(cl.d), *blk = static_cast<double *>(cl.pin);
+  hipLaunchKernelGGL(gather_marginal_kernel, dim3(static_cast<unsigned>((N * nsel + 255) / 256)), dim3(256), 0, cs, p->means,
+                     p->bandwidth, p->weights, p->perm, N, D, nsel, md, d_blk);
+  KDEHIP_CHECK(hipGetLastError());
+  KDEHIP_CHECK(hipMemcpyAsync(blk, d_blk, cl.bytes, hipMemcpyDeviceToHost, cs));
+  KDEHIP_CHECK(hipStreamSynchronize(cs));
+  cl.st = nullptr;
+  double ks[KDEHIP_MAX_DIMS];
+  for (int s = 0; s < nsel; ++s) ks[s] = std::sqrt(blk[N * nsel + N + md.d[s]]);  // getBW(p, [1])[dims]
+  kdehip_device_density *h = new (std::nothrow) kdehip_device_density();
+  if (!h) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
+  cl.h = h;
+  h->device = p->device; h->N = N; h->D = nsel; h->Lown = nlevels_for(N);
+  KDEHIP_CHECK(alloc_mirror(h, mirror_layout(h)));
+  const kdehip_device_density::Mirror &m = h->m;
+  rc = kdehip_make_density(nsel, N, blk, ks, nsel, blk + N * nsel, m.centers, m.ranges, m.weights, m.left, m.right, m.lowest,
+                           m.highest, m.perm, m.means, m.bandwidth, m.bwmin, m.bwmax);
+  if (rc != KDEHIP_OK) return rc;
+  for (int s = 0; s < nsel; ++s) h->bw[s] = ks[s];
+  h->built = true;
+  const kdehip_density host{N, nsel, m.means, m.bandwidth, m.weights, m.left, m.right, m.perm};
+  rc = upload_common(h, host, cs);
+  if (rc != KDEHIP_OK) return rc;
   cl.h = nullptr;
   *out = h;
   return KDEHIP_OK;

@@ -482,6 +482,69 @@ hip_minkld(p::BallTreeDensity, q::BallTreeDensity; device::Int=0) =
   min(abs(hip_kld(p, q; device=device)), abs(hip_kld(q, p; device=device)))
 
 """
+    hip_getKDEMax(p; N=200, device=0)
+
+`getKDEMax(p; N)` (src/DualTree01.jl:558-570) on the GPU (`kdehip_kde_max`, include/kdehip.h section 5c): per dimension the
+1-D marginal on the N-point grid over its range with extend 0.1, by the direct sum, and the grid point of the FIRST maximum.
+The grid is lo + k h, each operation rounded on its own, where `range` forms its points in double-double: they may differ
+in the last bit.  Not installed by `enable!()`.
+"""
+function hip_getKDEMax(p::BallTreeDensity; N::Int=200, device::Int=0)
+  m = zeros(Ndim(p))
+  cd = Ref(CDensity(p))
+  GC.@preserve p begin
+    check(ccall((:kdehip_kde_max, libkdehip), Cint, (Ref{CDensity}, Int64, Ptr{Float64}, Ptr{Float64}, Cint),
+                cd, N, m, C_NULL, device))
+  end
+  return m
+end
+
+"The same for a resident density (`kdehip_density_summary`, extend 0.1)."
+function hip_getKDEMax(d::DeviceDensity; N::Int=200)
+  m = zeros(d.ndim)
+  check(ccall((:kdehip_density_summary, libkdehip), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              d.handle, C_NULL, N, C_NULL, C_NULL, C_NULL, m, C_NULL))
+  return m
+end
+
+"""
+    hip_getKDEfit(d::DeviceDensity)
+
+`getKDEfit(p)` (src/DualTree01.jl:574-578) = `fit(MvNormal, getPoints(p))` of a resident density (`kdehip_density_summary`):
+the sequential mean of getKDEMean and the MLE covariance (1/N) sum (x - mu)(x - mu)', summed in original point order.
+A host density: `hip_getKDEfit(DeviceDensity(p))`.  Not installed by `enable!()`.
+"""
+function hip_getKDEfit(d::DeviceDensity)
+  D = d.ndim
+  mu = zeros(D)
+  sig = zeros(D, D)
+  check(ccall((:kdehip_density_summary, libkdehip), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              d.handle, C_NULL, 2, C_NULL, mu, sig, C_NULL, C_NULL))
+  return KDE.MvNormal(mu, sig)
+end
+hip_getKDEfit(p::BallTreeDensity; device::Int=0) = hip_getKDEfit(DeviceDensity(p; device=device))
+
+"""
+    hip_intersIntgAppxIS(p, q; N=201, device=0)
+
+`intersIntgAppxIS(p, q; N)` (src/DualTree01.jl:581-618) for 1-D and 2-D densities (`kdehip_inters_intg_appx_is`): p and q
+evaluated by the direct sum on the grid over p's marginal ranges with extend 0.3, the products summed row by row in order
+(the reference's `sum` is pairwise: equal to a tolerance).  Not installed by `enable!()`.
+"""
+function hip_intersIntgAppxIS(p::BallTreeDensity, q::BallTreeDensity; N::Int=201, device::Int=0)
+  out = Ref{Float64}(0.0)
+  cp = Ref(CDensity(p))
+  cq = Ref(CDensity(q))
+  GC.@preserve p q begin
+    check(ccall((:kdehip_inters_intg_appx_is, libkdehip), Cint, (Ref{CDensity}, Ref{CDensity}, Int64, Ptr{Float64}, Cint),
+                cp, cq, N, out, device))
+  end
+  return out[]
+end
+
+"""
     kde!(points)
 
 `kde!(points)` (src/KDE01.jl:3-27) in ONE library call (`kdehip_make_density_auto`): the per-dimension LOOCV bandwidth is

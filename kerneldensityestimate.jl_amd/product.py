@@ -324,6 +324,17 @@ class DeviceDensity:
         out.bw, out.nevals = bw, int(ne.value)
         return out
 
+    def marginal(self, dims) -> "DeviceDensity":
+        """`marginal(p, dims)` (reference src/KDE01.jl:143-153), dims 0-based, built on this density's device
+        (kdehip_density_marginal_device): the same arrays as the host `marginal` of the same density."""
+        from .summary import _marginal_device
+        return _marginal_device(self, dims)
+
+    def getKDEMax(self, N=200, *, values=False):
+        """`getKDEMax(p; N)` (reference src/DualTree01.jl:558-570) on the device (kdehip_density_summary)."""
+        from .summary import getKDEMax
+        return getKDEMax(self, N, values=values)
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib.kdehip_density_free(self._h)
