@@ -288,6 +288,12 @@ int kdehip_prod_philox_resident(int Ndens, kdehip_device_density *const *trees, 
  * nevals are optional.  N >= 2. */
 int kdehip_density_from_device_points(kdehip_device_density **out, const double *d_points, int64_t D, int64_t N,
                                       int device, void *stream, double *bw_out, int32_t *nevals);
+/* The same with a per-dimension manifold for the bandwidth search (section 5d: only the leave-one-out likelihoods of the
+ * search wrap; the tree is the Euclidean builder's).  manifold == NULL or all zeros is the entry above, bit for bit; bw_out
+ * and nevals are bit for bit kdehip_auto_bandwidth_manifold's for the same points. */
+int kdehip_density_from_device_points_manifold(kdehip_device_density **out, const double *d_points, int64_t D, int64_t N,
+                                               int device, void *stream, double *bw_out, int32_t *nevals,
+                                               const uint8_t *manifold /* D bytes or NULL */);
 /* `*(trees; addEntropy)` (src/MSGibbs01.jl:707-726) on handles: Np = round(mean Npts), Niter = 5, device Philox keyed by
  * `seed`, then kde!(pGM) -- the product matrix never leaves the device; one density with addEntropy = 0 is the reference's
  * shortcut (:713-716: kde! of its own points).  Blocking, on the calling thread's stream.  Same numbers as
@@ -548,12 +554,62 @@ int kdehip_evaluate_device(const kdehip_device_density *bd, const double *d_pos,
  * its permutation, as getPoints orders them); enqueue only on `stream`. */
 int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out, void *stream);
 
+/* ---- (5d) circular dimensions in evaluation, log-likelihoods and the bandwidth search ------------------------------------
+ * The entries of sections 5, 5b and 2d with a trailing per-dimension `manifold` (KDEHIP_MANIFOLD_EUCLIDEAN /
+ * KDEHIP_MANIFOLD_CIRCULAR, ndims bytes or NULL, as kdehip_gibbs1_manifold takes it), at the places where the reference
+ * threads `diffop` (evalDirect -> maxDistKer! -> distGauss!, src/DualTree01.jl:14-47, 130-162; evalAvgLogL / entropy / kld /
+ * minkld, :450-510, as compositions; kde!(points, addop, diffop) -> ksize -> golden -> nLOO_LL -> entropy,
+ * src/KDE01.jl:3-27, src/CrossValidation.jl:15-120) and nowhere deeper.  Semantic, with wrap() of "manifolds" above:
+ *   - in a circular dimension k every difference x_qk - c_ik becomes wrap(x_qk - c_ik) before it is squared -- the ONE fp64
+ *     expression (csrc/circ_wrap.hpp) the sampler, oracle/kde_oracle.c and tests/pymodel.py wrapRad share, divide included,
+ *     same constants.  Nothing else changes: the same -1/(2 bw_k), the same exponential, the same Gaussian normalisation
+ *     (a circular density keeps the Gaussian constant, :325-335), the same division by 1 - w_q for leave-one-out.
+ *   - inputs need not lie in [-pi, pi): the wrap is applied to the difference, any representative works.
+ *   - manifold == NULL or all zeros IS the existing entry, bit for bit (the existing entries forward here with NULL).
+ *   - wrap(t) == t exactly whenever -pi <= t < pi, so a circular call on data in which no pair difference leaves that
+ *     interval returns the Euclidean call's bits: the split of every sum stays a function of (N, Nq) alone (section 5b).
+ *   - a manifold byte other than 0 or 1 is KDEHIP_ERR_ARG, checked before any device is touched.
+ * Bandwidth search: only the leave-one-out likelihoods wrap.  The marginal's sort, neighborMinMax and with it the search
+ * bracket are the Euclidean ones, as in the reference (marginal(p, [i]) and the kde! inside ksize build their 1-D trees with
+ * the default operators), and kdehip_make_density_auto_manifold / kdehip_density_from_device_points_manifold still build the
+ * tree with the Euclidean builder: tree construction on a manifold is not supported.  mul_device, mul_device_batch,
+ * resample and the summaries of 5c stay Euclidean. */
+int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out,
+                             int device, const uint8_t *manifold);
+int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,
+                                    double *d_out, void *stream, const uint8_t *manifold);
+int kdehip_evaluate_device_at_manifold(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out,
+                                       void *stream, const uint8_t *manifold);
+int kdehip_eval_avg_logl_manifold(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
+                                  int device, const uint8_t *manifold);
+int kdehip_eval_avg_logl_device_manifold(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                         double *out, const uint8_t *manifold);
+/* The batch takes a manifold per item, as a mask (bit d = dimension d circular; a bit at or above the item's ndims is
+ * KDEHIP_ERR_ARG).  kdehip_logl_item's reserved_ word was never checked, so it keeps having no meaning:
+ * kdehip_eval_avg_logl_device_batch forwards here with mask 0.  Euclidean and circular items of any D may be mixed; each
+ * result is bit for bit the single call's. */
+typedef struct kdehip_logl_manifold_item {
+  const kdehip_device_density *bd;
+  const kdehip_device_density *at;
+  int32_t leave_one_out;
+  uint32_t circular_mask;
+} kdehip_logl_manifold_item;
+int kdehip_eval_avg_logl_device_batch_manifold(int n, const kdehip_logl_manifold_item *items, double *d_out, void *stream);
+int kdehip_auto_bandwidth_manifold(int64_t D, int64_t N, const double *points, double *bw_out, int32_t *nevals, int device,
+                                   const uint8_t *manifold);
+int kdehip_make_density_auto_manifold(int64_t D, int64_t N, const double *points, double *bw_out, int32_t *nevals, int device,
+                                      double *centers, double *ranges, double *weights, int64_t *left_child,
+                                      int64_t *right_child, int64_t *lowest_leaf, int64_t *highest_leaf, int64_t *permutation,
+                                      double *means, double *bandwidth, double *bandwidthMin, double *bandwidthMax,
+                                      const uint8_t *manifold);
+
 /* ---- (5c) summaries: marginal, getKDERange, getKDEMax, getKDEMean, getKDEfit, intersIntgAppxIS -------------------------
  * The calls a belief-propagation host makes after a solve (src/KDE01.jl:143-153, src/DualTree01.jl:512-618), on densities
  * that live in HBM (and, for getKDEMax / intersIntgAppxIS, on host densities uploaded for the call).  A density's points are
  * its leaf means (as in 5b); "original order" is getPoints order, through the permutation.  dims are 1-based here (0-based in
- * the Python mirror).  Only the Euclidean operators exist: the reference's addop / diffop arguments of these functions (and
- * the circular semantics of the tree build, the bandwidth search and the evaluation they would need) are not supported.
+ * the Python mirror).  Only the Euclidean operators exist HERE: the reference's addop / diffop arguments of these functions
+ * are not supported (their grids would have to be defined on the circle first, and marginal's tree build on a manifold is
+ * not supported either); evaluation, log-likelihoods and the bandwidth search take a manifold in section 5d.
  *   marginal(p, dims)  = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims], getWeights(p)): size(bandwidth, 2) > 2N is false
  *                        for the flat arrays, so the bandwidth is that of ORIGINAL point 1; getBW returns sqrt(variance) and
  *                        kde! squares it again, so the marginal's variance is fl(sqrt(v))^2, not v.  The weights are

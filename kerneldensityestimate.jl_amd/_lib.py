@@ -55,6 +55,11 @@ class CLoglItem(C.Structure):
     _fields_ = [("bd", C.c_void_p), ("at", C.c_void_p), ("leave_one_out", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class CLoglManifoldItem(C.Structure):
+    """struct kdehip_logl_manifold_item"""
+    _fields_ = [("bd", C.c_void_p), ("at", C.c_void_p), ("leave_one_out", C.c_int32), ("circular_mask", C.c_uint32)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -129,6 +134,17 @@ SIGNATURES = {
     "kdehip_eval_avg_logl_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p]),
     "kdehip_evaluate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "kdehip_evaluate_device_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kdehip_evaluate_manifold": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_evaluate_device_manifold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_evaluate_device_at_manifold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_eval_avg_logl_manifold": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_eval_avg_logl_device_manifold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p, u8p]),
+    "kdehip_eval_avg_logl_device_batch_manifold": (C.c_int, [C.c_int, C.POINTER(CLoglManifoldItem), C.c_void_p, C.c_void_p]),
+    "kdehip_auto_bandwidth_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, u8p]),
+    "kdehip_make_density_auto_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p,
+                                                    i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),
+    "kdehip_density_from_device_points_manifold": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int64,
+                                                             C.c_int, C.c_void_p, f64p, i32p, u8p]),
     "kdehip_density_marginal_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, i32p]),
     "kdehip_summary_device_batch": (C.c_int, [C.c_int, C.POINTER(CSummaryItem), C.c_void_p]),
     "kdehip_density_summary": (C.c_int, [C.c_void_p, f64p, C.c_int64, f64p, f64p, f64p, f64p, f64p]),

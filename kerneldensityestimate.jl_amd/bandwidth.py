@@ -8,12 +8,21 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import f64p, ptr
+from ._lib import f64p, ptr, u8p
 from .density import BallTreeDensity, kde
 
 
-def auto_bandwidth(points, device=0, return_evals=False):
-    """Per-dimension LOOCV bandwidth (standard deviations) that `kde!(points)` selects."""
+def _man_ptr(manifold, ndims):
+    """(array kept alive, ctypes pointer or None) of a `manifold=` keyword: None, or one 'euclid' / 'circular' / 0 / 1 per
+    dimension (include/kdehip.h section 5d)"""
+    from .product import _manifold_array
+    man = _manifold_array(manifold, ndims)
+    return man, (None if man is None else ptr(man, u8p))
+
+
+def auto_bandwidth(points, device=0, return_evals=False, manifold=None):
+    """Per-dimension LOOCV bandwidth (standard deviations) that `kde!(points)` selects; `manifold`: the leave-one-out
+    likelihoods of a circular dimension's search take wrapped differences (`kde!(points, addop, diffop)`)."""
     pts = np.asarray(points, dtype=np.float64)
     if pts.ndim == 1:
         pts = pts.reshape(1, -1)
@@ -21,11 +30,12 @@ def auto_bandwidth(points, device=0, return_evals=False):
     flat = np.ascontiguousarray(pts.T).ravel()
     bw = np.zeros(D)
     ne = C.c_int32(0)
-    _lib.check(_lib.lib.kdehip_auto_bandwidth(D, N, ptr(flat, f64p), ptr(bw, f64p), C.byref(ne), int(device)))
+    man, mp = _man_ptr(manifold, D)
+    _lib.check(_lib.lib.kdehip_auto_bandwidth_manifold(D, N, ptr(flat, f64p), ptr(bw, f64p), C.byref(ne), int(device), mp))
     return (bw, ne.value) if return_evals else bw
 
 
-def kde_auto(points, device=0, overlap=None) -> BallTreeDensity:
+def kde_auto(points, device=0, overlap=None, manifold=None) -> BallTreeDensity:
     """`kde!(points)`: LOOCV bandwidth per dimension, then `kde!(points, bwds)` (src/KDE01.jl:24).
 
     The tree's topology, bounding boxes, weights and means do not depend on the bandwidth: the host builder runs on the
@@ -38,31 +48,33 @@ def kde_auto(points, device=0, overlap=None) -> BallTreeDensity:
     D, N = pts.shape
     if overlap is None:
         overlap = True
+    man, mp = _man_ptr(manifold, D)
     if N < 2 or not overlap:
-        return kde(pts, auto_bandwidth(pts, device=device))
+        return kde(pts, auto_bandwidth(pts, device=device, manifold=manifold))
     from .density import _empty_density
     flat = np.ascontiguousarray(pts.T).ravel()
     bd = _empty_density(D, N)
     bt = bd.bt
     bw = np.empty(D)
     i64p = _lib.i64p
-    _lib.check(_lib.lib.kdehip_make_density_auto(
+    _lib.check(_lib.lib.kdehip_make_density_auto_manifold(
         D, N, ptr(flat, f64p), ptr(bw, f64p), None, int(device), ptr(bt.centers, f64p), ptr(bt.ranges, f64p),
         ptr(bt.weights, f64p), ptr(bt.left_child, i64p), ptr(bt.right_child, i64p), ptr(bt.lowest_leaf, i64p),
         ptr(bt.highest_leaf, i64p), ptr(bt.permutation, i64p), ptr(bd.means, f64p), ptr(bd.bandwidth, f64p),
-        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p)))
+        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), mp))
     return bd
 
 
-def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, device=0):
+def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, device=0, manifold=None):
     """`evaluateDualTree(bd, pos, lvFlag)` (src/DualTree01.jl:370-421) with FORCE_EVAL_DIRECT = true
     (errTol is then unused, as in the reference).  pos: (D, Nq) matrix, a vector of 1-D positions, or a
     BallTreeDensity whose points are used; lvFlag=True (or pos is bd) evaluates leave-one-out at bd's
     own points and returns the values in the original point order."""
     cd = bd._cstruct()
+    man, mp = _man_ptr(manifold, bd.bt.dims)  # (manifold: circular differences in those dimensions, kdehip.h section 5d)
     if lvFlag or pos is bd:
         out = np.zeros(bd.bt.num_points)
-        _lib.check(_lib.lib.kdehip_evaluate(C.byref(cd), None, 0, 1, ptr(out, f64p), int(device)))
+        _lib.check(_lib.lib.kdehip_evaluate_manifold(C.byref(cd), None, 0, 1, ptr(out, f64p), int(device), mp))
         return out
     if isinstance(pos, BallTreeDensity):
         from .density import getPoints
@@ -74,5 +86,6 @@ def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, d
         raise ValueError("bd and pos must have the same dimension")
     flat = np.ascontiguousarray(pos.T).ravel()
     out = np.zeros(pos.shape[1])
-    _lib.check(_lib.lib.kdehip_evaluate(C.byref(cd), ptr(flat, f64p), pos.shape[1], 0, ptr(out, f64p), int(device)))
+    _lib.check(_lib.lib.kdehip_evaluate_manifold(C.byref(cd), ptr(flat, f64p), pos.shape[1], 0, ptr(out, f64p), int(device),
+                                                 mp))
     return out

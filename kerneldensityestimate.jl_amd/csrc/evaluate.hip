@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "circ_wrap.hpp"
 #include "device_density.hpp"
 #include "fastexp.hpp"
 #include "host_pool.hpp"
@@ -49,6 +50,19 @@ inline GroupSplit split_chunks(int64_t N, int64_t Nq, int nprob) {
   g.chunks_per_group = (nchunks + want - 1) / want;
   g.ngroups = static_cast<int>((nchunks + g.chunks_per_group - 1) / g.chunks_per_group);
   return g;
+}
+
+// The per-dimension manifold enum of include/kdehip.h as a mask (bit k = dimension k is circular); NULL = all Euclidean.
+// Checked before any device is touched: a byte other than 0 / 1 is KDEHIP_ERR_ARG.
+inline int manifold_mask(const uint8_t *manifold, int64_t D, unsigned *mask) {
+  *mask = 0;
+  if (!manifold || D < 1 || D > KDEHIP_MAX_DIMS) return KDEHIP_OK;  // (a bad D is the caller's own refusal)
+  for (int64_t k = 0; k < D; ++k) {
+    if (manifold[k] == KDEHIP_MANIFOLD_CIRCULAR) *mask |= 1u << k;
+    else if (manifold[k] != KDEHIP_MANIFOLD_EUCLIDEAN)
+      return set_error(KDEHIP_ERR_ARG, "manifold: every entry is KDEHIP_MANIFOLD_EUCLIDEAN or KDEHIP_MANIFOLD_CIRCULAR");
+  }
+  return KDEHIP_OK;
 }
 
 #define KDEHIP_CHECK(expr)                                                                  \
@@ -87,8 +101,11 @@ struct EvalBatch { EvalProblem p[KDEHIP_MAX_DIMS]; };
 // A block owns kEvalThreads queries and ONE group of consecutive 128-point source chunks, which it walks in
 // order with the running sum in a register: the scratch is [ngroups][Nq] with ngroups <= kEvalMaxGroups
 // whatever N is (grid.y stays far below the 65535 limit), and the summation order is fixed by (N, ngroups).
-template <int D>
-__global__ __launch_bounds__(kEvalThreads) void eval_partial_kernel(const EvalBatch batch, int loo) {
+// CIRC: bit k of `circ` (uniform over the launch) makes dimension k circular -- its difference goes through circ_wrap
+// before it is squared (diffop inside distGauss!, src/DualTree01.jl:14-47); nothing else changes, so data in which no
+// difference wraps gives the bits of the Euclidean instantiation (circ_wrap(t) == t for -pi <= t < pi).
+template <int D, bool CIRC = false>
+__global__ __launch_bounds__(kEvalThreads) void eval_partial_kernel(const EvalBatch batch, int loo, unsigned circ = 0) {
   __shared__ double sSrc[2][kEvalChunk * (D + 1)];
   __shared__ double sExpTab[32];
   if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
@@ -124,7 +141,10 @@ __global__ __launch_bounds__(kEvalThreads) void eval_partial_kernel(const EvalBa
       double acc = 0.0;
 #pragma unroll
       for (int k = 0; k < D; ++k) {
-        const double d = x[k] - s[k];
+        double d = x[k] - s[k];
+        if constexpr (CIRC) {
+          if ((circ >> k) & 1u) d = circ_wrap(d);  // (wave-uniform: a Euclidean dimension costs the test)
+        }
         acc = fma(d * d, pb.nhib[k], acc);
       }
       double v = s[D] * exp_nonpos(acc, sExpTab);  // acc <= 0
@@ -161,24 +181,25 @@ __global__ void eval_finish_kernel(const FinishBatch batch, int loo) {
 }
 
 template <int D>
-void launch_partial(const EvalBatch &d_problems, int nprob, int64_t maxNq, int ngroups, int loo,
+void launch_partial(const EvalBatch &d_problems, int nprob, int64_t maxNq, int ngroups, int loo, unsigned circ,
                     hipStream_t st) {
   dim3 grid(static_cast<unsigned>((maxNq + kEvalThreads - 1) / kEvalThreads),
             static_cast<unsigned>(ngroups), static_cast<unsigned>(nprob));
-  hipLaunchKernelGGL((eval_partial_kernel<D>), grid, dim3(kEvalThreads), 0, st, d_problems, loo);
+  if (circ) hipLaunchKernelGGL((eval_partial_kernel<D, true>), grid, dim3(kEvalThreads), 0, st, d_problems, loo, circ);
+  else hipLaunchKernelGGL((eval_partial_kernel<D, false>), grid, dim3(kEvalThreads), 0, st, d_problems, loo, 0u);
 }
 
-int launch_partial_dims(int D, const EvalBatch &d_problems, int nprob, int64_t maxNq, int ngroups, int loo,
+int launch_partial_dims(int D, const EvalBatch &d_problems, int nprob, int64_t maxNq, int ngroups, int loo, unsigned circ,
                         hipStream_t st) {
   switch (D) {
-    case 1: launch_partial<1>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 2: launch_partial<2>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 3: launch_partial<3>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 4: launch_partial<4>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 5: launch_partial<5>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 6: launch_partial<6>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 7: launch_partial<7>(d_problems, nprob, maxNq, ngroups, loo, st); break;
-    case 8: launch_partial<8>(d_problems, nprob, maxNq, ngroups, loo, st); break;
+    case 1: launch_partial<1>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 2: launch_partial<2>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 3: launch_partial<3>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 4: launch_partial<4>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 5: launch_partial<5>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 6: launch_partial<6>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 7: launch_partial<7>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
+    case 8: launch_partial<8>(d_problems, nprob, maxNq, ngroups, loo, circ, st); break;
     default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   }
   const hipError_t e = hipGetLastError();
@@ -200,10 +221,17 @@ using namespace kdehip;
 
 extern "C" int kdehip_evaluate(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,
                                double *p_out, int device) {
+  return kdehip_evaluate_manifold(bd, pos, Nq, leave_one_out, p_out, device, nullptr);
+}
+
+extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,
+                                        double *p_out, int device, const uint8_t *manifold) {
   if (!bd || !p_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
   if (D < 1 || D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  unsigned circ = 0;
+  if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (N < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
     return set_error(KDEHIP_ERR_ARG, "malformed density");
   if (leave_one_out) Nq = N;
@@ -267,7 +295,7 @@ extern "C" int kdehip_evaluate(const kdehip_density *bd, const double *pos, int6
   fp.out_idx = leave_one_out ? reinterpret_cast<const int64_t *>(du + o_q) : nullptr;
   fp.out = d_out.as<double>(); fp.inv_norm = 1.0 / gauss_norm(bw, D); fp.Nq = Nq; fp.nchunks = nchunks;
   PhaseTimer timer(kPhaseEvaluate, st);
-  rc = launch_partial_dims(D, eb, 1, Nq, gs.ngroups, leave_one_out ? 1 : 0, st);
+  rc = launch_partial_dims(D, eb, 1, Nq, gs.ngroups, leave_one_out ? 1 : 0, circ, st);
   if (rc != KDEHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
   hipLaunchKernelGGL(eval_finish_kernel, dim3(static_cast<unsigned>((Nq + 255) / 256), 1), dim3(256), 0, st,
                      fb, leave_one_out ? 1 : 0);
@@ -579,6 +607,8 @@ struct LooRound {
   unsigned *arrivals;     // [D][T] slots delivered per tile (one launch per round; zero between rounds)
   int joint;              // one launch per round: the first launch evaluates BOTH opening probes of every search (a second
                           // set of slots, counters and shares behind the first), the second launch books both
+  unsigned circ;          // 0: every search is Euclidean.  Else bits 0..7: the circular dimensions of a matrix, bits 8..15:
+                          // its dimension count D0 -- search m is circular when bit m % D0 is set (read by the CIRC kernels only)
   double *hpart;          // [2][D][nfb] block partials of W*log p of the evaluation in flight (by round parity)
   Golden *state;          // [2][D]
   int64_t N;
@@ -588,8 +618,23 @@ struct LooRound {
   int spec;               // speculative rounds (loo_round_spec_kernel): three sets of slots / counters, shares [2][3][D][nfb]
 };
 
+// Is the 1-D search of marginal m on a circular dimension?  (wave-uniform: r and m are)
+__device__ __forceinline__ bool loo_circular(const LooRound &r, int m) {
+  return ((r.circ & 0xffu) >> (m % static_cast<int>(r.circ >> 8))) & 1u;
+}
+// The difference of a circular search: circ_wrap(a - b).  The padding points at +-infinity must still contribute exactly
+// 0: floor(inf) = inf and inf - inf is NaN, so a difference that is not finite stays as it is (its square is +inf,
+// exp(-inf) = 0, as in the Euclidean form).  circ_wrap(-t)^2 == circ_wrap(t)^2 (t = +-pi, the one asymmetric point, squares
+// to the same value), so the pair kernels' "each value once for both orders" holds on the circle too.
+__device__ __forceinline__ double loo_circ_diff(double a, double b) {
+  const double d = a - b;
+  const double w = circ_wrap(d);
+  return fabs(d) < INFINITY ? w : d;
+}
+
 // Round, first launch: advance the search of this block's dimension, then the all-pairs leave-one-out sums
 // partial[g][q] = sum_{i in group g, i != q} exp(-1/2 (x_q - x_i)^2 / bw)   (weights are uniform: applied later)
+template <bool CIRC>
 __global__ __launch_bounds__(kLooThreads) void loo_round_partial_kernel(const LooRound r) {
   __shared__ double sSrc[2][kLooChunk];
   __shared__ double sExpTab[32];
@@ -613,6 +658,8 @@ __global__ __launch_bounds__(kLooThreads) void loo_round_partial_kernel(const Lo
   int64_t c_end = c_begin + r.chunks_per_group;
   if (c_end > nchunks) c_end = nchunks;
   const double xq = q < r.N ? x[q] : 0.0;
+  bool circ = false;
+  if constexpr (CIRC) circ = loo_circular(r, d);
   auto stage = [&](int64_t c, int buf) {
     const int64_t i = c * kLooChunk + threadIdx.x;
     if (threadIdx.x < kLooChunk) sSrc[buf][threadIdx.x] = i < r.N ? x[i] : INFINITY;  // (a point at infinity contributes exp(-inf) = 0)
@@ -627,7 +674,10 @@ __global__ __launch_bounds__(kLooThreads) void loo_round_partial_kernel(const Lo
     double sum = 0.0;
 #pragma unroll 4
     for (int i = 0; i < kLooChunk; ++i) {
-      const double dlt = xq - sSrc[buf][i];
+      double dlt = xq - sSrc[buf][i];
+      if constexpr (CIRC) {
+        if (circ) dlt = loo_circ_diff(xq, sSrc[buf][i]);
+      }
       double v = exp_nonpos((dlt * dlt) * nhib, sExpTab);
       if (i0 + i == q) v = 0.0;  // leave-one-out: skip the self term (:141)
       sum += v;
@@ -724,6 +774,8 @@ __device__ __forceinline__ void pairs_arrive(const LooRound &r, const PairSet &p
 
 // One tile pair (I, I + k mod T) of dimension d by one wavefront: the 64 x 64 kernel values, each computed once and added to
 // a row sum (own point) and a column sum (visiting point), left in the (tile, source tile) slots; then the arrival.
+// (CIRC: every difference is loo_circ_diff's -- the caller has tested the search's bit once, for the whole wavefront)
+template <bool CIRC>
 __device__ __forceinline__ void pairs_item(const LooRound &r, const PairSet &ps, int d, int e, int lane, double bw_eval,
                                            const double *sExpTab) {
   const int T = r.ngroups, K = T / 2;
@@ -742,7 +794,7 @@ __device__ __forceinline__ void pairs_item(const LooRound &r, const PairSet &ps,
     xj = wave_rotate(xj);
 #pragma unroll 4
     for (int s = 1; s < kTile; ++s) {
-      const double dlt = xi - xj;
+      const double dlt = CIRC ? loo_circ_diff(xi, xj) : xi - xj;
       row += exp256_nonpos((dlt * dlt) * nhib, sExpTab);
       xj = wave_rotate(xj);
     }
@@ -754,7 +806,7 @@ __device__ __forceinline__ void pairs_item(const LooRound &r, const PairSet &ps,
   double col = 0.0;
 #pragma unroll 4
   for (int s = 0; s < kTile; ++s) {
-    const double dlt = xi - xj;
+    const double dlt = CIRC ? loo_circ_diff(xi, xj) : xi - xj;
     const double v = exp256_nonpos((dlt * dlt) * nhib, sExpTab);
     row += v;
     col = wave_rotate(col + v);
@@ -768,7 +820,7 @@ __device__ __forceinline__ void pairs_item(const LooRound &r, const PairSet &ps,
 // OPENING: 0 = a round of one evaluation per search; 1 = the first launch, both opening probes; 2 = the launch after it
 // (reqd_work_group_size: where the compiler keeps a thread's temporaries in LDS it indexes them by the flat thread id,
 // and without the sizes it reads them from the dispatch packet -- in host memory: 2-15 us on every workgroup's path)
-template <int OPENING>
+template <int OPENING, bool CIRC>
 __global__ __launch_bounds__(kTile *kPairWaves) void loo_round_pairs_kernel(const LooRound r) {
   __shared__ double sExpTab[256];
   __shared__ double sPart[OPENING == 2 ? 2 : 1][kFusedMaxN / kTile];
@@ -813,7 +865,10 @@ __global__ __launch_bounds__(kTile *kPairWaves) void loo_round_pairs_kernel(cons
   }
   __syncthreads();
   if (sPhase == 3) return;  // this dimension's search is over
-  pairs_item(r, ps, d, blockIdx.x * kPairWaves + wave, lane, sBw, sExpTab);
+  if constexpr (CIRC) {
+    if (loo_circular(r, d)) { pairs_item<true>(r, ps, d, blockIdx.x * kPairWaves + wave, lane, sBw, sExpTab); return; }
+  }
+  pairs_item<false>(r, ps, d, blockIdx.x * kPairWaves + wave, lane, sBw, sExpTab);
 }
 
 // A SPECULATIVE round (golden_advance_spec above): blockIdx.z = probe * D + dimension; probe 0 evaluates the point that is
@@ -822,7 +877,7 @@ __global__ __launch_bounds__(kTile *kPairWaves) void loo_round_pairs_kernel(cons
 // the host when three evaluations still fit the chip a few wavefronts deep (small marginals: a round is then mostly its
 // fixed ~12 us of launch, prologue and hand-over, and two evaluations per launch nearly halve the search: 6 x 1000 points
 // 0.36 -> 0.2x ms); the numbers golden sees are those of the plain rounds, bit for bit (same tiles, same order).
-template <bool FIRST>
+template <bool FIRST, bool CIRC>
 __global__ __launch_bounds__(kTile *kPairWaves) void loo_round_spec_kernel(const LooRound r) {
   __shared__ double sExpTab[256];
   __shared__ double sPart[3][kFusedMaxN / kTile];
@@ -857,7 +912,10 @@ __global__ __launch_bounds__(kTile *kPairWaves) void loo_round_spec_kernel(const
   }
   __syncthreads();
   if (sPhase == 3) return;  // this dimension's search is over, or the bracket closes before this candidate
-  pairs_item(r, ps, d, blockIdx.x * kPairWaves + wave, lane, sBw, sExpTab);
+  if constexpr (CIRC) {
+    if (loo_circular(r, d)) { pairs_item<true>(r, ps, d, blockIdx.x * kPairWaves + wave, lane, sBw, sExpTab); return; }
+  }
+  pairs_item<false>(r, ps, d, blockIdx.x * kPairWaves + wave, lane, sBw, sExpTab);
 }
 
 // Round, second launch: p_q = w * (sum over groups) / norm / (1 - w); block partial of W_q * log p_q
@@ -934,7 +992,7 @@ __global__ void loo_finalize_kernel(const LooRound r) {
 // the next batch enqueued) -> ... -> finish (bandwidths).  Several searches (different N) can be in flight on one stream.
 class kdehip::LoocvSearch {
  public:
-  int begin(int nb, int D, int64_t N, const double *points, const double *d_points, hipStream_t st);
+  int begin(int nb, int D, int64_t N, const double *points, const double *d_points, hipStream_t st, unsigned circ_mask = 0);
   int poll(bool *done);
   int finish(double *bw_out, int32_t *nevals_out);  // bw_out: nb * D standard deviations; nevals_out: nb counts
   int rounds() const { return rounds_; }
@@ -960,7 +1018,11 @@ class kdehip::LoocvSearch {
   int64_t qblocks_ = 0;
 };
 
-int kdehip::LoocvSearch::begin(int nb, int D, int64_t N, const double *points, const double *d_points, hipStream_t st) {
+// `circ_mask`: bit k = dimension k of every matrix is circular.  Only the likelihood evaluations of the rounds wrap: the
+// preparation (sort, interval arithmetic = neighborMinMax, the bracket) is the Euclidean one, as in the reference, where
+// marginal(p, [i]) and the kde! inside ksize build their 1-D trees with the default operators (src/CrossValidation.jl:110-120).
+int kdehip::LoocvSearch::begin(int nb, int D, int64_t N, const double *points, const double *d_points, hipStream_t st,
+                               unsigned circ_mask) {
   st_ = st; nb_ = nb; D_ = D;
   const int nm = nm_ = nb * D;
   if (nb < 1 || nm > kLoocvMaxMarginals) return set_error(KDEHIP_ERR_UNSUPPORTED, "bandwidth search: too many marginals for one launch");
@@ -990,6 +1052,7 @@ int kdehip::LoocvSearch::begin(int nb, int D, int64_t N, const double *points, c
   r.ngroups = pairs ? ntiles : static_cast<int>((nchunks + r.chunks_per_group - 1) / r.chunks_per_group);
   r.nfb = pairs ? ntiles : static_cast<int>(qblocks);  // blocks of the log-likelihood reduction (64 / 256 queries each)
   r.N = N; r.D = nm; r.w = w1; r.round = 0;
+  r.circ = circ_mask ? ((circ_mask & 0xffu) | (static_cast<unsigned>(D) << 8)) : 0u;
   r.sqrt_2pi = std::pow(2.0 * M_PI, 1 / 2.0);
 
   // one device block: [points N*D | xo nm*N | partial nm*ngroups*N | hpart nm*nfb | state 2*nm]
@@ -1070,16 +1133,31 @@ int kdehip::LoocvSearch::enqueue_batch(int batch) {
   const dim3 gridP(static_cast<unsigned>((pair_items_ + kPairWaves - 1) / kPairWaves), 1, nm);
   const dim3 gridP2(gridP.x, 1, 2 * nm);  // the joint first launch
   const dim3 gridS2(gridP.x, 1, 2 * nm), gridS3(gridP.x, 1, 3 * nm);
+  const bool circ = r.circ != 0;  // (a search with a circular dimension runs the CIRC instantiations, every round)
+  const dim3 blockP(kTile * kPairWaves);
   for (int k = 0; k < batch; ++k) {
     if (r.spec) {
-      if (r.round == 0) hipLaunchKernelGGL(loo_round_spec_kernel<true>, gridS2, dim3(kTile * kPairWaves), 0, st, r);
-      else hipLaunchKernelGGL(loo_round_spec_kernel<false>, gridS3, dim3(kTile * kPairWaves), 0, st, r);
+      if (r.round == 0) {
+        if (circ) hipLaunchKernelGGL((loo_round_spec_kernel<true, true>), gridS2, blockP, 0, st, r);
+        else hipLaunchKernelGGL((loo_round_spec_kernel<true, false>), gridS2, blockP, 0, st, r);
+      } else {
+        if (circ) hipLaunchKernelGGL((loo_round_spec_kernel<false, true>), gridS3, blockP, 0, st, r);
+        else hipLaunchKernelGGL((loo_round_spec_kernel<false, false>), gridS3, blockP, 0, st, r);
+      }
     } else if (pairs_) {
-      if (r.joint && r.round == 0) hipLaunchKernelGGL(loo_round_pairs_kernel<1>, gridP2, dim3(kTile * kPairWaves), 0, st, r);
-      else if (r.joint && r.round == 1) hipLaunchKernelGGL(loo_round_pairs_kernel<2>, gridP, dim3(kTile * kPairWaves), 0, st, r);
-      else hipLaunchKernelGGL(loo_round_pairs_kernel<0>, gridP, dim3(kTile * kPairWaves), 0, st, r);
+      if (r.joint && r.round == 0) {
+        if (circ) hipLaunchKernelGGL((loo_round_pairs_kernel<1, true>), gridP2, blockP, 0, st, r);
+        else hipLaunchKernelGGL((loo_round_pairs_kernel<1, false>), gridP2, blockP, 0, st, r);
+      } else if (r.joint && r.round == 1) {
+        if (circ) hipLaunchKernelGGL((loo_round_pairs_kernel<2, true>), gridP, blockP, 0, st, r);
+        else hipLaunchKernelGGL((loo_round_pairs_kernel<2, false>), gridP, blockP, 0, st, r);
+      } else {
+        if (circ) hipLaunchKernelGGL((loo_round_pairs_kernel<0, true>), gridP, blockP, 0, st, r);
+        else hipLaunchKernelGGL((loo_round_pairs_kernel<0, false>), gridP, blockP, 0, st, r);
+      }
     } else {
-      hipLaunchKernelGGL(loo_round_partial_kernel, gridA, dim3(kLooThreads), 0, st, r);
+      if (circ) hipLaunchKernelGGL(loo_round_partial_kernel<true>, gridA, dim3(kLooThreads), 0, st, r);
+      else hipLaunchKernelGGL(loo_round_partial_kernel<false>, gridA, dim3(kLooThreads), 0, st, r);
       hipLaunchKernelGGL(loo_round_entropy_kernel<kLooThreads>, gridB, dim3(kLooThreads), 0, st, r);
     }
     ++r.round;
@@ -1129,13 +1207,13 @@ int kdehip::loocv_poll(LoocvSearch *s, bool *done) { return s->poll(done); }
 int kdehip::loocv_finish(LoocvSearch *s, double *bw_out, int32_t *nevals_out) { return s->finish(bw_out, nevals_out); }
 
 int kdehip::auto_bandwidth_run(int D, int64_t N, const double *points, const double *d_points, void *stream,
-                               double *bw_out, int32_t *nevals_out, const std::function<void()> *overlap) {
+                               double *bw_out, int32_t *nevals_out, const std::function<void()> *overlap, unsigned circ_mask) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool timing = std::getenv("KDEHIP_TIMING") != nullptr;
   auto tnow = [] { return std::chrono::steady_clock::now(); };
   auto t_begin = tnow();
   LoocvSearch search;
-  int rc = search.begin(1, D, N, points, d_points, st);
+  int rc = search.begin(1, D, N, points, d_points, st, circ_mask);
   if (rc != KDEHIP_OK) return rc;
   auto t_prep = tnow();
   if (overlap) (*overlap)();  // (the first batch is in flight: the caller's host work runs under it)
@@ -1156,14 +1234,21 @@ int kdehip::auto_bandwidth_run(int D, int64_t N, const double *points, const dou
 
 extern "C" int kdehip_auto_bandwidth(int64_t D64, int64_t N, const double *points, double *bw_out,
                                      int32_t *nevals_out, int device) {
+  return kdehip_auto_bandwidth_manifold(D64, N, points, bw_out, nevals_out, device, nullptr);
+}
+
+extern "C" int kdehip_auto_bandwidth_manifold(int64_t D64, int64_t N, const double *points, double *bw_out,
+                                              int32_t *nevals_out, int device, const uint8_t *manifold) {
   if (!points || !bw_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   if (D64 < 1 || D64 > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   if (N < 2) return set_error(KDEHIP_ERR_ARG, "kde!(points) needs at least two points");
+  unsigned circ = 0;
+  if (manifold_mask(manifold, D64, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   const int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
   try {  // (host-prepared marginals use std::vector / std::thread: nothing may throw out of an extern "C" entry point)
-    return auto_bandwidth_run(static_cast<int>(D64), N, points, nullptr, hipStreamPerThread, bw_out, nevals_out);
+    return auto_bandwidth_run(static_cast<int>(D64), N, points, nullptr, hipStreamPerThread, bw_out, nevals_out, nullptr, circ);
   } catch (const std::exception &e) {
     return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_auto_bandwidth: ") + e.what());
   }
@@ -1176,8 +1261,21 @@ extern "C" int kdehip_make_density_auto(int64_t D, int64_t N, const double *poin
                                         int64_t *right_child, int64_t *lowest_leaf, int64_t *highest_leaf,
                                         int64_t *permutation, double *means, double *bandwidth, double *bandwidthMin,
                                         double *bandwidthMax) {
+  return kdehip_make_density_auto_manifold(D, N, points, bw_out, nevals, device, centers, ranges, weights, left_child,
+                                           right_child, lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin,
+                                           bandwidthMax, nullptr);
+}
+
+// (the tree is still the Euclidean builder's: only the bandwidth search takes the manifold)
+extern "C" int kdehip_make_density_auto_manifold(int64_t D, int64_t N, const double *points, double *bw_out, int32_t *nevals,
+                                                 int device, double *centers, double *ranges, double *weights,
+                                                 int64_t *left_child, int64_t *right_child, int64_t *lowest_leaf,
+                                                 int64_t *highest_leaf, int64_t *permutation, double *means, double *bandwidth,
+                                                 double *bandwidthMin, double *bandwidthMax, const uint8_t *manifold) {
   using namespace kdehip;
   if (D < 1 || N < 2) return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_auto: need D >= 1 and N >= 2");
+  unsigned circ = 0;  // (checked here too: before the tree build starts)
+  if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (!points || !bw_out || !centers || !ranges || !weights || !left_child || !right_child || !lowest_leaf ||
       !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin || !bandwidthMax)
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_auto: null pointer");
@@ -1189,7 +1287,7 @@ extern "C" int kdehip_make_density_auto(int64_t D, int64_t N, const double *poin
       tree_rc = kdehip_make_density(D, N, points, &one, 1, nullptr, centers, ranges, weights, left_child, right_child,
                                     lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin, bandwidthMax);
     });
-    rc = kdehip_auto_bandwidth(D, N, points, bw_out, nevals, device);
+    rc = kdehip_auto_bandwidth_manifold(D, N, points, bw_out, nevals, device, manifold);
     group.wait();
   } catch (const std::exception &e) {
     return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_make_density_auto: ") + e.what());
@@ -1257,15 +1355,20 @@ __device__ __forceinline__ int item_of_block(const int32_t *__restrict__ first, 
 
 // eval_partial_kernel for the items [0, n) of one D: item i owns blocks [first[i], first[i+1]) - first[0], its block k is
 // query block k % qblocks of source group k / qblocks.  The body is eval_partial_kernel's, line for line.
-template <int D>
+// CIRC: masks[i] (uniform over the block) = the circular dimensions of item i, as eval_partial_kernel's `circ`; the host
+// launches the items that have one with this instantiation and all others with the Euclidean one.
+template <int D, bool CIRC = false>
 __global__ __launch_bounds__(kEvalThreads) void logl_partial_kernel(const LoglItem *__restrict__ items,
-                                                                    const int32_t *__restrict__ first, int n) {
+                                                                    const int32_t *__restrict__ first, int n,
+                                                                    const uint32_t *__restrict__ masks = nullptr) {
   __shared__ double sSrc[2][kEvalChunk * (D + 1)];
   __shared__ double sExpTab[32];
   if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
   const int b = static_cast<int>(blockIdx.x) + first[0];
   const int i = item_of_block(first, n, b);
   const LoglItem pb = items[i];
+  unsigned circ = 0;
+  if constexpr (CIRC) circ = __builtin_amdgcn_readfirstlane(masks[i]);
   const int64_t qblocks = (pb.Nq + kEvalThreads - 1) / kEvalThreads;
   const int64_t kb = b - first[i];
   const int64_t qb = kb % qblocks, grp = kb / qblocks;
@@ -1303,7 +1406,10 @@ __global__ __launch_bounds__(kEvalThreads) void logl_partial_kernel(const LoglIt
       double acc = 0.0;
 #pragma unroll
       for (int k = 0; k < D; ++k) {
-        const double d = x[k] - s[k];
+        double d = x[k] - s[k];
+        if constexpr (CIRC) {
+          if ((circ >> k) & 1u) d = circ_wrap(d);
+        }
         acc = fma(d * d, nhib[k], acc);
       }
       double v = s[D] * exp_nonpos(acc, sExpTab);  // acc <= 0
@@ -1373,20 +1479,27 @@ __global__ void logl_reduce_kernel(const LoglItem *__restrict__ items, int n) {
 }
 
 template <int D>
-void launch_logl_partial(const LoglItem *d_items, const int32_t *d_first, int n, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL(logl_partial_kernel<D>, dim3(static_cast<unsigned>(blocks)), dim3(kEvalThreads), 0, st, d_items,
-                     d_first, n);
+void launch_logl_partial(const LoglItem *d_items, const int32_t *d_first, int n, int blocks, const uint32_t *d_masks,
+                         hipStream_t st) {
+  if (d_masks)
+    hipLaunchKernelGGL((logl_partial_kernel<D, true>), dim3(static_cast<unsigned>(blocks)), dim3(kEvalThreads), 0, st, d_items,
+                       d_first, n, d_masks);
+  else
+    hipLaunchKernelGGL((logl_partial_kernel<D, false>), dim3(static_cast<unsigned>(blocks)), dim3(kEvalThreads), 0, st, d_items,
+                       d_first, n, static_cast<const uint32_t *>(nullptr));
 }
-int launch_logl_partial_dims(int D, const LoglItem *d_items, const int32_t *d_first, int n, int blocks, hipStream_t st) {
+// d_masks: the items' circular masks (all nonzero), or null: Euclidean items
+int launch_logl_partial_dims(int D, const LoglItem *d_items, const int32_t *d_first, int n, int blocks, const uint32_t *d_masks,
+                             hipStream_t st) {
   switch (D) {
-    case 1: launch_logl_partial<1>(d_items, d_first, n, blocks, st); break;
-    case 2: launch_logl_partial<2>(d_items, d_first, n, blocks, st); break;
-    case 3: launch_logl_partial<3>(d_items, d_first, n, blocks, st); break;
-    case 4: launch_logl_partial<4>(d_items, d_first, n, blocks, st); break;
-    case 5: launch_logl_partial<5>(d_items, d_first, n, blocks, st); break;
-    case 6: launch_logl_partial<6>(d_items, d_first, n, blocks, st); break;
-    case 7: launch_logl_partial<7>(d_items, d_first, n, blocks, st); break;
-    case 8: launch_logl_partial<8>(d_items, d_first, n, blocks, st); break;
+    case 1: launch_logl_partial<1>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 2: launch_logl_partial<2>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 3: launch_logl_partial<3>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 4: launch_logl_partial<4>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 5: launch_logl_partial<5>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 6: launch_logl_partial<6>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 7: launch_logl_partial<7>(d_items, d_first, n, blocks, d_masks, st); break;
+    case 8: launch_logl_partial<8>(d_items, d_first, n, blocks, d_masks, st); break;
     default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   }
   KDEHIP_CHECK(hipGetLastError());
@@ -1400,6 +1513,7 @@ int launch_logl_partial_dims(int D, const LoglItem *d_items, const int32_t *d_fi
 class LoglRun {
  public:
   std::vector<LoglItem> items;
+  std::vector<uint32_t> circ;  // per item: its circular dimensions (bit k = dimension k); shorter than `items`: 0 for the rest
   ~LoglRun() {
     if (armed_) (void)hipStreamSynchronize(st_);  // (an error return after launches: nothing goes back to a cache in use)
     if (d_) cached_free(d_, dbytes_);
@@ -1420,7 +1534,8 @@ class LoglRun {
     if (pblocks > INT32_MAX || fblocks > INT32_MAX) return set_error(KDEHIP_ERR_UNSUPPORTED, "evaluation too large for one launch");
     o_items_ = al(prefix);
     o_first_ = al(o_items_ + sizeof(LoglItem) * n);
-    o_res_ = al(o_first_ + sizeof(int32_t) * 2 * (n + 1));
+    o_masks_ = o_first_ + sizeof(int32_t) * 2 * (n + 1);
+    o_res_ = al(o_masks_ + sizeof(uint32_t) * n);
     size_t o = al(o_res_ + sizeof(double) * n);
     scratch_.resize(n);
     for (size_t k = 0; k < n; ++k) {
@@ -1439,7 +1554,7 @@ class LoglRun {
   double *result(size_t k) const { return reinterpret_cast<double *>(dev() + o_res_) + k; }  // (device) an item's own result slot
   double *host_result(size_t k) const { return reinterpret_cast<double *>(host() + o_res_) + k; }
 
-  // scratch pointers, descriptors sorted by D, one upload, the launches -- all on `st`
+  // scratch pointers, descriptors sorted by D (Euclidean items before circular ones), one upload, the launches -- all on `st`
   int enqueue(hipStream_t st) {
     st_ = st;
     const size_t n = items.size();
@@ -1450,7 +1565,19 @@ class LoglRun {
       it.bpart = it.partial + static_cast<int64_t>(it.ngroups) * it.Nq;
       it.bzero = reinterpret_cast<int32_t *>(it.bpart + it.nfb);
     }
-    std::stable_sort(items.begin(), items.end(), [](const LoglItem &a, const LoglItem &b) { return a.D < b.D; });
+    circ.resize(n, 0u);
+    {
+      std::vector<size_t> ord(n);
+      for (size_t k = 0; k < n; ++k) ord[k] = k;
+      auto key = [&](size_t k) { return 2 * items[k].D + (circ[k] ? 1 : 0); };
+      std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return key(a) < key(b); });
+      std::vector<LoglItem> si(n);
+      std::vector<uint32_t> sc(n);
+      for (size_t k = 0; k < n; ++k) { si[k] = items[ord[k]]; sc[k] = circ[ord[k]]; }
+      items.swap(si);
+      circ.swap(sc);
+    }
+    if (n) std::memcpy(host() + o_masks_, circ.data(), sizeof(uint32_t) * n);
     int32_t *pfirst = reinterpret_cast<int32_t *>(host() + o_first_), *ffirst = pfirst + (n + 1);
     pfirst[0] = ffirst[0] = 0;
     for (size_t k = 0; k < n; ++k) {
@@ -1463,12 +1590,14 @@ class LoglRun {
     KDEHIP_CHECK(hipMemcpyAsync(d_, h_, o_res_, hipMemcpyHostToDevice, st));
     const LoglItem *d_items = reinterpret_cast<const LoglItem *>(dev() + o_items_);
     const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 1);
-    for (size_t a = 0; a < n;) {  // one launch per distinct D
+    const uint32_t *d_masks = reinterpret_cast<const uint32_t *>(dev() + o_masks_);
+    for (size_t a = 0; a < n;) {  // one launch per distinct D, and one more for its items with a circular dimension
       size_t e = a;
-      while (e < n && items[e].D == items[a].D) ++e;
+      while (e < n && items[e].D == items[a].D && !circ[e] == !circ[a]) ++e;
       const int blocks = pfirst[e] - pfirst[a];
       if (blocks > 0) {
-        const int rc = launch_logl_partial_dims(items[a].D, d_items + a, d_pfirst + a, static_cast<int>(e - a), blocks, st);
+        const int rc = launch_logl_partial_dims(items[a].D, d_items + a, d_pfirst + a, static_cast<int>(e - a), blocks,
+                                                circ[a] ? d_masks + a : nullptr, st);
         if (rc != KDEHIP_OK) return rc;
       }
       a = e;
@@ -1502,7 +1631,7 @@ class LoglRun {
 
  private:
   void *d_ = nullptr, *h_ = nullptr;
-  size_t dbytes_ = 0, hbytes_ = 0, o_items_ = 0, o_first_ = 0, o_res_ = 0;
+  size_t dbytes_ = 0, hbytes_ = 0, o_items_ = 0, o_first_ = 0, o_masks_ = 0, o_res_ = 0;
   std::vector<size_t> scratch_;
   hipStream_t st_ = nullptr;
   bool armed_ = false;
@@ -1550,6 +1679,11 @@ LoglItem pair_item(const kdehip_device_density *bd, const kdehip_device_density 
 
 extern "C" int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
                                     int device) {
+  return kdehip_eval_avg_logl_manifold(bd, at, leave_one_out, out, device, nullptr);
+}
+
+extern "C" int kdehip_eval_avg_logl_manifold(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
+                                             int device, const uint8_t *manifold) {
   // every check that needs no device comes first
   if (!bd || !out) return set_error(KDEHIP_ERR_ARG, "null argument");
   if (leave_one_out && at && at != bd) return set_error(KDEHIP_ERR_ARG, "leave_one_out needs at == bd (or at == NULL)");
@@ -1566,6 +1700,8 @@ extern "C" int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_densi
     for (int k = 0; k < D; ++k)
       if (bd->bandwidth[(N + i) * D + k] != bw[k])
         return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  unsigned circ = 0;
+  if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -1579,6 +1715,7 @@ extern "C" int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_densi
   it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
   it.N = N; it.Nq = Nq; it.D = static_cast<int32_t>(D); it.loo = leave_one_out ? 1 : 0;
   run.items.push_back(it);
+  run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix));
   unsigned char *h = run.host(), *d = run.dev();
   std::memcpy(h, bd->means + N * D, sizeof(double) * N * D);
@@ -1604,10 +1741,25 @@ extern "C" int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_densi
 extern "C" int kdehip_eval_avg_logl_device_batch(int n, const kdehip_logl_item *items, double *d_out, void *stream) {
   if (n < 0 || (n > 0 && (!items || !d_out))) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: bad item list");
   if (n == 0) return KDEHIP_OK;
+  try {  // (the old entry forwards with mask 0; its reserved_ word stays unread)
+    std::vector<kdehip_logl_manifold_item> mi(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) mi[i] = kdehip_logl_manifold_item{items[i].bd, items[i].at, items[i].leave_one_out, 0u};
+    return kdehip_eval_avg_logl_device_batch_manifold(n, mi.data(), d_out, stream);
+  } catch (const std::exception &e) {
+    return set_error(KDEHIP_ERR_ALLOC, std::string("evalAvgLogL batch: ") + e.what());
+  }
+}
+
+extern "C" int kdehip_eval_avg_logl_device_batch_manifold(int n, const kdehip_logl_manifold_item *items, double *d_out,
+                                                          void *stream) {
+  if (n < 0 || (n > 0 && (!items || !d_out))) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: bad item list");
+  if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
     const int rc = check_pair(items[i].bd, items[i].at, items[i].leave_one_out);
     if (rc != KDEHIP_OK) return rc;
     if (items[i].bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: densities on different devices");
+    if (items[i].circular_mask >> items[i].bd->D)
+      return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: circular_mask names a dimension the densities do not have");
   }
   const int device = items[0].bd->device;
   DeviceGuard guard;
@@ -1617,6 +1769,7 @@ extern "C" int kdehip_eval_avg_logl_device_batch(int n, const kdehip_logl_item *
   for (int i = 0; i < n; ++i) {
     run.items.push_back(pair_item(items[i].bd, items[i].at, items[i].leave_one_out, true));
     run.items.back().logl = d_out + i;
+    run.circ.push_back(items[i].circular_mask);
   }
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
@@ -1625,14 +1778,22 @@ extern "C" int kdehip_eval_avg_logl_device_batch(int n, const kdehip_logl_item *
 
 extern "C" int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
                                            double *out) {
+  return kdehip_eval_avg_logl_device_manifold(bd, at, leave_one_out, out, nullptr);
+}
+
+extern "C" int kdehip_eval_avg_logl_device_manifold(const kdehip_device_density *bd, const kdehip_device_density *at,
+                                                    int leave_one_out, double *out, const uint8_t *manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
   int rc = check_pair(bd, at, leave_one_out);
   if (rc != KDEHIP_OK) return rc;
+  unsigned circ = 0;
+  if (manifold_mask(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;
   LoglRun run;
   run.items.push_back(pair_item(bd, at, leave_one_out, true));
+  run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   run.items[0].logl = run.result(0);
   KDEHIP_CHECK_RC(run.enqueue(hipStreamPerThread));
@@ -1643,11 +1804,18 @@ extern "C" int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, cons
 
 extern "C" int kdehip_evaluate_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,
                                       double *d_out, void *stream) {
+  return kdehip_evaluate_device_manifold(bd, d_pos, Nq, leave_one_out, d_out, stream, nullptr);
+}
+
+extern "C" int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, const double *d_pos, int64_t Nq,
+                                               int leave_one_out, double *d_out, void *stream, const uint8_t *manifold) {
   if (!bd || !d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  if (leave_one_out) return kdehip_evaluate_device_at(bd, bd, d_out, stream);
+  if (leave_one_out) return kdehip_evaluate_device_at_manifold(bd, bd, d_out, stream, manifold);
   if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
   int rc = check_pair(bd, bd, 0);
   if (rc != KDEHIP_OK) return rc;
+  unsigned circ = 0;
+  if (manifold_mask(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
   rc = guard.enter(bd->device);
@@ -1656,6 +1824,7 @@ extern "C" int kdehip_evaluate_device(const kdehip_device_density *bd, const dou
   LoglItem it = pair_item(bd, bd, 0, false);
   it.qry = d_pos; it.perm = nullptr; it.Nq = Nq; it.out = d_out;
   run.items.push_back(it);
+  run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
   return run.defer(bd->device);
@@ -1663,9 +1832,16 @@ extern "C" int kdehip_evaluate_device(const kdehip_device_density *bd, const dou
 
 extern "C" int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out,
                                          void *stream) {
+  return kdehip_evaluate_device_at_manifold(bd, at, d_out, stream, nullptr);
+}
+
+extern "C" int kdehip_evaluate_device_at_manifold(const kdehip_device_density *bd, const kdehip_device_density *at,
+                                                  double *d_out, void *stream, const uint8_t *manifold) {
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   int rc = check_pair(bd, at, at == bd);
   if (rc != KDEHIP_OK) return rc;
+  unsigned circ = 0;
+  if (manifold_mask(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;
@@ -1673,6 +1849,7 @@ extern "C" int kdehip_evaluate_device_at(const kdehip_device_density *bd, const 
   LoglItem it = pair_item(bd, at, at == bd, false);
   it.out = d_out;
   run.items.push_back(it);
+  run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
   return run.defer(bd->device);

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "circ_wrap.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
 #include "philox.hpp"
@@ -369,15 +370,6 @@ struct EvalFast {
     return eval<kdehip_f2>(r);
   }
 };
-
-// The circular (2 pi) member of the enumerated manifolds (include/kdehip.h "manifolds"; no reference counterpart -- the
-// reference takes its operators as callbacks, src/MSGibbs01.jl:650-653): wrap to [-pi, pi).  Same expression, same
-// constants as oracle/kde_oracle.c circ_wrap (fp64: bit for bit).
-template <typename T>
-__device__ __forceinline__ T circ_wrap(T t) {
-  constexpr double kTwoPi = 6.283185307179586476925286766559, kPi = 3.141592653589793238462643383279;
-  return t - T(kTwoPi) * floor((t + T(kPi)) / T(kTwoPi));
-}
 
 // GENERIC: literally the reference's accumulation (:280-303) incl. inactive dimensions; `circ` bit d = the difference of
 // dimension d is the circular diffop (:290).

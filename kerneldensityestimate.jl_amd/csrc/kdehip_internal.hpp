@@ -345,7 +345,8 @@ int launch_tables_batch(int D, const PlanDev &plan, const RunArgs &args, void *s
 // (kLoocvPrepMaxN: marginals up to this size are prepared by the device from the matrix as it is -- no host copy needed.)
 constexpr int64_t kLoocvPrepMaxN = 2048;
 int auto_bandwidth_run(int D, int64_t N, const double *points, const double *d_points, void *stream, double *bw_out,
-                       int32_t *nevals_out, const std::function<void()> *overlap = nullptr);
+                       int32_t *nevals_out, const std::function<void()> *overlap = nullptr, unsigned circ_mask = 0);
+// (circ_mask: bit k = the leave-one-out likelihoods of dimension k's search take circular differences; evaluate.hip)
 
 // Chains per workgroup (= wavefronts per CU, one workgroup per CU at a time) of a sampling launch: 4, 8 or 16,
 // the width with the smallest estimated time rounds(width) * cost(width) unless `variant` pins it

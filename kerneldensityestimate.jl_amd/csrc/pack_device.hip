@@ -380,12 +380,25 @@ extern "C" int kdehip_density_upload(kdehip_device_density **out, const kdehip_d
 // link: 8*D*N bytes down, the density's block up; the caller's host never sees either.
 extern "C" int kdehip_density_from_device_points(kdehip_device_density **out, const double *d_points, int64_t D,
                                                  int64_t N, int device, void *stream, double *bw_out, int32_t *nevals) {
+  return kdehip_density_from_device_points_manifold(out, d_points, D, N, device, stream, bw_out, nevals, nullptr);
+}
+
+// (manifold: the bandwidth search's likelihoods wrap in the circular dimensions; the tree is the Euclidean builder's)
+extern "C" int kdehip_density_from_device_points_manifold(kdehip_device_density **out, const double *d_points, int64_t D,
+                                                          int64_t N, int device, void *stream, double *bw_out,
+                                                          int32_t *nevals, const uint8_t *manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (!d_points) return set_error(KDEHIP_ERR_ARG, "null points");
   int rc = check_shape(N, D);
   if (rc != KDEHIP_OK) return rc;
   if (N < 2) return set_error(KDEHIP_ERR_ARG, "kde!(points) needs at least two points");
+  unsigned circ = 0;
+  for (int64_t k = 0; manifold && k < D && k < KDEHIP_MAX_DIMS; ++k) {
+    if (manifold[k] == KDEHIP_MANIFOLD_CIRCULAR) circ |= 1u << k;
+    else if (manifold[k] != KDEHIP_MANIFOLD_EUCLIDEAN)
+      return set_error(KDEHIP_ERR_ARG, "manifold: every entry is KDEHIP_MANIFOLD_EUCLIDEAN or KDEHIP_MANIFOLD_CIRCULAR");
+  }
   DeviceGuard guard;
   rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -483,7 +496,7 @@ extern "C" int kdehip_density_from_device_points(kdehip_device_density **out, co
   if (under) {
     try {
       const std::function<void()> fn = host_side;
-      rc = auto_bandwidth_run(static_cast<int>(D), N, nullptr, d_points, cs, bw, nevals, &fn);
+      rc = auto_bandwidth_run(static_cast<int>(D), N, nullptr, d_points, cs, bw, nevals, &fn, circ);
     } catch (const std::exception &e) {
       return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_density_from_device_points: ") + e.what());
     }
@@ -496,7 +509,7 @@ extern "C" int kdehip_density_from_device_points(kdehip_device_density **out, co
         tree_rc = kdehip_make_density(D, N, pts, &one, 1, nullptr, centers, ranges, weights, left, right, lowest, highest,
                                       perm, means, bandwidth, bwmin, bwmax);
       });
-      rc = auto_bandwidth_run(static_cast<int>(D), N, pts, d_points, cs, bw, nevals);
+      rc = auto_bandwidth_run(static_cast<int>(D), N, pts, d_points, cs, bw, nevals, nullptr, circ);
       group.wait();
     } catch (const std::exception &e) {
       return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_density_from_device_points: ") + e.what());

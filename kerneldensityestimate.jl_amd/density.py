@@ -43,9 +43,9 @@ class BallTreeDensity:
         return cs
 
     # `bd(pos)`: evaluate the density at points (reference functor, src/DualTree01.jl:431-446)
-    def __call__(self, pos, lvFlag=False, errTol=1e-3):
+    def __call__(self, pos, lvFlag=False, errTol=1e-3, manifold=None):
         from .bandwidth import evaluateDualTree
-        return evaluateDualTree(self, pos, lvFlag, errTol)
+        return evaluateDualTree(self, pos, lvFlag, errTol, manifold=manifold)
 
     # `p1 * p2` / `*([p1, p2, ...])`, reference src/MSGibbs01.jl:707-736
     def __mul__(self, other):
@@ -100,7 +100,7 @@ def _empty_density(D, N) -> BallTreeDensity:
     return bd
 
 
-def kde(points, ks=None, weights=None, device=None) -> BallTreeDensity:
+def kde(points, ks=None, weights=None, device=None, manifold=None) -> BallTreeDensity:
     """`kde!(points, ks)` / `kde!(points, ks, weights)` (reference src/KDE01.jl:34-84); with ks=None the
     automatic LOOCV bandwidth `kde!(points)` (src/KDE01.jl:3-27, GPU).
 
@@ -108,12 +108,17 @@ def kde(points, ks=None, weights=None, device=None) -> BallTreeDensity:
     DEVIATION, one entry (repeated over dimensions, :41-43) or D entries.  weights: N values,
     normalised to sum 1 (:46); default ones (:67).  device: None = the host builder (csrc/balltree.cpp);
     a HIP ordinal = the GPU builder (csrc/treebuild.hip, bit-identical arrays) where the density fits it.
+    manifold: only with ks=None -- the bandwidth search of a circular dimension wraps its differences (the tree is the
+    Euclidean builder's).  With an explicit bandwidth there is no search to make circular: ValueError.
     """
     if ks is None:
         if weights is not None:
             raise ValueError("kde!(points) with automatic bandwidth takes no weights")
         from .bandwidth import kde_auto
-        return kde_auto(points, device=0 if device is None else device)
+        return kde_auto(points, device=0 if device is None else device, manifold=manifold)
+    if manifold is not None:
+        raise ValueError("kde(points, ks, manifold=...): an explicit bandwidth leaves nothing to search on the circle, and "
+                         "the tree builder is Euclidean")
     if device is not None:
         return kde_batch([(points, ks, weights)], device=device)[0]
     D, N, flat, ks, w = _prepare(points, ks, weights)

@@ -408,6 +408,81 @@ function evaluateDualTree(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, lvF
   return out
 end
 
+# per-dimension manifold enum of include/kdehip.h: a vector of 0 / 1 or :euclid / :circular, one per dimension
+function manifold_bytes(manifold, D::Int)
+  length(manifold) == D || error("manifold needs one entry per dimension")
+  return UInt8[(m === :circular || m == 1) ? 0x01 : ((m === :euclid || m == 0) ? 0x00 : error("manifold entries are :euclid or :circular")) for m in manifold]
+end
+
+"""
+    hip_evaluateDualTree(bd, pos, manifold, lvFlag=false; device=0)
+
+`evaluateDualTree` with circular differences in the dimensions `manifold` marks (`kdehip_evaluate_manifold`,
+include/kdehip.h section 5d: `wrap(a - b)` before the square, nothing else changes).  The circular semantic is the
+library's own; a caller's `diffop` need not be it, so this is not installed by `enable!()`.
+"""
+function hip_evaluateDualTree(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, manifold::AbstractVector, lvFlag::Bool=false;
+                              device::Int=0)
+  Ndim(bd) == size(pos, 1) || error("bd and pos must have the same dimension")
+  man = manifold_bytes(manifold, Ndim(bd))
+  Nq = lvFlag ? Npts(bd) : size(pos, 2)
+  out = zeros(Nq)
+  cd = Ref(CDensity(bd))
+  posd = Matrix{Float64}(pos)
+  GC.@preserve bd posd man begin
+    check(ccall((:kdehip_evaluate_manifold, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Cint, Ptr{UInt8}),
+                cd, posd, size(pos, 2), lvFlag ? 1 : 0, out, device, man))
+  end
+  return out
+end
+
+"""
+    hip_evalAvgLogL(bd1, bd2, manifold; device=0)
+
+`evalAvgLogL` with circular differences in the marked dimensions (`kdehip_eval_avg_logl_manifold`); `hip_entropy`,
+`hip_kld` and `hip_minkld` with a manifold are its compositions.  Not installed by `enable!()`.
+"""
+function hip_evalAvgLogL(bd1::BallTreeDensity, bd2::BallTreeDensity, manifold::AbstractVector; device::Int=0)
+  Ndim(bd1) == Ndim(bd2) || error("evaluate -- dimensions of two BallTreeDensities must match")
+  man = manifold_bytes(manifold, Ndim(bd1))
+  loo = bd1 === bd2
+  c1 = Ref(CDensity(bd1))
+  c2 = loo ? c1 : Ref(CDensity(bd2))
+  out = Ref{Float64}(0.0)
+  GC.@preserve bd1 bd2 man begin
+    check(ccall((:kdehip_eval_avg_logl_manifold, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Cint, Ptr{Float64}, Cint, Ptr{UInt8}),
+                c1, c2, loo ? 1 : 0, out, device, man))
+  end
+  return out[]
+end
+hip_entropy(bd::BallTreeDensity, manifold::AbstractVector; device::Int=0) = -hip_evalAvgLogL(bd, bd, manifold; device=device)
+hip_kld(p1::BallTreeDensity, p2::BallTreeDensity, manifold::AbstractVector; device::Int=0) =
+  hip_evalAvgLogL(p1, p1, manifold; device=device) - hip_evalAvgLogL(p2, p1, manifold; device=device)
+hip_minkld(p::BallTreeDensity, q::BallTreeDensity, manifold::AbstractVector; device::Int=0) =
+  min(abs(hip_kld(p, q, manifold; device=device)), abs(hip_kld(q, p, manifold; device=device)))
+
+"""
+    hip_auto_bandwidth(points, manifold; device=0)
+
+The bandwidth of `kde!(points, addop, diffop)` with the library's circular `diffop` in the marked dimensions
+(`kdehip_auto_bandwidth_manifold`): only the leave-one-out likelihoods of the search wrap, as in the reference.
+"""
+function hip_auto_bandwidth(points::AbstractMatrix{Float64}, manifold::AbstractVector; device::Int=0)
+  D, N = size(points)
+  man = manifold_bytes(manifold, D)
+  bw = zeros(D)
+  nev = Ref{Int32}(0)
+  pts = Matrix{Float64}(points)
+  GC.@preserve man begin
+    check(ccall((:kdehip_auto_bandwidth_manifold, libkdehip), Cint,
+                (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}, Cint, Ptr{UInt8}),
+                D, N, pts, bw, nev, device, man))
+  end
+  return bw
+end
+
 """
     hip_sample(bd, Npts[, ind]; seed=nothing, sample_offset=0, device=0) -> (points, ind)
 

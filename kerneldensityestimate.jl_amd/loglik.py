@@ -30,7 +30,16 @@ def _dims(d):
     return d.bt.dims if isinstance(d, BallTreeDensity) else d.dims
 
 
-def evalAvgLogL(bd1, bd2, *, device=0) -> float:
+def _man(manifold, ndims):
+    from .product import _manifold_array
+    return _manifold_array(manifold, ndims)
+
+
+def _mask(man):
+    return 0 if man is None else int(sum(int(v) << k for k, v in enumerate(man)))
+
+
+def evalAvgLogL(bd1, bd2, *, device=0, manifold=None) -> float:
     """`evalAvgLogL(bd1, bd2)` (src/DualTree01.jl:450-470): sum over bd2's points of W log L, L = bd1 at those points
     (leave-one-out when `bd1 is bd2`), W = bd2's weights; -inf when an L == 0 carries weight."""
     kind = _kind(bd1, bd2)
@@ -38,21 +47,23 @@ def evalAvgLogL(bd1, bd2, *, device=0) -> float:
         raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
     out = C.c_double(0.0)
     loo = 1 if bd1 is bd2 else 0
+    man = _man(manifold, _dims(bd1))  # (circular differences in those dimensions: include/kdehip.h section 5d)
+    mp = None if man is None else _lib.ptr(man, _lib.u8p)
     if kind == "host":
         c1 = bd1._cstruct()
         c2 = c1 if loo else bd2._cstruct()
-        _lib.check(_lib.lib.kdehip_eval_avg_logl(C.byref(c1), C.byref(c2), loo, C.byref(out), int(device)))
+        _lib.check(_lib.lib.kdehip_eval_avg_logl_manifold(C.byref(c1), C.byref(c2), loo, C.byref(out), int(device), mp))
     else:
-        _lib.check(_lib.lib.kdehip_eval_avg_logl_device(bd1._h, bd2._h, loo, C.byref(out)))
+        _lib.check(_lib.lib.kdehip_eval_avg_logl_device_manifold(bd1._h, bd2._h, loo, C.byref(out), mp))
     return float(out.value)
 
 
-def entropy(bd, *, device=0) -> float:
+def entropy(bd, *, device=0, manifold=None) -> float:
     """`entropy(bd)` (src/DualTree01.jl:505-508) = -evalAvgLogL(bd, bd)."""
-    return -evalAvgLogL(bd, bd, device=device)
+    return -evalAvgLogL(bd, bd, device=device, manifold=manifold)
 
 
-def kld(p1, p2, method="direct", *, device=0) -> float:
+def kld(p1, p2, method="direct", *, device=0, manifold=None) -> float:
     """`kld(p1, p2; method=:direct)` (src/DualTree01.jl:477-503) = evalAvgLogL(p1, p1) - evalAvgLogL(p2, p1)."""
     if method != "direct":
         raise ValueError(f"kld: method {method!r} is not supported (only 'direct'; the reference's 'unscented' builds "
@@ -60,32 +71,37 @@ def kld(p1, p2, method="direct", *, device=0) -> float:
     _kind(p1, p2)
     if _dims(p1) != _dims(p2):
         raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
-    return evalAvgLogL(p1, p1, device=device) - evalAvgLogL(p2, p1, device=device)
+    return evalAvgLogL(p1, p1, device=device, manifold=manifold) - evalAvgLogL(p2, p1, device=device, manifold=manifold)
 
 
-def minkld(p, q, *, device=0) -> float:
+def minkld(p, q, *, device=0, manifold=None) -> float:
     """`minkld(p, q)` (src/DualTree01.jl:510) = min(|kld(p, q)|, |kld(q, p)|)."""
-    return min(abs(kld(p, q, device=device)), abs(kld(q, p, device=device)))
+    return min(abs(kld(p, q, device=device, manifold=manifold)), abs(kld(q, p, device=device, manifold=manifold)))
 
 
-def eval_avg_logl_device_batch(pairs, d_out, stream=None):
+def eval_avg_logl_device_batch(pairs, d_out, stream=None, manifolds=None):
     """evalAvgLogL of many (bd, at) DeviceDensity pairs in ONE call (kdehip_eval_avg_logl_device_batch): d_out[i] (a
     float64 device tensor or address of len(pairs) doubles) = evalAvgLogL(bd_i, at_i), leave-one-out where `bd_i is
-    at_i`.  Enqueues on `stream` and returns."""
+    at_i`.  `manifolds`: None, or one manifold (or None) per pair.  Enqueues on `stream` and returns."""
     from .product import DeviceDensity, ProductPlan
     pairs = list(pairs)
     n = len(pairs)
-    arr = (_lib.CLoglItem * max(1, n))()
+    if manifolds is not None and len(manifolds) != n:
+        raise ValueError("eval_avg_logl_device_batch: one manifold per pair")
+    arr = (_lib.CLoglManifoldItem * max(1, n))()
     for k, (bd, at) in enumerate(pairs):
         if not (isinstance(bd, DeviceDensity) and isinstance(at, DeviceDensity)):
             raise TypeError("eval_avg_logl_device_batch: pairs of DeviceDensity")
         arr[k].bd, arr[k].at, arr[k].leave_one_out = bd._h, at._h, 1 if bd is at else 0
-    _lib.check(_lib.lib.kdehip_eval_avg_logl_device_batch(n, arr, ProductPlan._addr(d_out), ProductPlan._addr(stream)))
+        arr[k].circular_mask = 0 if manifolds is None else _mask(_man(manifolds[k], bd.dims))
+    _lib.check(_lib.lib.kdehip_eval_avg_logl_device_batch_manifold(n, arr, ProductPlan._addr(d_out),
+                                                                   ProductPlan._addr(stream)))
 
 
-def kld_batch(pairs):
+def kld_batch(pairs, manifold=None, manifolds=None):
     """kld(p_i, q_i) for many DeviceDensity pairs: ONE batch call of 2n items (evalAvgLogL(p, p), evalAvgLogL(q, p) per
-    pair), one synchronisation; returns a numpy array of n values, each bit for bit `kld(p_i, q_i)`."""
+    pair), one synchronisation; returns a numpy array of n values, each bit for bit `kld(p_i, q_i)`.  `manifold`: one for
+    all pairs; `manifolds`: one (or None) per pair."""
     from .product import DeviceDensity
     pairs = [(p, q) for p, q in pairs]
     n = len(pairs)
@@ -98,13 +114,19 @@ def kld_batch(pairs):
             raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
     import torch
     dev = torch.device("cuda", pairs[0][0].device)
-    items = []
-    for p, q in pairs:
+    if manifold is not None and manifolds is not None:
+        raise ValueError("kld_batch: manifold= (one for all pairs) or manifolds= (one per pair), not both")
+    if manifolds is not None and len(manifolds) != n:
+        raise ValueError("kld_batch: one manifold per pair")
+    per = [manifold] * n if manifolds is None else list(manifolds)
+    items, mans = [], []
+    for (p, q), m in zip(pairs, per):
         items += [(p, p), (q, p)]
+        mans += [m, m]
     out = torch.empty(2 * n, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev)
-        eval_avg_logl_device_batch(items, out, stream=st.cuda_stream)
+        eval_avg_logl_device_batch(items, out, stream=st.cuda_stream, manifolds=mans)
         st.synchronize()
     v = out.cpu().numpy()
     return v[0::2] - v[1::2]

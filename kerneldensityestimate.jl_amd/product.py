@@ -230,16 +230,18 @@ class DeviceDensity:
         self.nevals = None  # likelihood evaluations of that search
 
     @classmethod
-    def from_device_points(cls, d_points, D, N, device=0, stream=None):
+    def from_device_points(cls, d_points, D, N, device=0, stream=None, manifold=None):
         """`kde!(points)` (reference src/KDE01.jl:3-27) of a D x N column-major matrix that lives in HBM (a torch tensor or
         an address; `stream` = the stream that produced it): LOOCV bandwidth search on the device matrix, ball tree from one
-        copy that comes down meanwhile, the density's block straight back up (kdehip_density_from_device_points)."""
+        copy that comes down meanwhile, the density's block straight back up (kdehip_density_from_device_points).
+        `manifold`: the bandwidth search of a circular dimension wraps its differences (the tree stays Euclidean)."""
         h = C.c_void_p()
         bw = np.empty(int(D))
         ne = C.c_int32(0)
-        _lib.check(_lib.lib.kdehip_density_from_device_points(C.byref(h), ProductPlan._addr(d_points), int(D), int(N),
-                                                              int(device), ProductPlan._addr(stream), ptr(bw, f64p),
-                                                              C.byref(ne)))
+        man = _manifold_array(manifold, int(D))
+        _lib.check(_lib.lib.kdehip_density_from_device_points_manifold(
+            C.byref(h), ProductPlan._addr(d_points), int(D), int(N), int(device), ProductPlan._addr(stream), ptr(bw, f64p),
+            C.byref(ne), None if man is None else ptr(man, u8p)))
         out = cls(device=device, _handle=h)
         out.bw, out.nevals = bw, int(ne.value)
         return out
@@ -259,15 +261,18 @@ class DeviceDensity:
     def __mul__(self, other):
         return mul_device([self, other])
 
-    def evaluate(self, pos=None, lvFlag=False):
+    def evaluate(self, pos=None, lvFlag=False, manifold=None):
         """`evaluateDualTree(bd, pos, lvFlag)` (reference src/DualTree01.jl:370-421, FORCE_EVAL_DIRECT) on the device
         (kdehip_evaluate_device / kdehip_evaluate_device_at): every value is bit for bit what `evaluateDualTree` gives on the
         density's host arrays.  `pos`: a (D, Nq) numpy array -- values in query order, as a numpy array --, a float64 (D, Nq)
         torch tensor on the density's device -- a device tensor, enqueued on the current torch stream --, or a DeviceDensity
         -- values at its points in ITS original order (getPoints order), as a numpy array.  `pos is self` or lvFlag=True:
-        leave-one-out at the density's own points, original order."""
+        leave-one-out at the density's own points, original order.  `manifold`: circular differences in those dimensions
+        (include/kdehip.h section 5d)."""
         import torch
         dev = torch.device("cuda", self.device)
+        man = _manifold_array(manifold, self.dims)
+        mp = None if man is None else ptr(man, u8p)
         if lvFlag:
             pos = self
         if pos is None:
@@ -278,7 +283,8 @@ class DeviceDensity:
                 if pos.dims != self.dims:
                     raise ValueError("bd and pos must have the same dimension")
                 out = torch.empty(max(1, pos.num_points), dtype=torch.float64, device=dev)
-                _lib.check(_lib.lib.kdehip_evaluate_device_at(self._h, pos._h, ProductPlan._addr(out), ProductPlan._addr(st.cuda_stream)))
+                _lib.check(_lib.lib.kdehip_evaluate_device_at_manifold(self._h, pos._h, ProductPlan._addr(out),
+                                                                       ProductPlan._addr(st.cuda_stream), mp))
                 st.synchronize()
                 return out.cpu().numpy()[:pos.num_points].copy()
             tensor = hasattr(pos, "data_ptr")
@@ -291,15 +297,15 @@ class DeviceDensity:
             # column-major D x Nq = the (Nq, D) row-major array
             flat = P.t().contiguous().to(dev, torch.float64) if tensor else torch.from_numpy(np.ascontiguousarray(P.T)).to(dev)
             out = torch.empty(max(1, Nq), dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib.kdehip_evaluate_device(self._h, ProductPlan._addr(flat), Nq, 0, ProductPlan._addr(out),
-                                                       ProductPlan._addr(st.cuda_stream)))
+            _lib.check(_lib.lib.kdehip_evaluate_device_manifold(self._h, ProductPlan._addr(flat), Nq, 0, ProductPlan._addr(out),
+                                                                ProductPlan._addr(st.cuda_stream), mp))
             if tensor:
                 return out[:Nq]
             st.synchronize()
             return out.cpu().numpy()[:Nq].copy()
 
-    def __call__(self, pos=None, lvFlag=False):
-        return self.evaluate(pos, lvFlag)
+    def __call__(self, pos=None, lvFlag=False, manifold=None):
+        return self.evaluate(pos, lvFlag, manifold=manifold)
 
     def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None):
         """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):
