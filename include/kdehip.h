@@ -497,7 +497,7 @@ int kdehip_evaluate(const kdehip_density *bd, const double *pos, int64_t Nq, int
  * `ksize` of the 1-D marginal = golden-section search (tol 1e-2) over the leave-one-out
  * log-likelihood (src/CrossValidation.jl:15-120).  points: D x N column-major; bw_out: D standard
  * deviations; nevals (optional): number of likelihood evaluations -- the reference's count: for the smaller marginals
- * the search evaluates the two possible successors of the point in flight in the same launch (csrc/evaluate.hip
+ * the search evaluates the two possible successors of the point in flight in the same launch (csrc/loocv.hip
  * loo_round_spec_kernel); the ones golden does not ask for are neither booked nor counted. */
 int kdehip_auto_bandwidth(int64_t D, int64_t N, const double *points, double *bw_out, int32_t *nevals,
                           int device);

@@ -1,0 +1,85 @@
+// entry_helpers.hpp -- the small things every file of entry points (evaluate, loocv, summary, sample, treebuild,
+// pack_device, product) used to define for itself.  Not in kdehip_internal.hpp: that header is part of every sampler
+// translation unit and holds declarations only (hip_runtime_api.h); this one has macros and device code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <type_traits>
+
+#include "kdehip_internal.hpp"
+
+// a HIP call that fails ends the entry point with KDEHIP_ERR_HIP and the call's text
+#define KDEHIP_CHECK(expr)                                                                  \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return set_error(KDEHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+// a step that has already set its own message
+#define KDEHIP_CHECK_RC(expr)          \
+  do {                                 \
+    const int rc_ = (expr);            \
+    if (rc_ != KDEHIP_OK) return rc_;  \
+  } while (0)
+
+namespace kdehip {
+
+// the item that owns global block b: the last i with first[i] <= b (first[] ascending, first[n] = the number of blocks)
+__device__ __forceinline__ int item_of_block(const int32_t *__restrict__ first, int n, int b) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// f(std::integral_constant<int, D>) for a run-time D in 1..KDEHIP_MAX_DIMS: the way into a `template <int D>` launcher
+template <typename F>
+int dispatch_dims(int D, F &&f) {
+  static_assert(KDEHIP_MAX_DIMS == 8, "one case per dimension count");
+  switch (D) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  }
+  return KDEHIP_OK;
+}
+
+// Device scratch of one call from the library's allocation cache (devmem.cpp).  It goes back when the call returns, so the
+// work that uses it must be over by then.
+struct DevBuf {
+  void *p = nullptr;
+  size_t n = 0;
+  ~DevBuf() { if (p) cached_free(p, n); }
+  hipError_t alloc(size_t bytes) { n = bytes ? bytes : 1; return cached_malloc(&p, n); }
+  template <typename T> T *as() { return static_cast<T *>(p); }
+};
+
+// At most this many partial sums per query in the all-pairs sums of the evaluation and of the bandwidth search
+// (scratch = 64 * Nq doubles).
+constexpr int kEvalMaxGroups = 64;
+
+// The per-dimension manifold enum of include/kdehip.h as a mask (bit k = dimension k is circular); NULL = all Euclidean.
+// Checked before any device is touched: a byte other than 0 / 1 is KDEHIP_ERR_ARG.
+inline int manifold_mask(const uint8_t *manifold, int64_t D, unsigned *mask) {
+  *mask = 0;
+  if (!manifold || D < 1 || D > KDEHIP_MAX_DIMS) return KDEHIP_OK;  // (a bad D is the caller's own refusal)
+  for (int64_t k = 0; k < D; ++k) {
+    if (manifold[k] == KDEHIP_MANIFOLD_CIRCULAR) *mask |= 1u << k;
+    else if (manifold[k] != KDEHIP_MANIFOLD_EUCLIDEAN)
+      return set_error(KDEHIP_ERR_ARG, "manifold: every entry is KDEHIP_MANIFOLD_EUCLIDEAN or KDEHIP_MANIFOLD_CIRCULAR");
+  }
+  return KDEHIP_OK;
+}
+
+}  // namespace kdehip

@@ -338,7 +338,7 @@ int launch_gibbs(int precision, int mode, const PlanDev &plan, const RunArgs &ar
 int launch_gibbs_batch(int D, int M, const PlanDev &plan, const RunArgs &args, void *stream);
 int launch_tables_batch(int D, const PlanDev &plan, const RunArgs &args, void *stream);
 
-// kde!(points)'s LOOCV bandwidth search (evaluate.hip) on `stream` of the current device, from the host's copy of the
+// kde!(points)'s LOOCV bandwidth search (loocv.hip) on `stream` of the current device, from the host's copy of the
 // D x N matrix and/or a copy that already lives in HBM (`d_points`: nothing is uploaded then).  Blocking.
 // `overlap` (optional) is called ONCE, on the calling thread, after the preparation and the first batch of rounds have
 // been enqueued and before the host waits for them: work that needs the host but not the bandwidth runs under the search.
@@ -346,7 +346,7 @@ int launch_tables_batch(int D, const PlanDev &plan, const RunArgs &args, void *s
 constexpr int64_t kLoocvPrepMaxN = 2048;
 int auto_bandwidth_run(int D, int64_t N, const double *points, const double *d_points, void *stream, double *bw_out,
                        int32_t *nevals_out, const std::function<void()> *overlap = nullptr, unsigned circ_mask = 0);
-// (circ_mask: bit k = the leave-one-out likelihoods of dimension k's search take circular differences; evaluate.hip)
+// (circ_mask: bit k = the leave-one-out likelihoods of dimension k's search take circular differences; loocv.hip)
 
 // Chains per workgroup (= wavefronts per CU, one workgroup per CU at a time) of a sampling launch: 4, 8 or 16,
 // the width with the smallest estimated time rounds(width) * cost(width) unless `variant` pins it

@@ -1,5 +1,5 @@
 // loocv_search.hpp -- the LOOCV bandwidth search of kde!(points) (src/KDE01.jl:3-27, src/CrossValidation.jl:15-120) as
-// non-blocking pieces (evaluate.hip), for callers that keep several searches in flight (pack_device.hip).
+// non-blocking pieces (loocv.hip), for callers that keep several searches in flight (pack_device.hip).
 #pragma once
 #include <cstdint>
 

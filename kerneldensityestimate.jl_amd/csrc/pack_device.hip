@@ -26,18 +26,12 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "entry_helpers.hpp"
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
 #include "loocv_search.hpp"
 
 using namespace kdehip;
-
-#define KDEHIP_CHECK(expr)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_error(KDEHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace kdehip {
 

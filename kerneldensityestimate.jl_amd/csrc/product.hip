@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
 
@@ -51,13 +52,6 @@ struct kdehip_product {
 };
 
 namespace {
-
-#define KDEHIP_CHECK(expr)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_error(KDEHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // The stream of the BLOCKING entry points (host buffers in and out): the calling thread's own stream.  On the legacy
 // null stream the calls of concurrent host threads -- a multi-threaded belief-propagation host issues many small

@@ -20,17 +20,11 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "philox.hpp"
 
 using namespace kdehip;
-
-#define KDEHIP_CHECK(expr)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_error(KDEHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -214,11 +208,7 @@ __global__ __launch_bounds__(kDrawBlock) void sample_batch_kernel(const SampleIt
   __shared__ double stage[kDrawBlock * D];
   __shared__ double lds_cdf[kLdsCdf];
   const int b = blockIdx.x;
-  int lo = 0, hi = nitems - 1;  // the last item with first[i] <= b
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (first[mid] <= b) lo = mid; else hi = mid - 1;
-  }
+  const int lo = item_of_block(first, nitems, b);
   const SampleItem it = items[lo];
   const int64_t nb = first[lo + 1] - first[lo];
   const double *cdf = stage_cdf(it, lds_cdf);
@@ -230,42 +220,24 @@ int blocks_for(int64_t Npts) {
   return static_cast<int>(t < kMaxBlocksPerItem ? t : kMaxBlocksPerItem);
 }
 
-template <int D>
-void launch_one(const SampleItem &it, hipStream_t st) {
-  hipLaunchKernelGGL(sample_kernel<D>, dim3(blocks_for(it.Npts)), dim3(kDrawBlock), 0, st, it);
-}
+// device scratch of a blocking call whose work runs on the calling thread's stream: an error return waits for what has
+// been enqueued before the block goes back to the cache
+struct SyncedDevBuf : DevBuf {
+  ~SyncedDevBuf() { if (p) (void)hipStreamSynchronize(hipStreamPerThread); }
+};
+
 int launch_draw(int D, const SampleItem &it, hipStream_t st) {
-  switch (D) {
-    case 1: launch_one<1>(it, st); break;
-    case 2: launch_one<2>(it, st); break;
-    case 3: launch_one<3>(it, st); break;
-    case 4: launch_one<4>(it, st); break;
-    case 5: launch_one<5>(it, st); break;
-    case 6: launch_one<6>(it, st); break;
-    case 7: launch_one<7>(it, st); break;
-    case 8: launch_one<8>(it, st); break;
-    default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  }
+  KDEHIP_CHECK_RC(dispatch_dims(D, [&](auto dim) {
+    hipLaunchKernelGGL(sample_kernel<decltype(dim)::value>, dim3(blocks_for(it.Npts)), dim3(kDrawBlock), 0, st, it);
+  }));
   KDEHIP_CHECK(hipGetLastError());
   return KDEHIP_OK;
 }
 
-template <int D>
-void launch_many(const SampleItem *d_items, const int32_t *d_first, int n, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL(sample_batch_kernel<D>, dim3(blocks), dim3(kDrawBlock), 0, st, d_items, d_first, n);
-}
 int launch_draw_batch(int D, const SampleItem *d_items, const int32_t *d_first, int n, int blocks, hipStream_t st) {
-  switch (D) {
-    case 1: launch_many<1>(d_items, d_first, n, blocks, st); break;
-    case 2: launch_many<2>(d_items, d_first, n, blocks, st); break;
-    case 3: launch_many<3>(d_items, d_first, n, blocks, st); break;
-    case 4: launch_many<4>(d_items, d_first, n, blocks, st); break;
-    case 5: launch_many<5>(d_items, d_first, n, blocks, st); break;
-    case 6: launch_many<6>(d_items, d_first, n, blocks, st); break;
-    case 7: launch_many<7>(d_items, d_first, n, blocks, st); break;
-    case 8: launch_many<8>(d_items, d_first, n, blocks, st); break;
-    default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  }
+  KDEHIP_CHECK_RC(dispatch_dims(D, [&](auto dim) {
+    hipLaunchKernelGGL(sample_batch_kernel<decltype(dim)::value>, dim3(blocks), dim3(kDrawBlock), 0, st, d_items, d_first, n);
+  }));
   KDEHIP_CHECK(hipGetLastError());
   return KDEHIP_OK;
 }
@@ -300,16 +272,12 @@ int build_tables(const std::vector<kdehip_device_density *> &hs) {
     jobs[q] = TableJob{h->weights + h->N, h->perm + h->N, h->N, reinterpret_cast<double *>(b),
                        reinterpret_cast<int32_t *>(b + cl.o_inv), reinterpret_cast<int32_t *>(b + cl.o_status)};
   }
-  struct Scratch {
-    void *d = nullptr; size_t n = 0;
-    ~Scratch() { if (d) cached_free(d, n); }
-  } sj;
-  sj.n = sizeof(TableJob) * nj;
-  KDEHIP_CHECK(cached_malloc(&sj.d, sj.n));
+  DevBuf sj;
+  KDEHIP_CHECK(sj.alloc(sizeof(TableJob) * nj));
   std::vector<int32_t> status(nj, -1);
-  hipError_t e = hipMemcpyAsync(sj.d, jobs.data(), sj.n, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(sj.p, jobs.data(), sj.n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(cdf_build_kernel, dim3(static_cast<unsigned>(nj)), dim3(64), 0, st, static_cast<const TableJob *>(sj.d));
+    hipLaunchKernelGGL(cdf_build_kernel, dim3(static_cast<unsigned>(nj)), dim3(64), 0, st, static_cast<const TableJob *>(sj.p));
     e = hipGetLastError();
   }
   for (size_t q = 0; q < nj && e == hipSuccess; ++q)
@@ -464,13 +432,9 @@ extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t see
   const size_t o_inv = al(sizeof(double) * N), o_m = al(o_inv + sizeof(int32_t) * N), o_v = al(o_m + nd), o_in = al(o_v + nd),
                o_pts = al(o_in + (ind_in ? sizeof(int64_t) * Npts : 0)), o_ind = al(o_pts + sizeof(double) * Npts * D),
                total = al(o_ind + sizeof(int64_t) * Npts);
-  struct Scratch {
-    void *d = nullptr; size_t n = 0;
-    ~Scratch() { if (d) { (void)hipStreamSynchronize(hipStreamPerThread); cached_free(d, n); } }
-  } sc;
-  KDEHIP_CHECK(cached_malloc(&sc.d, total));
-  sc.n = total;
-  unsigned char *b = static_cast<unsigned char *>(sc.d);
+  SyncedDevBuf sc;
+  KDEHIP_CHECK(sc.alloc(total));
+  unsigned char *b = sc.as<unsigned char>();
   KDEHIP_CHECK(hipMemcpyAsync(b, C.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
   KDEHIP_CHECK(hipMemcpyAsync(b + o_inv, inv.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
   KDEHIP_CHECK(hipMemcpyAsync(b + o_m, p->means + N * D, nd, hipMemcpyHostToDevice, st));
@@ -594,15 +558,11 @@ extern "C" int kdehip_resample_device(kdehip_device_density **out, kdehip_device
   hipStream_t cs = hipStreamPerThread;
   const int D = p->D;
   auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  struct Scratch {
-    void *d = nullptr; size_t n = 0;
-    ~Scratch() { if (d) { (void)hipStreamSynchronize(hipStreamPerThread); cached_free(d, n); } }
-  } sc;
+  SyncedDevBuf sc;
   const size_t o_ind = al(sizeof(double) * Np * D);
-  KDEHIP_CHECK(cached_malloc(&sc.d, o_ind + sizeof(int64_t) * Np));
-  sc.n = o_ind + sizeof(int64_t) * Np;
-  double *d_pts = static_cast<double *>(sc.d);
-  int64_t *d_ind = reinterpret_cast<int64_t *>(static_cast<unsigned char *>(sc.d) + o_ind);
+  KDEHIP_CHECK(sc.alloc(o_ind + sizeof(int64_t) * Np));
+  double *d_pts = sc.as<double>();
+  int64_t *d_ind = reinterpret_cast<int64_t *>(sc.as<unsigned char>() + o_ind);
   rc = kdehip_sample_device(p, Np, seed, 0, nullptr, d_pts, d_ind, cs);
   if (rc != KDEHIP_OK) return rc;
   return kdehip_density_from_device_points(out, d_pts, D, Np, p->device, cs, bw_out, nevals);

@@ -22,23 +22,12 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "entry_helpers.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
 
 namespace kdehip {
 namespace {
-
-#define KDEHIP_CHECK(expr)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_error(KDEHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define KDEHIP_CHECK_RC(expr)          \
-  do {                                 \
-    const int rc_ = (expr);            \
-    if (rc_ != KDEHIP_OK) return rc_;  \
-  } while (0)
 
 constexpr int kSumThreads = 256;      // moments: one workgroup per item
 constexpr int kGridThreads = 256;     // grid points per block
@@ -59,16 +48,6 @@ struct SumItem {
   int64_t N, Ngrid, chunks_per_group;
   int32_t D, ngroups, gblocks, grid;  // grid: the grid kernels run for this item
 };
-
-// the item that owns global block b: the last i with first[i] <= b (first[] ascending)
-__device__ __forceinline__ int item_of_block(const int32_t *__restrict__ first, int n, int b) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (first[mid] <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // x_k of the grid over [lo, hi]: lo + k h with h = (hi - lo) / (Ngrid - 1), the last point hi; every operation rounded
 // on its own (the build compiles with -ffp-contract=off)

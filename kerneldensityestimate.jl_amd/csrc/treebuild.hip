@@ -28,18 +28,12 @@
 #include <string>
 #include <vector>
 
+#include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
 
 namespace kdehip {
 namespace {
-
-#define KDEHIP_CHECK(expr)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return set_error(KDEHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr int kTB = 1024;    // threads of the workgroup
 constexpr int kSeqMax = 32;  // ranges up to this many leaves: one lane replays the scan

@@ -1,5 +1,5 @@
 """Circular against Euclidean form of the same binary and shape (include/kdehip.h section 5d; CIRC instantiations of
-csrc/evaluate.hip): evaluation 6-D 10,000 x 65,536 with eeeccc, bandwidth search 6 x 2048 with eeeccc, kld_batch of 64
+csrc/evaluate.hip, csrc/loocv.hip): evaluation 6-D 10,000 x 65,536 with eeeccc, bandwidth search 6 x 2048 with eeeccc, kld_batch of 64
 pairs of 200 points.  Host wall clock around blocking calls (median and min of the repetitions), the two forms interleaved.
 `--profile evaluate|loocv|kld [euclid|circular]`: only that call, 10 times, for a run under
 `rocprofv3 --kernel-trace --stats`, whose stats give the kernel times.  Prints one line per measurement; nothing is gated."""

@@ -1,4 +1,4 @@
-"""Timings of evalAvgLogL / kld / entropy (csrc/evaluate.hip logl_* kernels, include/kdehip.h section 5b).
+"""Timings of evalAvgLogL / kld / entropy (csrc/evaluate.hip, include/kdehip.h section 5b).
 
   1. 64 kld of densities shaped like bench config 2 (2-D, 200 points each), resident: one kld_batch call (128 items,
      one synchronisation) against 64 single kld calls (two blocking evalAvgLogL calls each); host wall clock around work

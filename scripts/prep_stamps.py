@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phases of loocv_prep_kernel (a -DKDEHIP_PREP_STAMPS build of csrc/evaluate.hip linked as a development library):
+"""Phases of loocv_prep_kernel (a -DKDEHIP_PREP_STAMPS build of csrc/loocv.hip linked as a development library):
 s_memtime of block 0 at the phase boundaries, in shader-clock cycles.
     KDEHIP_LIB=.../libkdehip_prep.so python scripts/prep_stamps.py"""
 import ctypes as C, os, sys

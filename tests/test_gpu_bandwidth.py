@@ -168,7 +168,7 @@ print("RESULT " + json.dumps(out))
 
 def test_fused_loocv_rounds_equal_the_two_launch_rounds():
     """The one-launch LOOCV round hands its slots between workgroups and XCDs inside the launch with device-scope relaxed
-    atomics (csrc/evaluate.hip slot_store / pairs_arrive: leaning on gfx950's write-through behaviour, see there).  The
+    atomics (csrc/loocv.hip slot_store / pairs_arrive: leaning on gfx950's write-through behaviour, see there).  The
     two-launch rounds have no such hand-over (kernel boundaries order everything): both forms must select the same bandwidth
     with the same number of likelihood evaluations -- tile counts 2 .. 64, odd and even circles, ragged last tiles."""
     import json
@@ -177,7 +177,7 @@ def test_fused_loocv_rounds_equal_the_two_launch_rounds():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = []
-    # the library's choice (speculative rounds -- three evaluations per launch, csrc/evaluate.hip loo_round_spec_kernel -- for
+    # the library's choice (speculative rounds -- three evaluations per launch, csrc/loocv.hip loo_round_spec_kernel -- for
     # the smaller marginals, plain one-launch rounds for the larger), plain one-launch rounds everywhere, two-launch rounds
     for extra in ({}, {"KDEHIP_LOOCV_SPEC": "0"}, {"KDEHIP_LOOCV_TWO_LAUNCH": "1"}):
         env = dict(os.environ, PYTHONPATH=root, **extra)
