@@ -5,16 +5,19 @@
 // of its time in them.  Freed blocks are therefore kept, per device, in power-of-two size classes and
 // handed out again; kdehip_clear_cache() returns everything to the driver (SURVEY.md 8b "Ownership").
 // Blocks are only recycled after the work that used them has completed: every entry point that frees
-// into the cache has synchronised its stream / finished its blocking copies before doing so.
+// into the cache has synchronised its stream / finished its blocking copies before doing so, or has
+// parked its blocks in the deferred-release queue below (call_block.hpp).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <cstddef>
 #include <cstdlib>
+#include <deque>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "call_block.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
 
@@ -24,7 +27,6 @@ namespace {
 constexpr int kClasses = 40;                              // size class c holds blocks of 2^c bytes
 constexpr size_t kMinBlock = size_t(1) << 16;             // 64 KiB: everything smaller shares one class
 constexpr size_t kCacheLimit = size_t(1) << 30;           // per device and kind: at most 1 GiB kept
-constexpr int kMaxDevices = 64;
 
 struct Cache {
   std::mutex mu;
@@ -125,6 +127,92 @@ void cached_host_free(void *p, size_t bytes) {
   (void)hipHostFree(p);
 }
 
+
+// ---- the deferred-release queue (call_block.hpp) -----------------------------------------------------------------------
+// Blocks of enqueue-only calls live until the work that uses them has run: they wait here, with an event recorded behind
+// the call's last launch, and are released by later calls (or kdehip_clear_cache) once the event has fired.
+namespace {
+struct Deferred {
+  hipEvent_t done = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;  // the stream the work was enqueued on
+  void *d = nullptr, *h = nullptr;
+  size_t dbytes = 0, hbytes = 0;
+  ReleaseHook hook = nullptr;
+  void *ctx = nullptr;
+};
+struct DeferredQueue {
+  std::mutex mu;
+  std::deque<Deferred> q;
+};
+DeferredQueue g_deferred[kMaxDevices + 1];  // (the last one: every ordinal beyond the slots)
+DeferredQueue &deferred_of(int device) { return g_deferred[device >= 0 && device < kMaxDevices ? device : kMaxDevices]; }
+
+void release_deferred(Deferred &f) {  // (the work is over, the entry's device is current)
+  if (f.hook) f.hook(f.ctx, f.stream);
+  if (f.done) (void)hipEventDestroy(f.done);
+  if (f.d) cached_free(f.d, f.dbytes);
+  if (f.h) cached_host_free(f.h, f.hbytes);
+}
+
+// all = true: wait for everything of `device`
+void reap(int device, bool all, hipStream_t mine, size_t limit) {
+  DeferredQueue &dq = deferred_of(device);
+  for (;;) {
+    std::vector<Deferred> finished;
+    Deferred wait_for;
+    bool have_wait = false;
+    {
+      std::lock_guard<std::mutex> lock(dq.mu);
+      size_t of_mine = 0, left = 0;
+      for (auto it = dq.q.begin(); it != dq.q.end();) {
+        if (it->device != device) { ++it; continue; }
+        if (hipEventQuery(it->done) == hipSuccess) { finished.push_back(*it); it = dq.q.erase(it); }
+        else { ++left; if (it->stream == mine) ++of_mine; ++it; }
+      }
+      (void)hipGetLastError();  // (hipEventQuery reports "not ready" as an error)
+      if (all ? left > 0 : (limit > 0 && of_mine > limit)) {
+        for (auto it = dq.q.begin(); it != dq.q.end(); ++it)
+          if (it->device == device && (all || it->stream == mine)) { wait_for = *it; dq.q.erase(it); have_wait = true; break; }
+      }
+    }
+    for (Deferred &f : finished) release_deferred(f);
+    if (!have_wait) return;
+    (void)hipEventSynchronize(wait_for.done);  // (outside the lock)
+    release_deferred(wait_for);
+  }
+}
+}  // namespace
+
+void reap_deferred(int device, hipStream_t mine, size_t limit) { reap(device, false, mine, limit); }
+
+int defer_release(int device, hipStream_t stream, void *d, size_t dbytes, void *h, size_t hbytes, ReleaseHook hook, void *ctx) {
+  Deferred f;
+  f.device = device; f.stream = stream;
+  f.d = d; f.dbytes = dbytes; f.h = h; f.hbytes = hbytes;
+  f.hook = hook; f.ctx = ctx;
+  hipError_t e = hipEventCreateWithFlags(&f.done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(f.done, stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(stream);
+    release_deferred(f);
+    return set_error(KDEHIP_ERR_HIP, std::string("deferred release: ") + hipGetErrorString(e));
+  }
+  DeferredQueue &dq = deferred_of(device);
+  std::lock_guard<std::mutex> lock(dq.mu);
+  dq.q.push_back(f);
+  return KDEHIP_OK;
+}
+
+void drain_deferred(int device) {
+  if (device >= 0) { reap(device, true, nullptr, 0); return; }
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return;
+  DeviceGuard guard;
+  for (int d = 0; d < n; ++d)
+    if (guard.enter(d) == KDEHIP_OK) reap(d, true, nullptr, 0);
+}
+
 }  // namespace kdehip
 
 
@@ -162,8 +250,7 @@ namespace kdehip { std::atomic<unsigned> g_peer_epoch{0}; }  // product.hip: the
 extern "C" void kdehip_clear_cache(void) {
   using namespace kdehip;
   g_peer_epoch.fetch_add(1, std::memory_order_relaxed);  // verdicts cached per raw pointer do not survive a cache reset
-  kdehip::drain_pending();  // product.hip: plans of enqueue-only device products still waiting for their work
-  kdehip::drain_sample_pending();  // sample.hip: descriptor blocks of batched draws
+  drain_deferred();  // blocks (and plans) of enqueue-only calls still waiting for their work
   int cur = 0;
   const bool have_cur = hipGetDevice(&cur) == hipSuccess;
   int n = 0;

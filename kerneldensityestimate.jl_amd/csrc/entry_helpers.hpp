@@ -1,6 +1,7 @@
 // entry_helpers.hpp -- the small things every file of entry points (evaluate, loocv, summary, sample, treebuild,
 // pack_device, product) used to define for itself.  Not in kdehip_internal.hpp: that header is part of every sampler
-// translation unit and holds declarations only (hip_runtime_api.h); this one has macros and device code.
+// translation unit and holds declarations only (hip_runtime_api.h); this one has macros and device code.  The blocks of
+// a call (device block, pinned image, their release) are call_block.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,8 +56,8 @@ int dispatch_dims(int D, F &&f) {
   return KDEHIP_OK;
 }
 
-// Device scratch of one call from the library's allocation cache (devmem.cpp).  It goes back when the call returns, so the
-// work that uses it must be over by then.
+// Bare device scratch of one call from the library's allocation cache (devmem.cpp).  It goes back when the call returns, so
+// the work that uses it must be over by then (a call that may return early with work in flight holds a CallBlock).
 struct DevBuf {
   void *p = nullptr;
   size_t n = 0;

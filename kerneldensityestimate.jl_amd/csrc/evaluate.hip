@@ -30,6 +30,7 @@
 
 #include "circ_wrap.hpp"
 #include "device_density.hpp"
+#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
@@ -234,13 +235,7 @@ class EvalRun {
  public:
   std::vector<EvalItem> items;
   std::vector<uint32_t> circ;  // per item: its circular dimensions (bit k = dimension k); shorter than `items`: 0 for the rest
-  ~EvalRun() {
-    if (armed_) (void)hipStreamSynchronize(st_);  // (an error return after launches: nothing goes back to a cache in use)
-    if (d_) cached_free(d_, dbytes_);
-    if (h_) cached_host_free(h_, hbytes_);
-  }
   int alloc(size_t prefix, size_t nresults = 0) {  // nresults == 0: one per item
-    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
     const size_t n = items.size();
     int64_t pblocks = 0, fblocks = 0;
     for (EvalItem &it : items) {
@@ -252,26 +247,23 @@ class EvalRun {
       fblocks += it.nfb;
     }
     if (pblocks > INT32_MAX || fblocks > INT32_MAX) return set_error(KDEHIP_ERR_UNSUPPORTED, "evaluation too large for one launch");
-    o_items_ = al(prefix);
-    o_first_ = al(o_items_ + sizeof(EvalItem) * n);
+    Carve c;
+    c.take(prefix);
+    o_items_ = c.take(sizeof(EvalItem) * n);
+    o_first_ = c.take(sizeof(int32_t) * 2 * (n + 1) + sizeof(uint32_t) * n);  // first[] of both kernels, then the masks
     o_masks_ = o_first_ + sizeof(int32_t) * 2 * (n + 1);
-    o_res_ = al(o_masks_ + sizeof(uint32_t) * n);
     nres_ = nresults ? nresults : n;
-    size_t o = al(o_res_ + sizeof(double) * nres_);
+    o_res_ = c.take(sizeof(double) * nres_);
     scratch_.resize(n);
     for (size_t k = 0; k < n; ++k) {
       const EvalItem &it = items[k];
-      scratch_[k] = o;
-      o = al(o + sizeof(double) * (it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
+      scratch_[k] = c.take(sizeof(double) * (it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
     }
-    dbytes_ = o;
-    hbytes_ = o_res_ + sizeof(double) * nres_;
-    KDEHIP_CHECK(cached_malloc(&d_, dbytes_));
-    KDEHIP_CHECK(cached_host_malloc(&h_, hbytes_));
+    KDEHIP_CHECK(blk_.alloc(c.mark(), o_res_ + sizeof(double) * nres_));
     return KDEHIP_OK;
   }
-  unsigned char *dev() const { return static_cast<unsigned char *>(d_); }
-  unsigned char *host() const { return static_cast<unsigned char *>(h_); }
+  unsigned char *dev() const { return blk_.dev(); }
+  unsigned char *host() const { return blk_.host(); }
   double *result(size_t k) const { return reinterpret_cast<double *>(dev() + o_res_) + k; }  // (device) result k: item k's own slot
   double *host_result(size_t k) const { return reinterpret_cast<double *>(host() + o_res_) + k; }
 
@@ -281,7 +273,6 @@ class EvalRun {
   }
   // scratch pointers, descriptors sorted by D (Euclidean items before circular ones), one upload on `st`
   int upload(hipStream_t st) {
-    st_ = st;
     const size_t n = items.size();
     for (size_t k = 0; k < n; ++k) {
       EvalItem &it = items[k];
@@ -311,13 +302,12 @@ class EvalRun {
       ffirst[k + 1] = ffirst[k] + it.nfb;
     }
     if (n) std::memcpy(host() + o_items_, items.data(), sizeof(EvalItem) * n);
-    armed_ = true;
-    KDEHIP_CHECK(hipMemcpyAsync(d_, h_, o_res_, hipMemcpyHostToDevice, st));
+    KDEHIP_CHECK(blk_.upload(o_res_, st));
     return KDEHIP_OK;
   }
   // the launches behind the upload: two kernels, and the per-item reduce when an item asks for a log-likelihood
   int launch() {
-    const hipStream_t st = st_;
+    const hipStream_t st = blk_.stream();
     const size_t n = items.size();
     const int32_t *pfirst = reinterpret_cast<const int32_t *>(host() + o_first_), *ffirst = pfirst + (n + 1);
     const EvalItem *d_items = reinterpret_cast<const EvalItem *>(dev() + o_items_);
@@ -345,27 +335,22 @@ class EvalRun {
   // blocking calls: the results come back to host_result()
   int wait() {
     hipError_t e = hipSuccess;
-    if (nres_) e = hipMemcpyAsync(host_result(0), result(0), sizeof(double) * nres_, hipMemcpyDeviceToHost, st_);
-    const hipError_t se = hipStreamSynchronize(st_);
-    armed_ = false;
+    if (nres_) e = blk_.download(o_res_, sizeof(double) * nres_, blk_.stream());
+    const hipError_t se = blk_.wait();
     KDEHIP_CHECK(e);
     KDEHIP_CHECK(se);
     return KDEHIP_OK;
   }
   // enqueue-only calls: both blocks go back once the work on the stream is done
   int defer(int device) {
-    const int rc = release_after(device, d_, dbytes_, h_, hbytes_, st_);
-    d_ = h_ = nullptr;
-    armed_ = false;
-    return rc;
+    reap_deferred(device);
+    return blk_.defer(device);
   }
 
  private:
-  void *d_ = nullptr, *h_ = nullptr;
-  size_t dbytes_ = 0, hbytes_ = 0, o_items_ = 0, o_first_ = 0, o_masks_ = 0, o_res_ = 0, nres_ = 0;
+  CallBlock blk_;
+  size_t o_items_ = 0, o_first_ = 0, o_masks_ = 0, o_res_ = 0, nres_ = 0;
   std::vector<size_t> scratch_;
-  hipStream_t st_ = nullptr;
-  bool armed_ = false;
 };
 
 }  // namespace

@@ -308,11 +308,6 @@ enum ArithMode : int {
 hipError_t cached_malloc(void **out, size_t bytes);
 void cached_free(void *p, size_t bytes);
 hipError_t cached_host_malloc(void **out, size_t bytes);
-void drain_pending();  // (product.hip) releases the plans of enqueue-only device products once their work is over
-void drain_sample_pending();  // (sample.hip) the same for the descriptor blocks of kdehip_sample_device_batch
-// (sample.hip; the device is current) hands a device block and a pinned block (either may be null) of enqueue-only work
-// on `stream` to the same list: they go back to the caches once an event recorded on `stream` now has fired
-int release_after(int device, void *d, size_t dbytes, void *h, size_t hbytes, void *stream);
 void cached_host_free(void *p, size_t bytes);
 
 // Makes `device` the thread's current HIP device for the lifetime of the guard and restores the caller's

@@ -19,6 +19,7 @@
 
 #include "circ_wrap.hpp"
 #include "device_density.hpp"
+#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "fastexp.hpp"
 #include "host_pool.hpp"
@@ -715,22 +716,16 @@ class kdehip::LoocvSearch {
   int finish(double *bw_out, int32_t *nevals_out);  // bw_out: nb * D standard deviations; nevals_out: nb counts
   int rounds() const { return rounds_; }
   int batches() const { return batches_; }
-  ~LoocvSearch() {
-    // an early error return waits for whatever has been enqueued before the device block and the pinned block go back
-    // to the caches (where another thread may be handed them at once); on the regular path the stream is already idle
-    if (armed_) (void)hipStreamSynchronize(st_);
-    if (pin_) cached_host_free(pin_, pin_bytes_);
-  }
 
  private:
   int enqueue_batch(int batch);
   LooRound r_{};
-  DevBuf dev_;
-  void *pin_ = nullptr;
-  size_t pin_bytes_ = 0;
+  // the device block and a pinned block (the points on their way up, then the state on its way back): an early error return
+  // waits for whatever has been enqueued before they go back to the caches; on the regular path the stream is already idle
+  CallBlock blk_;
   Golden *h_state_ = nullptr;
   hipStream_t st_ = nullptr;
-  bool armed_ = false, pairs_ = false;
+  bool pairs_ = false;
   std::unique_ptr<PhaseTimer> timer_;  // kdehip_profile_phase_read(0): the batch of rounds in flight
   int nb_ = 0, D_ = 0, nm_ = 0, rounds_ = 0, batches_ = 0, pair_items_ = 0;
   int64_t qblocks_ = 0;
@@ -774,9 +769,9 @@ int kdehip::LoocvSearch::begin(int nb, int D, int64_t N, const double *points, c
   r.sqrt_2pi = std::pow(2.0 * M_PI, 1 / 2.0);
 
   // one device block: [points N*D | xo nm*N | partial nm*ngroups*N | hpart nm*nfb | state 2*nm]
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  const size_t off_x = al(d_points ? 0 : sizeof(double) * N * D);
-  const size_t off_part = al(off_x + sizeof(double) * N * nm);
+  Carve c;
+  c.take(d_points ? 0 : sizeof(double) * N * D);
+  const size_t off_x = c.take(sizeof(double) * N * nm);
   r.joint = pairs ? 1 : 0;
   // speculative rounds (three evaluations per launch, two of them booked: loo_round_spec_kernel) while three evaluations
   // are still only a few wavefronts per SIMD: nm T (T/2 + 1) tile pairs per evaluation on 4 SIMDs per CU
@@ -784,28 +779,27 @@ int kdehip::LoocvSearch::begin(int nb, int D, int64_t N, const double *points, c
   static const int spec_per_cu = [] { const char *e = std::getenv("KDEHIP_LOOCV_SPEC"); return e && e[0] ? std::atoi(e) : 8; }();
   const int pair_items = pair_items_ = ntiles * (ntiles / 2 + 1);  // per marginal: the diagonal and the offsets 1 .. T/2 of every tile
   r.spec = (pairs && static_cast<int64_t>(nm) * pair_items <= int64_t(spec_per_cu) * device_cu_count()) ? 1 : 0;
-  const size_t off_h = al(off_part + sizeof(double) * nm * r.ngroups * (pairs ? 3 * int64_t(ntiles) * kTile : N));
-  const size_t off_state = al(off_h + sizeof(double) * 6 * nm * r.nfb);
-  const size_t off_arr = al(off_state + sizeof(Golden) * 2 * nm);
+  const size_t off_part = c.take(sizeof(double) * nm * r.ngroups * (pairs ? 3 * int64_t(ntiles) * kTile : N));
+  const size_t off_h = c.take(sizeof(double) * 6 * nm * r.nfb);
+  const size_t off_state = c.take(sizeof(Golden) * 2 * nm);
+  const size_t off_arr = c.mark();
   const size_t total = off_arr + (pairs ? sizeof(unsigned) * 3 * nm * ntiles * kCounterStride : 0);
-  KDEHIP_CHECK(dev_.alloc(total));
-  unsigned char *base = dev_.as<unsigned char>();
+  KDEHIP_CHECK(blk_.alloc(total, std::max(d_points ? size_t(0) : sizeof(double) * N * D, sizeof(Golden) * 2 * nm)));
+  blk_.touch(st);
+  unsigned char *base = blk_.dev();
   double *d_pts = reinterpret_cast<double *>(base);
   r.x = reinterpret_cast<double *>(base + off_x);
   r.partial = reinterpret_cast<double *>(base + off_part);
   r.hpart = reinterpret_cast<double *>(base + off_h);
   r.state = reinterpret_cast<Golden *>(base + off_state);
   r.arrivals = reinterpret_cast<unsigned *>(base + off_arr);
-  pin_bytes_ = std::max(d_points ? size_t(0) : sizeof(double) * N * D, sizeof(Golden) * 2 * nm);
-  KDEHIP_CHECK(cached_host_malloc(&pin_, pin_bytes_));
-  h_state_ = static_cast<Golden *>(pin_);
-  armed_ = true;
+  h_state_ = reinterpret_cast<Golden *>(blk_.host());
   timer_.reset(new PhaseTimer(kPhaseLoocv, st));
 
   if (N <= kPrepMaxN) {
     if (!d_points) {
-      std::memcpy(pin_, points, sizeof(double) * N * D);
-      KDEHIP_CHECK(hipMemcpyAsync(d_pts, pin_, sizeof(double) * N * D, hipMemcpyHostToDevice, st));
+      std::memcpy(blk_.host(), points, sizeof(double) * N * D);
+      KDEHIP_CHECK(blk_.upload(sizeof(double) * N * D, st));
     }
     int64_t P = 1;
     while (P < N) P <<= 1;
@@ -895,7 +889,7 @@ int kdehip::LoocvSearch::poll(bool *done) {
   bool all = true;
   for (int m = 0; m < nm_; ++m) all = all && h_state_[m].phase == 3;
   *done = all;
-  if (all) { armed_ = false; return KDEHIP_OK; }
+  if (all) { (void)blk_.wait(); return KDEHIP_OK; }  // (disarms; the caller has synchronised the stream)
   if (batches_ >= 16) return set_error(KDEHIP_ERR_HIP, "bandwidth search did not converge");
   timer_.reset(new PhaseTimer(kPhaseLoocv, st_));
   return enqueue_batch(r_.spec ? 4 : 8);

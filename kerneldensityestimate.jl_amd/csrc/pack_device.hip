@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
@@ -209,12 +210,12 @@ namespace {
 struct BlockLayout {
   size_t o_mean = 0, o_bw = 0, o_w = 0, o_perm = 0, o_front = 0, total = 0, nd = 0, n2 = 0;
   BlockLayout(int64_t N, int64_t D, size_t nfront) {
-    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
     nd = sizeof(double) * 2 * N * D;
     n2 = sizeof(double) * 2 * N;
-    o_mean = 0; o_bw = al(o_mean + nd); o_w = al(o_bw + nd); o_perm = al(o_w + n2);
-    o_front = al(o_perm + sizeof(int64_t) * 2 * N);
-    total = al(o_front + sizeof(int32_t) * nfront);
+    Carve c;
+    o_mean = c.take(nd); o_bw = c.take(nd); o_w = c.take(n2); o_perm = c.take(sizeof(int64_t) * 2 * N);
+    o_front = c.take(sizeof(int32_t) * nfront);
+    total = c.mark();
   }
 };
 void bind_block(kdehip_device_density *h, const BlockLayout &bl) {
@@ -306,9 +307,8 @@ BlockLayout mirror_layout(const kdehip_device_density *h) {
 // one pinned block whose head is the image of the device block `bl`; h->m points into it
 hipError_t alloc_mirror(kdehip_device_density *h, const BlockLayout &bl) {
   const size_t nd = static_cast<size_t>(2 * h->N * h->D), n2 = static_cast<size_t>(2 * h->N);
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
   const size_t o_extra = bl.total;  // centers, ranges (nd each), bwmin, bwmax (nd / 2 each), left, right, lowest, highest (n2 each)
-  h->mirror_bytes = al(o_extra + sizeof(double) * (2 * nd + nd) + sizeof(int64_t) * 4 * n2);
+  h->mirror_bytes = align256(o_extra + sizeof(double) * (2 * nd + nd) + sizeof(int64_t) * 4 * n2);
   const hipError_t e = cached_host_malloc(&h->mirror, h->mirror_bytes);
   if (e != hipSuccess) { h->mirror = nullptr; return e; }
   unsigned char *mb = static_cast<unsigned char *>(h->mirror);
@@ -570,28 +570,24 @@ extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const
   rc = guard.enter(p->device);
   if (rc != KDEHIP_OK) return rc;
   hipStream_t cs = hipStreamPerThread;
-  struct Cleanup {
-    kdehip_device_density *h = nullptr; void *d = nullptr, *pin = nullptr; size_t bytes = 0; hipStream_t st = nullptr;
+  struct Cleanup {  // (the handle, until it is the caller's)
+    kdehip_device_density *h = nullptr;
     ~Cleanup() {
-      if (st) (void)hipStreamSynchronize(st);
-      if (d) cached_free(d, bytes);
-      if (pin) cached_host_free(pin, bytes);
       if (h && h->d_blob) cached_free(h->d_blob, h->blob_bytes);
       if (h && h->mirror) cached_host_free(h->mirror, h->mirror_bytes);
       delete h;
     }
   } cl;
-  cl.bytes = sizeof(double) * (N * nsel + N + D);
-  KDEHIP_CHECK(cached_malloc(&cl.d, cl.bytes));
-  KDEHIP_CHECK(cached_host_malloc(&cl.pin, cl.bytes));
-  cl.st = cs;
-  double *d_blk = static_cast<double *>(cl.d), *blk = static_cast<double *>(cl.pin);
+  const size_t bytes = sizeof(double) * (N * nsel + N + D);
+  CallBlock gathered;
+  KDEHIP_CHECK(gathered.alloc(bytes, bytes));
+  gathered.touch(cs);
+  double *d_blk = reinterpret_cast<double *>(gathered.dev()), *blk = reinterpret_cast<double *>(gathered.host());
   hipLaunchKernelGGL(gather_marginal_kernel, dim3(static_cast<unsigned>((N * nsel + 255) / 256)), dim3(256), 0, cs, p->means,
                      p->bandwidth, p->weights, p->perm, N, D, nsel, md, d_blk);
   KDEHIP_CHECK(hipGetLastError());
-  KDEHIP_CHECK(hipMemcpyAsync(blk, d_blk, cl.bytes, hipMemcpyDeviceToHost, cs));
-  KDEHIP_CHECK(hipStreamSynchronize(cs));
-  cl.st = nullptr;
+  KDEHIP_CHECK(gathered.download(0, bytes, cs));
+  KDEHIP_CHECK(gathered.wait());
   double ks[KDEHIP_MAX_DIMS];
   for (int s = 0; s < nsel; ++s) ks[s] = std::sqrt(blk[N * nsel + N + md.d[s]]);  // getBW(p, [1])[dims]
   kdehip_device_density *h = new (std::nothrow) kdehip_device_density();
@@ -630,30 +626,24 @@ extern "C" int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
   hipStream_t cs = hipStreamPerThread;
-  struct Scratch {
-    void *p = nullptr; size_t n = 0; hipStream_t st;
-    ~Scratch() { if (p) { (void)hipStreamSynchronize(st); cached_free(p, n); } }
-  } sc;
-  sc.st = cs;
+  CallBlock sc;  // (it waits for the thread's stream before the scratch goes back)
+  sc.touch(cs);
   if (Ndens == 1 && !addEntropy) {
     const int64_t N = trees[0]->N;
-    sc.n = sizeof(double) * N * D;
-    KDEHIP_CHECK(cached_malloc(&sc.p, sc.n));
+    KDEHIP_CHECK(sc.alloc(sizeof(double) * N * D));
     const int64_t items = N * D;
     hipLaunchKernelGGL(unpermute_points_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, cs,
-                       trees[0]->means, trees[0]->perm, N, D, static_cast<double *>(sc.p));
+                       trees[0]->means, trees[0]->perm, N, D, reinterpret_cast<double *>(sc.dev()));
     KDEHIP_CHECK(hipGetLastError());
-    return kdehip_density_from_device_points(out, static_cast<const double *>(sc.p), D, N, device, cs, bw_out, nevals);
+    return kdehip_density_from_device_points(out, reinterpret_cast<const double *>(sc.dev()), D, N, device, cs, bw_out, nevals);
   }
   double sum = 0.0;  // numpts = round(Int, mean(Npts.(trees))): Julia rounds halves to even, like nearbyint
   for (int j = 0; j < Ndens; ++j) sum += static_cast<double>(trees[j]->N);
   const int64_t Np = static_cast<int64_t>(std::nearbyint(sum / static_cast<double>(Ndens)));
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  const size_t off_i = al(sizeof(double) * Np * D);
-  sc.n = off_i + sizeof(int64_t) * Np * Ndens;
-  KDEHIP_CHECK(cached_malloc(&sc.p, sc.n));
-  double *d_pts = static_cast<double *>(sc.p);
-  int64_t *d_ind = reinterpret_cast<int64_t *>(static_cast<unsigned char *>(sc.p) + off_i);
+  const size_t off_i = align256(sizeof(double) * Np * D);
+  KDEHIP_CHECK(sc.alloc(off_i + sizeof(int64_t) * Np * Ndens));
+  double *d_pts = reinterpret_cast<double *>(sc.dev());
+  int64_t *d_ind = reinterpret_cast<int64_t *>(sc.dev() + off_i);
   rc = prod_philox_device_blocking_stream(Ndens, trees, Np, /*Niter=*/5, seed, 0, addEntropy, nullptr, 64, d_pts, d_ind, cs);
   if (rc != KDEHIP_OK) return rc;
   return kdehip_density_from_device_points(out, d_pts, D, Np, device, cs, bw_out, nevals);
@@ -731,7 +721,6 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
   hipStream_t cs = hipStreamPerThread, xs = side_stream(device);
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
 
   // groups of equal (D, N): their searches share launches and their matrices sit one behind the other
   std::vector<MulGroup> groups;
@@ -754,19 +743,19 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
       MulPlan &m = mp[i];
       m.pts_off = pts_bytes; pts_bytes += sizeof(double) * m.N * m.D;  // (no padding inside a group: LoocvSearch strides by N * D)
     }
-    pts_bytes = al(pts_bytes);
+    pts_bytes = align256(pts_bytes);
   }
   int nbatched = 0;
   for (int i = 0; i < nprod; ++i) {
     MulPlan &m = mp[i];
     if (m.loose) continue;
     ++nbatched;
-    if (!m.shortcut) { m.ind_off = ind_bytes; ind_bytes = al(ind_bytes + sizeof(int64_t) * m.N * m.M); }
+    if (!m.shortcut) { m.ind_off = ind_bytes; ind_bytes = align256(ind_bytes + sizeof(int64_t) * m.N * m.M); }
     const size_t nd = sizeof(double) * 2 * m.N * m.D, n2 = sizeof(double) * 2 * m.N;
     m.front_cap = static_cast<size_t>(nlevels_for(m.N) + 1) * static_cast<size_t>(m.N) + 64;
-    m.a_off = a_bytes; a_bytes = al(a_bytes + al(nd) + al(n2) + al(n2) + sizeof(int32_t) * m.front_cap);
-    m.b_off = b_bytes; b_bytes = al(b_bytes + nd);
-    m.x_off = x_bytes; x_bytes = al(x_bytes + nd * 3 + sizeof(int64_t) * 4 * 2 * m.N);  // centers, ranges, bwmin + bwmax, left .. highest
+    m.a_off = a_bytes; a_bytes = align256(a_bytes + align256(nd) + align256(n2) + align256(n2) + sizeof(int32_t) * m.front_cap);
+    m.b_off = b_bytes; b_bytes = align256(b_bytes + nd);
+    m.x_off = x_bytes; x_bytes = align256(x_bytes + nd * 3 + sizeof(int64_t) * 4 * 2 * m.N);  // centers, ranges, bwmin + bwmax, left .. highest
   }
 
   // everything the error paths have to take back
@@ -794,7 +783,7 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
   } cl{&mp, &groups, cs, xs};
 
   if (nbatched > 0) {
-    cl.scratch_bytes = al(pts_bytes) + ind_bytes + 256;
+    cl.scratch_bytes = align256(pts_bytes) + ind_bytes + 256;
     KDEHIP_CHECK(cached_malloc(&cl.scratch, cl.scratch_bytes));
     unsigned char *sc = static_cast<unsigned char *>(cl.scratch);
     // (1) the products: one batched call (its own groups by (D, M)); the shortcut items un-permute their own leaves
@@ -814,7 +803,7 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
       kdehip_batch_item b{};
       b.Ndens = m.M; b.Niter = 5; b.trees = items[i].trees; b.Np = m.N; b.seed = items[i].seed; b.sample_offset = 0;
       b.addEntropy = items[i].addEntropy; b.partialDimMask = nullptr; b.d_points = d_pts;
-      b.d_indices = reinterpret_cast<int64_t *>(sc + al(pts_bytes) + m.ind_off); b.d_labels = nullptr;
+      b.d_indices = reinterpret_cast<int64_t *>(sc + align256(pts_bytes) + m.ind_off); b.d_labels = nullptr;
       prod.push_back(b);
     }
     if (!prod.empty()) {
@@ -855,7 +844,7 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
       if (!h) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
       h->device = device; h->N = m.N; h->D = m.D; h->Lown = nlevels_for(m.N);
       const size_t nd = sizeof(double) * 2 * m.N * m.D, n2 = sizeof(double) * 2 * m.N;
-      const size_t o_w = al(nd), o_perm = o_w + al(n2), o_front = o_perm + al(n2);
+      const size_t o_w = align256(nd), o_perm = o_w + align256(n2), o_front = o_perm + align256(n2);
       unsigned char *a = mb + m.a_off, *x = mb + a_bytes + b_bytes + m.x_off;
       kdehip_device_density::Mirror &q = h->m;
       q.means = reinterpret_cast<double *>(a); q.weights = reinterpret_cast<double *>(a + o_w);
@@ -878,7 +867,7 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
       for (int i = 0; i < nprod; ++i) {
         MulPlan *m = &mp[i];
         if (m->loose) continue;
-        trees.run([m, pin, mb, al, &one] {
+        trees.run([m, pin, mb, &one] {
           kdehip_device_density *h = m->h;
           kdehip_device_density::Mirror &q = h->m;
           m->rc = kdehip_make_density(m->D, m->N, reinterpret_cast<const double *>(pin + m->pts_off), &one, 1, nullptr, q.centers, q.ranges,
@@ -889,7 +878,7 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
           if (m->rc != KDEHIP_OK) { m->msg = kdehip_last_error(); return; }
           if (h->fr.ids.size() > m->front_cap) { m->rc = KDEHIP_ERR_ARG; m->msg = "more frontier ids than a tree of N leaves has"; return; }
           const size_t nd = sizeof(double) * 2 * m->N * m->D, n2 = sizeof(double) * 2 * m->N;
-          std::memcpy(mb + m->a_off + al(nd) + 2 * al(n2), h->fr.ids.data(), sizeof(int32_t) * h->fr.ids.size());
+          std::memcpy(mb + m->a_off + align256(nd) + 2 * align256(n2), h->fr.ids.data(), sizeof(int32_t) * h->fr.ids.size());
         });
       }
       trees.wait();

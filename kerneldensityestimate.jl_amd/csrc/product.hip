@@ -9,12 +9,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "call_block.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
@@ -49,6 +49,11 @@ struct kdehip_product {
   std::mutex work_mutex;    // host-buffer calls on one plan are serialised
   int64_t packed_bytes = 0;
   PlanDev dev{};
+  // a plan private to one enqueue-only call (prod_philox_device, kdehip_prod_philox_batch): the call's next plan, and on its
+  // first plan the call's events -- `prepared`: tiles and tables are in place (recorded on the device's preparation stream);
+  // t_begin / t_end (kdehip_profile_sampler): around the sampling launch, on the caller's stream
+  kdehip_product *next = nullptr;
+  hipEvent_t prepared = nullptr, t_begin = nullptr, t_end = nullptr;
 };
 
 namespace {
@@ -130,7 +135,6 @@ int reserve_work(kdehip_product *plan, size_t bytes) {
   plan->work_cap = cap;
   return KDEHIP_OK;
 }
-inline size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 // Results of a host-buffer run: the output arrays sit back to back in the plan's scratch, so they come back with ONE
 // DMA transfer into pinned memory (from the library's cache) and are handed out from there -- two or three blocking
@@ -724,24 +728,6 @@ int kdehip_prod_philox(int Ndens, const kdehip_density *trees, int64_t Np, int N
 // ---- products of densities that live in HBM (pack_device.hip) ------------------------------------------------------
 namespace {
 
-constexpr int kMaxDevices = 64;  // devices the bookkeeping below has slots for (a node has 8)
-
-// Plans of enqueue-only calls live until the work that uses them has run: they wait here, with an event recorded behind
-// their last launch, and are released by later calls (or kdehip_clear_cache) once the event has fired.  One entry = one
-// call: the plan of kdehip_prod_philox_device, or all plans of a kdehip_prod_philox_batch (they share one device block).
-struct PendingPlan {
-  std::vector<kdehip_product *> plans;  // descriptors only when `d_blob` is set (the block below is theirs, shared)
-  void *d_blob = nullptr;               // a batch's one device block
-  size_t blob_bytes = 0;
-  hipEvent_t done = nullptr;
-  void *h_desc = nullptr;
-  size_t h_bytes = 0;
-  hipStream_t stream = nullptr;           // the caller's stream the work was enqueued on
-  hipEvent_t prepared = nullptr;          // tiles and tables are in place (recorded on the device's preparation stream)
-  hipEvent_t t_begin = nullptr, t_end = nullptr;  // kdehip_profile_sampler: around the sampling launch, on the caller's stream
-  int device = 0;
-};
-
 // kdehip_profile_sampler: durations of the sampling launches of released plans, per device and caller stream
 std::atomic<int> g_profile_sampler{0};
 std::mutex g_profile_mu;
@@ -768,82 +754,42 @@ hipStream_t prep_stream(int device) {  // (the device is current)
   }
   return g_prep_stream[device];
 }
-std::mutex g_pending_mu;
-std::deque<PendingPlan> g_pending[kMaxDevices];
-constexpr size_t kMaxPending = 8;  // per (device, stream)
+constexpr size_t kMaxPending = 8;  // calls in flight per (device, stream): reap_deferred's limit
 
-void release_pending(PendingPlan &pp) {
-  if (pp.t_begin && pp.t_end) {  // (the work is over: `done` was recorded behind t_end)
+// The plans of one enqueue-only call, chained through kdehip_product::next.  They live until the work that uses them has
+// run: the call hands them to the deferred-release queue (call_block.hpp) with its device block -- the plan of
+// kdehip_prod_philox_device, or all plans of a kdehip_prod_philox_batch, point into that one block -- and
+// release_call_plans is the queue's hook.  A call that fails before the hand-over releases them here.
+void release_call_plans(void *first, hipStream_t stream) {
+  kdehip_product *p = static_cast<kdehip_product *>(first);
+  if (!p) return;
+  if (p->t_begin && p->t_end) {  // (the work is over: the queue's event was recorded behind t_end)
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, pp.t_begin, pp.t_end) == hipSuccess && pp.device >= 0 && pp.device < kMaxDevices) {
+    if (hipEventElapsedTime(&ms, p->t_begin, p->t_end) == hipSuccess && p->device >= 0 && p->device < kMaxDevices) {
       std::lock_guard<std::mutex> lock(g_profile_mu);
       ProfileSum *ps = nullptr;
-      for (ProfileSum &c : g_profile[pp.device]) if (c.stream == pp.stream) ps = &c;
-      if (!ps) { g_profile[pp.device].push_back(ProfileSum{pp.stream, 0.0, 0}); ps = &g_profile[pp.device].back(); }
+      for (ProfileSum &c : g_profile[p->device]) if (c.stream == stream) ps = &c;
+      if (!ps) { g_profile[p->device].push_back(ProfileSum{stream, 0.0, 0}); ps = &g_profile[p->device].back(); }
       ps->ms += ms;
       ps->launches += 1;
     }
     (void)hipGetLastError();
   }
-  if (pp.t_begin) (void)hipEventDestroy(pp.t_begin);
-  if (pp.t_end) (void)hipEventDestroy(pp.t_end);
-  if (pp.done) (void)hipEventDestroy(pp.done);
-  if (pp.prepared) (void)hipEventDestroy(pp.prepared);
-  if (pp.h_desc) cached_host_free(pp.h_desc, pp.h_bytes);
-  for (kdehip_product *p : pp.plans) {
-    if (!p) continue;
-    if (!pp.d_blob && p->d_blob) cached_free(p->d_blob, p->blob_bytes);
+  for (hipEvent_t ev : {p->t_begin, p->t_end, p->prepared}) if (ev) (void)hipEventDestroy(ev);
+  while (p) {
+    kdehip_product *next = p->next;
     if (p->d_work) cached_free(p->d_work, p->work_cap);
     delete p;
-  }
-  if (pp.d_blob) cached_free(pp.d_blob, pp.blob_bytes);
-}
-// (current device = `device`)  Releases every queued call whose work is over, wherever it sits in the queue.  A caller
-// with more than kMaxPending calls in flight ON ITS OWN STREAM then waits for the oldest of THOSE -- outside the lock,
-// and never for another stream's work: a stalled stream (a long kernel, an event another host thread records later)
-// holds up neither the other threads nor, through them, itself.  all = true (kdehip_clear_cache, the profile read-out):
-// wait for everything.
-void reap_pending(int device, bool all, hipStream_t mine = nullptr) {
-  if (device < 0 || device >= kMaxDevices) return;
-  for (;;) {
-    std::vector<PendingPlan> finished;
-    PendingPlan wait_for;
-    bool have_wait = false;
-    {
-      std::lock_guard<std::mutex> lock(g_pending_mu);
-      auto &q = g_pending[device];
-      size_t of_mine = 0;
-      for (auto it = q.begin(); it != q.end();) {
-        if (hipEventQuery(it->done) == hipSuccess) { finished.push_back(std::move(*it)); it = q.erase(it); }
-        else { if (!all && it->stream == mine) ++of_mine; ++it; }
-      }
-      (void)hipGetLastError();  // (hipEventQuery reports "not ready" as an error)
-      if (all ? !q.empty() : of_mine > kMaxPending) {
-        for (auto it = q.begin(); it != q.end(); ++it)
-          if (all || it->stream == mine) { wait_for = std::move(*it); q.erase(it); have_wait = true; break; }
-      }
-    }
-    for (PendingPlan &f : finished) release_pending(f);
-    if (!have_wait) return;
-    (void)hipEventSynchronize(wait_for.done);
-    release_pending(wait_for);
+    p = next;
   }
 }
-
-}  // namespace
-
-}  // extern "C"
-void kdehip::drain_pending() {  // kdehip_clear_cache: nothing may stay behind
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return;
-  DeviceGuard guard;
-  for (int d = 0; d < n && d < kMaxDevices; ++d)
-    if (guard.enter(d) == KDEHIP_OK) reap_pending(d, true);
-}
-
-extern "C" {
-
-namespace {
+struct CallPlans {
+  kdehip_product *first = nullptr, *last = nullptr;
+  hipStream_t stream = nullptr;
+  ~CallPlans() { release_call_plans(first, stream); }
+  void add(kdehip_product *p) { (last ? last->next : first) = p; last = p; }
+  kdehip_product *hand_over() { kdehip_product *p = first; first = last = nullptr; return p; }
+};
 
 // The layout of one product of resident densities inside a device block: [counter | levels | table descriptors] in the
 // block's head (what crosses PCIe), [permutation | tiles | tables] in its body (written by the GPU).
@@ -944,65 +890,45 @@ int prod_philox_device(int Ndens, kdehip_device_density *const *trees, int64_t N
   if (Np > 0 && (!d_points || !d_indices)) return set_error(KDEHIP_ERR_ARG, "null output pointer");
   kdehip_product *p = new (std::nothrow) kdehip_product();
   if (!p) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CallPlans call;  // (deletes p on every return before the hand-over)
+  call.stream = st;
+  call.add(p);
   ResidentLayout lay;
   int rc = layout_resident(Ndens, trees, partialDimMask, precision, p, lay);
-  if (rc != KDEHIP_OK || Np == 0) { delete p; return rc; }
+  if (rc != KDEHIP_OK || Np == 0) return rc;
   const int device = p->device;
-  if (device < 0 || device >= kMaxDevices) { delete p; return set_error(KDEHIP_ERR_UNSUPPORTED, "device ordinal beyond the library's bookkeeping (64)"); }
+  if (device < 0 || device >= kMaxDevices) return set_error(KDEHIP_ERR_UNSUPPORTED, "device ordinal beyond the library's bookkeeping (64)");
   DeviceGuard guard;
   rc = guard.enter(device);
-  if (rc != KDEHIP_OK) { delete p; return rc; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  reap_pending(device, false, st);
+  if (rc != KDEHIP_OK) return rc;
+  reap_deferred(device, st, kMaxPending);
   // the block: head [counter | levels | table descriptors | fill jobs], body [permutation | tiles | tables]
   const size_t nlev = p->host.levels.size();
   const size_t off_jobs = lay.head_end, head_bytes = align256(off_jobs + nlev * sizeof(FillJob));
   const size_t total = head_bytes + lay.body_end;
-  PendingPlan pend;
-  pend.plans.push_back(p);
-  pend.h_bytes = head_bytes;
-  pend.stream = st;
-  pend.device = device;
   hipStream_t prep = own_prep ? prep_stream(device) : nullptr;
-  void *blob = nullptr;
-  hipError_t e = cached_malloc(&blob, total);
-  if (e == hipSuccess) { p->d_blob = blob; p->blob_bytes = total; }
-  if (e == hipSuccess) e = cached_host_malloc(&pend.h_desc, pend.h_bytes);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&pend.done, hipEventDisableTiming);
-  if (e == hipSuccess && prep) e = hipEventCreateWithFlags(&pend.prepared, hipEventDisableTiming);
+  CallBlock blk;  // (an error return after a launch: it waits for both streams before the blocks go back)
+  hipError_t e = blk.alloc(total, head_bytes);
+  if (e == hipSuccess && prep) e = hipEventCreateWithFlags(&p->prepared, hipEventDisableTiming);
   if (e == hipSuccess && g_profile_sampler.load(std::memory_order_relaxed)) {
-    e = hipEventCreate(&pend.t_begin);
-    if (e == hipSuccess) e = hipEventCreate(&pend.t_end);
+    e = hipEventCreate(&p->t_begin);
+    if (e == hipSuccess) e = hipEventCreate(&p->t_end);
   }
-  if (e != hipSuccess) {
-    release_pending(pend);
-    return set_error(KDEHIP_ERR_HIP, std::string("device product: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return set_error(KDEHIP_ERR_HIP, std::string("device product: ") + hipGetErrorString(e));
   // descriptors: a few KB from pinned memory, in front of the launches
-  unsigned char *hb = static_cast<unsigned char *>(pend.h_desc);
-  const int maxB = describe_resident(p, trees, lay, blob, hb, 0, head_bytes, reinterpret_cast<FillJob *>(hb + off_jobs));
+  unsigned char *hb = blk.host();
+  const int maxB = describe_resident(p, trees, lay, blk.dev(), hb, 0, head_bytes, reinterpret_cast<FillJob *>(hb + off_jobs));
   p->blob_bytes = total;
   hipStream_t ps = prep ? prep : st;  // where the plan is prepared
-  auto fail = [&](int code) {  // (nothing of this plan has been handed to the queue yet)
-    if (prep) (void)hipStreamSynchronize(prep);
-    (void)hipStreamSynchronize(st);
-    release_pending(pend);
-    return code;
-  };
-  if (hipMemcpyAsync(blob, hb, head_bytes, hipMemcpyHostToDevice, ps) != hipSuccess)
-    return fail(set_error(KDEHIP_ERR_HIP, "device product: descriptor upload failed"));
-  rc = launch_fill_tiles(precision, reinterpret_cast<const FillJob *>(static_cast<unsigned char *>(blob) + off_jobs),
-                         static_cast<int>(nlev), maxB, ps);
-  if (rc != KDEHIP_OK) return fail(rc);
+  if (blk.upload(head_bytes, ps) != hipSuccess) return set_error(KDEHIP_ERR_HIP, "device product: descriptor upload failed");
+  rc = launch_fill_tiles(precision, reinterpret_cast<const FillJob *>(blk.dev() + off_jobs), static_cast<int>(nlev), maxB, ps);
+  if (rc != KDEHIP_OK) return rc;
+  blk.touch(st);
   rc = enqueue_philox(p, Np, Niter, seed, sample_offset, addEntropy, d_points, d_indices, d_labels, stream,
-                      /*private_plan=*/true, nullptr, prep, pend.prepared, pend.t_begin, pend.t_end);
-  if (rc != KDEHIP_OK) return fail(rc);
-  if (hipEventRecord(pend.done, st) != hipSuccess) return fail(set_error(KDEHIP_ERR_HIP, "device product: hipEventRecord failed"));
-  {
-    std::lock_guard<std::mutex> lock(g_pending_mu);
-    g_pending[device].push_back(std::move(pend));
-  }
-  return KDEHIP_OK;
+                      /*private_plan=*/true, nullptr, prep, p->prepared, p->t_begin, p->t_end);
+  if (rc != KDEHIP_OK) return rc;
+  return blk.defer(device, release_call_plans, call.hand_over());
 }
 
 // whether a product can ride in a batched launch of the register-resident sampler (gibbs_lean.hip, BATCH instantiations:
@@ -1025,19 +951,10 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
   if (precision != 64 && precision != 32) return set_error(KDEHIP_ERR_ARG, "precision must be 64 or 32");
   if (nprod == 0) return KDEHIP_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  PendingPlan pend;
-  pend.stream = st;
-  struct Abort {  // on an error before the hand-over to the queue: nothing has been enqueued that uses the block
-    PendingPlan *pp; bool armed = true;
-    // (the blocks go back to the cache of the CURRENT device, and the function's own DeviceGuard -- declared later, destroyed
-    // earlier -- has restored the caller's by now: enter the batch's device again for the release)
-    ~Abort() {
-      if (!armed) return;
-      DeviceGuard g;
-      (void)g.enter(pp->device);
-      release_pending(*pp);
-    }
-  } abort_guard{&pend};
+  CallPlans call;  // (on an error before the hand-over to the queue it deletes the plans)
+  call.stream = st;
+  std::vector<kdehip_product *> plans;
+  plans.reserve(nprod);
   std::vector<ResidentLayout> lays(nprod);
   std::vector<size_t> head_at(nprod), body_at(nprod), jobs_at(nprod);
   size_t head = 0, body = 0, njobs = 0;
@@ -1050,7 +967,8 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
     if (it.Np > 0 && (!it.d_points || !it.d_indices)) return set_error(KDEHIP_ERR_ARG, "null output pointer");
     kdehip_product *p = new (std::nothrow) kdehip_product();
     if (!p) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
-    pend.plans.push_back(p);
+    call.add(p);
+    plans.push_back(p);
     const int rc = layout_resident(it.Ndens, it.trees, it.partialDimMask, precision, p, lays[i]);
     if (rc != KDEHIP_OK) return rc;
     if (device < 0) device = p->device;
@@ -1060,7 +978,6 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
     jobs_at[i] = njobs; njobs += p->host.levels.size();
   }
   if (device < 0 || device >= kMaxDevices) return set_error(KDEHIP_ERR_UNSUPPORTED, "device ordinal beyond the library's bookkeeping (64)");
-  pend.device = device;
   // groups of batchable products by (D, M); everything else runs one by one
   struct Group {
     int D, M;
@@ -1079,7 +996,7 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
   constexpr int kBatchWaves = 16;  // chains per workgroup of the batched instantiations
   for (int i = 0; i < nprod; ++i) {
     if (items[i].Np == 0) continue;
-    kdehip_product *p = pend.plans[i];
+    kdehip_product *p = plans[i];
     if (!batchable(p)) { singles.push_back(i); continue; }
     Group *g = nullptr;
     for (Group &c : groups) if (c.D == p->host.D && c.M == p->host.M) g = &c;
@@ -1095,7 +1012,7 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
   // tables when chains x tabulated levels x sweeps x densities >= 6.5 x rows.  KDEHIP_BATCH_TABLES=0/1 forces never/always.
   static const int force_tables = [] { const char *e = std::getenv("KDEHIP_BATCH_TABLES"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
   auto has_tables = [&](int i) {
-    const kdehip_product *p = pend.plans[i];
+    const kdehip_product *p = plans[i];
     if (p->mode == kModeGeneric || p->host.Lt <= 0 || p->host.tab_rows <= 0 || items[i].Np < kTabMinChains) return false;
     if (force_tables >= 0) return force_tables == 1;
     const double saved = static_cast<double>(items[i].Np) * p->host.Lt * items[i].Niter * p->host.M;
@@ -1105,7 +1022,7 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
     for (int i : g.members)
       if (has_tables(i)) {
         g.tabbed.push_back(i);
-        g.tab_blocks += (pend.plans[i]->host.tab_rows + kTabWaves - 1) / kTabWaves;
+        g.tab_blocks += (plans[i]->host.tab_rows + kTabWaves - 1) / kTabWaves;
       }
   const size_t off_jobs = head;
   size_t at = align256(off_jobs + njobs * sizeof(FillJob));
@@ -1121,18 +1038,14 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
   DeviceGuard guard;
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
-  reap_pending(device, false, st);
-  pend.h_bytes = head_bytes;
-  pend.blob_bytes = total;
-  hipError_t e = cached_malloc(&pend.d_blob, total);
-  if (e != hipSuccess) pend.d_blob = nullptr;
-  if (e == hipSuccess) e = cached_host_malloc(&pend.h_desc, pend.h_bytes);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&pend.done, hipEventDisableTiming);
+  reap_deferred(device, st, kMaxPending);
+  CallBlock blk;  // (work may have been enqueued when an error returns: it waits for the stream before the blocks go back)
+  const hipError_t e = blk.alloc(total, head_bytes);
   if (e != hipSuccess) return set_error(KDEHIP_ERR_HIP, std::string("batched products: ") + hipGetErrorString(e));
-  unsigned char *hb = static_cast<unsigned char *>(pend.h_desc), *db = static_cast<unsigned char *>(pend.d_blob);
+  unsigned char *hb = blk.host(), *db = blk.dev();
   int maxB = 1;
   for (int i = 0; i < nprod; ++i) {
-    const int b = describe_resident(pend.plans[i], items[i].trees, lays[i], pend.d_blob, hb, head_at[i], head_bytes + body_at[i],
+    const int b = describe_resident(plans[i], items[i].trees, lays[i], db, hb, head_at[i], head_bytes + body_at[i],
                                     reinterpret_cast<FillJob *>(hb + off_jobs) + jobs_at[i]);
     if (b > maxB) maxB = b;
   }
@@ -1144,7 +1057,7 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
       const int i = g.members[k];
       const kdehip_batch_item &it = items[i];
       BatchEntry be{};
-      const PlanDev &pd = pend.plans[i]->dev;
+      const PlanDev &pd = plans[i]->dev;
       be.head = BatchPlanHead{pd.data, pd.perm, pd.levels, pd.tables, pd.tabdesc, pd.tab_rows_total, pd.M, pd.L, pd.D, pd.Lt};
       be.run.Np = it.Np; be.run.seed = it.seed; be.run.sample_offset = it.sample_offset;
       be.run.points = it.d_points; be.run.indices = it.d_indices; be.run.labels = it.d_labels;
@@ -1163,20 +1076,15 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
       if (!ent[k].flags.use_tables) continue;
       tent[kt] = ent[k];
       tent[kt].flags.first_block = tblock;
-      const int32_t nb = static_cast<int32_t>((pend.plans[g.members[k]]->host.tab_rows + kTabWaves - 1) / kTabWaves);
+      const int32_t nb = static_cast<int32_t>((plans[g.members[k]]->host.tab_rows + kTabWaves - 1) / kTabWaves);
       for (int32_t q = 0; q < nb; ++q) tmap[tblock + q] = kt;
       tblock += nb;
       ++kt;
     }
   }
-  auto fail = [&](int code) {  // work may have been enqueued: wait for it before the block goes back to the cache
-    (void)hipStreamSynchronize(st);
-    return code;
-  };
-  if (hipMemcpyAsync(pend.d_blob, hb, head_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-    return fail(set_error(KDEHIP_ERR_HIP, "batched products: descriptor upload failed"));
+  if (blk.upload(head_bytes, st) != hipSuccess) return set_error(KDEHIP_ERR_HIP, "batched products: descriptor upload failed");
   rc = launch_fill_tiles(precision, reinterpret_cast<const FillJob *>(db + off_jobs), static_cast<int>(njobs), maxB, st);
-  if (rc != KDEHIP_OK) return fail(rc);
+  if (rc != KDEHIP_OK) return rc;
   for (const Group &g : groups) {
     if (g.tab_blocks > 0) {  // one launch fills the conditional tables of every member that has them
       RunArgs t{};
@@ -1184,30 +1092,24 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
       t.batch = reinterpret_cast<const BatchEntry *>(db + g.tent_at);
       t.batch_map = reinterpret_cast<const int32_t *>(db + g.tmap_at);
       t.Np = g.tab_blocks * kTabWaves;
-      rc = launch_tables_batch(g.D, pend.plans[g.tabbed[0]]->dev, t, st);
-      if (rc != KDEHIP_OK) return fail(rc);
+      rc = launch_tables_batch(g.D, plans[g.tabbed[0]]->dev, t, st);
+      if (rc != KDEHIP_OK) return rc;
     }
     RunArgs a{};
     a.rng_philox = 1;
     a.batch = reinterpret_cast<const BatchEntry *>(db + g.ent_at);
     a.batch_map = reinterpret_cast<const int32_t *>(db + g.map_at);
     a.Np = g.blocks * kBatchWaves;  // (the launcher's grid: g.blocks workgroups)
-    rc = launch_gibbs_batch(g.D, g.M, pend.plans[g.members[0]]->dev, a, st);
-    if (rc != KDEHIP_OK) return fail(rc);
+    rc = launch_gibbs_batch(g.D, g.M, plans[g.members[0]]->dev, a, st);
+    if (rc != KDEHIP_OK) return rc;
   }
   for (int i : singles) {
     const kdehip_batch_item &it = items[i];
-    rc = enqueue_philox(pend.plans[i], it.Np, it.Niter, it.seed, it.sample_offset, it.addEntropy, it.d_points, it.d_indices,
+    rc = enqueue_philox(plans[i], it.Np, it.Niter, it.seed, it.sample_offset, it.addEntropy, it.d_points, it.d_indices,
                         it.d_labels, stream, /*private_plan=*/true);
-    if (rc != KDEHIP_OK) return fail(rc);
+    if (rc != KDEHIP_OK) return rc;
   }
-  if (hipEventRecord(pend.done, st) != hipSuccess) return fail(set_error(KDEHIP_ERR_HIP, "batched products: hipEventRecord failed"));
-  abort_guard.armed = false;
-  {
-    std::lock_guard<std::mutex> lock(g_pending_mu);
-    g_pending[device].push_back(std::move(pend));
-  }
-  return KDEHIP_OK;
+  return blk.defer(device, release_call_plans, call.hand_over());
 }
 
 }  // extern "C"
@@ -1240,7 +1142,7 @@ int kdehip_profile_sampler_read(int device, void *stream, double *total_ms, int6
   DeviceGuard guard;
   const int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
-  reap_pending(device, true);  // (waits for the plans still in flight: their launches count too)
+  drain_deferred(device);  // (waits for the plans still in flight: their launches count too)
   std::lock_guard<std::mutex> lock(g_profile_mu);
   double ms = 0.0;
   long long n = 0;
@@ -1264,24 +1166,18 @@ int kdehip_prod_philox_resident(int Ndens, kdehip_device_density *const *trees, 
   int rc = guard.enter(trees[0]->device);
   if (rc != KDEHIP_OK) return rc;
   const size_t off_i = align256(sizeof(double) * D * Np), span = off_i + sizeof(int64_t) * M * Np;
-  void *d_out = nullptr, *h_out = nullptr;
-  KDEHIP_CHECK(cached_malloc(&d_out, span));
-  hipError_t e = cached_host_malloc(&h_out, span);
-  if (e != hipSuccess) { cached_free(d_out, span); return set_error(KDEHIP_ERR_HIP, "pinned result block"); }
-  unsigned char *w = static_cast<unsigned char *>(d_out);
+  CallBlock out;
+  KDEHIP_CHECK(out.alloc(span, span));
+  out.touch(call_stream());  // (the product below runs there: also an error waits for it before the blocks go back)
+  unsigned char *w = out.dev();
   rc = prod_philox_device(Ndens, trees, Np, Niter, seed, 0, addEntropy, partialDimMask, precision,
                           reinterpret_cast<double *>(w), reinterpret_cast<int64_t *>(w + off_i), nullptr, call_stream(),
                           /*own_prep=*/false);
-  if (rc == KDEHIP_OK) e = hipMemcpyAsync(h_out, d_out, span, hipMemcpyDeviceToHost, call_stream());
-  const hipError_t se = hipStreamSynchronize(call_stream());  // (also before the blocks go back to the caches on an error)
-  if (rc == KDEHIP_OK && e == hipSuccess && se == hipSuccess) {
-    std::memcpy(pts, h_out, sizeof(double) * D * Np);
-    std::memcpy(ind, static_cast<unsigned char *>(h_out) + off_i, sizeof(int64_t) * M * Np);
-  }
-  cached_host_free(h_out, span);
-  cached_free(d_out, span);
   if (rc != KDEHIP_OK) return rc;
+  const hipError_t e = out.download(0, span, call_stream()), se = out.wait();
   if (e != hipSuccess || se != hipSuccess) return set_error(KDEHIP_ERR_HIP, "device product: result copy failed");
+  std::memcpy(pts, out.host(), sizeof(double) * D * Np);
+  std::memcpy(ind, out.host() + off_i, sizeof(int64_t) * M * Np);
   return KDEHIP_OK;
 }
 

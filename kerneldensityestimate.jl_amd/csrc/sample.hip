@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "philox.hpp"
@@ -62,10 +63,11 @@ struct TableJob {
 struct CdfLayout {
   size_t o_inv = 0, o_status = 0, total = 0;
   explicit CdfLayout(int64_t N) {
-    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-    o_inv = al(sizeof(double) * N);
-    o_status = al(o_inv + sizeof(int32_t) * N);
-    total = o_status + 256;
+    Carve c;
+    c.take(sizeof(double) * N);
+    o_inv = c.take(sizeof(int32_t) * N);
+    o_status = c.take(sizeof(int32_t));
+    total = c.mark();
   }
 };
 
@@ -220,12 +222,6 @@ int blocks_for(int64_t Npts) {
   return static_cast<int>(t < kMaxBlocksPerItem ? t : kMaxBlocksPerItem);
 }
 
-// device scratch of a blocking call whose work runs on the calling thread's stream: an error return waits for what has
-// been enqueued before the block goes back to the cache
-struct SyncedDevBuf : DevBuf {
-  ~SyncedDevBuf() { if (p) (void)hipStreamSynchronize(hipStreamPerThread); }
-};
-
 int launch_draw(int D, const SampleItem &it, hipStream_t st) {
   KDEHIP_CHECK_RC(dispatch_dims(D, [&](auto dim) {
     hipLaunchKernelGGL(sample_kernel<decltype(dim)::value>, dim3(blocks_for(it.Npts)), dim3(kDrawBlock), 0, st, it);
@@ -323,69 +319,9 @@ SampleItem item_of(const kdehip_device_density *h, int64_t Npts, uint64_t seed, 
                     h->means + h->N * h->D, h->bandwidth + h->N * h->D, h->N, Npts, seed, offset, ind_in, pts, ind};
 }
 
-// Descriptor blocks of enqueue-only batch calls, released once the event recorded behind their launches has fired
-// (by later batch calls, or kdehip_clear_cache).
-struct PendingDesc {
-  hipEvent_t done = nullptr;
-  void *d = nullptr, *h = nullptr;
-  size_t bytes = 0;
-  size_t hbytes = 0;  // (0: the pinned block has `bytes` too)
-  int device = 0;
-};
-std::mutex g_desc_mu;
-std::vector<PendingDesc> g_desc;
-
-void release_desc(PendingDesc &p) {
-  if (p.done) (void)hipEventDestroy(p.done);
-  if (p.d) cached_free(p.d, p.bytes);
-  if (p.h) cached_host_free(p.h, p.hbytes ? p.hbytes : p.bytes);
-}
-// (the device is current) releases every finished entry of `device`; all = wait for the unfinished ones too
-void reap_desc(int device, bool all) {
-  std::vector<PendingDesc> take;
-  {
-    std::lock_guard<std::mutex> lock(g_desc_mu);
-    for (auto it = g_desc.begin(); it != g_desc.end();) {
-      if (it->device == device && (all || hipEventQuery(it->done) == hipSuccess)) { take.push_back(*it); it = g_desc.erase(it); }
-      else ++it;
-    }
-    (void)hipGetLastError();  // (hipEventQuery reports "not ready" as an error)
-  }
-  for (PendingDesc &p : take) {
-    if (all) (void)hipEventSynchronize(p.done);
-    release_desc(p);
-  }
-}
-
 bool weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }
 
 }  // namespace
-
-int kdehip::release_after(int device, void *d, size_t dbytes, void *h, size_t hbytes, void *stream) {
-  reap_desc(device, false);
-  PendingDesc pd;
-  pd.device = device;
-  pd.d = d; pd.bytes = dbytes ? dbytes : 1;
-  pd.h = h; pd.hbytes = hbytes ? hbytes : 1;
-  hipError_t e = hipEventCreateWithFlags(&pd.done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(pd.done, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
-    release_desc(pd);
-    return set_error(KDEHIP_ERR_HIP, std::string("release_after: ") + hipGetErrorString(e));
-  }
-  std::lock_guard<std::mutex> lock(g_desc_mu);
-  g_desc.push_back(pd);
-  return KDEHIP_OK;
-}
-
-void kdehip::drain_sample_pending() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return;
-  DeviceGuard guard;
-  for (int d = 0; d < n; ++d)
-    if (guard.enter(d) == KDEHIP_OK) reap_desc(d, true);
-}
 
 extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
                              const int64_t *ind_in, double *pts, int64_t *ind, int device) {
@@ -427,14 +363,16 @@ extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t see
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
   hipStream_t st = hipStreamPerThread;
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
   const size_t nd = sizeof(double) * N * D;
-  const size_t o_inv = al(sizeof(double) * N), o_m = al(o_inv + sizeof(int32_t) * N), o_v = al(o_m + nd), o_in = al(o_v + nd),
-               o_pts = al(o_in + (ind_in ? sizeof(int64_t) * Npts : 0)), o_ind = al(o_pts + sizeof(double) * Npts * D),
-               total = al(o_ind + sizeof(int64_t) * Npts);
-  SyncedDevBuf sc;
-  KDEHIP_CHECK(sc.alloc(total));
-  unsigned char *b = sc.as<unsigned char>();
+  Carve c;
+  c.take(sizeof(double) * N);
+  const size_t o_inv = c.take(sizeof(int32_t) * N), o_m = c.take(nd), o_v = c.take(nd),
+               o_in = c.take(ind_in ? sizeof(int64_t) * Npts : 0), o_pts = c.take(sizeof(double) * Npts * D),
+               o_ind = c.take(sizeof(int64_t) * Npts);
+  CallBlock sc;
+  KDEHIP_CHECK(sc.alloc(c.mark()));
+  sc.touch(st);
+  unsigned char *b = sc.dev();
   KDEHIP_CHECK(hipMemcpyAsync(b, C.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
   KDEHIP_CHECK(hipMemcpyAsync(b + o_inv, inv.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, st));
   KDEHIP_CHECK(hipMemcpyAsync(b + o_m, p->means + N * D, nd, hipMemcpyHostToDevice, st));
@@ -448,7 +386,7 @@ extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t see
   if (rc != KDEHIP_OK) return rc;
   KDEHIP_CHECK(hipMemcpyAsync(pts, b + o_pts, sizeof(double) * Npts * D, hipMemcpyDeviceToHost, st));
   KDEHIP_CHECK(hipMemcpyAsync(ind, b + o_ind, sizeof(int64_t) * Npts, hipMemcpyDeviceToHost, st));
-  KDEHIP_CHECK(hipStreamSynchronize(st));
+  KDEHIP_CHECK(sc.wait());
   return KDEHIP_OK;
 }
 
@@ -501,7 +439,7 @@ extern "C" int kdehip_sample_device_batch(int n, const kdehip_sample_item *items
     rc = ready_error(h);
     if (rc != KDEHIP_OK) return rc;
   }
-  reap_desc(device, false);
+  reap_deferred(device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // per D: [items | first blocks], one upload through a pinned block, one launch
   for (int D = 1; D <= KDEHIP_MAX_DIMS; ++D) {
@@ -517,30 +455,17 @@ extern "C" int kdehip_sample_device_batch(int n, const kdehip_sample_item *items
     }
     if (its.empty()) continue;
     const int m = static_cast<int>(its.size());
-    const size_t o_first = (sizeof(SampleItem) * m + 255) & ~static_cast<size_t>(255);
-    PendingDesc pd;
-    pd.device = device;
-    pd.bytes = o_first + sizeof(int32_t) * first.size();
-    KDEHIP_CHECK(cached_host_malloc(&pd.h, pd.bytes));
-    hipError_t e = cached_malloc(&pd.d, pd.bytes);
-    if (e != hipSuccess) { cached_host_free(pd.h, pd.bytes); return set_error(KDEHIP_ERR_HIP, std::string("sample batch: ") + hipGetErrorString(e)); }
-    std::memcpy(pd.h, its.data(), sizeof(SampleItem) * m);
-    std::memcpy(static_cast<unsigned char *>(pd.h) + o_first, first.data(), sizeof(int32_t) * first.size());
-    e = hipMemcpyAsync(pd.d, pd.h, pd.bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-      rc = launch_draw_batch(D, static_cast<const SampleItem *>(pd.d),
-                             reinterpret_cast<const int32_t *>(static_cast<unsigned char *>(pd.d) + o_first), m, first.back(), st);
-      if (rc != KDEHIP_OK) e = hipErrorLaunchFailure;
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&pd.done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(pd.done, st);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(st);
-      release_desc(pd);
-      return rc != KDEHIP_OK ? rc : set_error(KDEHIP_ERR_HIP, std::string("sample batch: ") + hipGetErrorString(e));
-    }
-    std::lock_guard<std::mutex> lock(g_desc_mu);
-    g_desc.push_back(pd);
+    const size_t o_first = align256(sizeof(SampleItem) * m), bytes = o_first + sizeof(int32_t) * first.size();
+    CallBlock blk;
+    hipError_t e = blk.alloc(bytes, bytes);
+    if (e != hipSuccess) return set_error(KDEHIP_ERR_HIP, std::string("sample batch: ") + hipGetErrorString(e));
+    std::memcpy(blk.host(), its.data(), sizeof(SampleItem) * m);
+    std::memcpy(blk.host() + o_first, first.data(), sizeof(int32_t) * first.size());
+    e = blk.upload(bytes, st);
+    if (e != hipSuccess) return set_error(KDEHIP_ERR_HIP, std::string("sample batch: ") + hipGetErrorString(e));
+    KDEHIP_CHECK_RC(launch_draw_batch(D, reinterpret_cast<const SampleItem *>(blk.dev()),
+                                      reinterpret_cast<const int32_t *>(blk.dev() + o_first), m, first.back(), st));
+    KDEHIP_CHECK_RC(blk.defer(device));
   }
   return KDEHIP_OK;
 }
@@ -557,12 +482,12 @@ extern "C" int kdehip_resample_device(kdehip_device_density **out, kdehip_device
   if (rc != KDEHIP_OK) return rc;
   hipStream_t cs = hipStreamPerThread;
   const int D = p->D;
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  SyncedDevBuf sc;
-  const size_t o_ind = al(sizeof(double) * Np * D);
+  const size_t o_ind = align256(sizeof(double) * Np * D);
+  CallBlock sc;
   KDEHIP_CHECK(sc.alloc(o_ind + sizeof(int64_t) * Np));
-  double *d_pts = sc.as<double>();
-  int64_t *d_ind = reinterpret_cast<int64_t *>(sc.as<unsigned char>() + o_ind);
+  sc.touch(cs);
+  double *d_pts = reinterpret_cast<double *>(sc.dev());
+  int64_t *d_ind = reinterpret_cast<int64_t *>(sc.dev() + o_ind);
   rc = kdehip_sample_device(p, Np, seed, 0, nullptr, d_pts, d_ind, cs);
   if (rc != KDEHIP_OK) return rc;
   return kdehip_density_from_device_points(out, d_pts, D, Np, p->device, cs, bw_out, nevals);

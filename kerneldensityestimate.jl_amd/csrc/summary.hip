@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_density.hpp"
+#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
@@ -324,13 +325,7 @@ __global__ __launch_bounds__(kSumThreads) void inters_reduce_kernel(const double
 class SumRun {
  public:
   std::vector<SumItem> items;
-  ~SumRun() {
-    if (armed_) (void)hipStreamSynchronize(st_);
-    if (d_) cached_free(d_, dbytes_);
-    if (h_) cached_host_free(h_, hbytes_);
-  }
   int alloc(size_t extra) {
-    auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
     const size_t n = items.size();
     const int64_t cu = device_cu_count();
     int64_t pblocks = 0;
@@ -349,21 +344,17 @@ class SumRun {
       pblocks += static_cast<int64_t>(it.D) * it.ngroups * it.gblocks;
     }
     if (pblocks > INT32_MAX || n > 65535) return set_error(KDEHIP_ERR_UNSUPPORTED, "summary too large for one launch");
-    o_items_ = 0;
-    o_first_ = al(sizeof(SumItem) * n);
-    o_extra_ = al(o_first_ + sizeof(int32_t) * 2 * (n + 1));
-    size_t o = al(o_extra_ + extra);
+    Carve c;
+    o_items_ = c.take(sizeof(SumItem) * n);
+    o_first_ = c.take(sizeof(int32_t) * 2 * (n + 1));
+    o_extra_ = c.take(extra);
     extra_ = extra;
     scratch_.resize(n);
     for (size_t k = 0; k < n; ++k) {
       const SumItem &it = items[k];
-      scratch_[k] = o;
-      o = al(o + sizeof(double) * (it.D * it.N + 3 * it.D + 1 + static_cast<int64_t>(it.D) * it.ngroups * it.Ngrid));
+      scratch_[k] = c.take(sizeof(double) * (it.D * it.N + 3 * it.D + 1 + static_cast<int64_t>(it.D) * it.ngroups * it.Ngrid));
     }
-    dbytes_ = o;
-    hbytes_ = o_extra_ + extra;
-    KDEHIP_CHECK(cached_malloc(&d_, dbytes_));
-    KDEHIP_CHECK(cached_host_malloc(&h_, hbytes_));
+    KDEHIP_CHECK(blk_.alloc(c.mark(), o_extra_ + extra));
     for (size_t k = 0; k < n; ++k) {
       SumItem &it = items[k];
       it.orig = reinterpret_cast<double *>(dev() + scratch_[k]);
@@ -372,14 +363,13 @@ class SumRun {
     }
     return KDEHIP_OK;
   }
-  unsigned char *dev() const { return static_cast<unsigned char *>(d_); }
+  unsigned char *dev() const { return blk_.dev(); }
   double *extra() const { return reinterpret_cast<double *>(dev() + o_extra_); }  // (device)
-  const double *host_extra() const { return reinterpret_cast<const double *>(static_cast<unsigned char *>(h_) + o_extra_); }
+  const double *host_extra() const { return reinterpret_cast<const double *>(blk_.host() + o_extra_); }
 
   int enqueue(hipStream_t st) {
-    st_ = st;
     const size_t n = items.size();
-    unsigned char *h = static_cast<unsigned char *>(h_);
+    unsigned char *h = blk_.host();
     int32_t *pfirst = reinterpret_cast<int32_t *>(h + o_first_), *ffirst = pfirst + (n + 1);
     pfirst[0] = ffirst[0] = 0;
     for (size_t k = 0; k < n; ++k) {
@@ -388,8 +378,7 @@ class SumRun {
       ffirst[k + 1] = ffirst[k] + (it.grid ? it.D : 0);
     }
     if (n) std::memcpy(h + o_items_, items.data(), sizeof(SumItem) * n);
-    armed_ = true;
-    KDEHIP_CHECK(hipMemcpyAsync(d_, h_, o_extra_, hipMemcpyHostToDevice, st));
+    KDEHIP_CHECK(blk_.upload(o_extra_, st));
     const SumItem *d_items = reinterpret_cast<const SumItem *>(dev() + o_items_);
     const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 1);
     if (n) hipLaunchKernelGGL(summary_moments_kernel, dim3(static_cast<unsigned>(n)), dim3(kSumThreads), 0, st, d_items);
@@ -404,26 +393,21 @@ class SumRun {
   }
   int wait() {
     hipError_t e = hipSuccess;
-    if (extra_) e = hipMemcpyAsync(static_cast<unsigned char *>(h_) + o_extra_, extra(), extra_, hipMemcpyDeviceToHost, st_);
-    const hipError_t se = hipStreamSynchronize(st_);
-    armed_ = false;
+    if (extra_) e = blk_.download(o_extra_, extra_, blk_.stream());
+    const hipError_t se = blk_.wait();
     KDEHIP_CHECK(e);
     KDEHIP_CHECK(se);
     return KDEHIP_OK;
   }
   int defer(int device) {
-    const int rc = release_after(device, d_, dbytes_, h_, hbytes_, st_);
-    d_ = h_ = nullptr;
-    armed_ = false;
-    return rc;
+    reap_deferred(device);
+    return blk_.defer(device);
   }
 
  private:
-  void *d_ = nullptr, *h_ = nullptr;
-  size_t dbytes_ = 0, hbytes_ = 0, o_items_ = 0, o_first_ = 0, o_extra_ = 0, extra_ = 0;
+  CallBlock blk_;
+  size_t o_items_ = 0, o_first_ = 0, o_extra_ = 0, extra_ = 0;
   std::vector<size_t> scratch_;
-  hipStream_t st_ = nullptr;
-  bool armed_ = false;
 };
 
 // the descriptor of a resident density (outputs, extend, grid set by the caller)
@@ -473,10 +457,11 @@ int inters_resident(const kdehip_device_density *p, const kdehip_device_density 
   DeviceGuard guard;
   KDEHIP_CHECK_RC(guard.enter(p->device));
   hipStream_t st = hipStreamPerThread;
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
   // extra: [result | query points Nq x D | p values | q values | row sums]
-  const size_t o_pts = 256, o_pv = al(o_pts + sizeof(double) * Nq * D), o_qv = al(o_pv + sizeof(double) * Nq);
-  const size_t o_rows = al(o_qv + sizeof(double) * Nq), extra = o_rows + sizeof(double) * Ngrid;
+  Carve c;
+  c.take(sizeof(double));
+  const size_t o_pts = c.take(sizeof(double) * Nq * D), o_pv = c.take(sizeof(double) * Nq), o_qv = c.take(sizeof(double) * Nq);
+  const size_t o_rows = c.mark(), extra = o_rows + sizeof(double) * Ngrid;
   SumRun run;
   run.items.push_back(density_item(p, 0.3, Ngrid));  // LD[d] = getKDERangeLinspace(marginal(p, [d]), extend=0.3) (:599)
   KDEHIP_CHECK_RC(run.alloc(extra));

@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
@@ -60,19 +61,19 @@ struct TreeLds {
   size_t off_u, off_keys, off_slot, off_cur, off_nxt, off_dim, total;
   size_t u_bytes;
 };
+__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
 inline TreeLds tree_lds(int64_t N, int D) {
-  auto al = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
   TreeLds l;
   const size_t pts_bytes = static_cast<size_t>(N) * D * 8;
-  const size_t sel_bytes = al(static_cast<size_t>(N) * 8) + al(static_cast<size_t>(N) * 2) + al(static_cast<size_t>(N) * 4) * 2;
-  l.u_bytes = al(pts_bytes > sel_bytes ? pts_bytes : sel_bytes);
+  const size_t sel_bytes = align16(static_cast<size_t>(N) * 8) + align16(static_cast<size_t>(N) * 2) + align16(static_cast<size_t>(N) * 4) * 2;
+  l.u_bytes = align16(pts_bytes > sel_bytes ? pts_bytes : sel_bytes);
   l.off_u = 0;
   l.off_keys = l.off_u + l.u_bytes;
-  l.off_slot = l.off_keys + al(static_cast<size_t>(N) * 8);
-  l.off_cur = l.off_slot + al(static_cast<size_t>(N) * 2);
-  l.off_nxt = l.off_cur + al((static_cast<size_t>(N) / 2 + 1) * sizeof(Range));
-  l.off_dim = l.off_nxt + al((static_cast<size_t>(N) / 2 + 1) * sizeof(Range));
-  l.total = l.off_dim + al(static_cast<size_t>(N) / 2 + 1);
+  l.off_slot = l.off_keys + align16(static_cast<size_t>(N) * 8);
+  l.off_cur = l.off_slot + align16(static_cast<size_t>(N) * 2);
+  l.off_nxt = l.off_cur + align16((static_cast<size_t>(N) / 2 + 1) * sizeof(Range));
+  l.off_dim = l.off_nxt + align16((static_cast<size_t>(N) / 2 + 1) * sizeof(Range));
+  l.total = l.off_dim + align16(static_cast<size_t>(N) / 2 + 1);
   return l;
 }
 
@@ -210,11 +211,10 @@ __global__ __launch_bounds__(kTB) void tree_build_kernel(const TreeBatch batch, 
   Range *nxt = reinterpret_cast<Range *>(smem + L.off_nxt);
   uint8_t *dimv = smem + L.off_dim;
   // select-phase view of the union region
-  auto al = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
   double *K2 = U;
-  uint16_t *S2 = reinterpret_cast<uint16_t *>(smem + L.off_u + al(static_cast<size_t>(N) * 8));
-  uint16_t *tp = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(S2) + al(static_cast<size_t>(N) * 2));
-  uint16_t *tq = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(tp) + al(static_cast<size_t>(N) * 4));
+  uint16_t *S2 = reinterpret_cast<uint16_t *>(smem + L.off_u + align16(static_cast<size_t>(N) * 8));
+  uint16_t *tp = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(S2) + align16(static_cast<size_t>(N) * 2));
+  uint16_t *tq = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(tp) + align16(static_cast<size_t>(N) * 4));
 
   // ---- makeBallTree / buildTree! initial state (:437-463, :415-434) ----
   for (int i = tid; i < 2 * N * D; i += kTB) { J.centers[i] = 0.0; J.ranges[i] = 0.0; J.means[i] = 0.0; J.bw[i] = 0.0; }
@@ -424,38 +424,26 @@ extern "C" int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns
   // one device block and one pinned block for the whole batch:
   //   in:  per density [points N*D | wnorm N]          out: [centers, ranges, means, bw: 2N*D each | weights 2N |
   //        left, right, lo, hi, perm: 2N int64 each] + scratch N int32
-  auto al = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  struct Off { size_t pts, wn, cen, rng, mea, bw, w, l, r, lo, hi, pm, scratch, in_end, out_begin, out_end; };
+  struct Off { size_t pts, wn, cen, rng, mea, bw, w, l, r, lo, hi, pm, scratch; };
   std::vector<Off> off(nb);
-  size_t in_total = 0;
+  Carve c;
   for (int j = 0; j < nb; ++j) {
-    off[j].pts = in_total; in_total = al(in_total + sizeof(double) * Ns[j] * D);
-    off[j].wn = in_total; in_total = al(in_total + sizeof(double) * Ns[j]);
+    off[j].pts = c.take(sizeof(double) * Ns[j] * D);
+    off[j].wn = c.take(sizeof(double) * Ns[j]);
   }
-  size_t total = in_total;
-  const size_t out_begin = total;
+  const size_t in_total = c.mark(), out_begin = in_total;
   for (int j = 0; j < nb; ++j) {
     const size_t nd = sizeof(double) * 2 * Ns[j] * D, n2 = sizeof(double) * 2 * Ns[j];
-    off[j].cen = total; total = al(total + nd);
-    off[j].rng = total; total = al(total + nd);
-    off[j].mea = total; total = al(total + nd);
-    off[j].bw = total; total = al(total + nd);
-    off[j].w = total; total = al(total + n2);
-    off[j].l = total; total = al(total + n2);
-    off[j].r = total; total = al(total + n2);
-    off[j].lo = total; total = al(total + n2);
-    off[j].hi = total; total = al(total + n2);
-    off[j].pm = total; total = al(total + n2);
+    Off &o = off[j];
+    for (size_t *q : {&o.cen, &o.rng, &o.mea, &o.bw}) *q = c.take(nd);
+    for (size_t *q : {&o.w, &o.l, &o.r, &o.lo, &o.hi, &o.pm}) *q = c.take(n2);
   }
-  const size_t out_end = total;
-  for (int j = 0; j < nb; ++j) { off[j].scratch = total; total = al(total + sizeof(int32_t) * Ns[j]); }
+  const size_t out_end = c.mark();
+  for (int j = 0; j < nb; ++j) off[j].scratch = c.take(sizeof(int32_t) * Ns[j]);
 
-  void *d_base = nullptr, *h_base = nullptr;
-  KDEHIP_CHECK(cached_malloc(&d_base, total));
-  struct Free { void *d, *h; size_t nd, nh; ~Free() { if (d) cached_free(d, nd); if (h) cached_host_free(h, nh); } } fr{d_base, nullptr, total, out_end};
-  KDEHIP_CHECK(cached_host_malloc(&h_base, out_end));
-  fr.h = h_base;
-  unsigned char *hb = static_cast<unsigned char *>(h_base), *db = static_cast<unsigned char *>(d_base);
+  CallBlock blk;
+  KDEHIP_CHECK(blk.alloc(c.mark(), out_end));
+  unsigned char *hb = blk.host(), *db = blk.dev();
 
   TreeBatch batch{};
   for (int j = 0; j < nb; ++j) {
@@ -486,7 +474,7 @@ extern "C" int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns
     J.perm = reinterpret_cast<int64_t *>(db + off[j].pm);
     J.nodes_by_depth = reinterpret_cast<int32_t *>(db + off[j].scratch);
   }
-  KDEHIP_CHECK(hipMemcpyAsync(d_base, h_base, in_total, hipMemcpyHostToDevice, hipStreamPerThread));
+  KDEHIP_CHECK(blk.upload(in_total, hipStreamPerThread));
   const TreeLds L = tree_lds(maxN, static_cast<int>(D));
   // (per call: the attribute belongs to the function ON THE CURRENT DEVICE, and concurrent host threads get here)
   KDEHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(tree_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -495,8 +483,8 @@ extern "C" int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns
   hipLaunchKernelGGL(tree_build_kernel, dim3(nb), dim3(kTB), L.total, hipStreamPerThread, batch, L);
   KDEHIP_CHECK(hipGetLastError());
   timer.stop();
-  KDEHIP_CHECK(hipMemcpyAsync(hb + out_begin, db + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, hipStreamPerThread));
-  KDEHIP_CHECK(hipStreamSynchronize(hipStreamPerThread));
+  KDEHIP_CHECK(blk.download(out_begin, out_end - out_begin, hipStreamPerThread));
+  KDEHIP_CHECK(blk.wait());
   timer.collect();
   for (int j = 0; j < nb; ++j) {
     const int64_t N = Ns[j];
