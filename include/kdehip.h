@@ -268,12 +268,30 @@ int kdehip_density_ndim(const kdehip_device_density *d);
 int kdehip_prod_philox_device(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
                               int64_t sample_offset, int addEntropy, const uint8_t *partialDimMask, int precision,
                               double *d_points, int64_t *d_indices, int32_t *d_labels, void *stream);
+/* The same on a manifold (`manifold`: ndims bytes of KDEHIP_MANIFOLD_EUCLIDEAN / KDEHIP_MANIFOLD_CIRCULAR or NULL, the
+ * operators of "manifolds" above, as kdehip_gibbs1_manifold takes them): resident inputs, device outputs, device Philox -- the
+ * tiles are re-laid-out on the GPU, no random numbers and no tiles cross PCIe.  A density set whose node values qualify for
+ * the fast arithmetic (finite, variances in range) runs the sampler's circular fast mode -- fast reciprocals, the
+ * product/rsqrt normalisation, the uniform-bandwidth and per-node fast evaluators with wrap() on the differences of the
+ * circular dimensions, the tangent-space getMu, wrap() where a sample is composed with its noise; no conditional tables and
+ * no fp32 screens --, any other set the generic arithmetic of kdehip_gibbs1_manifold.  Labels are those of that entry on the
+ * host twin of the Philox streams, points agree to rounding (1e-12).  manifold == NULL or all zeros IS the entry above, bit
+ * for bit.  A manifold byte above 1 is KDEHIP_ERR_ARG, more than KDEHIP_MAX_DIMS dimensions KDEHIP_ERR_UNSUPPORTED, a
+ * circular dimension with precision 32 KDEHIP_ERR_UNSUPPORTED. */
+int kdehip_prod_philox_device_manifold(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
+                                       int64_t sample_offset, int addEntropy, const uint8_t *partialDimMask,
+                                       const uint8_t *manifold, int precision, double *d_points, int64_t *d_indices,
+                                       int32_t *d_labels, void *stream);
 
 /* The same with host output buffers (pts: ndims*Np, ind: Ndens*Np), blocking: for hosts that keep no device arrays of
  * their own -- a Julia caller without AMDGPU.jl uploads its densities once and then pays neither the host re-layout
  * nor the upload of the tiles per product (sample offset 0). */
 int kdehip_prod_philox_resident(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
                                 int addEntropy, const uint8_t *partialDimMask, int precision, double *pts, int64_t *ind);
+/* ... on a manifold: kdehip_prod_philox_device_manifold (sample offset 0) with host output buffers, bit for bit. */
+int kdehip_prod_philox_resident_manifold(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
+                                         int addEntropy, const uint8_t *partialDimMask, const uint8_t *manifold,
+                                         int precision, double *pts, int64_t *ind);
 
 /* ---- (2d) the resident chain: products feed products without leaving HBM -----------------------------------
  * The reference's `*` is `pGM, = prodAppxMSGibbsS(...); kde!(pGM)` (src/MSGibbs01.jl:707-726), and in a belief-propagation
@@ -300,6 +318,12 @@ int kdehip_density_from_device_points_manifold(kdehip_device_density **out, cons
  * kdehip_prod_philox(seed) followed by kdehip_make_density_auto on the host. */
 int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees, uint64_t seed,
                       int addEntropy, double *bw_out, int32_t *nevals);
+/* `*` on a manifold: kdehip_prod_philox_device_manifold (Niter = 5, Np = round(mean Npts), sample offset 0), then
+ * kdehip_density_from_device_points_manifold on the product matrix with the same manifold -- bit for bit those two calls; the
+ * result stays resident.  One density with addEntropy = 0 is the shortcut, its kde! with the manifold.  manifold == NULL or
+ * all zeros IS kdehip_mul_device.  Manifold errors as kdehip_prod_philox_device_manifold. */
+int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees, uint64_t seed,
+                               int addEntropy, double *bw_out, int32_t *nevals, const uint8_t *manifold /* ndims bytes or NULL */);
 /* `*` for MANY products in one call -- the reference's serving shape: a belief-propagation sweep calls `*`
  * (src/MSGibbs01.jl:707-726) dozens of times on densities of 100-300 points (test/runtests.jl:189-201), and one at a time
  * each is a blocking call of >= 10 dependent small launches.  Here every product is sampled by the batched sampler
@@ -320,6 +344,14 @@ typedef struct kdehip_mul_item {
 } kdehip_mul_item;
 int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, kdehip_device_density **out, double *bw_out,
                             int32_t *nevals);
+/* The same with a manifold per item: manifolds == NULL, or nprod rows of KDEHIP_MAX_DIMS bytes (as bw_out has nprod rows of
+ * KDEHIP_MAX_DIMS doubles), row i holding the manifold of item i in its first ndims bytes.  Items without a
+ * circular dimension take the batched sampler as above; circular items are sampled one by one inside the same call (as
+ * masked products are in kdehip_prod_philox_batch), and the bandwidth searches of the circular items of one (ndims, size,
+ * manifold) advance in shared launches with their likelihoods wrapped.  out[i] is bit for bit what
+ * kdehip_mul_device_manifold(items[i], row i) returns; manifolds == NULL IS the entry above. */
+int kdehip_mul_device_batch_manifold(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+                                     kdehip_device_density **out, double *bw_out, int32_t *nevals);
 /* The reference's arrays of a density the library built (the two entries above), shaped as in kdehip_make_density; any
  * pointer may be NULL; bw_out: its D LOOCV bandwidths (standard deviations).  A density that came from
  * kdehip_density_upload has no such mirror (KDEHIP_ERR_UNSUPPORTED): its arrays are the caller's. */
@@ -410,7 +442,8 @@ int kdehip_resample_device(kdehip_device_density **out, kdehip_device_density *p
  * caller's stream; kdehip_profile_sampler_read waits for the device's calls in flight and returns the sum of those
  * durations and their count for the calls that were enqueued on `stream` since the switch was last set (which also resets
  * the sums).  The switch is process-wide; the sums are kept per device and caller stream, so concurrent callers on
- * streams of their own do not mix. */
+ * streams of their own do not mix.  The blocking one-shot entries (kdehip_gibbs1*, kdehip_prod_philox) are bracketed too; they
+ * run on the calling thread's stream, which kdehip_profile_sampler_read knows as hipStreamPerThread ((hipStream_t)2). */
 void kdehip_profile_sampler(int enable);
 int kdehip_profile_sampler_read(int device, void *stream, double *total_ms, int64_t *launches);
 /* With the switch on, kdehip_product_multi_sample_philox brackets every device's sampling launch too; this returns, for
@@ -572,8 +605,11 @@ int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_devi
  * Bandwidth search: only the leave-one-out likelihoods wrap.  The marginal's sort, neighborMinMax and with it the search
  * bracket are the Euclidean ones, as in the reference (marginal(p, [i]) and the kde! inside ksize build their 1-D trees with
  * the default operators), and kdehip_make_density_auto_manifold / kdehip_density_from_device_points_manifold still build the
- * tree with the Euclidean builder: tree construction on a manifold is not supported.  mul_device, mul_device_batch,
- * resample and the summaries of 5c stay Euclidean. */
+ * tree with the Euclidean builder: tree construction on a manifold is not supported.
+ * Products: besides kdehip_gibbs1_manifold (host trees, caller streams, the generic arithmetic), the resident entries take a
+ * manifold -- kdehip_prod_philox_device_manifold, kdehip_prod_philox_resident_manifold (2c), kdehip_mul_device_manifold,
+ * kdehip_mul_device_batch_manifold (2d) -- and run the sampler's circular fast mode.  Still Euclidean only: tree
+ * construction, kdehip_resample_device and the summaries of 5c. */
 int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out,
                              int device, const uint8_t *manifold);
 int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,

@@ -166,6 +166,16 @@ SIGNATURES = {
                                                     C.c_void_p, f64p, i32p]),
     "kdehip_mul_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_uint64, C.c_int, f64p, i32p]),
     "kdehip_mul_device_batch": (C.c_int, [C.c_int, C.POINTER(CMulItem), C.POINTER(C.c_void_p), f64p, i32p]),
+    # the resident entries on a manifold (include/kdehip.h sections 2c-2e): the manifold follows partialDimMask where there is
+    # one, and is the last argument of the `*` entries
+    "kdehip_prod_philox_device_manifold": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int, C.c_uint64, C.c_int64,
+                                                     C.c_int, u8p, u8p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kdehip_prod_philox_resident_manifold": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.c_int, C.c_uint64, C.c_int,
+                                                       u8p, u8p, C.c_int, f64p, i64p]),
+    "kdehip_mul_device_manifold": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_uint64, C.c_int, f64p,
+                                             i32p, u8p]),
+    "kdehip_mul_device_batch_manifold": (C.c_int, [C.c_int, C.POINTER(CMulItem), u8p, C.POINTER(C.c_void_p), f64p,
+                                                   i32p]),
     "kdehip_density_download": (C.c_int, [C.c_void_p, f64p, f64p, f64p, i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p,
                                           f64p, f64p]),
     "kdehip_prod_philox_batch": (C.c_int, [C.c_int, C.POINTER(CBatchItem), C.c_int, C.c_void_p]),

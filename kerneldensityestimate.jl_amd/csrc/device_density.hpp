@@ -129,5 +129,8 @@ bool leaves_share_bandwidth(const kdehip_device_density *h);
 // caller that waits for the product anyway uses (kdehip_mul_device).
 int prod_philox_device_blocking_stream(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
                                        int64_t sample_offset, int addEntropy, const uint8_t *partialDimMask, int precision,
-                                       double *d_points, int64_t *d_indices, void *stream);
+                                       double *d_points, int64_t *d_indices, void *stream, const uint8_t *manifold = nullptr);
+// kdehip_prod_philox_batch with a manifold per item (product.hip; manifolds or any of its entries may be NULL)
+int prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items, const uint8_t *const *manifolds, int precision,
+                               void *stream);
 }  // namespace kdehip

@@ -180,16 +180,24 @@ __device__ __forceinline__ kdehip_f2 load_pair(P p) {
 // (fp32 keeps the subtract-first form: measured at config 5, the two-instruction form buys 0.9 % there -- 19.01 ->
 // 18.84 ms, profiles/r04_experiments.md -- and would change the labels the fp32 gates were tuned on)
 template <typename T> constexpr bool kUniformTwoOp = std::is_same<T, double>::value;
-template <typename T, int D, bool OFF = false>
-struct EvalUniform {
+// CIRC evaluators (kModeFastCirc, fp64) carry the plan's circular bits: bit d = the difference of dimension d is the circular
+// diffop (:290), circ_wrap before it is squared.  Wave-uniform run-time data; the other evaluators have no such member.
+template <bool CIRC> struct CircBits { static constexpr uint32_t circ = 0; };
+template <> struct CircBits<true> { uint32_t circ; };
+// (CIRC, a circular dimension: center[d] holds mu_d itself and t_d = circ_wrap(m_d - mu_d) * s_d -- the wrap needs the
+// difference, so the two-instruction form does not apply there; Euclidean dimensions keep it)
+template <typename T, int D, bool OFF = false, bool CIRC = false>
+struct EvalUniform : CircBits<CIRC> {
+  static_assert(!CIRC || kUniformTwoOp<T>, "the circular fast forms are fp64 only");
   T center[D], ninv[D], scale;
   T xoff;
   const double *tab;
-  __device__ __forceinline__ EvalUniform<T, D, true> with_offset(T o) const {
-    EvalUniform<T, D, true> e;
+  __device__ __forceinline__ EvalUniform<T, D, true, CIRC> with_offset(T o) const {
+    EvalUniform<T, D, true, CIRC> e;
 #pragma unroll
     for (int d = 0; d < D; ++d) { e.center[d] = center[d]; e.ninv[d] = ninv[d]; }
     e.scale = scale; e.tab = tab; e.xoff = o;
+    if constexpr (CIRC) e.circ = this->circ;
     return e;
   }
   // what the dimension lanes hand to the evaluator (lanes = dimensions: `mean`, `c` = bandwidth + leave-one-out variance
@@ -223,7 +231,13 @@ struct EvalUniform {
       acc = V(0);
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        const V t = Num<V>::fma(r.m[d], V(ninv[d]), -V(center[d]));
+        V t;
+        if constexpr (CIRC) {
+          if ((this->circ >> d) & 1u) t = circ_wrap(r.m[d] - V(center[d])) * V(ninv[d]);
+          else t = Num<V>::fma(r.m[d], V(ninv[d]), -V(center[d]));
+        } else {
+          t = Num<V>::fma(r.m[d], V(ninv[d]), -V(center[d]));
+        }
         acc = Num<V>::fma(t, t, acc);
       }
       if constexpr (OFF) acc = clamp_hi(V(xoff) - acc, V(T(126)));
@@ -288,17 +302,19 @@ __device__ __forceinline__ void fraction_sum(const V *d2, const V *c, V &n, V &e
 }
 
 // FAST: per-node bandwidths; one rsqrt instead of D divides and D logs.
-template <typename T, int D, bool MASKED, bool OFF = false>
-struct EvalFast {
+template <typename T, int D, bool MASKED, bool OFF = false, bool CIRC = false>
+struct EvalFast : CircBits<CIRC> {
+  static_assert(!CIRC || sizeof(T) == 8, "the circular fast forms are fp64 only");
   T center[D], cov[D];
   T xoff;
   const double *tab;
   uint32_t act;  // MASKED: dimensions that take part (:282); an inactive one contributes c = 1, delta = 0
-  __device__ __forceinline__ EvalFast<T, D, MASKED, true> with_offset(T o) const {
-    EvalFast<T, D, MASKED, true> e;
+  __device__ __forceinline__ EvalFast<T, D, MASKED, true, CIRC> with_offset(T o) const {
+    EvalFast<T, D, MASKED, true, CIRC> e;
 #pragma unroll
     for (int d = 0; d < D; ++d) { e.center[d] = center[d]; e.cov[d] = cov[d]; }
     e.tab = tab; e.act = act; e.xoff = o;
+    if constexpr (CIRC) e.circ = this->circ;
     return e;
   }
   template <typename V> struct RowT { V m[D], v[D], w; };
@@ -317,7 +333,10 @@ struct EvalFast {
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       c[d] = row.v[d] + cov[d];
-      const V dl = row.m[d] - center[d];
+      V dl = row.m[d] - center[d];
+      if constexpr (CIRC) {
+        if ((this->circ >> d) & 1u) dl = circ_wrap(dl);  // (diffop of a circular dimension, :290)
+      }
       d2[d] = dl * dl;
       if constexpr (MASKED) {
         const bool on = (act >> d) & 1u;

@@ -55,7 +55,8 @@ int lean_waves(int64_t Np, int variant) {
   int launch_lean_hi_d##d(int, int, const PlanDev &, const RunArgs &, void *);          \
   int launch_lean_batch_d##d(int, const PlanDev &, const RunArgs &, void *);            \
   int launch_tables_batch_d##d(const PlanDev &, const RunArgs &, void *);               \
-  int launch_lean_f32_d##d(int, int, const PlanDev &, const RunArgs &, void *);
+  int launch_lean_f32_d##d(int, int, const PlanDev &, const RunArgs &, void *);  \
+  int launch_gibbs_circ_d##d(const PlanDev &, const RunArgs &, void *);
 KDEHIP_DECL(1) KDEHIP_DECL(2) KDEHIP_DECL(3) KDEHIP_DECL(4) KDEHIP_DECL(5) KDEHIP_DECL(6) KDEHIP_DECL(7) KDEHIP_DECL(8)
 #undef KDEHIP_DECL
 
@@ -64,6 +65,20 @@ int launch_gibbs(int precision, int mode, const PlanDev &plan, const RunArgs &ar
   const int v = args.variant % 1000;
   const bool generic_only = (v >= kVariantGenericBase && v < kVariantGenericBase + 20);
   if (generic_only) args.variant -= kVariantGenericBase;
+  if (mode == kModeFastCirc) {  // circular dimensions, fast forms: the general kernel's own translation units, any density count
+    if (precision != 64) return set_error(KDEHIP_ERR_UNSUPPORTED, "circular dimensions need precision 64");
+    switch (plan.D) {
+      case 1: return launch_gibbs_circ_d1(plan, args, stream);
+      case 2: return launch_gibbs_circ_d2(plan, args, stream);
+      case 3: return launch_gibbs_circ_d3(plan, args, stream);
+      case 4: return launch_gibbs_circ_d4(plan, args, stream);
+      case 5: return launch_gibbs_circ_d5(plan, args, stream);
+      case 6: return launch_gibbs_circ_d6(plan, args, stream);
+      case 7: return launch_gibbs_circ_d7(plan, args, stream);
+      case 8: return launch_gibbs_circ_d8(plan, args, stream);
+      default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+    }
+  }
   if (!generic_only && plan.M == 8 && precision == 64) {  // 8 densities, fp64 (BASELINE config 4): its own translation unit
     int rc = kLeanNotCovered;
     switch (plan.D) {

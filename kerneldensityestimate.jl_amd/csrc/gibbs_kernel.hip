@@ -62,7 +62,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
   const PlanDev &plan = view.plan;
   const auto &a = view.a;
   constexpr bool FAST = (MODE != kModeGeneric);      // product/rsqrt + uniform-bandwidth forms
-  constexpr bool MASKED = (MODE == kModeFastMasked);  // ... with inactive dimensions
+  constexpr bool CIRC = (MODE == kModeFastCirc);     // ... with the circular operators (plan.circ_bits != 0, fp64)
+  constexpr bool MASKED = (MODE == kModeFastMasked) || CIRC;  // ... with inactive dimensions
   constexpr bool kAllDimsOn = (MODE == kModeFast);    // the plan checked it: no mask tests in this build
   // pass 1 prefetches the next row's fields while it evaluates the current one; the 16-wavefront fp64
   // builds have 128 VGPRs and would spill from D = 6 on
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
     if (lane < D) {
       lam[j * D + dl] = l;
       // (a circular dimension keeps the angle itself: its getMu works on the angles, product_dim below)
-      lmu[j * D + dl] = on ? ((!FAST && ((plan.circ_bits >> dl) & 1u)) ? mu : mu * l) : T(0);
+      lmu[j * D + dl] = on ? (((!FAST || CIRC) && ((plan.circ_bits >> dl) & 1u)) ? mu : mu * l) : T(0);
     }
     if (lane == 0) psel[j] = pos;
   };
@@ -132,11 +133,11 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
       if (lane < D) { lam[skip * D + dl] = T(0); lmu[skip * D + dl] = T(0); }
       wave_sync();
     }
-    if constexpr (!FAST) {
+    if constexpr (!FAST || CIRC) {
       // The enumerated circular operators (include/kdehip.h "manifolds") at the reference's hooks getLambda / getMu
       // (:183-184, applied :210-213): getLambda = the same sum; getMu = the information-weighted mean in the tangent space at
       // the FIRST contributing kernel's angle, mapped back -- the sums in density order, as oracle/kde_oracle.c forms them.
-      if (plan.circ_bits != 0u) {  // (wave-uniform; plans without a circular dimension never come here)
+      if (CIRC || plan.circ_bits != 0u) {  // (wave-uniform; plans without a circular dimension never come here)
         const bool circ = (plan.circ_bits >> dl) & 1u;
         T ls = T(0), ref = T(0);
         bool have = false;
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
           acc += circ ? l * circ_wrap(m - ref) : m;  // (Euclidean slots hold mean * lambda already)
         }
         const bool on = kAllDimsOn || ((info_bits >> dl) & 1u);
-        cov = on ? T(1) / ls : T(0);
+        cov = on ? (FAST ? fast_rcp(ls) : T(1) / ls) : T(0);
         mean = on ? (circ ? circ_wrap(ref + cov * acc) : cov * acc) : T(0);
         return;
       }
@@ -181,8 +182,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
     if constexpr (FAST) {
       const uint32_t act = ds.mask_bits & ds.others_bits;
       if (ds.uniform_bw) {
-        EvalUniform<T, D> ev;
+        EvalUniform<T, D, false, CIRC> ev;
         ev.tab = sExpTab;
+        if constexpr (CIRC) ev.circ = plan.circ_bits;
         T c = hdr[dl] + cov;
         bool on = true;
         if constexpr (MASKED) {  // an inactive dimension contributes nothing: c = 1, weight 0
@@ -191,6 +193,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
         }
         T cen, nin;
         EvalUniform<T, D>::operands(mean, c, on, cen, nin);
+        if constexpr (CIRC) {  // (a circular dimension hands over the angle itself: its difference is wrapped per node)
+          if ((plan.circ_bits >> dl) & 1u) cen = on ? mean : T(0);
+        }
         T Pr = T(1);
 #pragma unroll
         for (int d = 0; d < D; ++d) {
@@ -201,9 +206,10 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
         ev.scale = Num<T>::rsqrt(Pr);
         return run(ev);
       }
-      EvalFast<T, D, MASKED> ev;
+      EvalFast<T, D, MASKED, false, CIRC> ev;
       ev.tab = sExpTab;
       ev.act = act;
+      if constexpr (CIRC) ev.circ = plan.circ_bits;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         ev.center[d] = lane_read(mean, d);
@@ -398,7 +404,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
       T mean, cov;
       product_dim(-1, any_bits, mean, cov);
       x = mean + Num<T>::sqrt(cov) * static_cast<T>(normal_for_lane(l - 1));
-      if constexpr (!FAST) {
+      if constexpr (!FAST || CIRC) {
         if ((plan.circ_bits >> dl) & 1u) x = circ_wrap(x);  // addop of a circular dimension (:456)
       }
     }
@@ -539,7 +545,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_
     T xf = mean;
     if (a.addEntropy) {
       xf = mean + Num<T>::sqrt(cov) * static_cast<T>(normal_for_lane(L));
-      if constexpr (!FAST) {
+      if constexpr (!FAST || CIRC) {
         if ((plan.circ_bits >> dl) & 1u) xf = circ_wrap(xf);
       }
     }
@@ -568,7 +574,7 @@ template <typename T, int D, int MODE>
 static int launch_one(const PlanDev &plan, const RunArgs &args, hipStream_t stream) {
   if (args.Np <= 0) return KDEHIP_OK;
   if (args.table_build) {  // the table-only instantiation: 4 wavefronts per workgroup, no tile pool
-    if constexpr (MODE != kModeGeneric) {
+    if constexpr (MODE != kModeGeneric && MODE != kModeFastCirc) {  // (generic and circular plans carry no tables)
       constexpr int TW = 4;
       const int64_t blocks = (args.Np + TW - 1) / TW;
       hipLaunchKernelGGL((gibbs_product_kernel<T, D, MODE, TW, true>), dim3(static_cast<unsigned>(blocks)), dim3(TW * 64), 0,
@@ -591,11 +597,20 @@ static int launch_one(const PlanDev &plan, const RunArgs &args, hipStream_t stre
 
 // This file is compiled once per dimension count (-DKDEHIP_DIM=1..8, see the Makefile) so the 24 kernel
 // variants of each dimension (2 precisions x 3 arithmetic modes x 4 workgroup widths) build in parallel.
+// With -DKDEHIP_CIRC_TU it is the translation unit of the circular fast mode of that dimension count instead (fp64, three
+// workgroup widths): the instantiations above are not part of it, and theirs hold none of its code.
 #ifndef KDEHIP_DIM
 #error "compile gibbs_kernel.hip with -DKDEHIP_DIM=<1..8>"
 #endif
 #define KDEHIP_CAT2(a, b) a##b
 #define KDEHIP_CAT(a, b) KDEHIP_CAT2(a, b)
+
+#ifdef KDEHIP_CIRC_TU
+int KDEHIP_CAT(launch_gibbs_circ_d, KDEHIP_DIM)(const PlanDev &plan, const RunArgs &args, void *stream) {
+  if (plan.circ_bits == 0u) return set_error(KDEHIP_ERR_ARG, "the circular mode needs a circular dimension");
+  return launch_one<double, KDEHIP_DIM, kModeFastCirc>(plan, args, static_cast<hipStream_t>(stream));
+}
+#else
 
 // kdehip_prod_philox_batch: the conditional tables of a group of fp64 products in one launch; args.Np = workgroups x 4
 int KDEHIP_CAT(launch_tables_batch_d, KDEHIP_DIM)(const PlanDev &plan, const RunArgs &args, void *stream) {
@@ -623,5 +638,6 @@ int KDEHIP_CAT(launch_gibbs_d, KDEHIP_DIM)(int precision, int mode, const PlanDe
     default: return set_error(KDEHIP_ERR_ARG, "unknown arithmetic mode");
   }
 }
+#endif  // KDEHIP_CIRC_TU
 
 }  // namespace kdehip

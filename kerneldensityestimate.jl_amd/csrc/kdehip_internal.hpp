@@ -181,7 +181,8 @@ struct PlanDev {
   int32_t M, L, D, Lt;       // Lt: levels 1..Lt are tabulated (0 = none)
   int32_t screened;          // 1: the plan carries screen tiles (descriptors behind the level table) and they are built; 2: some chunked
   // bit d: dimension d is CIRCULAR (2 pi) -- the enumerated on-manifold operators of include/kdehip.h "manifolds", applied at
-  // the reference's hook points (src/MSGibbs01.jl:290, 183-184 / 210-213, 456) by the general sampler's generic mode only
+  // the reference's hook points (src/MSGibbs01.jl:290, 183-184 / 210-213, 456) by the general sampler's generic and
+  // circular fast modes (kModeGeneric, kModeFastCirc)
   uint32_t circ_bits;
   int32_t reserved_[2];
 };
@@ -301,7 +302,10 @@ int nlevels_for(int64_t maxNp);
 enum ArithMode : int {
   kModeGeneric = 0,    // the reference's per-dimension divide + log with its NaN rules
   kModeFast = 1,       // product/rsqrt + uniform-bandwidth forms, every dimension active
-  kModeFastMasked = 2  // the same with partialDimMask / uninformed dimensions
+  kModeFastMasked = 2, // the same with partialDimMask / uninformed dimensions
+  // the fast forms with the circular operators (PlanDev::circ_bits != 0, fp64 only, masks as kModeFastMasked, no conditional
+  // tables and no fp32 screens: neither knows about wrapping) -- a translation unit of its own per dimension count
+  kModeFastCirc = 3
 };
 // Device / pinned-host allocations through the library's cache (devmem.cpp).  `bytes` of the free must be the
 // `bytes` of the allocation.  Only free a block once the work using it has completed.

@@ -912,8 +912,8 @@ int kdehip::LoocvSearch::finish(double *bw_out, int32_t *nevals_out) {
 
 kdehip::LoocvSearch *kdehip::loocv_new() { return new (std::nothrow) LoocvSearch(); }
 void kdehip::loocv_delete(LoocvSearch *s) { delete s; }
-int kdehip::loocv_begin(LoocvSearch *s, int nb, int D, int64_t N, const double *d_points, void *stream) {
-  return s->begin(nb, D, N, nullptr, d_points, static_cast<hipStream_t>(stream));
+int kdehip::loocv_begin(LoocvSearch *s, int nb, int D, int64_t N, const double *d_points, void *stream, unsigned circ_mask) {
+  return s->begin(nb, D, N, nullptr, d_points, static_cast<hipStream_t>(stream), circ_mask);
 }
 int kdehip::loocv_poll(LoocvSearch *s, bool *done) { return s->poll(done); }
 int kdehip::loocv_finish(LoocvSearch *s, double *bw_out, int32_t *nevals_out) { return s->finish(bw_out, nevals_out); }

@@ -13,7 +13,8 @@ constexpr int kLoocvMaxMarginals = 21000;
 class LoocvSearch;
 LoocvSearch *loocv_new();
 void loocv_delete(LoocvSearch *s);  // (waits for the stream when the search was abandoned half-way)
-int loocv_begin(LoocvSearch *s, int nb, int D, int64_t N, const double *d_points, void *stream);
+// (circ_mask: bit k = the likelihoods of dimension k of every matrix take circular differences, as auto_bandwidth_run's)
+int loocv_begin(LoocvSearch *s, int nb, int D, int64_t N, const double *d_points, void *stream, unsigned circ_mask = 0);
 int loocv_poll(LoocvSearch *s, bool *done);
 int loocv_finish(LoocvSearch *s, double *bw_out, int32_t *nevals_out);
 }  // namespace kdehip

@@ -613,6 +613,23 @@ extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const
 // the "hack fix for #70" (:713-716: one density, no entropy -> kde! of its own points).
 extern "C" int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees, uint64_t seed,
                                  int addEntropy, double *bw_out, int32_t *nevals) {
+  return kdehip_mul_device_manifold(out, Ndens, trees, seed, addEntropy, bw_out, nevals, nullptr);
+}
+
+// The manifold of a `*` on handles: an enum value above 1 is KDEHIP_ERR_ARG, more than KDEHIP_MAX_DIMS dimensions
+// KDEHIP_ERR_UNSUPPORTED (as the one-shot entries); NULL and all zeros are the Euclidean `*`.
+static int mul_manifold_mask(const uint8_t *manifold, int D, unsigned *mask) {
+  *mask = 0;
+  if (!manifold) return KDEHIP_OK;
+  if (D < 1 || D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  return manifold_mask(manifold, D, mask);
+}
+
+// The same on a manifold: the circular product, then kde!(pGM) with the same manifold (the bandwidth search's likelihoods
+// wrap; the tree is the Euclidean builder's).
+extern "C" int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees,
+                                          uint64_t seed, int addEntropy, double *bw_out, int32_t *nevals,
+                                          const uint8_t *manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (Ndens < 1 || !trees) return set_error(KDEHIP_ERR_ARG, "need at least one density");
@@ -622,6 +639,10 @@ extern "C" int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_
     if (trees[j]->device != trees[0]->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
   }
   const int D = trees[0]->D, device = trees[0]->device;
+  unsigned circ = 0;
+  const int mrc = mul_manifold_mask(manifold, D, &circ);
+  if (mrc != KDEHIP_OK) return mrc;
+  if (circ == 0) manifold = nullptr;
   DeviceGuard guard;
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -635,7 +656,8 @@ extern "C" int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_
     hipLaunchKernelGGL(unpermute_points_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, cs,
                        trees[0]->means, trees[0]->perm, N, D, reinterpret_cast<double *>(sc.dev()));
     KDEHIP_CHECK(hipGetLastError());
-    return kdehip_density_from_device_points(out, reinterpret_cast<const double *>(sc.dev()), D, N, device, cs, bw_out, nevals);
+    return kdehip_density_from_device_points_manifold(out, reinterpret_cast<const double *>(sc.dev()), D, N, device, cs, bw_out,
+                                                      nevals, manifold);
   }
   double sum = 0.0;  // numpts = round(Int, mean(Npts.(trees))): Julia rounds halves to even, like nearbyint
   for (int j = 0; j < Ndens; ++j) sum += static_cast<double>(trees[j]->N);
@@ -644,9 +666,10 @@ extern "C" int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_
   KDEHIP_CHECK(sc.alloc(off_i + sizeof(int64_t) * Np * Ndens));
   double *d_pts = reinterpret_cast<double *>(sc.dev());
   int64_t *d_ind = reinterpret_cast<int64_t *>(sc.dev() + off_i);
-  rc = prod_philox_device_blocking_stream(Ndens, trees, Np, /*Niter=*/5, seed, 0, addEntropy, nullptr, 64, d_pts, d_ind, cs);
+  rc = prod_philox_device_blocking_stream(Ndens, trees, Np, /*Niter=*/5, seed, 0, addEntropy, nullptr, 64, d_pts, d_ind, cs,
+                                          manifold);
   if (rc != KDEHIP_OK) return rc;
-  return kdehip_density_from_device_points(out, d_pts, D, Np, device, cs, bw_out, nevals);
+  return kdehip_density_from_device_points_manifold(out, d_pts, D, Np, device, cs, bw_out, nevals, manifold);
 }
 
 // ---- `*` for MANY products in one call ----------------------------------------------------------------------------
@@ -663,6 +686,8 @@ namespace {
 
 struct MulPlan {   // what one item of the batch becomes
   int D = 0, M = 0;
+  unsigned circ = 0;                     // bit d: dimension d is circular (0: the Euclidean `*`)
+  const uint8_t *manifold = nullptr;     // the item's manifold when circ != 0
   int64_t N = 0;          // points of the result (Np of the product, or the density's own count for the shortcut)
   bool shortcut = false, loose = false;  // loose: outside the batched path (fewer than 2 or more than 2048 points): a call of its own
   int group = -1;                        // its (D, N) group
@@ -674,25 +699,34 @@ struct MulPlan {   // what one item of the batch becomes
   int rc = KDEHIP_OK;
   std::string msg;
 };
-struct MulGroup { int D; int64_t N; std::vector<int> members; size_t pts_off = 0; LoocvSearch *search = nullptr; };
+// (a group's searches share their launches AND their manifold: the round kernels take the wrap flag per marginal from one
+// mask per matrix)
+struct MulGroup { int D; int64_t N; std::vector<int> members; size_t pts_off = 0; LoocvSearch *search = nullptr; unsigned circ = 0; };
 
 }  // namespace
 
-static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip_device_density **out, double *bw_out,
-                                 int32_t *nevals);
+static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+                                 kdehip_device_density **out, double *bw_out, int32_t *nevals);
 extern "C" int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, kdehip_device_density **out, double *bw_out,
                                        int32_t *nevals) {
+  return kdehip_mul_device_batch_manifold(nprod, items, nullptr, out, bw_out, nevals);
+}
+// manifolds: NULL, or nprod rows of KDEHIP_MAX_DIMS bytes (row i: the manifold of item i in its first ndims bytes).  Items without a circular dimension take the batched
+// sampler as before; circular items are sampled one by one inside the same call (kModeFastCirc is outside the batched
+// kernel's domain, like a mask), and their bandwidth searches run in the shared launches of their (D, N, manifold) group.
+extern "C" int kdehip_mul_device_batch_manifold(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+                                                kdehip_device_density **out, double *bw_out, int32_t *nevals) {
   // (the bookkeeping below lives in std::vectors: nothing may throw out of an extern "C" entry point -- the unwinding runs the
   // clean-up that takes every block and handle back first)
   try {
-    return mul_device_batch_impl(nprod, items, out, bw_out, nevals);
+    return mul_device_batch_impl(nprod, items, manifolds, out, bw_out, nevals);
   } catch (const std::exception &e) {
     if (out) for (int i = 0; i < nprod; ++i) out[i] = nullptr;
     return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_mul_device_batch: ") + e.what());
   }
 }
-static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip_device_density **out, double *bw_out,
-                                 int32_t *nevals) {
+static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+                                 kdehip_device_density **out, double *bw_out, int32_t *nevals) {
   if (nprod < 0 || (nprod > 0 && (!items || !out))) return set_error(KDEHIP_ERR_ARG, "kdehip_mul_device_batch: bad item list");
   for (int i = 0; i < nprod; ++i) out[i] = nullptr;
   if (nprod == 0) return KDEHIP_OK;
@@ -709,6 +743,10 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
     }
     MulPlan &m = mp[i];
     m.D = it.trees[0]->D; m.M = it.Ndens;
+    const uint8_t *man = manifolds ? manifolds + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr;
+    const int mrc = mul_manifold_mask(man, m.D, &m.circ);
+    if (mrc != KDEHIP_OK) return mrc;
+    m.manifold = m.circ ? man : nullptr;
     m.shortcut = it.Ndens == 1 && !it.addEntropy;  // the "hack fix for #70" (:713-716)
     if (m.shortcut) m.N = it.trees[0]->N;
     else {
@@ -731,8 +769,8 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
     int g = -1;
     const size_t cap = static_cast<size_t>(kLoocvMaxMarginals / m.D);  // (products per search: its launches index marginals)
     for (size_t k = 0; k < groups.size(); ++k)
-      if (groups[k].D == m.D && groups[k].N == m.N && groups[k].members.size() < cap) g = static_cast<int>(k);
-    if (g < 0) { groups.push_back(MulGroup{m.D, m.N, {}}); g = static_cast<int>(groups.size()) - 1; }
+      if (groups[k].D == m.D && groups[k].N == m.N && groups[k].circ == m.circ && groups[k].members.size() < cap) g = static_cast<int>(k);
+    if (g < 0) { groups.push_back(MulGroup{m.D, m.N, {}}); g = static_cast<int>(groups.size()) - 1; groups[g].circ = m.circ; }
     m.group = g;
     groups[g].members.push_back(i);
   }
@@ -788,6 +826,8 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
     unsigned char *sc = static_cast<unsigned char *>(cl.scratch);
     // (1) the products: one batched call (its own groups by (D, M)); the shortcut items un-permute their own leaves
     std::vector<kdehip_batch_item> prod;
+    std::vector<const uint8_t *> prod_manifold;
+    bool any_circ = false;
     for (int i = 0; i < nprod; ++i) {
       MulPlan &m = mp[i];
       if (m.loose) continue;
@@ -805,9 +845,11 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
       b.addEntropy = items[i].addEntropy; b.partialDimMask = nullptr; b.d_points = d_pts;
       b.d_indices = reinterpret_cast<int64_t *>(sc + align256(pts_bytes) + m.ind_off); b.d_labels = nullptr;
       prod.push_back(b);
+      prod_manifold.push_back(m.manifold);
+      any_circ = any_circ || m.circ != 0;
     }
     if (!prod.empty()) {
-      rc = kdehip_prod_philox_batch(static_cast<int>(prod.size()), prod.data(), 64, cs);
+      rc = prod_philox_batch_manifold(static_cast<int>(prod.size()), prod.data(), any_circ ? prod_manifold.data() : nullptr, 64, cs);
       if (rc != KDEHIP_OK) return rc;
     }
     // (2) the matrices come down in one copy on the side stream, behind the products
@@ -826,7 +868,8 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
     for (MulGroup &g : groups) {
       g.search = loocv_new();
       if (!g.search) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
-      rc = loocv_begin(g.search, static_cast<int>(g.members.size()), g.D, g.N, reinterpret_cast<const double *>(sc + g.pts_off), cs);
+      rc = loocv_begin(g.search, static_cast<int>(g.members.size()), g.D, g.N, reinterpret_cast<const double *>(sc + g.pts_off), cs,
+                       g.circ);
       if (rc != KDEHIP_OK) return rc;
     }
     // (4) UNDER the searches: handles, the shared blocks, and -- once the copy is down -- the trees (one pool task each)
@@ -945,8 +988,9 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, kdehip
   // items outside the batched path: a call of their own each
   for (int i = 0; i < nprod; ++i) {
     if (!mp[i].loose) continue;
-    rc = kdehip_mul_device(&mp[i].h, items[i].Ndens, items[i].trees, items[i].seed, items[i].addEntropy,
-                           bw_out ? bw_out + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr, nevals ? nevals + i : nullptr);
+    rc = kdehip_mul_device_manifold(&mp[i].h, items[i].Ndens, items[i].trees, items[i].seed, items[i].addEntropy,
+                                    bw_out ? bw_out + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr,
+                                    nevals ? nevals + i : nullptr, mp[i].manifold);
     if (rc != KDEHIP_OK) {
       for (MulPlan &m : mp) if (m.loose && m.h) { kdehip_density_free(m.h); m.h = nullptr; }
       return rc;

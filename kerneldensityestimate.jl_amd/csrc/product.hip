@@ -30,6 +30,7 @@ struct kdehip_product {
   int precision = 64;
   bool fast = true;
   int mode = kModeFast;
+  uint32_t circ_bits = 0;  // bit d: dimension d is circular (resident entries with a manifold; PlanDev::circ_bits)
   int variant = 0;
   PackedProduct host;  // descriptors (payload vectors are released after upload)
   void *d_blob = nullptr;   // the one device allocation of the plan; the pointers below point into it
@@ -156,7 +157,8 @@ int copy_out(const void *d_base, size_t span, const OutPiece *pieces, int npiece
 // The two run forms, enqueue only (no bookkeeping of who waits for the work: see the callers).
 int enqueue_streams(kdehip_product *plan, int64_t Np, int Niter, const double *d_randU, int64_t nU,
                     const double *d_randN, int64_t nN, int addEntropy, double *d_points, int64_t *d_indices,
-                    int32_t *d_labels, void *stream, bool private_plan = false) {
+                    int32_t *d_labels, void *stream, bool private_plan = false, hipEvent_t t_begin = nullptr,
+                    hipEvent_t t_end = nullptr) {
   int rc = check_run(plan, Np, Niter, d_points, d_indices);
   if (rc != KDEHIP_OK) return rc;
   if (Np == 0) return KDEHIP_OK;
@@ -180,8 +182,16 @@ int enqueue_streams(kdehip_product *plan, int64_t Np, int Niter, const double *d
   if (rc != KDEHIP_OK) return rc;
   rc = maybe_build_tables(plan, Np, a, stream, private_plan);
   if (rc != KDEHIP_OK) return rc;
-  return launch_gibbs(plan->precision, plan->mode, plan->dev, a, stream);
+  if (t_begin) KDEHIP_CHECK(hipEventRecord(t_begin, static_cast<hipStream_t>(stream)));
+  rc = launch_gibbs(plan->precision, plan->mode, plan->dev, a, stream);
+  if (rc == KDEHIP_OK && t_end) KDEHIP_CHECK(hipEventRecord(t_end, static_cast<hipStream_t>(stream)));
+  return rc;
 }
+
+// kdehip_profile_sampler (defined with the resident entries below): is the switch on / add one sampling launch, bracketed by
+// the two events on `stream`, to the sums of (device, stream) -- after the stream has been waited for
+bool profile_sampler_on();
+void profile_sampler_note(int device, hipStream_t stream, hipEvent_t t_begin, hipEvent_t t_end);
 
 // the other devices' output arrays of a multi-GPU run (kernel epilogue stores, RunArgs.peer_*)
 struct PeerOutputs {
@@ -312,7 +322,9 @@ void bind_plan(kdehip_product *p, size_t off_lev, size_t off_count, size_t off_t
   p->dev.M = p->host.M;
   p->dev.L = p->host.L;
   p->dev.D = p->host.D;
-  p->dev.Lt = (p->mode == kModeGeneric) ? 0 : p->host.Lt;
+  // (the conditional tables do not know about wrapping: a circular plan runs without them, as the generic mode does)
+  p->dev.Lt = (p->mode == kModeGeneric || p->mode == kModeFastCirc) ? 0 : p->host.Lt;
+  p->dev.circ_bits = p->circ_bits;
   p->dev.screened = (p->mode == kModeFast && !p->host.screens.empty()) ? 1 : 0;
   if (p->dev.screened)
     for (const LevelDesc &sc : p->host.screens)
@@ -557,7 +569,9 @@ struct Shard {
   int64_t lo = 0, hi = 0;
   size_t off_p = 0, off_i = 0, off_l = 0, span = 0;  // layout of the plan's scratch: [streams ..][points][indices][labels]
   void *h_out = nullptr;                              // pinned landing zone of the results
+  hipEvent_t t_begin = nullptr, t_end = nullptr;      // kdehip_profile_sampler: around the sampling launch
   ~Shard() {
+    for (hipEvent_t ev : {t_begin, t_end}) if (ev) (void)hipEventDestroy(ev);
     if (h_out) cached_host_free(h_out, span);
     kdehip_product_destroy(plan);
   }
@@ -650,14 +664,20 @@ int one_shot(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, doub
     double *dp = reinterpret_cast<double *>(w + S.off_p);
     int64_t *di = reinterpret_cast<int64_t *>(w + S.off_i);
     int32_t *dl = trace ? reinterpret_cast<int32_t *>(w + S.off_l) : nullptr;
+    if (profile_sampler_on()) {
+      KDEHIP_CHECK(hipEventCreate(&S.t_begin));
+      KDEHIP_CHECK(hipEventCreate(&S.t_end));
+    }
     if (streams) {
       double *du = reinterpret_cast<double *>(w), *dn = reinterpret_cast<double *>(w + off_n);
       // sample s of this shard reads element (s - lo)*K + c - 1 of its slice = element s*K + c - 1 of the caller's array
       KDEHIP_CHECK(hipMemcpyAsync(du, randU + S.lo * K, sizeof(double) * useU, hipMemcpyHostToDevice, call_stream()));
       KDEHIP_CHECK(hipMemcpyAsync(dn, randN + S.lo * R, sizeof(double) * useN, hipMemcpyHostToDevice, call_stream()));
-      rc = enqueue_streams(S.plan, n, Niter, du, useU, dn, useN, addEntropy, dp, di, dl, call_stream(), /*private_plan=*/true);
+      rc = enqueue_streams(S.plan, n, Niter, du, useU, dn, useN, addEntropy, dp, di, dl, call_stream(), /*private_plan=*/true,
+                           S.t_begin, S.t_end);
     } else {
-      rc = enqueue_philox(S.plan, n, Niter, seed, S.lo, addEntropy, dp, di, dl, call_stream(), /*private_plan=*/true);
+      rc = enqueue_philox(S.plan, n, Niter, seed, S.lo, addEntropy, dp, di, dl, call_stream(), /*private_plan=*/true, nullptr,
+                          nullptr, nullptr, S.t_begin, S.t_end);
     }
     if (rc != KDEHIP_OK) return rc;
     KDEHIP_CHECK(cached_host_malloc(&S.h_out, S.span));
@@ -670,6 +690,7 @@ int one_shot(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, doub
     rc = guard.enter(S.device);
     if (rc != KDEHIP_OK) return rc;
     KDEHIP_CHECK(hipStreamSynchronize(call_stream()));
+    if (S.t_begin && S.t_end) profile_sampler_note(S.device, call_stream(), S.t_begin, S.t_end);
     if (g == ngpus - 1) us_wait = us_since(t_begin);
     const int64_t n = S.hi - S.lo;
     const unsigned char *h = static_cast<const unsigned char *>(S.h_out);
@@ -760,21 +781,24 @@ constexpr size_t kMaxPending = 8;  // calls in flight per (device, stream): reap
 // run: the call hands them to the deferred-release queue (call_block.hpp) with its device block -- the plan of
 // kdehip_prod_philox_device, or all plans of a kdehip_prod_philox_batch, point into that one block -- and
 // release_call_plans is the queue's hook.  A call that fails before the hand-over releases them here.
+bool profile_sampler_on() { return g_profile_sampler.load(std::memory_order_relaxed) != 0; }
+void profile_sampler_note(int device, hipStream_t stream, hipEvent_t t_begin, hipEvent_t t_end) {
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, t_begin, t_end) == hipSuccess && device >= 0 && device < kMaxDevices) {
+    std::lock_guard<std::mutex> lock(g_profile_mu);
+    ProfileSum *ps = nullptr;
+    for (ProfileSum &c : g_profile[device]) if (c.stream == stream) ps = &c;
+    if (!ps) { g_profile[device].push_back(ProfileSum{stream, 0.0, 0}); ps = &g_profile[device].back(); }
+    ps->ms += ms;
+    ps->launches += 1;
+  }
+  (void)hipGetLastError();
+}
 void release_call_plans(void *first, hipStream_t stream) {
   kdehip_product *p = static_cast<kdehip_product *>(first);
   if (!p) return;
-  if (p->t_begin && p->t_end) {  // (the work is over: the queue's event was recorded behind t_end)
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, p->t_begin, p->t_end) == hipSuccess && p->device >= 0 && p->device < kMaxDevices) {
-      std::lock_guard<std::mutex> lock(g_profile_mu);
-      ProfileSum *ps = nullptr;
-      for (ProfileSum &c : g_profile[p->device]) if (c.stream == stream) ps = &c;
-      if (!ps) { g_profile[p->device].push_back(ProfileSum{stream, 0.0, 0}); ps = &g_profile[p->device].back(); }
-      ps->ms += ms;
-      ps->launches += 1;
-    }
-    (void)hipGetLastError();
-  }
+  // (the work is over: the queue's event was recorded behind t_end)
+  if (p->t_begin && p->t_end) profile_sampler_note(p->device, stream, p->t_begin, p->t_end);
   for (hipEvent_t ev : {p->t_begin, p->t_end, p->prepared}) if (ev) (void)hipEventDestroy(ev);
   while (p) {
     kdehip_product *next = p->next;
@@ -800,8 +824,10 @@ struct ResidentLayout {
 
 // Validates one product of resident densities and lays it out from the shapes of its densities' frontiers alone
 // (p->host, p->precision, p->mode, p->device are set; nothing is allocated).
+// circ_bits != 0: the product runs the circular operators -- in the fast forms (kModeFastCirc) when the node values
+// qualify for them, else in the generic arithmetic, which has always known them.
 int layout_resident(int Ndens, kdehip_device_density *const *trees, const uint8_t *partialDimMask, int precision,
-                    kdehip_product *p, ResidentLayout &lay) {
+                    kdehip_product *p, ResidentLayout &lay, uint32_t circ_bits = 0) {
   if (Ndens < 1 || !trees) return set_error(KDEHIP_ERR_ARG, "need at least one density");
   if (Ndens > KDEHIP_MAX_DENS) return set_error(KDEHIP_ERR_UNSUPPORTED, "more than KDEHIP_MAX_DENS densities in one product");
   for (int j = 0; j < Ndens; ++j) {
@@ -837,6 +863,8 @@ int layout_resident(int Ndens, kdehip_device_density *const *trees, const uint8_
   p->precision = precision;
   p->fast = p->host.fast;
   p->mode = !p->host.fast ? kModeGeneric : (p->host.all_active ? kModeFast : kModeFastMasked);
+  p->circ_bits = circ_bits;
+  if (circ_bits != 0u && p->host.fast) p->mode = kModeFastCirc;
   const size_t ntab = p->host.tabdesc.size();
   const size_t esz = (precision == 64) ? sizeof(double) : sizeof(float);
   lay.off_lev = 256;
@@ -879,11 +907,28 @@ int describe_resident(kdehip_product *p, kdehip_device_density *const *trees, co
   return maxB;
 }
 
+// The manifold of a resident entry (ndims bytes or NULL) as circular bits, with one_shot's argument errors: an enum value
+// above 1 is KDEHIP_ERR_ARG, ndims above KDEHIP_MAX_DIMS is KDEHIP_ERR_UNSUPPORTED; and the circular operators exist in
+// fp64 only.  (The densities themselves are validated by layout_resident.)
+int resident_circ_bits(const uint8_t *manifold, int Ndens, kdehip_device_density *const *trees, int precision, uint32_t *bits) {
+  *bits = 0;
+  if (!manifold || Ndens < 1 || !trees || !trees[0]) return KDEHIP_OK;
+  const int ndims = trees[0]->D;
+  if (ndims < 1 || ndims > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  for (int d = 0; d < ndims; ++d) {
+    if (manifold[d] > KDEHIP_MANIFOLD_CIRCULAR) return set_error(KDEHIP_ERR_ARG, "manifold: 0 (Euclidean) or 1 (circular) per dimension");
+    if (manifold[d] == KDEHIP_MANIFOLD_CIRCULAR) *bits |= 1u << d;
+  }
+  if (*bits != 0u && precision == 32) return set_error(KDEHIP_ERR_UNSUPPORTED, "circular dimensions need precision 64");
+  return KDEHIP_OK;
+}
+
 // own_prep: prepare on the library's stream (an asynchronous caller: the next product's preparation overlaps this
 // product's sampling); a blocking caller, who waits for every product, keeps everything on its own stream
 int prod_philox_device(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
                        int64_t sample_offset, int addEntropy, const uint8_t *partialDimMask, int precision,
-                       double *d_points, int64_t *d_indices, int32_t *d_labels, void *stream, bool own_prep) {
+                       double *d_points, int64_t *d_indices, int32_t *d_labels, void *stream, bool own_prep,
+                       uint32_t circ_bits = 0) {
   if (precision != 64 && precision != 32) return set_error(KDEHIP_ERR_ARG, "precision must be 64 or 32");
   if (Np < 0) return set_error(KDEHIP_ERR_ARG, "Np must be >= 0");
   if (Niter < 0) return set_error(KDEHIP_ERR_ARG, "Niter must be >= 0");
@@ -895,7 +940,7 @@ int prod_philox_device(int Ndens, kdehip_device_density *const *trees, int64_t N
   call.stream = st;
   call.add(p);
   ResidentLayout lay;
-  int rc = layout_resident(Ndens, trees, partialDimMask, precision, p, lay);
+  int rc = layout_resident(Ndens, trees, partialDimMask, precision, p, lay, circ_bits);
   if (rc != KDEHIP_OK || Np == 0) return rc;
   const int device = p->device;
   if (device < 0 || device >= kMaxDevices) return set_error(KDEHIP_ERR_UNSUPPORTED, "device ordinal beyond the library's bookkeeping (64)");
@@ -947,6 +992,13 @@ bool batchable(const kdehip_product *p) {
 // bit what kdehip_prod_philox_device gives for it (same layout, same kernel code, same Philox keys).  Products outside
 // the batched kernel's domain (fp32, masks, 1 or more than 4 densities) are enqueued one by one inside the same call.
 int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int precision, void *stream) {
+  return kdehip::prod_philox_batch_manifold(nprod, items, nullptr, precision, stream);
+}
+}  // extern "C"
+// (manifolds: NULL, or per item a manifold of its ndims bytes or NULL; an item with a circular dimension is outside the
+// batched kernel's domain and is enqueued on its own, like a masked one)
+int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items, const uint8_t *const *manifolds, int precision,
+                                       void *stream) {
   if (nprod < 0 || (nprod > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "kdehip_prod_philox_batch: bad item list");
   if (precision != 64 && precision != 32) return set_error(KDEHIP_ERR_ARG, "precision must be 64 or 32");
   if (nprod == 0) return KDEHIP_OK;
@@ -969,7 +1021,10 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
     if (!p) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
     call.add(p);
     plans.push_back(p);
-    const int rc = layout_resident(it.Ndens, it.trees, it.partialDimMask, precision, p, lays[i]);
+    uint32_t circ_bits = 0;
+    int rc = resident_circ_bits(manifolds ? manifolds[i] : nullptr, it.Ndens, it.trees, precision, &circ_bits);
+    if (rc != KDEHIP_OK) return rc;
+    rc = layout_resident(it.Ndens, it.trees, it.partialDimMask, precision, p, lays[i], circ_bits);
     if (rc != KDEHIP_OK) return rc;
     if (device < 0) device = p->device;
     if (p->device != device) return set_error(KDEHIP_ERR_ARG, "kdehip_prod_philox_batch: products on different devices");
@@ -1112,13 +1167,15 @@ int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int prec
   return blk.defer(device, release_call_plans, call.hand_over());
 }
 
-}  // extern "C"
 int kdehip::prod_philox_device_blocking_stream(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter,
                                                uint64_t seed, int64_t sample_offset, int addEntropy,
                                                const uint8_t *partialDimMask, int precision, double *d_points,
-                                               int64_t *d_indices, void *stream) {
+                                               int64_t *d_indices, void *stream, const uint8_t *manifold) {
+  uint32_t circ_bits = 0;
+  const int rc = resident_circ_bits(manifold, Ndens, trees, precision, &circ_bits);
+  if (rc != KDEHIP_OK) return rc;
   return prod_philox_device(Ndens, trees, Np, Niter, seed, sample_offset, addEntropy, partialDimMask, precision, d_points,
-                            d_indices, nullptr, stream, /*own_prep=*/false);
+                            d_indices, nullptr, stream, /*own_prep=*/false, circ_bits);
 }
 extern "C" {
 
@@ -1127,6 +1184,19 @@ int kdehip_prod_philox_device(int Ndens, kdehip_device_density *const *trees, in
                               double *d_points, int64_t *d_indices, int32_t *d_labels, void *stream) {
   return prod_philox_device(Ndens, trees, Np, Niter, seed, sample_offset, addEntropy, partialDimMask, precision, d_points,
                             d_indices, d_labels, stream, /*own_prep=*/true);
+}
+
+// The same on a manifold: the tiles are re-laid-out on the GPU as above, the sampler runs the circular operators (the fast
+// forms, kModeFastCirc, when the node values qualify, else the generic arithmetic).  NULL or all zeros IS the entry above.
+int kdehip_prod_philox_device_manifold(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
+                                       int64_t sample_offset, int addEntropy, const uint8_t *partialDimMask,
+                                       const uint8_t *manifold, int precision, double *d_points, int64_t *d_indices,
+                                       int32_t *d_labels, void *stream) {
+  uint32_t circ_bits = 0;
+  const int rc = resident_circ_bits(manifold, Ndens, trees, precision, &circ_bits);
+  if (rc != KDEHIP_OK) return rc;
+  return prod_philox_device(Ndens, trees, Np, Niter, seed, sample_offset, addEntropy, partialDimMask, precision, d_points,
+                            d_indices, d_labels, stream, /*own_prep=*/true, circ_bits);
 }
 
 // Diagnostic: time the sampling launch of every kdehip_prod_philox_device call with a pair of events on the caller's
@@ -1157,13 +1227,23 @@ int kdehip_profile_sampler_read(int device, void *stream, double *total_ms, int6
 // AMDGPU.jl) uses once its densities are uploaded -- no host re-layout, no upload of tiles, one copy back.
 int kdehip_prod_philox_resident(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
                                 int addEntropy, const uint8_t *partialDimMask, int precision, double *pts, int64_t *ind) {
+  return kdehip_prod_philox_resident_manifold(Ndens, trees, Np, Niter, seed, addEntropy, partialDimMask, nullptr, precision,
+                                              pts, ind);
+}
+
+int kdehip_prod_philox_resident_manifold(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
+                                         int addEntropy, const uint8_t *partialDimMask, const uint8_t *manifold,
+                                         int precision, double *pts, int64_t *ind) {
   if (Ndens < 1 || !trees || !trees[0]) return set_error(KDEHIP_ERR_ARG, "need at least one density");
+  uint32_t circ_bits = 0;
+  int rc = resident_circ_bits(manifold, Ndens, trees, precision, &circ_bits);
+  if (rc != KDEHIP_OK) return rc;
   if (Np < 0) return set_error(KDEHIP_ERR_ARG, "Np must be >= 0");
   if (Np > 0 && (!pts || !ind)) return set_error(KDEHIP_ERR_ARG, "null output pointer");
   if (Np == 0) return KDEHIP_OK;
   const size_t D = trees[0]->D, M = Ndens;
   DeviceGuard guard;
-  int rc = guard.enter(trees[0]->device);
+  rc = guard.enter(trees[0]->device);
   if (rc != KDEHIP_OK) return rc;
   const size_t off_i = align256(sizeof(double) * D * Np), span = off_i + sizeof(int64_t) * M * Np;
   CallBlock out;
@@ -1172,7 +1252,7 @@ int kdehip_prod_philox_resident(int Ndens, kdehip_device_density *const *trees, 
   unsigned char *w = out.dev();
   rc = prod_philox_device(Ndens, trees, Np, Niter, seed, 0, addEntropy, partialDimMask, precision,
                           reinterpret_cast<double *>(w), reinterpret_cast<int64_t *>(w + off_i), nullptr, call_stream(),
-                          /*own_prep=*/false);
+                          /*own_prep=*/false, circ_bits);
   if (rc != KDEHIP_OK) return rc;
   const hipError_t e = out.download(0, span, call_stream()), se = out.wait();
   if (e != hipSuccess || se != hipSuccess) return set_error(KDEHIP_ERR_HIP, "device product: result copy failed");

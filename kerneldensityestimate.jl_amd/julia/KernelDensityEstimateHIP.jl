@@ -306,6 +306,56 @@ function mul_batch(products::Vector{Vector{DeviceDensity}}; addEntropy::Bool=tru
 end
 
 """
+    hip_mul(trees::Vector{DeviceDensity}, manifold; addEntropy=true, seed=nothing) -> DeviceDensity
+
+`*` on resident densities on a manifold (`kdehip_mul_device_manifold`, include/kdehip.h section 2d): the circular product,
+then `kde!(pGM)` with the same manifold; the result stays in HBM.  `manifold`: a vector of `:euclid` / `:circular` (or 0 / 1),
+one per dimension.  Not installed by `enable!()`: `*` itself stays the Euclidean operator.
+"""
+function hip_mul(trees::Vector{DeviceDensity}, manifold::AbstractVector; addEntropy::Bool=true,
+                 seed::Union{Nothing,UInt64}=nothing)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  handles = Ptr{Cvoid}[t.handle for t in trees]
+  man = manifold_bytes(manifold, trees[1].ndim)
+  s = seed === nothing ? rand(UInt64) : seed
+  GC.@preserve trees handles man begin
+    check(ccall((:kdehip_mul_device_manifold, libkdehip), Cint,
+                (Ref{Ptr{Cvoid}}, Cint, Ptr{Ptr{Cvoid}}, UInt64, Cint, Ptr{Float64}, Ptr{Int32}, Ptr{UInt8}),
+                h, length(trees), handles, s, addEntropy ? 1 : 0, C_NULL, C_NULL, man))
+  end
+  return DeviceDensity(h[])
+end
+
+"""
+    hip_mul_batch(products, manifolds; addEntropy=true, seeds=nothing) -> Vector{DeviceDensity}
+
+`mul_batch` with a manifold per product (`kdehip_mul_device_batch_manifold`): `manifolds[i]` is `nothing` (Euclidean) or the
+manifold of product `i`.  Result `i` is bit for bit `hip_mul(products[i], manifolds[i]; addEntropy, seed=seeds[i])`.
+"""
+function hip_mul_batch(products::Vector{Vector{DeviceDensity}}, manifolds::AbstractVector; addEntropy::Bool=true,
+                       seeds::Union{Nothing,Vector{UInt64}}=nothing)
+  n = length(products)
+  n == 0 && return DeviceDensity[]
+  length(manifolds) == n || error("one manifold (or nothing) per product")
+  sds = seeds === nothing ? rand(UInt64, n) : seeds
+  handles = [Ptr{Cvoid}[t.handle for t in p] for p in products]
+  rows = zeros(UInt8, 8, n)          # column i = row i of the C array: KDEHIP_MAX_DIMS bytes per product
+  for i in 1:n
+    manifolds[i] === nothing && continue
+    D = products[i][1].ndim
+    rows[1:D, i] = manifold_bytes(manifolds[i], D)
+  end
+  out = fill(Ptr{Cvoid}(C_NULL), n)
+  GC.@preserve products handles rows begin
+    items = CMulItem[CMulItem(length(handles[i]), addEntropy ? 1 : 0, pointer(handles[i]), sds[i]) for i in 1:n]
+    check(ccall((:kdehip_mul_device_batch_manifold, libkdehip), Cint,
+                (Cint, Ptr{CMulItem}, Ptr{UInt8}, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Int32}),
+                n, items, rows, out, C_NULL, C_NULL))
+  end
+  return DeviceDensity[DeviceDensity(h) for h in out]
+end
+
+"""
     BallTreeDensity(d::DeviceDensity)
 
 The reference's struct for a density that was BUILT on the device (`*` above): `kdehip_density_download` returns the
@@ -385,6 +435,33 @@ function prodAppxMSGibbsS(npd0, trees::Vector{DeviceDensity}, anFcns, anParams;
     check(ccall((:kdehip_prod_philox_resident, libkdehip), Cint,
                 (Cint, Ptr{Ptr{Cvoid}}, Int64, Cint, UInt64, Cint, Ptr{UInt8}, Cint, Ptr{Float64}, Ptr{Int64}),
                 Ndens, handles, Np, Niter, s, addEntropy ? 1 : 0, mask, precision, points, indices))
+  end
+  return reshape(points, ndims, Np), indices
+end
+
+"""
+    hip_prodAppxMSGibbsS(npd0, trees::Vector{DeviceDensity}, manifold; Niter=3, addEntropy=true, ...)
+
+`prodAppxMSGibbsS` on resident densities on a manifold, host outputs (`kdehip_prod_philox_resident_manifold`, include/kdehip.h
+section 2c): the sampler's circular operators, nothing but descriptors goes up.  fp64 only.  Not installed by `enable!()`.
+(The device-output entry `kdehip_prod_philox_device_manifold` has no wrapper here, like `kdehip_prod_philox_device`: this
+shim holds no device arrays of its own.)
+"""
+function hip_prodAppxMSGibbsS(npd0, trees::Vector{DeviceDensity}, manifold::AbstractVector;
+                              Niter::Int=3, addEntropy::Bool=true, ndims::Integer=maximum(t.ndim for t in trees),
+                              Ndens=length(trees), Np=(npd0 isa BallTreeDensity ? Npts(npd0) : Int(npd0)),
+                              partialDimMask::AbstractVector{<:BitVector}=[ones(Int, ndims) .== 1 for i in 1:length(trees)],
+                              seed::Union{Nothing,UInt64}=nothing)
+  points = zeros(ndims * Np)
+  indices = ones(Int, Ndens, Np)
+  handles = Ptr{Cvoid}[t.handle for t in trees]
+  mask = maskbytes(partialDimMask, Ndens, ndims)
+  man = manifold_bytes(manifold, Int(ndims))
+  s = seed === nothing ? rand(UInt64) : seed
+  GC.@preserve trees handles mask man begin
+    check(ccall((:kdehip_prod_philox_resident_manifold, libkdehip), Cint,
+                (Cint, Ptr{Ptr{Cvoid}}, Int64, Cint, UInt64, Cint, Ptr{UInt8}, Ptr{UInt8}, Cint, Ptr{Float64}, Ptr{Int64}),
+                Ndens, handles, Np, Niter, s, addEntropy ? 1 : 0, mask, man, 64, points, indices))
   end
   return reshape(points, ndims, Np), indices
 end

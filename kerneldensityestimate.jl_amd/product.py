@@ -228,6 +228,9 @@ class DeviceDensity:
         self.dims = int(_lib.lib.kdehip_density_ndim(h))
         self.bw = None      # LOOCV bandwidth (standard deviations) of a density built on the device
         self.nevals = None  # likelihood evaluations of that search
+        # the manifold it was built with (`from_device_points(manifold=)`, a circular `mul_device`), as the uint8 enum array,
+        # or None.  A record only: `a * b`, `resample` and the summaries stay Euclidean -- pass `manifold=` where it is taken
+        self.manifold = None
 
     @classmethod
     def from_device_points(cls, d_points, D, N, device=0, stream=None, manifold=None):
@@ -244,6 +247,7 @@ class DeviceDensity:
             C.byref(ne), None if man is None else ptr(man, u8p)))
         out = cls(device=device, _handle=h)
         out.bw, out.nevals = bw, int(ne.value)
+        out.manifold = man
         return out
 
     def download(self) -> BallTreeDensity:
@@ -259,6 +263,7 @@ class DeviceDensity:
         return bd
 
     def __mul__(self, other):
+        """the Euclidean `*`, also for densities that remember a manifold: use `mul_device(..., manifold=)` on the circle"""
         return mul_device([self, other])
 
     def evaluate(self, pos=None, lvFlag=False, manifold=None):
@@ -318,7 +323,8 @@ class DeviceDensity:
 
     def resample(self, Np=None, *, seed=None) -> "DeviceDensity":
         """`resample(p, Np, :lcv)` (reference src/BallTreeDensity01.jl:312-334) without leaving the device: Np samples
-        (None = Npts(p)), then `kde!(points)` on the device matrix (kdehip_resample_device)."""
+        (None = Npts(p)), then `kde!(points)` on the device matrix (kdehip_resample_device).  Euclidean, also for a density
+        that remembers a manifold."""
         if seed is None:
             seed = int.from_bytes(os.urandom(8), "little")
         h = C.c_void_p()
@@ -359,11 +365,14 @@ class DeviceDensity:
         self.close()
 
 
-def mul_device(trees, *, addEntropy=True, seed=None) -> DeviceDensity:
+def mul_device(trees, *, addEntropy=True, seed=None, manifold=None) -> DeviceDensity:
     """`*(trees; addEntropy)` (reference src/MSGibbs01.jl:707-726) on `DeviceDensity` handles, result in HBM: product with
     Niter = 5 and Np = round(mean(Npts)), then `kde!(pGM)` -- the sample matrix never leaves the device
-    (kdehip_mul_device).  Same numbers as `mul(host trees, seed=seed)`."""
+    (kdehip_mul_device).  Same numbers as `mul(host trees, seed=seed)`.
+    `manifold`: the circular product (`prodAppxMSGibbsS_device(manifold=)`), then `from_device_points(manifold=)` on its
+    matrix (kdehip_mul_device_manifold); the result remembers it."""
     trees = list(trees)
+    man = _manifold_array(manifold, trees[0].dims)
     if seed is None:
         seed = int.from_bytes(os.urandom(8), "little")
     M = len(trees)
@@ -371,18 +380,37 @@ def mul_device(trees, *, addEntropy=True, seed=None) -> DeviceDensity:
     h = C.c_void_p()
     bw = np.empty(trees[0].dims)
     ne = C.c_int32(0)
-    _lib.check(_lib.lib.kdehip_mul_device(C.byref(h), M, arr, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(bool(addEntropy)),
-                                          ptr(bw, f64p), C.byref(ne)))
+    _lib.check(_lib.lib.kdehip_mul_device_manifold(C.byref(h), M, arr, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                   int(bool(addEntropy)), ptr(bw, f64p), C.byref(ne),
+                                                   None if man is None else ptr(man, u8p)))
     out = DeviceDensity(device=trees[0].device, _handle=h)
     out.bw, out.nevals = bw, int(ne.value)
+    out.manifold = man
     return out
 
 
-def mul_device_batch(products, *, addEntropy=True, seeds=None):
+def _batch_manifolds(manifold, dims):
+    """The `manifold=` argument of a batch as one enum array (or None) per product: None; ONE manifold for all products (a
+    flat sequence of enum values, every product then has that many dimensions); or one entry per product (each None or a
+    manifold of that product's dimensions).  `dims`: the products' dimension counts."""
+    n = len(dims)
+    if manifold is None:
+        return [None] * n
+    manifold = list(manifold)
+    shared = len(manifold) > 0 and all(m is not None and (isinstance(m, str) or np.ndim(m) == 0) for m in manifold)
+    if shared:
+        return [_manifold_array(manifold, d) for d in dims]
+    if len(manifold) != n:
+        raise ValueError("manifold: one manifold for all products, or one entry per product")
+    return [_manifold_array(m, d) for m, d in zip(manifold, dims)]
+
+
+def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None):
     """Many `*` in ONE call (kdehip_mul_device_batch): `products` = a list of lists of `DeviceDensity`; returns one
     `DeviceDensity` per product, each bit for bit what `mul_device(products[i], addEntropy=..., seed=seeds[i])` returns --
     batched sampler, the LOOCV searches of all results of one size in shared launches, trees built under them.
-    `addEntropy`: one flag or one per product."""
+    `addEntropy`: one flag or one per product.  `manifold`: one for all products or one per product (None = Euclidean);
+    circular products are sampled one by one inside the call, their searches share launches (kdehip_mul_device_batch_manifold)."""
     products = [list(p) for p in products]
     n = len(products)
     if n == 0:
@@ -397,14 +425,20 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None):
         keep.append(arr)
         items[k].Ndens, items[k].addEntropy, items[k].trees = len(trees), int(flags[k]), arr
         items[k].seed = int(seeds[k]) & (2 ** 64 - 1)
+    mans = _batch_manifolds(manifold, [p[0].dims if p else 0 for p in products])   # (an empty product: the library refuses it)
+    marr = np.zeros((n, _lib.MAX_DIMS), dtype=np.uint8)   # row k: product k's manifold (zeros = Euclidean)
+    for k, m in enumerate(mans):
+        if m is not None:
+            marr[k, :len(m)] = m
     out = (C.c_void_p * n)()
     bw = np.zeros((n, _lib.MAX_DIMS))
     ne = np.zeros(n, dtype=np.int32)
-    _lib.check(_lib.lib.kdehip_mul_device_batch(n, items, out, ptr(bw, f64p), ptr(ne, _lib.i32p)))
+    _lib.check(_lib.lib.kdehip_mul_device_batch_manifold(n, items, ptr(marr, u8p), out, ptr(bw, f64p), ptr(ne, _lib.i32p)))
     res = []
     for k in range(n):
         d = DeviceDensity(device=products[k][0].device, _handle=C.c_void_p(out[k]))
         d.bw, d.nevals = bw[k, :d.dims].copy(), int(ne[k])
+        d.manifold = mans[k]
         res.append(d)
     return res
 
@@ -455,34 +489,40 @@ def prodAppxMSGibbsS_batch(products, *, precision=64, stream=None):
 
 
 def prodAppxMSGibbsS_device(trees, d_points, d_indices, *, Np, Niter=3, seed=0, sample_offset=0, addEntropy=True,
-                            partialDimMask=None, precision=64, d_labels=None, stream=None):
+                            partialDimMask=None, precision=64, d_labels=None, stream=None, manifold=None):
     """`prodAppxMSGibbsS` (reference src/MSGibbs01.jl:645-703) on densities that live in HBM (`DeviceDensity`), results
     left in HBM: d_points (float64[ndims*Np]) and d_indices (int64[Ndens*Np]) are device arrays (torch tensors or
-    addresses).  Enqueues on `stream` and returns; same numbers as `prodAppxMSGibbsS(..., seed=seed)`."""
+    addresses).  Enqueues on `stream` and returns; same numbers as `prodAppxMSGibbsS(..., seed=seed)`.
+    `manifold`: the per-dimension enum of `gibbs1` -- the circular operators in the sampler, nothing leaves the device
+    (kdehip_prod_philox_device_manifold; precision 64 only)."""
     trees = list(trees)
     M = len(trees)
     arr = (C.c_void_p * M)(*[t._h for t in trees])
     ndims = trees[0].dims
     mask = _mask_array(partialDimMask, M, ndims)
-    _lib.check(_lib.lib.kdehip_prod_philox_device(
+    man = _manifold_array(manifold, ndims)
+    _lib.check(_lib.lib.kdehip_prod_philox_device_manifold(
         M, arr, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset), int(bool(addEntropy)),
-        None if mask is None else ptr(mask, u8p), int(precision), ProductPlan._addr(d_points), ProductPlan._addr(d_indices),
-        ProductPlan._addr(d_labels), ProductPlan._addr(stream)))
+        None if mask is None else ptr(mask, u8p), None if man is None else ptr(man, u8p), int(precision),
+        ProductPlan._addr(d_points), ProductPlan._addr(d_indices), ProductPlan._addr(d_labels), ProductPlan._addr(stream)))
 
 
-def prodAppxMSGibbsS_resident(trees, *, Np, Niter=3, seed=0, addEntropy=True, partialDimMask=None, precision=64):
+def prodAppxMSGibbsS_resident(trees, *, Np, Niter=3, seed=0, addEntropy=True, partialDimMask=None, precision=64,
+                              manifold=None):
     """`prodAppxMSGibbsS` on `DeviceDensity` inputs with host outputs (blocking): returns (points[ndims, Np],
     indices[Ndens, Np]) -- the numbers of `prodAppxMSGibbsS(..., seed=seed)` without the per-call host re-layout and
-    upload."""
+    upload.  `manifold`: as `prodAppxMSGibbsS_device` (kdehip_prod_philox_resident_manifold)."""
     trees = list(trees)
     M, D = len(trees), trees[0].dims
     arr = (C.c_void_p * M)(*[t._h for t in trees])
     mask = _mask_array(partialDimMask, M, D)
+    man = _manifold_array(manifold, D)
     pts = np.empty(D * Np)   # (every element is written by the call)
     ind = np.empty(M * Np, dtype=np.int64)
-    _lib.check(_lib.lib.kdehip_prod_philox_resident(M, arr, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                                    int(bool(addEntropy)), None if mask is None else ptr(mask, u8p),
-                                                    int(precision), ptr(pts, f64p), ptr(ind, i64p)))
+    _lib.check(_lib.lib.kdehip_prod_philox_resident_manifold(
+        M, arr, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(bool(addEntropy)),
+        None if mask is None else ptr(mask, u8p), None if man is None else ptr(man, u8p), int(precision), ptr(pts, f64p),
+        ptr(ind, i64p)))
     return pts.reshape(Np, D).T, ind.reshape(Np, M).T
 
 
