@@ -112,7 +112,7 @@ int kdehip_gibbs1_multi(int Ndens, const kdehip_density *trees, int64_t Np, int 
  *                      lambdas_j > 0   (the information-weighted mean in the tangent space at ref; the Euclidean formula
  *                      whenever no difference wraps)
  * The densities are the caller's arrays as built (the reference's tree construction has hooks of its own,
- * src/BallTree01.jl:315, which are the caller's business).  Runs the general sampler's generic arithmetic (the
+ * src/BallTree01.jl:315: kdehip_make_density_tree, section 4, for callers who build here).  Runs the general sampler's generic arithmetic (the
  * reference's divide + log accumulation); caller streams in the reference's order, as kdehip_gibbs1_trace.  manifold == NULL
  * = all Euclidean = kdehip_gibbs1_trace.  oracle/kde_oracle.c okde_gibbs1_manifold is the same enum on the CPU; the Julia
  * shim maps NOTHING to it automatically (a caller's circular functions need not be these). */
@@ -352,7 +352,24 @@ int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, kdehip_devi
  * kdehip_mul_device_manifold(items[i], row i) returns; manifolds == NULL IS the entry above. */
 int kdehip_mul_device_batch_manifold(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
                                      kdehip_device_density **out, double *bw_out, int32_t *nevals);
-/* The reference's arrays of a density the library built (the two entries above), shaped as in kdehip_make_density; any
+/* The three entries above with the operators of tree construction (section 4, "tree construction on a manifold"): the
+ * named entry plus a trailing tree_manifold (ndims bytes or NULL) that the host builder of the result's tree takes
+ * (kdehip_make_density_tree); `manifold` keeps its meaning (the sampler and the bandwidth search).  The reference's
+ * kde!(points, addop, diffop) is the call with both set to the same value.  tree_manifold == NULL or all zeros IS the
+ * _manifold entry, bit for bit; a byte above 1 is KDEHIP_ERR_ARG before any device is touched.  kdehip_mul_device_tree covers
+ * the one-density shortcut.  The batch takes tree_manifolds as it takes manifolds (NULL, or nprod rows of KDEHIP_MAX_DIMS
+ * bytes): out[i] is bit for bit what kdehip_mul_device_tree(items[i], row i of manifolds, row i of tree_manifolds) returns,
+ * and items with and without a circular tree may be mixed. */
+int kdehip_density_from_device_points_tree(kdehip_device_density **out, const double *d_points, int64_t D, int64_t N,
+                                           int device, void *stream, double *bw_out, int32_t *nevals,
+                                           const uint8_t *manifold /* D bytes or NULL */,
+                                           const uint8_t *tree_manifold /* D bytes or NULL */);
+int kdehip_mul_device_tree(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees, uint64_t seed,
+                           int addEntropy, double *bw_out, int32_t *nevals, const uint8_t *manifold,
+                           const uint8_t *tree_manifold);
+int kdehip_mul_device_batch_tree(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+                                 const uint8_t *tree_manifolds, kdehip_device_density **out, double *bw_out, int32_t *nevals);
+/* The reference's arrays of a density the library built (the entries above), shaped as in kdehip_make_density; any
  * pointer may be NULL; bw_out: its D LOOCV bandwidths (standard deviations).  A density that came from
  * kdehip_density_upload has no such mirror (KDEHIP_ERR_UNSUPPORTED): its arrays are the caller's. */
 int kdehip_density_download(const kdehip_device_density *d, double *centers, double *ranges, double *weights,
@@ -493,6 +510,38 @@ int kdehip_make_density(int64_t D, int64_t N, const double *points, const double
                         int64_t *highest_leaf, int64_t *permutation, double *means,
                         double *bandwidth, double *bandwidthMin, double *bandwidthMax);
 
+/* Tree construction on a manifold: kde!(points, ks, weights, addop, diffop) (src/KDE01.jl:34-57 -> makeBallTreeDensity ->
+ * buildTree! -> buildBall!).  tree_manifold: D bytes of KDEHIP_MANIFOLD_EUCLIDEAN / KDEHIP_MANIFOLD_CIRCULAR or NULL.  In a
+ * circular dimension addop(a, b) = wrap(a + b) and diffop(a, b) = wrap(a - b) ("manifolds" above; csrc/circ_wrap.hpp, the one
+ * expression host and device share) replace + / - at exactly the reference's hook points; nothing is added, clamped or repaired:
+ *   most_spread_coord (src/BallTree01.jl:142-173)   mean = addop(mean, w c); variance += diffop(c, mean)^2.  The sums stay
+ *                        sequential, the last leaf of the range is left out, w = 1 / (high - low), the comparison a strict >.
+ *   select! (:223-242)   the test c_i - c_pivot < 0 becomes diffop(c_i, c_pivot) < 0.  Pivot choice, the single forward scan,
+ *                        the final swap and the m <= pos / m >= pos updates are unchanged.  The wrapped comparison is not a
+ *                        total order; every pass still fixes its pivot and shrinks the range, so the loop ends, and the
+ *                        result is whatever the reference's scan produces.
+ *   getMiniMaxi / calcStatsBall! (:249-336)   a = addop(c_L, r_L), b = addop(c_R, r_R), maxi = a > b ? a : b;
+ *                        c = diffop(c_L, r_L), c2 = diffop(c_R, r_R), mini = c < c2 ? c : c2; halfspan = diffop(maxi, mini) / 2
+ *                        (stored in ranges); center = addop(mini, halfspan).  Half-spans can come out NEGATIVE on data spread
+ *                        round the circle; they are stored as computed.
+ * What stays Euclidean, as in the reference: calcStatsDensity! (src/BallTreeDensity01.jl:156-185: node weights, the
+ * moment-matched means / bandwidth, bandwidthMin / Max -- the reference passes its operators down to calcStatsBall! only),
+ * the child numbering and lowest / highest_leaf, and the leaf values (points are stored as given, any representative, no
+ * wrapping of inputs).
+ *   - wrap(t) == t for -pi <= t < pi: a circular build on data in which no hooked expression leaves that interval returns the
+ *     Euclidean build's bits.  Any data inside [-1, 1] qualifies (means and differences stay below 2, box edges inside
+ *     [-1, 1], spans at most 2).
+ *   - tree_manifold == NULL or all zeros IS kdehip_make_density, bit for bit (it forwards here with NULL).
+ *   - a byte above 1 is KDEHIP_ERR_ARG, checked before any array is written.
+ * `manifold` (sections 2c, 2d, 5d: the sampler, evaluation, the bandwidth search) and `tree_manifold` (the builders) are
+ * separate arguments: the _manifold entries keep building Euclidean trees. */
+int kdehip_make_density_tree(int64_t D, int64_t N, const double *points, const double *ks, int64_t nks,
+                             const double *weights_in, double *centers, double *ranges, double *weights,
+                             int64_t *left_child, int64_t *right_child, int64_t *lowest_leaf,
+                             int64_t *highest_leaf, int64_t *permutation, double *means,
+                             double *bandwidth, double *bandwidthMin, double *bandwidthMax,
+                             const uint8_t *tree_manifold /* D bytes or NULL */);
+
 /* The bandwidth-dependent half of the construction on an existing tree: topology, bounding boxes, weights and means
  * do not depend on ks, only `bandwidth` (leaves ks^2, internal nodes by moment matching,
  * src/BallTreeDensity01.jl:141-187) and bandwidthMin/Max do.  Lets kde!(points) build its tree while the GPU searches
@@ -516,6 +565,18 @@ int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns, const dou
                                  int64_t *const *lowest_leaf, int64_t *const *highest_leaf,
                                  int64_t *const *permutation, double *const *means, double *const *bandwidth,
                                  double *const *bandwidthMin, double *const *bandwidthMax, int device);
+/* The same with the operators of kdehip_make_density_tree: ONE tree_manifold of D bytes (or NULL) for the whole batch;
+ * bit-identical to kdehip_make_density_tree per member.  An all-Euclidean batch runs the kernel of the entry above (which
+ * forwards here with NULL); a byte above 1 is KDEHIP_ERR_ARG before any device is touched.
+ * kdehip_make_density_device_supported is unchanged. */
+int kdehip_make_densities_device_tree(int nb, int64_t D, const int64_t *Ns, const double *const *points,
+                                      const double *const *ks, int64_t nks, const double *const *weights_in,
+                                      double *const *centers, double *const *ranges, double *const *weights,
+                                      int64_t *const *left_child, int64_t *const *right_child,
+                                      int64_t *const *lowest_leaf, int64_t *const *highest_leaf,
+                                      int64_t *const *permutation, double *const *means, double *const *bandwidth,
+                                      double *const *bandwidthMin, double *const *bandwidthMax, int device,
+                                      const uint8_t *tree_manifold /* D bytes or NULL */);
 
 /* ---- (5) direct evaluation and automatic bandwidth (the callers either side of the product) ----
  * kdehip_evaluate: `evaluateDualTree(bd, pos)` / `bd(pos)` with the reference's default
@@ -604,12 +665,16 @@ int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_devi
  *   - a manifold byte other than 0 or 1 is KDEHIP_ERR_ARG, checked before any device is touched.
  * Bandwidth search: only the leave-one-out likelihoods wrap.  The marginal's sort, neighborMinMax and with it the search
  * bracket are the Euclidean ones, as in the reference (marginal(p, [i]) and the kde! inside ksize build their 1-D trees with
- * the default operators), and kdehip_make_density_auto_manifold / kdehip_density_from_device_points_manifold still build the
- * tree with the Euclidean builder: tree construction on a manifold is not supported.
+ * the default operators), and kdehip_make_density_auto_manifold / kdehip_density_from_device_points_manifold build the
+ * tree with the Euclidean builder.  The tree's own operators are a separate argument, tree_manifold (section 4, "tree
+ * construction on a manifold"): kdehip_make_density_auto_tree below takes both, and the reference's kde!(points, addop, diffop)
+ * is the call with both set to the same value; its search is untouched by tree_manifold.
  * Products: besides kdehip_gibbs1_manifold (host trees, caller streams, the generic arithmetic), the resident entries take a
  * manifold -- kdehip_prod_philox_device_manifold, kdehip_prod_philox_resident_manifold (2c), kdehip_mul_device_manifold,
- * kdehip_mul_device_batch_manifold (2d) -- and run the sampler's circular fast mode.  Still Euclidean only: tree
- * construction, kdehip_resample_device and the summaries of 5c. */
+ * kdehip_mul_device_batch_manifold (2d) -- and run the sampler's circular fast mode; their _tree forms (2d) add the
+ * builder's operators.  Still Euclidean only: kdehip_resample_device, kdehip_density_marginal_device, the summaries of 5c and
+ * the Python mirror's `a * b`; kdehip_density_set_bandwidth needs no manifold (topology and means do not depend on the
+ * bandwidth, and the moment matching is Euclidean in the reference). */
 int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out,
                              int device, const uint8_t *manifold);
 int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,
@@ -638,14 +703,21 @@ int kdehip_make_density_auto_manifold(int64_t D, int64_t N, const double *points
                                       int64_t *right_child, int64_t *lowest_leaf, int64_t *highest_leaf, int64_t *permutation,
                                       double *means, double *bandwidth, double *bandwidthMin, double *bandwidthMax,
                                       const uint8_t *manifold);
+/* kde!(points, addop, diffop) (src/KDE01.jl:3-27): `manifold` for the bandwidth search as above, `tree_manifold` for the
+ * builder of the final tree (:24; kdehip_make_density_tree).  tree_manifold == NULL or all zeros IS the entry above. */
+int kdehip_make_density_auto_tree(int64_t D, int64_t N, const double *points, double *bw_out, int32_t *nevals, int device,
+                                  double *centers, double *ranges, double *weights, int64_t *left_child,
+                                  int64_t *right_child, int64_t *lowest_leaf, int64_t *highest_leaf, int64_t *permutation,
+                                  double *means, double *bandwidth, double *bandwidthMin, double *bandwidthMax,
+                                  const uint8_t *manifold, const uint8_t *tree_manifold);
 
 /* ---- (5c) summaries: marginal, getKDERange, getKDEMax, getKDEMean, getKDEfit, intersIntgAppxIS -------------------------
  * The calls a belief-propagation host makes after a solve (src/KDE01.jl:143-153, src/DualTree01.jl:512-618), on densities
  * that live in HBM (and, for getKDEMax / intersIntgAppxIS, on host densities uploaded for the call).  A density's points are
  * its leaf means (as in 5b); "original order" is getPoints order, through the permutation.  dims are 1-based here (0-based in
  * the Python mirror).  Only the Euclidean operators exist HERE: the reference's addop / diffop arguments of these functions
- * are not supported (their grids would have to be defined on the circle first, and marginal's tree build on a manifold is
- * not supported either); evaluation, log-likelihoods and the bandwidth search take a manifold in section 5d.
+ * are not supported (their grids would have to be defined on the circle first, and marginal builds its tree with the
+ * Euclidean operators); evaluation, log-likelihoods and the bandwidth search take a manifold in section 5d.
  *   marginal(p, dims)  = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims], getWeights(p)): size(bandwidth, 2) > 2N is false
  *                        for the flat arrays, so the bandwidth is that of ORIGINAL point 1; getBW returns sqrt(variance) and
  *                        kde! squares it again, so the marginal's variance is fl(sqrt(v))^2, not v.  The weights are

@@ -188,6 +188,18 @@ SIGNATURES = {
                                            i64p, i64p, f64p, f64p, f64p, f64p]),
     "kdehip_make_density": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, C.c_int64, f64p, f64p, f64p, f64p,
                                       i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p]),
+    # tree construction on a manifold (include/kdehip.h section 4): the named entry plus a trailing tree_manifold
+    "kdehip_make_density_tree": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, C.c_int64, f64p, f64p, f64p, f64p,
+                                           i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),
+    "kdehip_make_densities_device_tree": (C.c_int, [C.c_int, C.c_int64, i64p] + [C.POINTER(C.c_void_p)] * 2 + [C.c_int64] +
+                                          [C.POINTER(C.c_void_p)] * 13 + [C.c_int, u8p]),
+    "kdehip_make_density_auto_tree": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p,
+                                                i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p, u8p]),
+    "kdehip_density_from_device_points_tree": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int64,
+                                                         C.c_int, C.c_void_p, f64p, i32p, u8p, u8p]),
+    "kdehip_mul_device_tree": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_uint64, C.c_int, f64p,
+                                         i32p, u8p, u8p]),
+    "kdehip_mul_device_batch_tree": (C.c_int, [C.c_int, C.POINTER(CMulItem), u8p, u8p, C.POINTER(C.c_void_p), f64p, i32p]),
 }
 
 

@@ -35,13 +35,14 @@ def auto_bandwidth(points, device=0, return_evals=False, manifold=None):
     return (bw, ne.value) if return_evals else bw
 
 
-def kde_auto(points, device=0, overlap=None, manifold=None) -> BallTreeDensity:
+def kde_auto(points, device=0, overlap=None, manifold=None, tree_manifold=None) -> BallTreeDensity:
     """`kde!(points)`: LOOCV bandwidth per dimension, then `kde!(points, bwds)` (src/KDE01.jl:24).
 
     The tree's topology, bounding boxes, weights and means do not depend on the bandwidth: the host builder runs on the
     library's worker threads WHILE the GPU searches the bandwidth, and the variances are filled in afterwards
     (kdehip_make_density_auto) -- bit-identical to building with the final bandwidth.  `overlap=False`: the two steps one
-    after the other (what the tests compare with)."""
+    after the other (what the tests compare with).  `manifold`: the search's; `tree_manifold`: the final tree's operators
+    (kdehip_make_density_auto_tree) -- `kde!(points, addop, diffop)` is both set to the same value."""
     pts = np.asarray(points, dtype=np.float64)
     if pts.ndim == 1:
         pts = pts.reshape(1, -1)
@@ -49,19 +50,21 @@ def kde_auto(points, device=0, overlap=None, manifold=None) -> BallTreeDensity:
     if overlap is None:
         overlap = True
     man, mp = _man_ptr(manifold, D)
+    tman, tptr = _man_ptr(tree_manifold, D)
     if N < 2 or not overlap:
-        return kde(pts, auto_bandwidth(pts, device=device, manifold=manifold))
+        return kde(pts, auto_bandwidth(pts, device=device, manifold=manifold), tree_manifold=tree_manifold)
     from .density import _empty_density
     flat = np.ascontiguousarray(pts.T).ravel()
     bd = _empty_density(D, N)
     bt = bd.bt
     bw = np.empty(D)
     i64p = _lib.i64p
-    _lib.check(_lib.lib.kdehip_make_density_auto_manifold(
+    _lib.check(_lib.lib.kdehip_make_density_auto_tree(
         D, N, ptr(flat, f64p), ptr(bw, f64p), None, int(device), ptr(bt.centers, f64p), ptr(bt.ranges, f64p),
         ptr(bt.weights, f64p), ptr(bt.left_child, i64p), ptr(bt.right_child, i64p), ptr(bt.lowest_leaf, i64p),
         ptr(bt.highest_leaf, i64p), ptr(bt.permutation, i64p), ptr(bd.means, f64p), ptr(bd.bandwidth, f64p),
-        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), mp))
+        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), mp, tptr))
+    bd.tree_manifold = tman
     return bd
 
 

@@ -19,9 +19,11 @@
 #include <vector>
 
 #include "../../include/kdehip.h"
+#include "circ_wrap.hpp"
 #include "device_density.hpp"
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
+#include "tree_manifold.hpp"
 
 namespace kdehip {
 namespace {
@@ -37,13 +39,23 @@ namespace {
 // before either is built (the same closed form the device builder uses, treebuild.hip).  The top two or three levels
 // of a large density therefore build their left side on another host thread; every node is still computed by the same
 // expressions from the same operands, so the arrays do not depend on the number of threads (host_pool.hpp).
+//
+// On a manifold (kdehip_make_density_tree; include/kdehip.h section 4) the reference threads addop / diffop through
+// exactly three places -- most_spread_coord, select! and getMiniMaxi / calcStatsBall! -- and in a dimension flagged
+// circular those become wrap(a + b) / wrap(a - b) (circ_wrap.hpp).  calcStatsDensity!, the child numbering and the leaf
+// values stay as they are.  The Euclidean loops are untouched: the circular form is chosen per call (widest_dim) or per
+// selected dimension (quick_select, summarize), never per element.
 class DensityBuilder {
  public:
   DensityBuilder(int64_t D, int64_t N, const double *points, double *centers, double *ranges,
                  double *weights, int64_t *left, int64_t *right, int64_t *lo, int64_t *hi, int64_t *perm,
-                 double *means, double *bw)
+                 double *means, double *bw, const uint8_t *tree_manifold)
       : D_(D), N_(N), pts_(points), centers_(centers), ranges_(ranges), weights_(weights), left_(left),
         right_(right), lo_(lo), hi_(hi), perm_(perm), means_(means), bw_(bw) {
+    for (int64_t k = 0; tree_manifold && k < D; ++k)
+      if (tree_manifold[k] == KDEHIP_MANIFOLD_CIRCULAR) circ_.push_back(k);
+    circ_flag_.assign(static_cast<size_t>(D), 0);
+    for (int64_t k : circ_) circ_flag_[static_cast<size_t>(k)] = 1;
     slot_.resize(static_cast<size_t>(N));
     for (int64_t i = 0; i < N; ++i) slot_[static_cast<size_t>(i)] = i;  // buildTree!, :419-429
   }
@@ -152,6 +164,17 @@ class DensityBuilder {
         v[k] += dlt * dlt;
       }
     }
+    // circular dimensions: the same two sequential sums with mean = addop(mean, w c) and diffop(c, mean)^2 (:155, :161),
+    // one strided pass per such dimension (the wrap makes each a dependent chain of its own anyway)
+    for (int64_t k : circ_) {
+      double mk = 0.0, vk = 0.0;
+      for (int64_t id = first; id < last; ++id) mk = circ_wrap(mk + scale * pts_[slot_[static_cast<size_t>(id - N_ - 1)] * D_ + k]);
+      for (int64_t id = first; id < last; ++id) {
+        const double dlt = circ_wrap(pts_[slot_[static_cast<size_t>(id - N_ - 1)] * D_ + k] - mk);
+        vk += dlt * dlt;
+      }
+      v[k] = vk;
+    }
     int64_t best = 0;
     double best_var = 0.0;
     for (int64_t k = 0; k < D_; ++k)
@@ -162,7 +185,14 @@ class DensityBuilder {
   // Quick-select (select!, BallTree01.jl:223-242): afterwards leaves first..pos are <= those after.
   // The scan is the reference's single forward pass ("if less than the pivot: ++store, swap(store, i)"),
   // written branch-free on a contiguous copy of the keys: a not-less element swaps with itself.
+  // In a circular dimension the test is diffop(c_i, c_pivot) < 0 (:232): not a total order, but every pass still fixes its
+  // pivot and shrinks the range, and the result is whatever the reference's scan produces.
   void quick_select(int64_t k, int64_t pos, int64_t first, int64_t last, Scratch &s) {
+    if (circ_flag_[static_cast<size_t>(k)]) quick_select_on<true>(k, pos, first, last, s);
+    else quick_select_on<false>(k, pos, first, last, s);
+  }
+  template <bool CIRC>
+  void quick_select_on(int64_t k, int64_t pos, int64_t first, int64_t last, Scratch &s) {
     if (first >= last) return;
     const int64_t base = first;
     const int64_t n0 = last - first + 1;
@@ -179,7 +209,7 @@ class DensityBuilder {
       const double pivot = kk[lo];
       int64_t store = lo;
       for (int64_t i = lo; i <= hi; ++i) {
-        const bool lt = (kk[i] - pivot < 0.0);
+        const bool lt = CIRC ? (circ_wrap(kk[i] - pivot) < 0.0) : (kk[i] - pivot < 0.0);
         store += lt ? 1 : 0;
         const double ka = kk[store], kb = kk[i];
         const int64_t sa = sl[store], sb = sl[i];
@@ -208,6 +238,17 @@ class DensityBuilder {
       const double half = (top - bottom) / 2.0;
       rng(id)[k] = half;
       ctr(id)[k] = bottom + half;
+    }
+    // circular dimensions (getMiniMaxi, :249-278; calcStatsBall!, :315-321): every + / - above through addop / diffop.  A
+    // half-span may come out negative; it is stored as computed.
+    for (int64_t k : circ_) {
+      const double upA = circ_wrap(ctr(a)[k] + rng(a)[k]), upB = circ_wrap(ctr(b)[k] + rng(b)[k]);
+      const double dnA = circ_wrap(ctr(a)[k] - rng(a)[k]), dnB = circ_wrap(ctr(b)[k] - rng(b)[k]);
+      const double top = (upA > upB) ? upA : upB;
+      const double bottom = (dnA < dnB) ? dnA : dnB;
+      const double half = circ_wrap(top - bottom) / 2.0;
+      rng(id)[k] = half;
+      ctr(id)[k] = circ_wrap(bottom + half);
     }
     weights_[id - 1] = (a != b) ? weights_[a - 1] + weights_[b - 1] : weights_[a - 1];
 
@@ -255,6 +296,8 @@ class DensityBuilder {
   double *means_, *bw_;
   const double *wnorm_ = nullptr, *leaf_var_ = nullptr;
   std::vector<int64_t> slot_;
+  std::vector<int64_t> circ_;       // the circular dimensions, ascending (empty: the Euclidean builder)
+  std::vector<uint8_t> circ_flag_;  // [D]
 };
 
 }  // namespace
@@ -266,6 +309,17 @@ extern "C" int kdehip_make_density(int64_t D, int64_t N, const double *points, c
                                    int64_t *right_child, int64_t *lowest_leaf, int64_t *highest_leaf,
                                    int64_t *permutation, double *means, double *bandwidth,
                                    double *bandwidthMin, double *bandwidthMax) {
+  return kdehip_make_density_tree(D, N, points, ks, nks, weights_in, centers, ranges, weights, left_child, right_child,
+                                  lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin, bandwidthMax, nullptr);
+}
+
+// kde!(points, ks, weights, addop, diffop) (src/KDE01.jl:34-57): tree_manifold = D bytes of the manifold enum or NULL
+extern "C" int kdehip_make_density_tree(int64_t D, int64_t N, const double *points, const double *ks,
+                                        int64_t nks, const double *weights_in, double *centers,
+                                        double *ranges, double *weights, int64_t *left_child,
+                                        int64_t *right_child, int64_t *lowest_leaf, int64_t *highest_leaf,
+                                        int64_t *permutation, double *means, double *bandwidth,
+                                        double *bandwidthMin, double *bandwidthMax, const uint8_t *tree_manifold) {
   using namespace kdehip;
   if (D < 1 || N < 1) return set_error(KDEHIP_ERR_ARG, "kdehip_make_density: need D >= 1 and N >= 1");
   if (nks != 1 && nks != D)
@@ -274,6 +328,7 @@ extern "C" int kdehip_make_density(int64_t D, int64_t N, const double *points, c
       !lowest_leaf || !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin ||
       !bandwidthMax)
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_density: null pointer");
+  if (tree_manifold_mask(tree_manifold, D, nullptr) != KDEHIP_OK) return KDEHIP_ERR_ARG;
 
   const size_t nd = static_cast<size_t>(2 * N * D);
   std::memset(centers, 0, nd * sizeof(double));
@@ -305,7 +360,7 @@ extern "C" int kdehip_make_density(int64_t D, int64_t N, const double *points, c
   }
   try {
     DensityBuilder(D, N, points, centers, ranges, weights, left_child, right_child, lowest_leaf, highest_leaf,
-                   permutation, means, bandwidth)
+                   permutation, means, bandwidth, tree_manifold)
         .build(wnorm.data(), var.data());
   } catch (const std::exception &e) {  // (scratch allocation on this or a worker thread: nothing may cross the C boundary)
     return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_make_density: ") + e.what());

@@ -26,6 +26,7 @@
 #include "kdehip_internal.hpp"
 #include "loocv_search.hpp"
 #include "phase_timer.hpp"
+#include "tree_manifold.hpp"
 
 using namespace kdehip;
 
@@ -984,10 +985,24 @@ extern "C" int kdehip_make_density_auto_manifold(int64_t D, int64_t N, const dou
                                                  int64_t *left_child, int64_t *right_child, int64_t *lowest_leaf,
                                                  int64_t *highest_leaf, int64_t *permutation, double *means, double *bandwidth,
                                                  double *bandwidthMin, double *bandwidthMax, const uint8_t *manifold) {
+  return kdehip_make_density_auto_tree(D, N, points, bw_out, nevals, device, centers, ranges, weights, left_child, right_child,
+                                       lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin, bandwidthMax,
+                                       manifold, nullptr);
+}
+
+// kde!(points, addop, diffop) (src/KDE01.jl:3-27): `manifold` for the bandwidth search, `tree_manifold` for the builder of
+// the final tree (:24).  The search itself -- the marginals' 1-D trees, neighborMinMax, the bracket -- stays as it is.
+extern "C" int kdehip_make_density_auto_tree(int64_t D, int64_t N, const double *points, double *bw_out, int32_t *nevals,
+                                             int device, double *centers, double *ranges, double *weights,
+                                             int64_t *left_child, int64_t *right_child, int64_t *lowest_leaf,
+                                             int64_t *highest_leaf, int64_t *permutation, double *means, double *bandwidth,
+                                             double *bandwidthMin, double *bandwidthMax, const uint8_t *manifold,
+                                             const uint8_t *tree_manifold) {
   using namespace kdehip;
   if (D < 1 || N < 2) return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_auto: need D >= 1 and N >= 2");
   unsigned circ = 0;  // (checked here too: before the tree build starts)
   if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  if (tree_manifold_mask(tree_manifold, D, nullptr) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (!points || !bw_out || !centers || !ranges || !weights || !left_child || !right_child || !lowest_leaf ||
       !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin || !bandwidthMax)
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_auto: null pointer");
@@ -996,8 +1011,9 @@ extern "C" int kdehip_make_density_auto_manifold(int64_t D, int64_t N, const dou
     TaskGroup group(HostPool::get());
     group.run([&] {
       const double one = 1.0;  // (placeholder bandwidth: only `bandwidth`, bandwidthMin/Max depend on it)
-      tree_rc = kdehip_make_density(D, N, points, &one, 1, nullptr, centers, ranges, weights, left_child, right_child,
-                                    lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin, bandwidthMax);
+      tree_rc = kdehip_make_density_tree(D, N, points, &one, 1, nullptr, centers, ranges, weights, left_child, right_child,
+                                         lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin, bandwidthMax,
+                                         tree_manifold);
     });
     rc = kdehip_auto_bandwidth_manifold(D, N, points, bw_out, nevals, device, manifold);
     group.wait();

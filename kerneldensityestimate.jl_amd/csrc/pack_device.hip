@@ -31,6 +31,7 @@
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
 #include "loocv_search.hpp"
+#include "tree_manifold.hpp"
 
 using namespace kdehip;
 
@@ -381,6 +382,21 @@ extern "C" int kdehip_density_from_device_points(kdehip_device_density **out, co
 extern "C" int kdehip_density_from_device_points_manifold(kdehip_device_density **out, const double *d_points, int64_t D,
                                                           int64_t N, int device, void *stream, double *bw_out,
                                                           int32_t *nevals, const uint8_t *manifold) {
+  return kdehip_density_from_device_points_tree(out, d_points, D, N, device, stream, bw_out, nevals, manifold, nullptr);
+}
+
+// A tree_manifold byte other than 0 or 1 is KDEHIP_ERR_ARG (tree_manifold.hpp); all zeros becomes NULL (the Euclidean builder).
+static int tree_manifold_arg(const uint8_t *&tree_manifold, int64_t D) {
+  uint32_t mask = 0;
+  const int rc = tree_manifold_mask(tree_manifold, D < KDEHIP_MAX_DIMS ? D : KDEHIP_MAX_DIMS, &mask);
+  if (rc == KDEHIP_OK && mask == 0) tree_manifold = nullptr;
+  return rc;
+}
+
+// (tree_manifold: the host builder's operators, kdehip_make_density_tree -- kde!(points, addop, diffop), src/KDE01.jl:24)
+extern "C" int kdehip_density_from_device_points_tree(kdehip_device_density **out, const double *d_points, int64_t D,
+                                                      int64_t N, int device, void *stream, double *bw_out, int32_t *nevals,
+                                                      const uint8_t *manifold, const uint8_t *tree_manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (!d_points) return set_error(KDEHIP_ERR_ARG, "null points");
@@ -393,6 +409,8 @@ extern "C" int kdehip_density_from_device_points_manifold(kdehip_device_density 
     else if (manifold[k] != KDEHIP_MANIFOLD_EUCLIDEAN)
       return set_error(KDEHIP_ERR_ARG, "manifold: every entry is KDEHIP_MANIFOLD_EUCLIDEAN or KDEHIP_MANIFOLD_CIRCULAR");
   }
+  rc = tree_manifold_arg(tree_manifold, D);
+  if (rc != KDEHIP_OK) return rc;
   DeviceGuard guard;
   rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -458,8 +476,8 @@ extern "C" int kdehip_density_from_device_points_manifold(kdehip_device_density 
   std::vector<int64_t> order;
   auto host_side_body = [&]() {
     if (hipStreamSynchronize(xs) != hipSuccess) { side_rc = KDEHIP_ERR_HIP; side_msg = "the copy of the points failed"; return; }
-    tree_rc = kdehip_make_density(D, N, pts, &one, 1, nullptr, centers, ranges, weights, left, right, lowest, highest, perm,
-                                  means, bandwidth, bwmin, bwmax);
+    tree_rc = kdehip_make_density_tree(D, N, pts, &one, 1, nullptr, centers, ranges, weights, left, right, lowest, highest, perm,
+                                       means, bandwidth, bwmin, bwmax, tree_manifold);
     us_tree = us();
     if (tree_rc != KDEHIP_OK) return;
     side_rc = expand_frontier_ids(host, h->D, h->Lown, h->fr);
@@ -500,8 +518,8 @@ extern "C" int kdehip_density_from_device_points_manifold(kdehip_device_density 
     try {
       TaskGroup group(HostPool::get());
       group.run([&] {
-        tree_rc = kdehip_make_density(D, N, pts, &one, 1, nullptr, centers, ranges, weights, left, right, lowest, highest,
-                                      perm, means, bandwidth, bwmin, bwmax);
+        tree_rc = kdehip_make_density_tree(D, N, pts, &one, 1, nullptr, centers, ranges, weights, left, right, lowest, highest,
+                                           perm, means, bandwidth, bwmin, bwmax, tree_manifold);
       });
       rc = auto_bandwidth_run(static_cast<int>(D), N, pts, d_points, cs, bw, nevals, nullptr, circ);
       group.wait();
@@ -630,6 +648,13 @@ static int mul_manifold_mask(const uint8_t *manifold, int D, unsigned *mask) {
 extern "C" int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees,
                                           uint64_t seed, int addEntropy, double *bw_out, int32_t *nevals,
                                           const uint8_t *manifold) {
+  return kdehip_mul_device_tree(out, Ndens, trees, seed, addEntropy, bw_out, nevals, manifold, nullptr);
+}
+
+// ... and with the operators of tree_manifold in the construction of the result's tree (the shortcut included)
+extern "C" int kdehip_mul_device_tree(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees,
+                                      uint64_t seed, int addEntropy, double *bw_out, int32_t *nevals,
+                                      const uint8_t *manifold, const uint8_t *tree_manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (Ndens < 1 || !trees) return set_error(KDEHIP_ERR_ARG, "need at least one density");
@@ -643,6 +668,8 @@ extern "C" int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens
   const int mrc = mul_manifold_mask(manifold, D, &circ);
   if (mrc != KDEHIP_OK) return mrc;
   if (circ == 0) manifold = nullptr;
+  const int trc = tree_manifold_arg(tree_manifold, D);
+  if (trc != KDEHIP_OK) return trc;
   DeviceGuard guard;
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -656,8 +683,8 @@ extern "C" int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens
     hipLaunchKernelGGL(unpermute_points_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, cs,
                        trees[0]->means, trees[0]->perm, N, D, reinterpret_cast<double *>(sc.dev()));
     KDEHIP_CHECK(hipGetLastError());
-    return kdehip_density_from_device_points_manifold(out, reinterpret_cast<const double *>(sc.dev()), D, N, device, cs, bw_out,
-                                                      nevals, manifold);
+    return kdehip_density_from_device_points_tree(out, reinterpret_cast<const double *>(sc.dev()), D, N, device, cs, bw_out,
+                                                  nevals, manifold, tree_manifold);
   }
   double sum = 0.0;  // numpts = round(Int, mean(Npts.(trees))): Julia rounds halves to even, like nearbyint
   for (int j = 0; j < Ndens; ++j) sum += static_cast<double>(trees[j]->N);
@@ -669,7 +696,7 @@ extern "C" int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens
   rc = prod_philox_device_blocking_stream(Ndens, trees, Np, /*Niter=*/5, seed, 0, addEntropy, nullptr, 64, d_pts, d_ind, cs,
                                           manifold);
   if (rc != KDEHIP_OK) return rc;
-  return kdehip_density_from_device_points_manifold(out, d_pts, D, Np, device, cs, bw_out, nevals, manifold);
+  return kdehip_density_from_device_points_tree(out, d_pts, D, Np, device, cs, bw_out, nevals, manifold, tree_manifold);
 }
 
 // ---- `*` for MANY products in one call ----------------------------------------------------------------------------
@@ -688,6 +715,7 @@ struct MulPlan {   // what one item of the batch becomes
   int D = 0, M = 0;
   unsigned circ = 0;                     // bit d: dimension d is circular (0: the Euclidean `*`)
   const uint8_t *manifold = nullptr;     // the item's manifold when circ != 0
+  const uint8_t *tree_manifold = nullptr;  // the operators of its tree build (NULL: the Euclidean builder)
   int64_t N = 0;          // points of the result (Np of the product, or the density's own count for the shortcut)
   bool shortcut = false, loose = false;  // loose: outside the batched path (fewer than 2 or more than 2048 points): a call of its own
   int group = -1;                        // its (D, N) group
@@ -705,7 +733,7 @@ struct MulGroup { int D; int64_t N; std::vector<int> members; size_t pts_off = 0
 
 }  // namespace
 
-static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds, const uint8_t *tree_manifolds,
                                  kdehip_device_density **out, double *bw_out, int32_t *nevals);
 extern "C" int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, kdehip_device_density **out, double *bw_out,
                                        int32_t *nevals) {
@@ -716,16 +744,23 @@ extern "C" int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, 
 // kernel's domain, like a mask), and their bandwidth searches run in the shared launches of their (D, N, manifold) group.
 extern "C" int kdehip_mul_device_batch_manifold(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
                                                 kdehip_device_density **out, double *bw_out, int32_t *nevals) {
+  return kdehip_mul_device_batch_tree(nprod, items, manifolds, nullptr, out, bw_out, nevals);
+}
+// tree_manifolds: NULL, or nprod rows of KDEHIP_MAX_DIMS bytes like manifolds: row i = the operators of item i's tree build
+// (the pool task of that item passes them to the host builder; Euclidean-tree and circular-tree items may be mixed).
+extern "C" int kdehip_mul_device_batch_tree(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+                                            const uint8_t *tree_manifolds, kdehip_device_density **out, double *bw_out,
+                                            int32_t *nevals) {
   // (the bookkeeping below lives in std::vectors: nothing may throw out of an extern "C" entry point -- the unwinding runs the
   // clean-up that takes every block and handle back first)
   try {
-    return mul_device_batch_impl(nprod, items, manifolds, out, bw_out, nevals);
+    return mul_device_batch_impl(nprod, items, manifolds, tree_manifolds, out, bw_out, nevals);
   } catch (const std::exception &e) {
     if (out) for (int i = 0; i < nprod; ++i) out[i] = nullptr;
     return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_mul_device_batch: ") + e.what());
   }
 }
-static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
+static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds, const uint8_t *tree_manifolds,
                                  kdehip_device_density **out, double *bw_out, int32_t *nevals) {
   if (nprod < 0 || (nprod > 0 && (!items || !out))) return set_error(KDEHIP_ERR_ARG, "kdehip_mul_device_batch: bad item list");
   for (int i = 0; i < nprod; ++i) out[i] = nullptr;
@@ -747,6 +782,9 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const 
     const int mrc = mul_manifold_mask(man, m.D, &m.circ);
     if (mrc != KDEHIP_OK) return mrc;
     m.manifold = m.circ ? man : nullptr;
+    m.tree_manifold = tree_manifolds ? tree_manifolds + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr;
+    const int trc = tree_manifold_arg(m.tree_manifold, m.D);
+    if (trc != KDEHIP_OK) return trc;
     m.shortcut = it.Ndens == 1 && !it.addEntropy;  // the "hack fix for #70" (:713-716)
     if (m.shortcut) m.N = it.trees[0]->N;
     else {
@@ -913,8 +951,9 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const 
         trees.run([m, pin, mb, &one] {
           kdehip_device_density *h = m->h;
           kdehip_device_density::Mirror &q = h->m;
-          m->rc = kdehip_make_density(m->D, m->N, reinterpret_cast<const double *>(pin + m->pts_off), &one, 1, nullptr, q.centers, q.ranges,
-                                      q.weights, q.left, q.right, q.lowest, q.highest, q.perm, q.means, q.bandwidth, q.bwmin, q.bwmax);
+          m->rc = kdehip_make_density_tree(m->D, m->N, reinterpret_cast<const double *>(pin + m->pts_off), &one, 1, nullptr, q.centers,
+                                           q.ranges, q.weights, q.left, q.right, q.lowest, q.highest, q.perm, q.means, q.bandwidth,
+                                           q.bwmin, q.bwmax, m->tree_manifold);
           const kdehip_density host{m->N, m->D, q.means, q.bandwidth, q.weights, q.left, q.right, q.perm};
           if (m->rc == KDEHIP_OK) m->rc = expand_frontier_ids(host, h->D, h->Lown, h->fr);
           if (m->rc == KDEHIP_OK) m->rc = children_first_order(m->N, q.left, q.right, m->order);
@@ -988,9 +1027,9 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const 
   // items outside the batched path: a call of their own each
   for (int i = 0; i < nprod; ++i) {
     if (!mp[i].loose) continue;
-    rc = kdehip_mul_device_manifold(&mp[i].h, items[i].Ndens, items[i].trees, items[i].seed, items[i].addEntropy,
-                                    bw_out ? bw_out + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr,
-                                    nevals ? nevals + i : nullptr, mp[i].manifold);
+    rc = kdehip_mul_device_tree(&mp[i].h, items[i].Ndens, items[i].trees, items[i].seed, items[i].addEntropy,
+                                bw_out ? bw_out + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr,
+                                nevals ? nevals + i : nullptr, mp[i].manifold, mp[i].tree_manifold);
     if (rc != KDEHIP_OK) {
       for (MulPlan &m : mp) if (m.loose && m.h) { kdehip_density_free(m.h); m.h = nullptr; }
       return rc;

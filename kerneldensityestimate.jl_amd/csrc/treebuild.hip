@@ -20,6 +20,14 @@
 // Then the leaves are written in their final order and the node statistics (calcStatsBall!, :282-336;
 // calcStatsDensity!, src/BallTreeDensity01.jl:141-187) are computed bottom-up, one depth at a time.
 //
+// On a manifold (kdehip_make_densities_device_tree): the kernel is a template on CIRC.  CIRC = false is the Euclidean
+// builder, the code every all-Euclidean batch launches; CIRC = true reads the job's circ_bits and, in a circular dimension,
+// puts wrap() (circ_wrap.hpp) at the reference's three hook points -- the two sequential sums of the widest-dimension phase
+// (mean = addop(mean, w c), diffop(c, mean)^2), the "less than the pivot" test of both quick-selects (diffop(c_i, c_pivot) <
+// 0; a range is circular when the bit of its split dimension is set, uniform for the wavefront or lane that owns it), and
+// the bounding box of the statistics phase.  The tape of wave_quick_select only assumes a predicate "less than the pivot",
+// so it carries over unchanged.  Moment matching, child numbering and the leaf values stay Euclidean, as in the reference.
+//
 // Compiled with -ffp-contract=off (the moment-matching expressions must not be fused).
 #include <hip/hip_runtime.h>
 
@@ -29,9 +37,11 @@
 #include <vector>
 
 #include "call_block.hpp"
+#include "circ_wrap.hpp"
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
+#include "tree_manifold.hpp"
 
 namespace kdehip {
 namespace {
@@ -43,6 +53,7 @@ constexpr int kMaxDepth = 40;
 struct TreeJob {
   int64_t N;
   int D;
+  uint32_t circ_bits;   // bit k: dimension k is circular (read by the CIRC = true kernel only)
   const double *pts;    // [N][D], input order
   const double *wnorm;  // [N] normalised weights
   double var[KDEHIP_MAX_DIMS];
@@ -85,8 +96,17 @@ __device__ __forceinline__ void wave_fence() {
 // ---- quick-select of one range by one wavefront --------------------------------------------------------------
 // K/S: keys and slots of the range (LDS, indexed from the range start), K2/S2: scratch of the same size,
 // tp/tq: tape arrays (parent pointer, element) of 2n entries.  pos = target position (the median).
+// circ (CIRC instantiation only): the range's split dimension is circular, "less" is wrap(key - pivot) < 0.
+template <bool CIRC>
+__device__ __forceinline__ bool less_than_pivot(double key, double pivot, bool circ) {
+  double d = key - pivot;
+  if (CIRC && circ) d = circ_wrap(d);
+  return d < 0.0;
+}
+
+template <bool CIRC>
 __device__ void wave_quick_select(double *K, uint16_t *S, double *K2, uint16_t *S2, uint16_t *tp, uint16_t *tq, int n,
-                                  int pos, int lane) {
+                                  int pos, int lane, bool circ) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int r = (lo + hi) >> 1;  // floor((low+high)/2), BallTree01.jl:228 (the range start shifts both ids alike)
@@ -103,7 +123,7 @@ __device__ void wave_quick_select(double *K, uint16_t *S, double *K2, uint16_t *
     for (int e0 = 1; e0 <= m; e0 += 64) {
       const int e = e0 + lane;
       const bool in = e <= m;
-      const bool less = in && (K[lo + e] - pivot < 0.0);
+      const bool less = in && less_than_pivot<CIRC>(K[lo + e], pivot, circ);
       const unsigned long long bl = __ballot(less), bg = __ballot(in && !less);
       if (first_ge > m && bg) first_ge = e0 + (__ffsll(static_cast<long long>(bg)) - 1);
       Ltot += __popcll(bl);
@@ -120,7 +140,7 @@ __device__ void wave_quick_select(double *K, uint16_t *S, double *K2, uint16_t *
       const bool in = e <= m;
       const double key = in ? K[lo + e] : 0.0;
       const uint16_t sl = in ? S[lo + e] : 0;
-      const bool less = in && (key - pivot < 0.0);
+      const bool less = in && less_than_pivot<CIRC>(key, pivot, circ);
       const bool ge = in && !less;
       const bool rot = less && e > first_ge;
       const unsigned long long bl = __ballot(less), bg = __ballot(ge), br = __ballot(rot);
@@ -171,7 +191,8 @@ __device__ void wave_quick_select(double *K, uint16_t *S, double *K2, uint16_t *
 }
 
 // ---- the same scan replayed by one lane (small ranges); identical to balltree.cpp's quick_select ----------------
-__device__ void lane_quick_select(double *K, uint16_t *S, int n, int pos) {
+template <bool CIRC>
+__device__ void lane_quick_select(double *K, uint16_t *S, int n, int pos, bool circ) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int r = (lo + hi) >> 1;
@@ -179,7 +200,7 @@ __device__ void lane_quick_select(double *K, uint16_t *S, int n, int pos) {
     const double pivot = K[lo];
     int store = lo;
     for (int i = lo; i <= hi; ++i) {
-      if (K[i] - pivot < 0.0) {
+      if (less_than_pivot<CIRC>(K[i], pivot, circ)) {
         ++store;
         const double tk = K[store]; K[store] = K[i]; K[i] = tk;
         const uint16_t ts = S[store]; S[store] = S[i]; S[i] = ts;
@@ -191,6 +212,7 @@ __device__ void lane_quick_select(double *K, uint16_t *S, int n, int pos) {
   }
 }
 
+template <bool CIRC>
 __global__ __launch_bounds__(kTB) void tree_build_kernel(const TreeBatch batch, const TreeLds L) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int s_nr, s_nnext, s_depth_off[kMaxDepth + 1];
@@ -203,6 +225,7 @@ __global__ __launch_bounds__(kTB) void tree_build_kernel(const TreeBatch batch, 
 #endif
   const TreeJob &J = batch.job[blockIdx.x];
   const int N = static_cast<int>(J.N), D = J.D;
+  const uint32_t circ_bits = CIRC ? J.circ_bits : 0u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double *U = reinterpret_cast<double *>(smem + L.off_u);
   double *K = reinterpret_cast<double *>(smem + L.off_keys);
@@ -258,13 +281,21 @@ __global__ __launch_bounds__(kTB) void tree_build_kernel(const TreeBatch batch, 
         const double scale = 1.0 / static_cast<double>(last - first);
         double m = 0.0;
         const double *x = U + static_cast<size_t>(first) * D + k;
-#pragma unroll 8
-        for (int i = 0; i < last - first; ++i) m = m + scale * x[static_cast<size_t>(i) * D];
         v = 0.0;
+        if (CIRC && ((circ_bits >> k) & 1u)) {  // mean = addop(mean, w c), variance += diffop(c, mean)^2 (:155, :161)
+          for (int i = 0; i < last - first; ++i) m = circ_wrap(m + scale * x[static_cast<size_t>(i) * D]);
+          for (int i = 0; i < last - first; ++i) {
+            const double dlt = circ_wrap(x[static_cast<size_t>(i) * D] - m);
+            v += dlt * dlt;
+          }
+        } else {
 #pragma unroll 8
-        for (int i = 0; i < last - first; ++i) {
-          const double dlt = x[static_cast<size_t>(i) * D] - m;
-          v += dlt * dlt;
+          for (int i = 0; i < last - first; ++i) m = m + scale * x[static_cast<size_t>(i) * D];
+#pragma unroll 8
+          for (int i = 0; i < last - first; ++i) {
+            const double dlt = x[static_cast<size_t>(i) * D] - m;
+            v += dlt * dlt;
+          }
         }
       }
       // argmax over the 8 lanes of the group with the reference's scan: best = 0; take k if v_k > best so far
@@ -291,12 +322,14 @@ __global__ __launch_bounds__(kTB) void tree_build_kernel(const TreeBatch batch, 
       const int first = cur[r].first, n = cur[r].last - first + 1;
       if (n > kSeqMax) {
         const int mid = (first + cur[r].last) >> 1;  // floor((low+high)/2) on ids = on positions (same offset twice)
-        wave_quick_select(K + first, S + first, K2 + first, S2 + first, tp + 2 * first, tq + 2 * first, n, mid - first, lane);
+        wave_quick_select<CIRC>(K + first, S + first, K2 + first, S2 + first, tp + 2 * first, tq + 2 * first, n, mid - first, lane,
+                                CIRC && ((circ_bits >> dimv[r]) & 1u));
       }
     }
     for (int r = tid; r < nr; r += kTB) {
       const int first = cur[r].first, n = cur[r].last - first + 1;
-      if (n <= kSeqMax) lane_quick_select(K + first, S + first, n, ((first + cur[r].last) >> 1) - first);
+      if (n <= kSeqMax)
+        lane_quick_select<CIRC>(K + first, S + first, n, ((first + cur[r].last) >> 1) - first, CIRC && ((circ_bits >> dimv[r]) & 1u));
     }
     __syncthreads();
     TSTAMP(4);
@@ -356,6 +389,14 @@ __global__ __launch_bounds__(kTB) void tree_build_kernel(const TreeBatch batch, 
       for (int k = 0; k < D; ++k) {
         const double ca = J.centers[(a - 1) * D + k], ra = J.ranges[(a - 1) * D + k];
         const double cb = J.centers[(b - 1) * D + k], rb = J.ranges[(b - 1) * D + k];
+        if (CIRC && ((circ_bits >> k) & 1u)) {  // getMiniMaxi / calcStatsBall! through addop / diffop (:249-321)
+          const double upA = circ_wrap(ca + ra), upB = circ_wrap(cb + rb), dnA = circ_wrap(ca - ra), dnB = circ_wrap(cb - rb);
+          const double top = (upA > upB) ? upA : upB, bottom = (dnA < dnB) ? dnA : dnB;
+          const double half = circ_wrap(top - bottom) / 2.0;
+          J.ranges[(id - 1) * D + k] = half;  // (on the circle a half-span may be negative: stored as computed)
+          J.centers[(id - 1) * D + k] = circ_wrap(bottom + half);
+          continue;
+        }
         const double upA = ca + ra, upB = cb + rb, dnA = ca - ra, dnB = cb - rb;
         const double top = (upA > upB) ? upA : upB, bottom = (dnA < dnB) ? dnA : dnB;
         const double half = (top - bottom) / 2.0;
@@ -406,11 +447,27 @@ extern "C" int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns
                                             int64_t *const *permutation, double *const *means,
                                             double *const *bandwidth, double *const *bandwidthMin,
                                             double *const *bandwidthMax, int device) {
+  return kdehip_make_densities_device_tree(nb, D, Ns, points, ks, nks, weights_in, centers, ranges, weights, left_child,
+                                           right_child, lowest_leaf, highest_leaf, permutation, means, bandwidth, bandwidthMin,
+                                           bandwidthMax, device, nullptr);
+}
+
+// ... with the operators of tree_manifold (D bytes or NULL, one manifold for the whole batch) in the construction
+extern "C" int kdehip_make_densities_device_tree(int nb, int64_t D, const int64_t *Ns, const double *const *points,
+                                                 const double *const *ks, int64_t nks, const double *const *weights_in,
+                                                 double *const *centers, double *const *ranges, double *const *weights,
+                                                 int64_t *const *left_child, int64_t *const *right_child,
+                                                 int64_t *const *lowest_leaf, int64_t *const *highest_leaf,
+                                                 int64_t *const *permutation, double *const *means,
+                                                 double *const *bandwidth, double *const *bandwidthMin,
+                                                 double *const *bandwidthMax, int device, const uint8_t *tree_manifold) {
   if (nb < 1 || nb > KDEHIP_MAX_DENS) return set_error(KDEHIP_ERR_ARG, "batch size outside 1..KDEHIP_MAX_DENS");
   if (!Ns || !points || !ks || !centers || !ranges || !weights || !left_child || !right_child || !lowest_leaf ||
       !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin || !bandwidthMax)
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_densities_device: null pointer");
   if (nks != 1 && nks != D) return set_error(KDEHIP_ERR_ARG, "kdehip_make_densities_device: ks must have 1 or D entries");
+  uint32_t circ_bits = 0;
+  if (tree_manifold_mask(tree_manifold, D < KDEHIP_MAX_DIMS ? D : KDEHIP_MAX_DIMS, &circ_bits) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   int64_t maxN = 0;
   for (int j = 0; j < nb; ++j) {
     if (!kdehip_make_density_device_supported(D, Ns[j]))
@@ -456,6 +513,7 @@ extern "C" int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns
     for (int64_t i = 0; i < N; ++i) wn[i] = (win ? win[i] : 1.0) / tot;  // KDE01.jl:46
     TreeJob &J = batch.job[j];
     J.N = N; J.D = static_cast<int>(D);
+    J.circ_bits = circ_bits;
     J.pts = reinterpret_cast<const double *>(db + off[j].pts);
     J.wnorm = reinterpret_cast<const double *>(db + off[j].wn);
     for (int64_t k = 0; k < D; ++k) {
@@ -477,10 +535,12 @@ extern "C" int kdehip_make_densities_device(int nb, int64_t D, const int64_t *Ns
   KDEHIP_CHECK(blk.upload(in_total, hipStreamPerThread));
   const TreeLds L = tree_lds(maxN, static_cast<int>(D));
   // (per call: the attribute belongs to the function ON THE CURRENT DEVICE, and concurrent host threads get here)
-  KDEHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(tree_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+  // an all-Euclidean batch launches the CIRC = false instantiation: no wrap, no mask read
+  auto *kernel = circ_bits ? tree_build_kernel<true> : tree_build_kernel<false>;
+  KDEHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(kTreeLdsLimit)));
   PhaseTimer timer(kPhaseTreeBuild, hipStreamPerThread);  // (kdehip_profile_phase_read(2): the kernel alone)
-  hipLaunchKernelGGL(tree_build_kernel, dim3(nb), dim3(kTB), L.total, hipStreamPerThread, batch, L);
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(kTB), L.total, hipStreamPerThread, batch, L);
   KDEHIP_CHECK(hipGetLastError());
   timer.stop();
   KDEHIP_CHECK(blk.download(out_begin, out_end - out_begin, hipStreamPerThread));

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from ._lib import f64p, i64p, ptr
+from ._lib import f64p, i64p, ptr, u8p
 
 
 class BallTree:
@@ -20,8 +20,10 @@ class BallTree:
 
 
 class BallTreeDensity:
-    """Fields of the reference `BallTreeDensity`; `bandwidth` holds VARIANCES (src/KDE01.jl:45)."""
-    __slots__ = ("bt", "multibandwidth", "means", "bandwidth", "bandwidthMin", "bandwidthMax", "_cstruct_cache")
+    """Fields of the reference `BallTreeDensity`; `bandwidth` holds VARIANCES (src/KDE01.jl:45).  `tree_manifold`: the
+    operators its tree was built with (`kde(..., tree_manifold=)`), as the uint8 enum array, or None -- a record only."""
+    __slots__ = ("bt", "multibandwidth", "means", "bandwidth", "bandwidthMin", "bandwidthMax", "_cstruct_cache",
+                 "tree_manifold")
 
     def __repr__(self):
         return f"BallTreeDensity(dims={Ndim(self)}, Npts={Npts(self)}, bws={np.round(getBW(self)[:, 0], 6)})"
@@ -95,12 +97,13 @@ def _empty_density(D, N) -> BallTreeDensity:
     bd = BallTreeDensity()
     bd.bt = bt
     bd.multibandwidth = 0
+    bd.tree_manifold = None
     for name in ("means", "bandwidth", "bandwidthMin", "bandwidthMax"):
         setattr(bd, name, views[name])
     return bd
 
 
-def kde(points, ks=None, weights=None, device=None, manifold=None) -> BallTreeDensity:
+def kde(points, ks=None, weights=None, device=None, manifold=None, tree_manifold=None) -> BallTreeDensity:
     """`kde!(points, ks)` / `kde!(points, ks, weights)` (reference src/KDE01.jl:34-84); with ks=None the
     automatic LOOCV bandwidth `kde!(points)` (src/KDE01.jl:3-27, GPU).
 
@@ -110,33 +113,45 @@ def kde(points, ks=None, weights=None, device=None, manifold=None) -> BallTreeDe
     a HIP ordinal = the GPU builder (csrc/treebuild.hip, bit-identical arrays) where the density fits it.
     manifold: only with ks=None -- the bandwidth search of a circular dimension wraps its differences (the tree is the
     Euclidean builder's).  With an explicit bandwidth there is no search to make circular: ValueError.
+    tree_manifold: the operators of tree construction, `kde!(points, ks, weights, addop, diffop)`: one 'euclid' / 'circular'
+    per dimension; a circular dimension's spread, quick-select test and bounding boxes use wrapped sums and differences
+    (include/kdehip.h section 4).  Separate from `manifold` on purpose; the reference's `kde!(points, addop, diffop)` is
+    `kde(points, manifold=m, tree_manifold=m)`.
     """
     if ks is None:
         if weights is not None:
             raise ValueError("kde!(points) with automatic bandwidth takes no weights")
         from .bandwidth import kde_auto
-        return kde_auto(points, device=0 if device is None else device, manifold=manifold)
+        return kde_auto(points, device=0 if device is None else device, manifold=manifold, tree_manifold=tree_manifold)
     if manifold is not None:
-        raise ValueError("kde(points, ks, manifold=...): an explicit bandwidth leaves nothing to search on the circle, and "
-                         "the tree builder is Euclidean")
+        raise ValueError("kde(points, ks, manifold=...): an explicit bandwidth leaves nothing to search on the circle; the "
+                         "tree builder's operators are tree_manifold=")
     if device is not None:
-        return kde_batch([(points, ks, weights)], device=device)[0]
+        return kde_batch([(points, ks, weights)], device=device, tree_manifold=tree_manifold)[0]
     D, N, flat, ks, w = _prepare(points, ks, weights)
+    tman = _tree_manifold_array(tree_manifold, D)
     bd = _empty_density(D, N)
     bt = bd.bt
-    _lib.check(_lib.lib.kdehip_make_density(
+    _lib.check(_lib.lib.kdehip_make_density_tree(
         D, N, ptr(flat, f64p), ptr(ks, f64p), ks.size, None if w is None else ptr(w, f64p),
         ptr(bt.centers, f64p), ptr(bt.ranges, f64p), ptr(bt.weights, f64p), ptr(bt.left_child, i64p),
         ptr(bt.right_child, i64p), ptr(bt.lowest_leaf, i64p), ptr(bt.highest_leaf, i64p),
         ptr(bt.permutation, i64p), ptr(bd.means, f64p), ptr(bd.bandwidth, f64p),
-        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p)))
+        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), None if tman is None else ptr(tman, u8p)))
+    bd.tree_manifold = tman
     return bd
 
 
-def kde_batch(items, device=0):
+def _tree_manifold_array(tree_manifold, ndims):
+    from .product import _manifold_array
+    return _manifold_array(tree_manifold, ndims)
+
+
+def kde_batch(items, device=0, tree_manifold=None):
     """Several `kde!(points, ks[, weights])` at once on the GPU (kdehip_make_densities_device: one workgroup per
     density).  items: (points, ks) or (points, ks, weights) tuples of ONE dimension count and ks length.  Densities
-    the device builder cannot hold (kdehip_make_density_device_supported) are built by the host builder instead."""
+    the device builder cannot hold (kdehip_make_density_device_supported) are built by the host builder instead.
+    tree_manifold: ONE value for all items (kdehip_make_densities_device_tree), as `kde` takes it."""
     import ctypes as C
     prepared = []
     for it in items:
@@ -145,11 +160,15 @@ def kde_batch(items, device=0):
         prepared.append(_prepare(points, ks, weights))
     out = [None] * len(prepared)
     groups = {}
+    tmans = {}
     for idx, (D, N, flat, ks, w) in enumerate(prepared):
+        if D not in tmans:
+            tmans[D] = _tree_manifold_array(tree_manifold, D)
         if N >= 2 and _lib.lib.kdehip_make_density_device_supported(D, N):
             groups.setdefault((D, ks.size), []).append(idx)
         else:
-            out[idx] = kde(np.asarray(items[idx][0]), items[idx][1], items[idx][2] if len(items[idx]) > 2 else None)
+            out[idx] = kde(np.asarray(items[idx][0]), items[idx][1], items[idx][2] if len(items[idx]) > 2 else None,
+                           tree_manifold=tree_manifold)
     for (D, nks), idxs in groups.items():
         for c0 in range(0, len(idxs), _lib.MAX_DENS):
             chunk = idxs[c0:c0 + _lib.MAX_DENS]
@@ -160,15 +179,18 @@ def kde_batch(items, device=0):
                 return (C.c_void_p * nb)(*[None if get(k) is None else get(k).ctypes.data for k in range(nb)])
             Ns = np.array([prepared[i][1] for i in chunk], dtype=np.int64)
             any_w = any(prepared[i][4] is not None for i in chunk)
-            _lib.check(_lib.lib.kdehip_make_densities_device(
+            tman = tmans[D]
+            _lib.check(_lib.lib.kdehip_make_densities_device_tree(
                 nb, D, ptr(Ns, i64p), arr(lambda k: prepared[chunk[k]][2]), arr(lambda k: prepared[chunk[k]][3]), nks,
                 arr(lambda k: prepared[chunk[k]][4]) if any_w else None,
                 arr(lambda k: dens[k].bt.centers), arr(lambda k: dens[k].bt.ranges), arr(lambda k: dens[k].bt.weights),
                 arr(lambda k: dens[k].bt.left_child), arr(lambda k: dens[k].bt.right_child),
                 arr(lambda k: dens[k].bt.lowest_leaf), arr(lambda k: dens[k].bt.highest_leaf),
                 arr(lambda k: dens[k].bt.permutation), arr(lambda k: dens[k].means), arr(lambda k: dens[k].bandwidth),
-                arr(lambda k: dens[k].bandwidthMin), arr(lambda k: dens[k].bandwidthMax), int(device)))
+                arr(lambda k: dens[k].bandwidthMin), arr(lambda k: dens[k].bandwidthMax), int(device),
+                None if tman is None else ptr(tman, u8p)))
             for k, i in enumerate(chunk):
+                dens[k].tree_manifold = tman
                 out[i] = dens[k]
     return out
 
@@ -189,6 +211,7 @@ def density_from_arrays(dims, num_points, means, bandwidth, weights, left_child,
     bd = BallTreeDensity()
     bd.bt = bt
     bd.multibandwidth = 0
+    bd.tree_manifold = None
     bd.means = np.ascontiguousarray(means, dtype=np.float64)
     bd.bandwidth = np.ascontiguousarray(bandwidth, dtype=np.float64)
     bd.bandwidthMin = bd.bandwidthMax = None

@@ -402,21 +402,39 @@ moment matching; pinned by the reference's own golden files) -- bit for bit with
 other weights the normalisation `weights ./ sum(weights)` (src/KDE01.jl:46) is a sequential sum in the library and a
 pairwise `@simd` sum in Julia: the total, hence every weight and moment-matched node, may differ in the last bit (which
 is why the override `enable!(trees=true)` installs hands only unit weights to the library).
+
+`tree_manifold`: `nothing`, or a vector of `:euclid` / `:circular` (or 0 / 1), one per dimension -- the operators of tree
+construction, `kde!(points, ks, weights, addop, diffop)`, as THIS library's enum (`kdehip_make_density_tree`, include/kdehip.h
+section 4: wrap to [-pi, pi) in most_spread_coord, select! and calcStatsBall!).  Nothing maps a caller's addop / diffop
+functions to it automatically: the overrides of `enable!()` keep sending non-Euclidean operators to the reference.
 """
-function kde!(points::AbstractMatrix{<:Real}, ks::Vector{Float64}, weights::Union{Nothing,Vector{Float64}}=nothing)
+function kde!(points::AbstractMatrix{<:Real}, ks::Vector{Float64}, weights::Union{Nothing,Vector{Float64}}=nothing;
+              tree_manifold::Union{Nothing,AbstractVector}=nothing)
   D, N = size(points)
   pts = Matrix{Float64}(points)
   weights === nothing || length(weights) == N || error("weights must have one entry per point")
   centers, ranges, means, bandwidth = zeros(2N * D), zeros(2N * D), zeros(2N * D), zeros(2N * D)
   bwmin, bwmax, w = zeros(N * D), zeros(N * D), zeros(2N)
   left, right, lowest, highest, perm = zeros(Int, 2N), zeros(Int, 2N), zeros(Int, 2N), zeros(Int, 2N), zeros(Int, 2N)
-  GC.@preserve pts ks weights begin
-    check(ccall((:kdehip_make_density, libkdehip), Cint,
-                (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-                 Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-                 Ptr{Float64}),
-                D, N, pts, ks, length(ks), weights === nothing ? C_NULL : pointer(weights), centers, ranges, w, left, right,
-                lowest, highest, perm, means, bandwidth, bwmin, bwmax))
+  if tree_manifold === nothing
+    GC.@preserve pts ks weights begin
+      check(ccall((:kdehip_make_density, libkdehip), Cint,
+                  (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}),
+                  D, N, pts, ks, length(ks), weights === nothing ? C_NULL : pointer(weights), centers, ranges, w, left, right,
+                  lowest, highest, perm, means, bandwidth, bwmin, bwmax))
+    end
+  else
+    tman = manifold_bytes(tree_manifold, D)
+    GC.@preserve pts ks weights tman begin
+      check(ccall((:kdehip_make_density_tree, libkdehip), Cint,
+                  (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Ptr{UInt8}),
+                  D, N, pts, ks, length(ks), weights === nothing ? C_NULL : pointer(weights), centers, ranges, w, left, right,
+                  lowest, highest, perm, means, bandwidth, bwmin, bwmax, tman))
+    end
   end
   return density_from_arrays(D, N, centers, ranges, w, left, right, lowest, highest, perm, means, bandwidth, bwmin, bwmax)
 end
@@ -703,22 +721,41 @@ end
 searched on the GPU while the library's pooled host builder makes the ball tree (topology, bounding boxes, weights and
 means do not depend on the bandwidth); the variances are filled in afterwards.  The arrays are those of
 `kde!(points, bw)` with the bandwidth found, bit for bit.
+
+`manifold` / `tree_manifold` (vectors of `:euclid` / `:circular`, or `nothing`): the bandwidth search's and the tree
+builder's operators as the library's enum (`kdehip_make_density_auto_tree`); the reference's `kde!(points, addop, diffop)`
+with circular operators of THIS semantic is both set to the same value.  Never chosen automatically.
 """
-function kde!(points::AbstractMatrix{Float64}; device::Int=0)
+function kde!(points::AbstractMatrix{Float64}; device::Int=0, manifold::Union{Nothing,AbstractVector}=nothing,
+              tree_manifold::Union{Nothing,AbstractVector}=nothing)
   D, N = size(points)
-  (N < 2 || D > 8) && return reference_kde_auto(points)   # (the library's limits: the reference path)
+  on_manifold = manifold !== nothing || tree_manifold !== nothing
+  (N < 2 || D > 8) && !on_manifold && return reference_kde_auto(points)   # (the library's limits: the reference path)
   bw = zeros(D)
   nev = Ref{Int32}(0)
   pts = Matrix{Float64}(points)
   centers, ranges, means, bandwidth = zeros(2N * D), zeros(2N * D), zeros(2N * D), zeros(2N * D)
   bwmin, bwmax, w = zeros(N * D), zeros(N * D), zeros(2N)
   left, right, lowest, highest, perm = zeros(Int, 2N), zeros(Int, 2N), zeros(Int, 2N), zeros(Int, 2N), zeros(Int, 2N)
-  check(ccall((:kdehip_make_density_auto, libkdehip), Cint,
-              (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-               Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-               Ptr{Float64}),
-              D, N, pts, bw, nev, device, centers, ranges, w, left, right, lowest, highest, perm, means, bandwidth, bwmin,
-              bwmax))
+  if !on_manifold
+    check(ccall((:kdehip_make_density_auto, libkdehip), Cint,
+                (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}),
+                D, N, pts, bw, nev, device, centers, ranges, w, left, right, lowest, highest, perm, means, bandwidth, bwmin,
+                bwmax))
+  else
+    man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+    tman = tree_manifold === nothing ? zeros(UInt8, D) : manifold_bytes(tree_manifold, D)
+    GC.@preserve man tman begin
+      check(ccall((:kdehip_make_density_auto_tree, libkdehip), Cint,
+                  (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Int32}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Ptr{UInt8}, Ptr{UInt8}),
+                  D, N, pts, bw, nev, device, centers, ranges, w, left, right, lowest, highest, perm, means, bandwidth, bwmin,
+                  bwmax, man, tman))
+    end
+  end
   return density_from_arrays(D, N, centers, ranges, w, left, right, lowest, highest, perm, means, bandwidth, bwmin, bwmax)
 end
 

@@ -231,23 +231,27 @@ class DeviceDensity:
         # the manifold it was built with (`from_device_points(manifold=)`, a circular `mul_device`), as the uint8 enum array,
         # or None.  A record only: `a * b`, `resample` and the summaries stay Euclidean -- pass `manifold=` where it is taken
         self.manifold = None
+        # the operators its tree was built with (`tree_manifold=`), likewise a record only; an uploaded density keeps its own
+        self.tree_manifold = getattr(tree, "tree_manifold", None) if _handle is None else None
 
     @classmethod
-    def from_device_points(cls, d_points, D, N, device=0, stream=None, manifold=None):
+    def from_device_points(cls, d_points, D, N, device=0, stream=None, manifold=None, tree_manifold=None):
         """`kde!(points)` (reference src/KDE01.jl:3-27) of a D x N column-major matrix that lives in HBM (a torch tensor or
         an address; `stream` = the stream that produced it): LOOCV bandwidth search on the device matrix, ball tree from one
         copy that comes down meanwhile, the density's block straight back up (kdehip_density_from_device_points).
-        `manifold`: the bandwidth search of a circular dimension wraps its differences (the tree stays Euclidean)."""
+        `manifold`: the bandwidth search of a circular dimension wraps its differences (the tree stays Euclidean);
+        `tree_manifold`: the tree builder's operators, as `kde(..., tree_manifold=)` (kdehip_density_from_device_points_tree)."""
         h = C.c_void_p()
         bw = np.empty(int(D))
         ne = C.c_int32(0)
         man = _manifold_array(manifold, int(D))
-        _lib.check(_lib.lib.kdehip_density_from_device_points_manifold(
+        tman = _manifold_array(tree_manifold, int(D))
+        _lib.check(_lib.lib.kdehip_density_from_device_points_tree(
             C.byref(h), ProductPlan._addr(d_points), int(D), int(N), int(device), ProductPlan._addr(stream), ptr(bw, f64p),
-            C.byref(ne), None if man is None else ptr(man, u8p)))
+            C.byref(ne), None if man is None else ptr(man, u8p), None if tman is None else ptr(tman, u8p)))
         out = cls(device=device, _handle=h)
         out.bw, out.nevals = bw, int(ne.value)
-        out.manifold = man
+        out.manifold, out.tree_manifold = man, tman
         return out
 
     def download(self) -> BallTreeDensity:
@@ -260,6 +264,7 @@ class DeviceDensity:
             self._h, ptr(bt.centers, f64p), ptr(bt.ranges, f64p), ptr(bt.weights, f64p), ptr(bt.left_child, i64p),
             ptr(bt.right_child, i64p), ptr(bt.lowest_leaf, i64p), ptr(bt.highest_leaf, i64p), ptr(bt.permutation, i64p),
             ptr(bd.means, f64p), ptr(bd.bandwidth, f64p), ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), None))
+        bd.tree_manifold = self.tree_manifold
         return bd
 
     def __mul__(self, other):
@@ -365,14 +370,16 @@ class DeviceDensity:
         self.close()
 
 
-def mul_device(trees, *, addEntropy=True, seed=None, manifold=None) -> DeviceDensity:
+def mul_device(trees, *, addEntropy=True, seed=None, manifold=None, tree_manifold=None) -> DeviceDensity:
     """`*(trees; addEntropy)` (reference src/MSGibbs01.jl:707-726) on `DeviceDensity` handles, result in HBM: product with
     Niter = 5 and Np = round(mean(Npts)), then `kde!(pGM)` -- the sample matrix never leaves the device
     (kdehip_mul_device).  Same numbers as `mul(host trees, seed=seed)`.
     `manifold`: the circular product (`prodAppxMSGibbsS_device(manifold=)`), then `from_device_points(manifold=)` on its
-    matrix (kdehip_mul_device_manifold); the result remembers it."""
+    matrix (kdehip_mul_device_manifold); the result remembers it.  `tree_manifold`: the operators of the result's tree
+    build, as `from_device_points(tree_manifold=)` (kdehip_mul_device_tree)."""
     trees = list(trees)
     man = _manifold_array(manifold, trees[0].dims)
+    tman = _manifold_array(tree_manifold, trees[0].dims)
     if seed is None:
         seed = int.from_bytes(os.urandom(8), "little")
     M = len(trees)
@@ -380,12 +387,13 @@ def mul_device(trees, *, addEntropy=True, seed=None, manifold=None) -> DeviceDen
     h = C.c_void_p()
     bw = np.empty(trees[0].dims)
     ne = C.c_int32(0)
-    _lib.check(_lib.lib.kdehip_mul_device_manifold(C.byref(h), M, arr, C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                                   int(bool(addEntropy)), ptr(bw, f64p), C.byref(ne),
-                                                   None if man is None else ptr(man, u8p)))
+    _lib.check(_lib.lib.kdehip_mul_device_tree(C.byref(h), M, arr, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                               int(bool(addEntropy)), ptr(bw, f64p), C.byref(ne),
+                                               None if man is None else ptr(man, u8p),
+                                               None if tman is None else ptr(tman, u8p)))
     out = DeviceDensity(device=trees[0].device, _handle=h)
     out.bw, out.nevals = bw, int(ne.value)
-    out.manifold = man
+    out.manifold, out.tree_manifold = man, tman
     return out
 
 
@@ -405,12 +413,14 @@ def _batch_manifolds(manifold, dims):
     return [_manifold_array(m, d) for m, d in zip(manifold, dims)]
 
 
-def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None):
+def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tree_manifold=None):
     """Many `*` in ONE call (kdehip_mul_device_batch): `products` = a list of lists of `DeviceDensity`; returns one
     `DeviceDensity` per product, each bit for bit what `mul_device(products[i], addEntropy=..., seed=seeds[i])` returns --
     batched sampler, the LOOCV searches of all results of one size in shared launches, trees built under them.
     `addEntropy`: one flag or one per product.  `manifold`: one for all products or one per product (None = Euclidean);
-    circular products are sampled one by one inside the call, their searches share launches (kdehip_mul_device_batch_manifold)."""
+    circular products are sampled one by one inside the call, their searches share launches (kdehip_mul_device_batch_manifold).
+    `tree_manifold`: the tree builders' operators, one for all products or one per product like `manifold`
+    (kdehip_mul_device_batch_tree); products with and without a circular tree may be mixed."""
     products = [list(p) for p in products]
     n = len(products)
     if n == 0:
@@ -430,15 +440,21 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None):
     for k, m in enumerate(mans):
         if m is not None:
             marr[k, :len(m)] = m
+    tmans = _batch_manifolds(tree_manifold, [p[0].dims if p else 0 for p in products])
+    tarr = np.zeros((n, _lib.MAX_DIMS), dtype=np.uint8)   # row k: the operators of product k's tree build
+    for k, m in enumerate(tmans):
+        if m is not None:
+            tarr[k, :len(m)] = m
     out = (C.c_void_p * n)()
     bw = np.zeros((n, _lib.MAX_DIMS))
     ne = np.zeros(n, dtype=np.int32)
-    _lib.check(_lib.lib.kdehip_mul_device_batch_manifold(n, items, ptr(marr, u8p), out, ptr(bw, f64p), ptr(ne, _lib.i32p)))
+    _lib.check(_lib.lib.kdehip_mul_device_batch_tree(n, items, ptr(marr, u8p), ptr(tarr, u8p), out, ptr(bw, f64p),
+                                                     ptr(ne, _lib.i32p)))
     res = []
     for k in range(n):
         d = DeviceDensity(device=products[k][0].device, _handle=C.c_void_p(out[k]))
         d.bw, d.nevals = bw[k, :d.dims].copy(), int(ne[k])
-        d.manifold = mans[k]
+        d.manifold, d.tree_manifold = mans[k], tmans[k]
         res.append(d)
     return res
 
