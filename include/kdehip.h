@@ -672,7 +672,7 @@ int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_devi
  * Products: besides kdehip_gibbs1_manifold (host trees, caller streams, the generic arithmetic), the resident entries take a
  * manifold -- kdehip_prod_philox_device_manifold, kdehip_prod_philox_resident_manifold (2c), kdehip_mul_device_manifold,
  * kdehip_mul_device_batch_manifold (2d) -- and run the sampler's circular fast mode; their _tree forms (2d) add the
- * builder's operators.  Still Euclidean only: kdehip_resample_device, kdehip_density_marginal_device, the summaries of 5c and
+ * builder's operators.  Drawing, resampling, marginals and the summaries take theirs in section 5e.  Still Euclidean only:
  * the Python mirror's `a * b`; kdehip_density_set_bandwidth needs no manifold (topology and means do not depend on the
  * bandwidth, and the moment matching is Euclidean in the reference). */
 int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out,
@@ -716,8 +716,8 @@ int kdehip_make_density_auto_tree(int64_t D, int64_t N, const double *points, do
  * that live in HBM (and, for getKDEMax / intersIntgAppxIS, on host densities uploaded for the call).  A density's points are
  * its leaf means (as in 5b); "original order" is getPoints order, through the permutation.  dims are 1-based here (0-based in
  * the Python mirror).  Only the Euclidean operators exist HERE: the reference's addop / diffop arguments of these functions
- * are not supported (their grids would have to be defined on the circle first, and marginal builds its tree with the
- * Euclidean operators); evaluation, log-likelihoods and the bandwidth search take a manifold in section 5d.
+ * are not part of THESE entries, which forward to the _manifold forms of section 5e with NULL; evaluation, log-likelihoods
+ * and the bandwidth search take a manifold in section 5d.
  *   marginal(p, dims)  = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims], getWeights(p)): size(bandwidth, 2) > 2N is false
  *                        for the flat arrays, so the bandwidth is that of ORIGINAL point 1; getBW returns sqrt(variance) and
  *                        kde! squares it again, so the marginal's variance is fl(sqrt(v))^2, not v.  The weights are
@@ -781,6 +781,76 @@ int kdehip_kde_max(const kdehip_density *p, int64_t Ngrid, double *out, double *
 int kdehip_inters_intg_appx_is(const kdehip_density *p, const kdehip_density *q, int64_t Ngrid, double *out, int device);
 int kdehip_inters_intg_appx_is_device(const kdehip_device_density *p, const kdehip_device_density *q, int64_t Ngrid,
                                       double *out);
+
+/* ---- (5e) circular dimensions in the summaries, marginal, sample and resample ----------------------------------------------
+ * The entries of 5c and 2f with the per-dimension enum of "manifolds" (KDEHIP_MANIFOLD_EUCLIDEAN / KDEHIP_MANIFOLD_CIRCULAR,
+ * ndims bytes or NULL).  The reference threads addop / diffop through getKDERange, getKDERangeLinspace, getKDEMax and
+ * intersIntgAppxIS (src/DualTree01.jl:512-618) and leaves getKDEMean / getKDEfit with a "TODO: update for on-manifold"; as with
+ * the sampler's circular mode the semantic here is this library's own, on the convention of 5d: wrap() (csrc/circ_wrap.hpp) to
+ * [-pi, pi), tangent space at a reference angle.  For a circular dimension k of a density with points x_j in original order
+ * the reference angle is a0 = x_1k (ORIGINAL point 1) and the tangent offsets are t_j = wrap(x_jk - a0).  pi and 2 pi are
+ * circ_wrap's constants; every operation below is rounded on its own.
+ *   getKDEMean         mu_k = wrap(a0 + s / N), s = the sequential left-to-right fp64 sum of the t_j in original order from
+ *                      +0.0; unweighted, as the reference's mean.  Euclidean dimensions keep the bits of 5c.  Bit for bit.
+ *   getKDEfit          the mean above; covariance (1/N) sum_j r_j r_j^T with r_jk = wrap(x_jk - mu_k) in a circular dimension
+ *                      and x_jk - mu_k otherwise, each entry a sequential sum in original order, then / N.
+ *   getKDERange(extend) lo_t = min_j t_j, hi_t = max_j t_j, dr = extend * (hi_t - lo_t), alo = a0 + lo_t, ahi = a0 + hi_t,
+ *                      range = (alo - dr, ahi + dr), left UNWRAPPED so that grid() stays a monotone linspace; if
+ *                      (ahi + dr) - (alo - dr) > 2 pi the range is (mid - pi, mid + pi) with mid = 0.5 * (alo + ahi), the
+ *                      midpoint of the unextended arc.  This is the arc through the data as seen from point 1, not the
+ *                      shortest arc.  Bit for bit.
+ *   grid values, getKDEMax  the 1-D marginal over [k] on grid(range) with every difference x - c_i wrapped before it is
+ *                      squared; otherwise exactly as 5c: same weights, variance fl(sqrt(v_1))^2, norm (a circular density keeps
+ *                      the Gaussian constant), leaf groups and exp.  argmax = wrap(x_k) of the first maximal k; d_values keeps
+ *                      its meaning (the values at the unwrapped grid points).
+ *   intersIntgAppxIS   D = 1, 2: the grids from p's circular range with extend 0.3, dx_d = x_1 - x_0, p and q evaluated by the
+ *                      kernels of kdehip_evaluate_manifold (every value bit for bit what that entry returns there), the sums
+ *                      of 5c.
+ *   marginal(p, dims)  the tree of the result is built with tree_manifold (nsel bytes: the caller passes the operators of the
+ *                      SELECTED dimensions, tree_manifold[dims]) by kdehip_make_density_tree; points, weights and the
+ *                      fl(sqrt(v))^2 bandwidth are those of 5c.
+ *   sample / rand      the Euclidean draw c + bw z of 2f, then wrap() in the circular dimensions: a circular coordinate is bit
+ *                      for bit circ_wrap of the value the Euclidean call returns; labels and Euclidean dimensions keep theirs.
+ *   resample           the wrapped draw, then kde!(pts, addop, diffop): kdehip_density_from_device_points_tree with `manifold`
+ *                      (the bandwidth search) and `tree_manifold` (the builder), without leaving HBM.
+ * Inputs need not lie in [-pi, pi).  fp64 only.  manifold == NULL or all zeros returns the bits of the entries of 5c / 2f
+ * (which forward here with NULL); a byte above 1 is KDEHIP_ERR_ARG, checked before any device is touched.  Not here: weighted
+ * circular means, a largest-gap range.
+ * The batches take the manifold per item as a mask (bit d = dimension d circular; a bit at or above the item's ndims is
+ * KDEHIP_ERR_ARG), as kdehip_eval_avg_logl_device_batch_manifold does.  Euclidean and circular items of any D may be mixed:
+ * items with a circular bit run the circular instantiation of each kernel, the others the launches of
+ * kdehip_summary_device_batch / kdehip_sample_device_batch; every item's result is bit for bit what it gets alone. */
+typedef struct kdehip_summary_manifold_item {
+  kdehip_summary_item item;
+  uint32_t circular_mask;
+  uint32_t reserved_;
+} kdehip_summary_manifold_item;
+int kdehip_summary_device_batch_manifold(int n, const kdehip_summary_manifold_item *items, void *stream);
+int kdehip_density_summary_manifold(const kdehip_device_density *p, const double *extend, int64_t Ngrid, double *range,
+                                    double *mean, double *cov, double *argmax, double *values,
+                                    const uint8_t *manifold /* ndims bytes or NULL */);
+int kdehip_kde_max_manifold(const kdehip_density *p, int64_t Ngrid, double *out, double *grid_values, int device,
+                            const uint8_t *manifold);
+int kdehip_inters_intg_appx_is_manifold(const kdehip_density *p, const kdehip_density *q, int64_t Ngrid, double *out,
+                                        int device, const uint8_t *manifold);
+int kdehip_inters_intg_appx_is_device_manifold(const kdehip_device_density *p, const kdehip_device_density *q, int64_t Ngrid,
+                                               double *out, const uint8_t *manifold);
+int kdehip_density_marginal_device_tree(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
+                                        const int32_t *dims, const uint8_t *tree_manifold /* nsel bytes or NULL */);
+int kdehip_sample_manifold(const kdehip_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset, const int64_t *ind_in,
+                           double *pts, int64_t *ind, int device, const uint8_t *manifold);
+int kdehip_sample_device_manifold(kdehip_device_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
+                                  const int64_t *d_ind_in, double *d_pts, int64_t *d_ind, void *stream,
+                                  const uint8_t *manifold);
+typedef struct kdehip_sample_manifold_item {
+  kdehip_sample_item item;
+  uint32_t circular_mask;
+  uint32_t reserved_;
+} kdehip_sample_manifold_item;
+int kdehip_sample_device_batch_manifold(int n, const kdehip_sample_manifold_item *items, void *stream);
+int kdehip_resample_device_manifold(kdehip_device_density **out, kdehip_device_density *p, int64_t Np, uint64_t seed,
+                                    double *bw_out, int32_t *nevals, const uint8_t *manifold /* ndims bytes or NULL */,
+                                    const uint8_t *tree_manifold /* ndims bytes or NULL */);
 
 #ifdef __cplusplus
 }

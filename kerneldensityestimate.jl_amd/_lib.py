@@ -50,6 +50,11 @@ class CSampleItem(C.Structure):
                 ("d_ind_in", C.c_void_p), ("d_pts", C.c_void_p), ("d_ind", C.c_void_p)]
 
 
+class CSampleManifoldItem(C.Structure):
+    """struct kdehip_sample_manifold_item"""
+    _fields_ = [("item", CSampleItem), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class CLoglItem(C.Structure):
     """struct kdehip_logl_item"""
     _fields_ = [("bd", C.c_void_p), ("at", C.c_void_p), ("leave_one_out", C.c_int32), ("reserved_", C.c_int32)]
@@ -64,6 +69,11 @@ class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
                 ("d_mean", C.c_void_p), ("d_cov", C.c_void_p), ("d_argmax", C.c_void_p), ("d_values", C.c_void_p)]
+
+
+class CSummaryManifoldItem(C.Structure):
+    """struct kdehip_summary_manifold_item"""
+    _fields_ = [("item", CSummaryItem), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
 class CProductInfo(C.Structure):
@@ -200,6 +210,20 @@ SIGNATURES = {
     "kdehip_mul_device_tree": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_uint64, C.c_int, f64p,
                                          i32p, u8p, u8p]),
     "kdehip_mul_device_batch_tree": (C.c_int, [C.c_int, C.POINTER(CMulItem), u8p, u8p, C.POINTER(C.c_void_p), f64p, i32p]),
+    "kdehip_summary_device_batch_manifold": (C.c_int, [C.c_int, C.POINTER(CSummaryManifoldItem), C.c_void_p]),
+    "kdehip_density_summary_manifold": (C.c_int, [C.c_void_p, f64p, C.c_int64, f64p, f64p, f64p, f64p, f64p, u8p]),
+    "kdehip_kde_max_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, f64p, f64p, C.c_int, u8p]),
+    "kdehip_inters_intg_appx_is_manifold": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int64, f64p, C.c_int,
+                                                      u8p]),
+    "kdehip_inters_intg_appx_is_device_manifold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, f64p, u8p]),
+    "kdehip_density_marginal_device_tree": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, i32p, u8p]),
+    "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
+                                         u8p]),
+    "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_sample_device_batch_manifold": (C.c_int, [C.c_int, C.POINTER(CSampleManifoldItem), C.c_void_p]),
+    "kdehip_resample_device_manifold": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_uint64, f64p, i32p,
+                                                  u8p, u8p]),
 }
 
 

@@ -570,9 +570,17 @@ extern "C" int kdehip_density_from_device_points_tree(kdehip_device_density **ou
 // kdehip_density_from_device_points without the bandwidth search), the block back up.  The sqrt of getBW is the host's.
 extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
                                               const int32_t *dims) {
+  return kdehip_density_marginal_device_tree(out, p, nsel, dims, nullptr);
+}
+
+// ... with the operators of tree_manifold (the nsel selected dimensions') in the builder (section 5e)
+extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
+                                                   const int32_t *dims, const uint8_t *tree_manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (nsel < 1 || nsel > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_ARG, "marginal: nsel outside 1..KDEHIP_MAX_DIMS");
+  const int trc = tree_manifold_arg(tree_manifold, nsel);
+  if (trc != KDEHIP_OK) return trc;
   if (!dims) return set_error(KDEHIP_ERR_ARG, "marginal: null dims");
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
   const int64_t N = p->N;
@@ -614,8 +622,8 @@ extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const
   h->device = p->device; h->N = N; h->D = nsel; h->Lown = nlevels_for(N);
   KDEHIP_CHECK(alloc_mirror(h, mirror_layout(h)));
   const kdehip_device_density::Mirror &m = h->m;
-  rc = kdehip_make_density(nsel, N, blk, ks, nsel, blk + N * nsel, m.centers, m.ranges, m.weights, m.left, m.right, m.lowest,
-                           m.highest, m.perm, m.means, m.bandwidth, m.bwmin, m.bwmax);
+  rc = kdehip_make_density_tree(nsel, N, blk, ks, nsel, blk + N * nsel, m.centers, m.ranges, m.weights, m.left, m.right,
+                                m.lowest, m.highest, m.perm, m.means, m.bandwidth, m.bwmin, m.bwmax, tree_manifold);
   if (rc != KDEHIP_OK) return rc;
   for (int s = 0; s < nsel; ++s) h->bw[s] = ks[s];
   h->built = true;

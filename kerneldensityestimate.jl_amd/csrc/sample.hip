@@ -8,6 +8,8 @@
 // in Box-Muller pairs; the points of a workgroup's 256 samples are staged in LDS and written out as one contiguous block.
 // The host entry (kdehip_sample) forms the same C on the host -- the same sequence of IEEE additions and divisions, so the
 // same bits -- and uploads it with the leaves; every entry point then runs the same draw kernel.
+// On a manifold (section 5e) the drawn coordinate of a circular dimension is wrapped on its way to the staging tile:
+// circ_wrap of the very value the Euclidean call stores; labels and the other dimensions are untouched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,9 +23,11 @@
 
 #include "device_density.hpp"
 #include "call_block.hpp"
+#include "circ_wrap.hpp"
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "philox.hpp"
+#include "tree_manifold.hpp"
 
 using namespace kdehip;
 
@@ -48,6 +52,7 @@ struct SampleItem {
   const int64_t *ind_in;  // NULL = draw the labels
   double *pts;
   int64_t *ind;
+  uint32_t circ;  // bit d: dimension d is circular, its coordinate is stored wrapped
 };
 
 // the table of one density: weights / permutation from the leaves (tree order), outputs in original order
@@ -180,7 +185,10 @@ __device__ __forceinline__ void draw_tile(const SampleItem &it, const double *cd
       const int64_t k = it.inv[lab];
       const double *m = it.means + k * D, *v = it.var + k * D;
 #pragma unroll
-      for (int d = 0; d < D; ++d) stage[t * D + d] = __dadd_rn(m[d], __dmul_rn(__dsqrt_rn(v[d]), n[d]));
+      for (int d = 0; d < D; ++d) {
+        const double x = __dadd_rn(m[d], __dmul_rn(__dsqrt_rn(v[d]), n[d]));
+        stage[t * D + d] = ((it.circ >> d) & 1u) ? circ_wrap(x) : x;
+      }
     } else {
 #pragma unroll
       for (int d = 0; d < D; ++d) stage[t * D + d] = __builtin_nan("");
@@ -312,22 +320,38 @@ int ensure_table(kdehip_device_density *h) {
 }
 
 SampleItem item_of(const kdehip_device_density *h, int64_t Npts, uint64_t seed, int64_t offset, const int64_t *ind_in,
-                   double *pts, int64_t *ind) {
+                   double *pts, int64_t *ind, uint32_t circ) {
   const CdfLayout cl(h->N);
   const unsigned char *b = static_cast<const unsigned char *>(h->d_cdf);
   return SampleItem{reinterpret_cast<const double *>(b), reinterpret_cast<const int32_t *>(b + cl.o_inv),
-                    h->means + h->N * h->D, h->bandwidth + h->N * h->D, h->N, Npts, seed, offset, ind_in, pts, ind};
+                    h->means + h->N * h->D, h->bandwidth + h->N * h->D, h->N, Npts, seed, offset, ind_in, pts, ind, circ};
 }
 
 bool weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }
+
+// the circular bits of a draw's manifold (a bad D is the entry's own refusal)
+int sample_mask(const uint8_t *manifold, int64_t D, uint32_t *circ) {
+  unsigned m = 0;
+  KDEHIP_CHECK_RC(manifold_mask(manifold, D, &m));
+  *circ = m;
+  return KDEHIP_OK;
+}
 
 }  // namespace
 
 extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
                              const int64_t *ind_in, double *pts, int64_t *ind, int device) {
+  return kdehip_sample_manifold(p, Npts, seed, sample_offset, ind_in, pts, ind, device, nullptr);
+}
+
+extern "C" int kdehip_sample_manifold(const kdehip_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
+                                      const int64_t *ind_in, double *pts, int64_t *ind, int device,
+                                      const uint8_t *manifold) {
   // every check that needs no device comes first
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
   if (Npts < 0) return set_error(KDEHIP_ERR_ARG, "sample: Npts < 0");
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(sample_mask(manifold, p->ndim, &circ));
   if (Npts == 0) return KDEHIP_OK;
   const int64_t N = p->npts, D = p->ndim;
   if (D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims above KDEHIP_MAX_DIMS");
@@ -381,7 +405,7 @@ extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t see
   const SampleItem it{reinterpret_cast<const double *>(b), reinterpret_cast<const int32_t *>(b + o_inv),
                       reinterpret_cast<const double *>(b + o_m), reinterpret_cast<const double *>(b + o_v), N, Npts, seed,
                       sample_offset, ind_in ? reinterpret_cast<const int64_t *>(b + o_in) : nullptr,
-                      reinterpret_cast<double *>(b + o_pts), reinterpret_cast<int64_t *>(b + o_ind)};
+                      reinterpret_cast<double *>(b + o_pts), reinterpret_cast<int64_t *>(b + o_ind), circ};
   rc = launch_draw(static_cast<int>(D), it, st);
   if (rc != KDEHIP_OK) return rc;
   KDEHIP_CHECK(hipMemcpyAsync(pts, b + o_pts, sizeof(double) * Npts * D, hipMemcpyDeviceToHost, st));
@@ -392,8 +416,16 @@ extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t see
 
 extern "C" int kdehip_sample_device(kdehip_device_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
                                     const int64_t *d_ind_in, double *d_pts, int64_t *d_ind, void *stream) {
+  return kdehip_sample_device_manifold(p, Npts, seed, sample_offset, d_ind_in, d_pts, d_ind, stream, nullptr);
+}
+
+extern "C" int kdehip_sample_device_manifold(kdehip_device_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
+                                             const int64_t *d_ind_in, double *d_pts, int64_t *d_ind, void *stream,
+                                             const uint8_t *manifold) {
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
   if (Npts < 0) return set_error(KDEHIP_ERR_ARG, "sample: Npts < 0");
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(sample_mask(manifold, p->D, &circ));
   if (Npts == 0) return KDEHIP_OK;
   if (p->D < 1 || p->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   if (!d_pts || !d_ind) return set_error(KDEHIP_ERR_ARG, "null output buffer");
@@ -401,17 +433,23 @@ extern "C" int kdehip_sample_device(kdehip_device_density *p, int64_t Npts, uint
   int rc = guard.enter(p->device);
   if (rc == KDEHIP_OK) rc = ensure_table(p);
   if (rc != KDEHIP_OK) return rc;
-  return launch_draw(p->D, item_of(p, Npts, seed, sample_offset, d_ind_in, d_pts, d_ind), static_cast<hipStream_t>(stream));
+  return launch_draw(p->D, item_of(p, Npts, seed, sample_offset, d_ind_in, d_pts, d_ind, circ),
+                     static_cast<hipStream_t>(stream));
 }
 
-extern "C" int kdehip_sample_device_batch(int n, const kdehip_sample_item *items, void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "sample batch: bad item list");
+namespace {
+
+// the batch over items of either struct: item(i) = the kdehip_sample_item, mask(i) = its circular bits
+template <typename Item, typename Mask>
+int sample_batch(int n, Item item, Mask mask, void *stream) {
   int device = -1;
   std::vector<kdehip_device_density *> hs;
   for (int i = 0; i < n; ++i) {
-    const kdehip_sample_item &it = items[i];
+    const kdehip_sample_item &it = item(i);
     if (!it.density) return set_error(KDEHIP_ERR_ARG, "sample batch: null density");
     if (it.Npts < 0) return set_error(KDEHIP_ERR_ARG, "sample batch: Npts < 0");
+    if (it.density->D >= 1 && it.density->D <= KDEHIP_MAX_DIMS && (mask(i) >> it.density->D))
+      return set_error(KDEHIP_ERR_ARG, "sample batch: a circular bit at or above the item's ndims");
     if (it.Npts == 0) continue;
     if (it.density->D < 1 || it.density->D > KDEHIP_MAX_DIMS)
       return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
@@ -446,9 +484,9 @@ extern "C" int kdehip_sample_device_batch(int n, const kdehip_sample_item *items
     std::vector<SampleItem> its;
     std::vector<int32_t> first(1, 0);
     for (int i = 0; i < n; ++i) {
-      const kdehip_sample_item &it = items[i];
+      const kdehip_sample_item &it = item(i);
       if (it.Npts == 0 || it.density->D != D) continue;
-      its.push_back(item_of(it.density, it.Npts, it.seed, it.sample_offset, it.d_ind_in, it.d_pts, it.d_ind));
+      its.push_back(item_of(it.density, it.Npts, it.seed, it.sample_offset, it.d_ind_in, it.d_pts, it.d_ind, mask(i)));
       const int64_t nb = static_cast<int64_t>(first.back()) + blocks_for(it.Npts);
       if (nb > INT32_MAX) return set_error(KDEHIP_ERR_UNSUPPORTED, "sample batch: too many workgroups");
       first.push_back(static_cast<int32_t>(nb));
@@ -470,13 +508,36 @@ extern "C" int kdehip_sample_device_batch(int n, const kdehip_sample_item *items
   return KDEHIP_OK;
 }
 
+}  // namespace
+
+extern "C" int kdehip_sample_device_batch(int n, const kdehip_sample_item *items, void *stream) {
+  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "sample batch: bad item list");
+  return sample_batch(n, [&](int i) -> const kdehip_sample_item & { return items[i]; }, [](int) { return 0u; }, stream);
+}
+
+extern "C" int kdehip_sample_device_batch_manifold(int n, const kdehip_sample_manifold_item *items, void *stream) {
+  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "sample batch: bad item list");
+  return sample_batch(n, [&](int i) -> const kdehip_sample_item & { return items[i].item; },
+                      [&](int i) { return items[i].circular_mask; }, stream);
+}
+
 extern "C" int kdehip_resample_device(kdehip_device_density **out, kdehip_device_density *p, int64_t Np, uint64_t seed,
                                       double *bw_out, int32_t *nevals) {
+  return kdehip_resample_device_manifold(out, p, Np, seed, bw_out, nevals, nullptr, nullptr);
+}
+
+// (manifold: the draw is wrapped and the bandwidth search takes circular differences; tree_manifold: the builder's operators)
+extern "C" int kdehip_resample_device_manifold(kdehip_device_density **out, kdehip_device_density *p, int64_t Np,
+                                               uint64_t seed, double *bw_out, int32_t *nevals, const uint8_t *manifold,
+                                               const uint8_t *tree_manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
   if (Np <= 0) Np = p->N;
   if (Np < 2) return set_error(KDEHIP_ERR_ARG, "resample: kde!(points) needs at least two points");
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(sample_mask(manifold, p->D, &circ));
+  KDEHIP_CHECK_RC(tree_manifold_mask(tree_manifold, p->D < KDEHIP_MAX_DIMS ? p->D : KDEHIP_MAX_DIMS, nullptr));
   DeviceGuard guard;
   int rc = guard.enter(p->device);
   if (rc != KDEHIP_OK) return rc;
@@ -488,7 +549,7 @@ extern "C" int kdehip_resample_device(kdehip_device_density **out, kdehip_device
   sc.touch(cs);
   double *d_pts = reinterpret_cast<double *>(sc.dev());
   int64_t *d_ind = reinterpret_cast<int64_t *>(sc.dev() + o_ind);
-  rc = kdehip_sample_device(p, Np, seed, 0, nullptr, d_pts, d_ind, cs);
+  rc = kdehip_sample_device_manifold(p, Np, seed, 0, nullptr, d_pts, d_ind, cs, manifold);
   if (rc != KDEHIP_OK) return rc;
-  return kdehip_density_from_device_points(out, d_pts, D, Np, p->device, cs, bw_out, nevals);
+  return kdehip_density_from_device_points_tree(out, d_pts, D, Np, p->device, cs, bw_out, nevals, manifold, tree_manifold);
 }

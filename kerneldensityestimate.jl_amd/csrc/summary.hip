@@ -13,16 +13,22 @@
 //   grid_finish_kernel      one workgroup per (item, dimension): the group sums in order, / norm, and the first index of the
 //                           maximum (a NaN wins, as Julia's maximum / isequal decide): wave shuffles, then LDS.
 // The leaf groups depend on the item's (N, Ngrid) alone, never on the batch: a single call and any batch give the same bits.
+// Circular dimensions (section 5e): every kernel has a compile-time CIRC instantiation -- the tangent offsets
+// wrap(x - a0) at original point 1's angle for the range and the mean, wrapped residuals for the covariance, wrapped
+// differences on the grid, the wrapped argmax.  Items with a circular bit run it, all others the plain one (the run keeps
+// its Euclidean items first): a Euclidean item runs the code it always ran.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device_density.hpp"
 #include "call_block.hpp"
+#include "circ_wrap.hpp"
 #include "entry_helpers.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
@@ -48,7 +54,10 @@ struct SumItem {
   double norm0;                  // sqrt(2 pi) as gauss_norm's libm rounds (2 pi)^(1/2)
   int64_t N, Ngrid, chunks_per_group;
   int32_t D, ngroups, gblocks, grid;  // grid: the grid kernels run for this item
+  uint32_t circ;                 // bit k: dimension k is circular (section 5e); such an item runs the CIRC instantiations
 };
+
+constexpr double kPi = 3.141592653589793238462643383279, kTwoPi = 6.283185307179586476925286766559;  // circ_wrap's
 
 // x_k of the grid over [lo, hi]: lo + k h with h = (hi - lo) / (Ngrid - 1), the last point hi; every operation rounded
 // on its own (the build compiles with -ffp-contract=off)
@@ -73,19 +82,33 @@ __device__ __forceinline__ bool better(double va, int ka, double vb, int kb) {
 __device__ __forceinline__ double nan_min(double a, double b) { return (a != a) ? a : (b != b) ? b : (b < a ? b : a); }
 __device__ __forceinline__ double nan_max(double a, double b) { return (a != a) ? a : (b != b) ? b : (b > a ? b : a); }
 
+template <bool CIRC>
 __global__ __launch_bounds__(kSumThreads) void summary_moments_kernel(const SumItem *__restrict__ items) {
   __shared__ double sRow[KDEHIP_MAX_DIMS + 1][kSumThreads + 1];  // (+1: the lanes of a sequential walk hit distinct banks)
   __shared__ double sMean[KDEHIP_MAX_DIMS];
+  __shared__ double sA0[KDEHIP_MAX_DIMS];  // CIRC: the reference angle a0 = original point 1 (NaN if no leaf claims it)
   const SumItem it = items[blockIdx.x];
   const int D = it.D;
   const int64_t N = it.N;
   const int tid = static_cast<int>(threadIdx.x);
   double *st = it.stats;
   if (tid < D) st[2 * D + tid] = NAN;  // (stays NaN if no leaf claims original point 1)
+  if constexpr (CIRC)
+    if (tid < D) sA0[tid] = NAN;
   __syncthreads();
   for (int64_t i = tid; i < N; i += kSumThreads)
     if (it.perm[i] == 1)
-      for (int k = 0; k < D; ++k) st[2 * D + k] = it.bw[i * D + k];
+      for (int k = 0; k < D; ++k) {
+        st[2 * D + k] = it.bw[i * D + k];
+        if constexpr (CIRC) sA0[k] = it.means[i * D + k];
+      }
+  if constexpr (CIRC) __syncthreads();
+  // (CIRC) x of a circular dimension d as its tangent offset at a0
+  auto offset = [&](double x, int d) {
+    if constexpr (CIRC)
+      if ((it.circ >> d) & 1u) return circ_wrap(x - sA0[d]);
+    return x;
+  };
   // 1. per dimension min and max, and the weight total: straight from the leaves in ONE pass (min / max are exact in any
   //    order; the total is a fixed tree -- lane t sums leaves t, t + 256, ... in order, then the lanes pairwise in LDS)
   double lo[KDEHIP_MAX_DIMS], hi[KDEHIP_MAX_DIMS], wsum = 0.0;
@@ -95,7 +118,7 @@ __global__ __launch_bounds__(kSumThreads) void summary_moments_kernel(const SumI
 #pragma unroll
     for (int d = 0; d < KDEHIP_MAX_DIMS; ++d) {
       if (d < D) {
-        const double x = it.means[i * D + d];
+        const double x = offset(it.means[i * D + d], d);
         lo[d] = nan_min(lo[d], x);
         hi[d] = nan_max(hi[d], x);
       }
@@ -120,7 +143,19 @@ __global__ __launch_bounds__(kSumThreads) void summary_moments_kernel(const SumI
       const int k = d / 2;
       const double a = sRow[0][0], b = sRow[1][0];
       const double dr = it.extend * (b - a);
-      const double rlo = a - dr, rhi = b + dr;
+      double rlo = a - dr, rhi = b + dr;
+      if constexpr (CIRC) {
+        if ((it.circ >> k) & 1u) {  // the arc (a0 + lo_t, a0 + hi_t), extended, unwrapped; at most one turn
+          const double alo = sA0[k] + a, ahi = sA0[k] + b;
+          rlo = alo - dr;
+          rhi = ahi + dr;
+          if (rhi - rlo > kTwoPi) {
+            const double mid = 0.5 * (alo + ahi);
+            rlo = mid - kPi;
+            rhi = mid + kPi;
+          }
+        }
+      }
       st[k] = rlo;
       st[D + k] = rhi;
       if (it.range) { it.range[k] = rlo; it.range[D + k] = rhi; }
@@ -143,21 +178,37 @@ __global__ __launch_bounds__(kSumThreads) void summary_moments_kernel(const SumI
     const int64_t o = it.perm[i] - 1;
     if (o >= 0 && o < N) it.orig[f * N + o] = it.means[i * D + f];  // (an uploaded density's permutation is the caller's)
   }
-  auto stage = [&](int64_t c0, int cnt) {
-    __syncthreads();  // the previous chunk is consumed; (first call) the scatter is complete
+  // (CIRC: the wraps are done HERE, one point per lane, not in the one-lane walks below -- the same operations on the same
+  // values, so the same bits: residual = false stages the tangent offsets, residual = true the residuals x - mu, wrapped in
+  // a circular dimension)
+  auto stage = [&](int64_t c0, int cnt, bool residual) {
+    __syncthreads();  // the previous chunk is consumed; (first call) the scatter is complete; (residual) sMean is published
     if (tid < cnt)
-      for (int f = 0; f < D; ++f) sRow[f][tid] = it.orig[f * N + c0 + tid];
+      for (int f = 0; f < D; ++f) {
+        double x = it.orig[f * N + c0 + tid];
+        if constexpr (CIRC) {
+          if (residual) {
+            x -= sMean[f];
+            if ((it.circ >> f) & 1u) x = circ_wrap(x);
+          } else {
+            x = offset(x, f);
+          }
+        }
+        sRow[f][tid] = x;
+      }
     __syncthreads();
   };
   double s = 0.0;
   for (int64_t c0 = 0; c0 < N; c0 += kSumThreads) {
     const int cnt = static_cast<int>(N - c0 < kSumThreads ? N - c0 : kSumThreads);
-    stage(c0, cnt);
+    stage(c0, cnt, false);
     if (tid < D)
       for (int j = 0; j < cnt; ++j) s += sRow[tid][j];
   }
   if (tid < D) {
-    const double mu = s / static_cast<double>(N);
+    double mu = s / static_cast<double>(N);
+    if constexpr (CIRC)
+      if ((it.circ >> tid) & 1u) mu = circ_wrap(sA0[tid] + mu);
     sMean[tid] = mu;
     if (it.mean) it.mean[tid] = mu;
   }
@@ -172,10 +223,14 @@ __global__ __launch_bounds__(kSumThreads) void summary_moments_kernel(const SumI
   s = 0.0;
   for (int64_t c0 = 0; c0 < N; c0 += kSumThreads) {
     const int cnt = static_cast<int>(N - c0 < kSumThreads ? N - c0 : kSumThreads);
-    stage(c0, cnt);  // (its first barrier also publishes sMean)
+    stage(c0, cnt, true);  // (its first barrier also publishes sMean)
     if (pair) {
-      const double ma = sMean[a], mb = sMean[b];
-      for (int j = 0; j < cnt; ++j) s += (sRow[a][j] - ma) * (sRow[b][j] - mb);
+      if constexpr (CIRC) {
+        for (int j = 0; j < cnt; ++j) s += sRow[a][j] * sRow[b][j];
+      } else {
+        const double ma = sMean[a], mb = sMean[b];
+        for (int j = 0; j < cnt; ++j) s += (sRow[a][j] - ma) * (sRow[b][j] - mb);
+      }
     }
   }
   if (pair) {
@@ -186,6 +241,7 @@ __global__ __launch_bounds__(kSumThreads) void summary_moments_kernel(const SumI
 }
 
 // item i owns blocks [first[i], first[i+1]): D x ngroups x gblocks, dimension-major, then leaf group, then grid block
+template <bool CIRC>
 __global__ __launch_bounds__(kGridThreads) void grid_partial_kernel(const SumItem *__restrict__ items,
                                                                     const int32_t *__restrict__ first, int n) {
   __shared__ double sM[2][kGridChunk], sW[2][kGridChunk];
@@ -207,6 +263,7 @@ __global__ __launch_bounds__(kGridThreads) void grid_partial_kernel(const SumIte
   const double sd = sqrt(st[2 * D + d]);
   const double nhib = -0.5 / (sd * sd);  // the marginal's variance: getBW's sqrt, squared again by kde!
   const double S = st[3 * D];
+  const bool wrapd = CIRC && ((it.circ >> d) & 1u);
   const int64_t nchunks = (N + kGridChunk - 1) / kGridChunk;
   const int64_t c_begin = grp * it.chunks_per_group;
   int64_t c_end = c_begin + it.chunks_per_group;
@@ -227,10 +284,18 @@ __global__ __launch_bounds__(kGridThreads) void grid_partial_kernel(const SumIte
     const int64_t i0 = c * kGridChunk;
     const int cnt = static_cast<int>((N - i0 < kGridChunk) ? (N - i0) : kGridChunk);
     double sum = 0.0;
-    for (int j = 0; j < cnt; ++j) {
-      const double dd = x - sM[buf][j];
-      const double acc = (dd * dd) * nhib;
-      sum += sW[buf][j] * exp_nonpos(acc, sExpTab);  // acc <= 0
+    if (CIRC && wrapd) {  // (block-uniform) the difference on the circle, then exactly the loop below
+      for (int j = 0; j < cnt; ++j) {
+        const double dd = circ_wrap(x - sM[buf][j]);
+        const double acc = (dd * dd) * nhib;
+        sum += sW[buf][j] * exp_nonpos(acc, sExpTab);
+      }
+    } else {
+      for (int j = 0; j < cnt; ++j) {
+        const double dd = x - sM[buf][j];
+        const double acc = (dd * dd) * nhib;
+        sum += sW[buf][j] * exp_nonpos(acc, sExpTab);  // acc <= 0
+      }
     }
     total += sum;
   }
@@ -238,6 +303,7 @@ __global__ __launch_bounds__(kGridThreads) void grid_partial_kernel(const SumIte
 }
 
 // item i owns blocks [first[i], first[i+1]): one per dimension
+template <bool CIRC>
 __global__ __launch_bounds__(kGridThreads) void grid_finish_kernel(const SumItem *__restrict__ items,
                                                                    const int32_t *__restrict__ first, int n) {
   constexpr int kWaves = kGridThreads / 64;
@@ -272,7 +338,12 @@ __global__ __launch_bounds__(kGridThreads) void grid_finish_kernel(const SumItem
   if (threadIdx.x == 0) {
     for (int w = 1; w < kWaves; ++w)
       if (better(sV[w], sK[w], bv, bk)) { bv = sV[w]; bk = sK[w]; }
-    if (it.argmax && bk >= 0) it.argmax[d] = grid_point(lo, hi, Ng, bk);
+    if (it.argmax && bk >= 0) {
+      double x = grid_point(lo, hi, Ng, bk);
+      if constexpr (CIRC)
+        if ((it.circ >> d) & 1u) x = circ_wrap(x);  // (the grid itself stays unwrapped: a monotone linspace)
+      it.argmax[d] = x;
+    }
   }
 }
 
@@ -320,8 +391,9 @@ __global__ __launch_bounds__(kSumThreads) void inters_reduce_kernel(const double
 
 // The blocks of one call: ONE device block [descriptors | first[] of the two grid kernels | caller's extra | per item:
 // original-order rows, stats, partial sums] and ONE pinned image of everything up to the extra, which goes up in one copy.
-// Protocol: fill `items` (densities' pointers, sizes, extend, outputs) -> alloc(extra bytes) -> enqueue(stream) -> wait()
-// (blocking calls: the extra comes back to host_extra()) or defer(device) (enqueue-only calls).
+// Protocol: fill `items` (densities' pointers, sizes, extend, outputs, circ; the Euclidean items first) -> alloc(extra bytes)
+// -> enqueue(stream) -> wait() (blocking calls: the extra comes back to host_extra()) or defer(device) (enqueue-only calls).
+// The Euclidean items [0, ne) and the circular ones [ne, n) each get their own launches and their own first[] arrays.
 class SumRun {
  public:
   std::vector<SumItem> items;
@@ -346,7 +418,7 @@ class SumRun {
     if (pblocks > INT32_MAX || n > 65535) return set_error(KDEHIP_ERR_UNSUPPORTED, "summary too large for one launch");
     Carve c;
     o_items_ = c.take(sizeof(SumItem) * n);
-    o_first_ = c.take(sizeof(int32_t) * 2 * (n + 1));
+    o_first_ = c.take(sizeof(int32_t) * 2 * (n + 2));
     o_extra_ = c.take(extra);
     extra_ = extra;
     scratch_.resize(n);
@@ -369,25 +441,42 @@ class SumRun {
 
   int enqueue(hipStream_t st) {
     const size_t n = items.size();
+    size_t ne = 0;
+    while (ne < n && items[ne].circ == 0) ++ne;
+    for (size_t k = ne; k < n; ++k)
+      if (items[k].circ == 0) return set_error(KDEHIP_ERR_ARG, "summary: Euclidean items come first");  // (internal)
     unsigned char *h = blk_.host();
-    int32_t *pfirst = reinterpret_cast<int32_t *>(h + o_first_), *ffirst = pfirst + (n + 1);
-    pfirst[0] = ffirst[0] = 0;
-    for (size_t k = 0; k < n; ++k) {
-      const SumItem &it = items[k];
-      pfirst[k + 1] = pfirst[k] + it.D * it.ngroups * it.gblocks;
-      ffirst[k + 1] = ffirst[k] + (it.grid ? it.D : 0);
-    }
+    // [Euclidean partial first (ne + 1) | circular partial first (n - ne + 1) | the same two for the finish kernel]
+    int32_t *pfirst = reinterpret_cast<int32_t *>(h + o_first_), *ffirst = pfirst + (n + 2);
+    const auto fill = [&](size_t k0, size_t k1, int32_t *pf, int32_t *ff) {
+      pf[0] = ff[0] = 0;
+      for (size_t k = k0; k < k1; ++k) {
+        const SumItem &it = items[k];
+        pf[k - k0 + 1] = pf[k - k0] + it.D * it.ngroups * it.gblocks;
+        ff[k - k0 + 1] = ff[k - k0] + (it.grid ? it.D : 0);
+      }
+    };
+    fill(0, ne, pfirst, ffirst);
+    fill(ne, n, pfirst + ne + 1, ffirst + ne + 1);
     if (n) std::memcpy(h + o_items_, items.data(), sizeof(SumItem) * n);
     KDEHIP_CHECK(blk_.upload(o_extra_, st));
     const SumItem *d_items = reinterpret_cast<const SumItem *>(dev() + o_items_);
-    const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 1);
-    if (n) hipLaunchKernelGGL(summary_moments_kernel, dim3(static_cast<unsigned>(n)), dim3(kSumThreads), 0, st, d_items);
-    if (pfirst[n] > 0)
-      hipLaunchKernelGGL(grid_partial_kernel, dim3(static_cast<unsigned>(pfirst[n])), dim3(kGridThreads), 0, st, d_items,
-                         d_pfirst, static_cast<int>(n));
-    if (ffirst[n] > 0)
-      hipLaunchKernelGGL(grid_finish_kernel, dim3(static_cast<unsigned>(ffirst[n])), dim3(kGridThreads), 0, st, d_items,
-                         d_ffirst, static_cast<int>(n));
+    const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 2);
+    const auto launch = [&](auto circ, size_t k0, size_t cnt, size_t f0) {
+      constexpr bool CIRC = decltype(circ)::value;
+      if (!cnt) return;
+      const int32_t np = pfirst[f0 + cnt], nf = ffirst[f0 + cnt];
+      hipLaunchKernelGGL(summary_moments_kernel<CIRC>, dim3(static_cast<unsigned>(cnt)), dim3(kSumThreads), 0, st,
+                         d_items + k0);
+      if (np > 0)
+        hipLaunchKernelGGL(grid_partial_kernel<CIRC>, dim3(static_cast<unsigned>(np)), dim3(kGridThreads), 0, st,
+                           d_items + k0, d_pfirst + f0, static_cast<int>(cnt));
+      if (nf > 0)
+        hipLaunchKernelGGL(grid_finish_kernel<CIRC>, dim3(static_cast<unsigned>(nf)), dim3(kGridThreads), 0, st,
+                           d_items + k0, d_ffirst + f0, static_cast<int>(cnt));
+    };
+    launch(std::false_type{}, 0, ne, 0);
+    launch(std::true_type{}, ne, n - ne, ne + 1);
     KDEHIP_CHECK(hipGetLastError());
     return KDEHIP_OK;
   }
@@ -411,7 +500,7 @@ class SumRun {
 };
 
 // the descriptor of a resident density (outputs, extend, grid set by the caller)
-SumItem density_item(const kdehip_device_density *p, double extend, int64_t Ngrid) {
+SumItem density_item(const kdehip_device_density *p, double extend, int64_t Ngrid, uint32_t circ = 0) {
   SumItem it{};
   const int64_t N = p->N;
   const int D = p->D;
@@ -419,6 +508,7 @@ SumItem density_item(const kdehip_device_density *p, double extend, int64_t Ngri
   it.extend = extend;
   it.norm0 = std::pow(2.0 * M_PI, 1 / 2.0);
   it.N = N; it.Ngrid = Ngrid; it.D = D;
+  it.circ = circ;
   return it;
 }
 
@@ -451,7 +541,10 @@ struct Uploaded {
   ~Uploaded() { if (h) kdehip_density_free(h); }
 };
 
-int inters_resident(const kdehip_device_density *p, const kdehip_device_density *q, int64_t Ngrid, double *out) {
+// (manifold / circ: NULL / 0 or the same manifold as bytes and as a mask -- the grid over p's circular range, p and q by the
+// kernels of kdehip_evaluate_manifold)
+int inters_resident(const kdehip_device_density *p, const kdehip_device_density *q, int64_t Ngrid, double *out,
+                    const uint8_t *manifold, uint32_t circ) {
   const int D = p->D;
   const int64_t Nq = D == 1 ? Ngrid : Ngrid * Ngrid;
   DeviceGuard guard;
@@ -463,7 +556,7 @@ int inters_resident(const kdehip_device_density *p, const kdehip_device_density 
   const size_t o_pts = c.take(sizeof(double) * Nq * D), o_pv = c.take(sizeof(double) * Nq), o_qv = c.take(sizeof(double) * Nq);
   const size_t o_rows = c.mark(), extra = o_rows + sizeof(double) * Ngrid;
   SumRun run;
-  run.items.push_back(density_item(p, 0.3, Ngrid));  // LD[d] = getKDERangeLinspace(marginal(p, [d]), extend=0.3) (:599)
+  run.items.push_back(density_item(p, 0.3, Ngrid, circ));  // LD[d] = getKDERangeLinspace(marginal(p, [d]), extend=0.3) (:599)
   KDEHIP_CHECK_RC(run.alloc(extra));
   unsigned char *x = reinterpret_cast<unsigned char *>(run.extra());
   double *d_res = reinterpret_cast<double *>(x), *d_pts = reinterpret_cast<double *>(x + o_pts);
@@ -475,8 +568,8 @@ int inters_resident(const kdehip_device_density *p, const kdehip_device_density 
                      d_pts);
   KDEHIP_CHECK(hipGetLastError());
   // p and q at the grid by the existing direct evaluation: the values kdehip_evaluate returns at those points
-  KDEHIP_CHECK_RC(kdehip_evaluate_device(p, d_pts, Nq, 0, d_pv, st));
-  KDEHIP_CHECK_RC(kdehip_evaluate_device(q, d_pts, Nq, 0, d_qv, st));
+  KDEHIP_CHECK_RC(kdehip_evaluate_device_manifold(p, d_pts, Nq, 0, d_pv, st, manifold));
+  KDEHIP_CHECK_RC(kdehip_evaluate_device_manifold(q, d_pts, Nq, 0, d_qv, st, manifold));
   hipLaunchKernelGGL(inters_reduce_kernel, dim3(1), dim3(kSumThreads), 0, st, d_stats, D, Ngrid, d_pv, d_qv, d_rows, d_res);
   KDEHIP_CHECK(hipGetLastError());
   KDEHIP_CHECK_RC(run.wait());
@@ -497,35 +590,71 @@ int check_inters_shapes(int64_t Dp, int64_t Dq, int64_t Ngrid) {
 
 using namespace kdehip;
 
-extern "C" int kdehip_summary_device_batch(int n, const kdehip_summary_item *items, void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "summary batch: bad item list");
+namespace {
+
+// the batch over items of either struct: item(i) = the kdehip_summary_item, mask(i) = its circular bits
+template <typename Item, typename Mask>
+int summary_batch(int n, Item item, Mask mask, void *stream) {
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
-    KDEHIP_CHECK_RC(check_resident(items[i].density));
-    KDEHIP_CHECK_RC(check_grid(items[i].Ngrid));
-    if (items[i].density->device != items[0].density->device)
+    const kdehip_summary_item &s = item(i);
+    KDEHIP_CHECK_RC(check_resident(s.density));
+    KDEHIP_CHECK_RC(check_grid(s.Ngrid));
+    if (s.density->device != item(0).density->device)
       return set_error(KDEHIP_ERR_ARG, "summary batch: densities on different devices");
+    if (mask(i) >> s.density->D) return set_error(KDEHIP_ERR_ARG, "summary batch: a circular bit at or above the item's ndims");
   }
-  const int device = items[0].density->device;
+  const int device = item(0).density->device;
   DeviceGuard guard;
   KDEHIP_CHECK_RC(guard.enter(device));
   SumRun run;
-  for (int i = 0; i < n; ++i) {
-    const kdehip_summary_item &s = items[i];
-    SumItem it = density_item(s.density, s.extend, s.Ngrid);
-    it.range = s.d_range; it.mean = s.d_mean; it.cov = s.d_cov; it.argmax = s.d_argmax; it.values = s.d_values;
-    it.grid = (s.d_argmax || s.d_values) ? 1 : 0;
-    run.items.push_back(it);
-  }
+  for (int pass = 0; pass < 2; ++pass)  // the Euclidean items first (SumRun)
+    for (int i = 0; i < n; ++i) {
+      if ((mask(i) != 0) != (pass == 1)) continue;
+      const kdehip_summary_item &s = item(i);
+      SumItem it = density_item(s.density, s.extend, s.Ngrid, mask(i));
+      it.range = s.d_range; it.mean = s.d_mean; it.cov = s.d_cov; it.argmax = s.d_argmax; it.values = s.d_values;
+      it.grid = (s.d_argmax || s.d_values) ? 1 : 0;
+      run.items.push_back(it);
+    }
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
   return run.defer(device);
 }
 
+// the circular bits of a host entry's manifold for a density of D dimensions (a bad D is check_resident / check_host's)
+int summary_mask(const uint8_t *manifold, int64_t D, uint32_t *circ) {
+  unsigned m = 0;
+  KDEHIP_CHECK_RC(manifold_mask(manifold, D, &m));
+  *circ = m;
+  return KDEHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int kdehip_summary_device_batch(int n, const kdehip_summary_item *items, void *stream) {
+  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "summary batch: bad item list");
+  return summary_batch(n, [&](int i) -> const kdehip_summary_item & { return items[i]; }, [](int) { return 0u; }, stream);
+}
+
+extern "C" int kdehip_summary_device_batch_manifold(int n, const kdehip_summary_manifold_item *items, void *stream) {
+  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "summary batch: bad item list");
+  return summary_batch(n, [&](int i) -> const kdehip_summary_item & { return items[i].item; },
+                       [&](int i) { return items[i].circular_mask; }, stream);
+}
+
 extern "C" int kdehip_density_summary(const kdehip_device_density *p, const double *extend, int64_t Ngrid, double *range,
                                       double *mean, double *cov, double *argmax, double *values) {
+  return kdehip_density_summary_manifold(p, extend, Ngrid, range, mean, cov, argmax, values, nullptr);
+}
+
+extern "C" int kdehip_density_summary_manifold(const kdehip_device_density *p, const double *extend, int64_t Ngrid,
+                                               double *range, double *mean, double *cov, double *argmax, double *values,
+                                               const uint8_t *manifold) {
   KDEHIP_CHECK_RC(check_resident(p));
   KDEHIP_CHECK_RC(check_grid(Ngrid));
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(summary_mask(manifold, p->D, &circ));
   const int64_t D = p->D;
   DeviceGuard guard;
   KDEHIP_CHECK_RC(guard.enter(p->device));
@@ -533,7 +662,7 @@ extern "C" int kdehip_density_summary(const kdehip_device_density *p, const doub
   const int64_t o_mean = 2 * D, o_cov = 3 * D, o_arg = o_cov + D * D, o_val = o_arg + D;
   const int64_t words = o_val + (values ? D * Ngrid : 0);
   SumRun run;
-  run.items.push_back(density_item(p, extend ? *extend : 0.1, Ngrid));
+  run.items.push_back(density_item(p, extend ? *extend : 0.1, Ngrid, circ));
   run.items[0].grid = (argmax || values) ? 1 : 0;  // (alloc sizes the grid scratch from it)
   KDEHIP_CHECK_RC(run.alloc(sizeof(double) * words));
   double *x = run.extra();
@@ -555,32 +684,53 @@ extern "C" int kdehip_density_summary(const kdehip_device_density *p, const doub
 }
 
 extern "C" int kdehip_kde_max(const kdehip_density *p, int64_t Ngrid, double *out, double *grid_values, int device) {
+  return kdehip_kde_max_manifold(p, Ngrid, out, grid_values, device, nullptr);
+}
+
+extern "C" int kdehip_kde_max_manifold(const kdehip_density *p, int64_t Ngrid, double *out, double *grid_values, int device,
+                                       const uint8_t *manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
   KDEHIP_CHECK_RC(check_host(p));
   KDEHIP_CHECK_RC(check_grid(Ngrid));
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(summary_mask(manifold, p->ndim, &circ));
   Uploaded up;
   KDEHIP_CHECK_RC(kdehip_density_upload(&up.h, p, device));
-  return kdehip_density_summary(up.h, nullptr, Ngrid, nullptr, nullptr, nullptr, out, grid_values);
+  return kdehip_density_summary_manifold(up.h, nullptr, Ngrid, nullptr, nullptr, nullptr, out, grid_values, manifold);
 }
 
 extern "C" int kdehip_inters_intg_appx_is_device(const kdehip_device_density *p, const kdehip_device_density *q,
                                                  int64_t Ngrid, double *out) {
+  return kdehip_inters_intg_appx_is_device_manifold(p, q, Ngrid, out, nullptr);
+}
+
+extern "C" int kdehip_inters_intg_appx_is_device_manifold(const kdehip_device_density *p, const kdehip_device_density *q,
+                                                          int64_t Ngrid, double *out, const uint8_t *manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
   KDEHIP_CHECK_RC(check_resident(p));
   KDEHIP_CHECK_RC(check_resident(q));
   KDEHIP_CHECK_RC(check_inters_shapes(p->D, q->D, Ngrid));
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(summary_mask(manifold, p->D, &circ));
   if (p->device != q->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
   if (!leaves_share_bandwidth(p) || !leaves_share_bandwidth(q))
     return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
-  return inters_resident(p, q, Ngrid, out);
+  return inters_resident(p, q, Ngrid, out, circ ? manifold : nullptr, circ);
 }
 
 extern "C" int kdehip_inters_intg_appx_is(const kdehip_density *p, const kdehip_density *q, int64_t Ngrid, double *out,
                                           int device) {
+  return kdehip_inters_intg_appx_is_manifold(p, q, Ngrid, out, device, nullptr);
+}
+
+extern "C" int kdehip_inters_intg_appx_is_manifold(const kdehip_density *p, const kdehip_density *q, int64_t Ngrid,
+                                                   double *out, int device, const uint8_t *manifold) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
   KDEHIP_CHECK_RC(check_host(p));
   KDEHIP_CHECK_RC(check_host(q));
   KDEHIP_CHECK_RC(check_inters_shapes(p->ndim, q->ndim, Ngrid));
+  uint32_t circ = 0;
+  KDEHIP_CHECK_RC(summary_mask(manifold, p->ndim, &circ));
   for (const kdehip_density *d : {p, q}) {
     const int64_t N = d->npts, D = d->ndim;
     for (int64_t i = 0; i < N; ++i)
@@ -591,5 +741,5 @@ extern "C" int kdehip_inters_intg_appx_is(const kdehip_density *p, const kdehip_
   Uploaded up, uq;
   KDEHIP_CHECK_RC(kdehip_density_upload(&up.h, p, device));
   KDEHIP_CHECK_RC(kdehip_density_upload(&uq.h, q, device));
-  return inters_resident(up.h, uq.h, Ngrid, out);
+  return inters_resident(up.h, uq.h, Ngrid, out, circ ? manifold : nullptr, circ);
 }

@@ -714,6 +714,134 @@ function hip_intersIntgAppxIS(p::BallTreeDensity, q::BallTreeDensity; N::Int=201
   return out[]
 end
 
+# ---- the same functions on a manifold (include/kdehip.h section 5e).  `manifold`: a vector of `:euclid` / `:circular` (or
+# 0 / 1), one per dimension -- the library's circular semantic (wrap to [-pi, pi), tangent offsets at original point 1's
+# angle), which a caller's own addop / diffop need not share: as with the other manifold functions, nothing maps the
+# reference's operator arguments to it automatically.  Module functions, not installed by `enable!()`.
+
+"`hip_sample` with the drawn coordinates of the circular dimensions wrapped to [-pi, pi) (`kdehip_sample_manifold`)."
+function hip_sample(bd::BallTreeDensity, Npts::Int, manifold::AbstractVector, ind::Union{Nothing,Vector{Int}}=nothing;
+                    seed::Union{Nothing,UInt64}=nothing, sample_offset::Int=0, device::Int=0)
+  D = Ndim(bd)
+  man = manifold_bytes(manifold, D)
+  pts = zeros(D, Npts)
+  out = zeros(Int, Npts)
+  s = seed === nothing ? rand(UInt64) : seed
+  cd = Ref(CDensity(bd))
+  lab = ind === nothing ? C_NULL : Vector{Int64}(ind)
+  GC.@preserve bd lab man begin
+    check(ccall((:kdehip_sample_manifold, libkdehip), Cint,
+                (Ref{CDensity}, Int64, UInt64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Cint, Ptr{UInt8}),
+                cd, Npts, s, sample_offset, lab, pts, out, device, man))
+  end
+  return pts, out
+end
+
+hip_rand(p::BallTreeDensity, manifold::AbstractVector, N::Int=1; seed::Union{Nothing,UInt64}=nothing) =
+  hip_sample(p, N, manifold; seed=seed)[1]
+
+"`resample(p, Np, :lcv)` on a manifold: the wrapped draw, then `kde!(pts; manifold, tree_manifold=manifold)`."
+function hip_resample(p::BallTreeDensity, manifold::AbstractVector, Np::Int=-1, ksType::Symbol=:lcv;
+                      seed::Union{Nothing,UInt64}=nothing)
+  ksType == :lcv || error("hip_resample: only ksType = :lcv")
+  n = Np <= 0 ? Npts(p) : Np
+  pts, = hip_sample(p, n, manifold; seed=seed)
+  return kde!(pts; manifold=manifold, tree_manifold=manifold)
+end
+
+"`resample` of a resident density without leaving the device (`kdehip_resample_device_manifold`)."
+function hip_resample(d::DeviceDensity, manifold::AbstractVector, Np::Int=-1; seed::Union{Nothing,UInt64}=nothing,
+                      tree_manifold::AbstractVector=manifold)
+  man = manifold_bytes(manifold, d.ndim)
+  tman = manifold_bytes(tree_manifold, d.ndim)
+  s = seed === nothing ? rand(UInt64) : seed
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve man tman begin
+    check(ccall((:kdehip_resample_device_manifold, libkdehip), Cint,
+                (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Int64, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{UInt8}, Ptr{UInt8}),
+                h, d.handle, Np, s, C_NULL, C_NULL, man, tman))
+  end
+  return DeviceDensity(h[])
+end
+
+"`marginal(p, dims)` of a resident density, its tree built with `tree_manifold[dims]` (`kdehip_density_marginal_device_tree`)."
+function hip_marginal(d::DeviceDensity, dims::Vector{Int}, tree_manifold::AbstractVector)
+  tman = manifold_bytes(tree_manifold, d.ndim)[dims]
+  sel = Vector{Int32}(dims)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve sel tman begin
+    check(ccall((:kdehip_density_marginal_device_tree, libkdehip), Cint,
+                (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{UInt8}), h, d.handle, length(sel), sel, tman))
+  end
+  return DeviceDensity(h[])
+end
+
+"`getKDEMax(p, addop, diffop; N)` with the library's circular operators (`kdehip_kde_max_manifold`): the argmax wrapped."
+function hip_getKDEMax(p::BallTreeDensity, manifold::AbstractVector; N::Int=200, device::Int=0)
+  man = manifold_bytes(manifold, Ndim(p))
+  m = zeros(Ndim(p))
+  cd = Ref(CDensity(p))
+  GC.@preserve p man begin
+    check(ccall((:kdehip_kde_max_manifold, libkdehip), Cint,
+                (Ref{CDensity}, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{UInt8}), cd, N, m, C_NULL, device, man))
+  end
+  return m
+end
+
+# (range: D x 2 column-major, mean: D, cov: D x D, argmax: D; any of them `nothing` to skip)
+function summary_manifold(d::DeviceDensity, manifold::AbstractVector, extend::Float64, N::Int, range, mean, cov, argmax)
+  man = manifold_bytes(manifold, d.ndim)
+  ext = Ref{Float64}(extend)
+  p(x) = x === nothing ? Ptr{Float64}(C_NULL) : pointer(x)
+  GC.@preserve man range mean cov argmax begin
+    check(ccall((:kdehip_density_summary_manifold, libkdehip), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{UInt8}), d.handle, ext, N, p(range), p(mean), p(cov), p(argmax), C_NULL, man))
+  end
+  return nothing
+end
+
+function hip_getKDEMax(d::DeviceDensity, manifold::AbstractVector; N::Int=200)
+  m = zeros(d.ndim)
+  summary_manifold(d, manifold, 0.1, N, nothing, nothing, nothing, m)
+  return m
+end
+
+"`getKDERange(p, addop, diffop; extend)` on the circle: the unwrapped arc per circular dimension (section 5e)."
+function hip_getKDERange(d::DeviceDensity, manifold::AbstractVector; extend::Float64=0.1)
+  r = zeros(d.ndim, 2)
+  summary_manifold(d, manifold, extend, 2, r, nothing, nothing, nothing)
+  return r
+end
+
+"`getKDEMean` on the circle: wrap(a0 + mean of the tangent offsets) per circular dimension (section 5e)."
+function hip_getKDEMean(d::DeviceDensity, manifold::AbstractVector)
+  mu = zeros(d.ndim)
+  summary_manifold(d, manifold, 0.1, 2, nothing, mu, nothing, nothing)
+  return mu
+end
+
+"`getKDEfit` on the circle: the circular mean and the covariance of the wrapped residuals."
+function hip_getKDEfit(d::DeviceDensity, manifold::AbstractVector)
+  mu = zeros(d.ndim)
+  sig = zeros(d.ndim, d.ndim)
+  summary_manifold(d, manifold, 0.1, 2, nothing, mu, sig, nothing)
+  return KDE.MvNormal(mu, sig)
+end
+
+"`intersIntgAppxIS(p, q, addop, diffop; N)` with the library's circular operators (`kdehip_inters_intg_appx_is_manifold`)."
+function hip_intersIntgAppxIS(p::BallTreeDensity, q::BallTreeDensity, manifold::AbstractVector; N::Int=201, device::Int=0)
+  man = manifold_bytes(manifold, Ndim(p))
+  out = Ref{Float64}(0.0)
+  cp = Ref(CDensity(p))
+  cq = Ref(CDensity(q))
+  GC.@preserve p q man begin
+    check(ccall((:kdehip_inters_intg_appx_is_manifold, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Int64, Ptr{Float64}, Cint, Ptr{UInt8}), cp, cq, N, out, device, man))
+  end
+  return out[]
+end
+
 """
     kde!(points)
 

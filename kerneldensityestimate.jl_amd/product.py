@@ -229,7 +229,7 @@ class DeviceDensity:
         self.bw = None      # LOOCV bandwidth (standard deviations) of a density built on the device
         self.nevals = None  # likelihood evaluations of that search
         # the manifold it was built with (`from_device_points(manifold=)`, a circular `mul_device`), as the uint8 enum array,
-        # or None.  A record only: `a * b`, `resample` and the summaries stay Euclidean -- pass `manifold=` where it is taken
+        # or None.  A record only: `a * b` stays Euclidean; `resample`, `sample` and the summaries take `manifold="inherit"`
         self.manifold = None
         # the operators its tree was built with (`tree_manifold=`), likewise a record only; an uploaded density keeps its own
         self.tree_manifold = getattr(tree, "tree_manifold", None) if _handle is None else None
@@ -317,40 +317,73 @@ class DeviceDensity:
     def __call__(self, pos=None, lvFlag=False, manifold=None):
         return self.evaluate(pos, lvFlag, manifold=manifold)
 
-    def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None):
+    def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None, manifold=None):
         """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):
         d_pts float64[D*Npts] (column-major D x Npts), d_ind int64[Npts] (1-based original indices), `ind` an optional
         device int64[Npts] of given labels.  The first call on the density builds its table and blocks; later calls only
-        enqueue on `stream` (kdehip_sample_device)."""
-        _lib.check(_lib.lib.kdehip_sample_device(self._h, int(Npts), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset),
-                                                 ProductPlan._addr(ind), ProductPlan._addr(d_pts), ProductPlan._addr(d_ind),
-                                                 ProductPlan._addr(stream)))
+        enqueue on `stream` (kdehip_sample_device).  `manifold` (a sequence or "inherit"): circular coordinates are stored
+        wrapped to [-pi, pi) (kdehip_sample_device_manifold)."""
+        from .summary import _manifold
+        man = _manifold(self, manifold)
+        args = (self._h, int(Npts), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset), ProductPlan._addr(ind),
+                ProductPlan._addr(d_pts), ProductPlan._addr(d_ind), ProductPlan._addr(stream))
+        if man is None:
+            _lib.check(_lib.lib.kdehip_sample_device(*args))
+        else:
+            _lib.check(_lib.lib.kdehip_sample_device_manifold(*args, ptr(man, u8p)))
 
-    def resample(self, Np=None, *, seed=None) -> "DeviceDensity":
+    def resample(self, Np=None, *, seed=None, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`resample(p, Np, :lcv)` (reference src/BallTreeDensity01.jl:312-334) without leaving the device: Np samples
-        (None = Npts(p)), then `kde!(points)` on the device matrix (kdehip_resample_device).  Euclidean, also for a density
-        that remembers a manifold."""
+        (None = Npts(p)), then `kde!(points)` on the device matrix (kdehip_resample_device).  The default is Euclidean, also
+        for a density that remembers a manifold; `manifold` / `tree_manifold` (sequences or "inherit"): the wrapped draw,
+        then `from_device_points(manifold=, tree_manifold=)` on it (kdehip_resample_device_manifold) -- the result
+        remembers both."""
+        from .summary import _manifold
+        man, tman = _manifold(self, manifold), _manifold(self, tree_manifold, attr="tree_manifold")
         if seed is None:
             seed = int.from_bytes(os.urandom(8), "little")
         h = C.c_void_p()
         bw = np.empty(self.dims)
         ne = C.c_int32(0)
-        _lib.check(_lib.lib.kdehip_resample_device(C.byref(h), self._h, 0 if Np is None else int(Np),
-                                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(bw, f64p), C.byref(ne)))
+        args = (C.byref(h), self._h, 0 if Np is None else int(Np), C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(bw, f64p),
+                C.byref(ne))
+        if man is None and tman is None:
+            _lib.check(_lib.lib.kdehip_resample_device(*args))
+        else:
+            _lib.check(_lib.lib.kdehip_resample_device_manifold(*args, None if man is None else ptr(man, u8p),
+                                                                None if tman is None else ptr(tman, u8p)))
         out = DeviceDensity(device=self.device, _handle=h)
         out.bw, out.nevals = bw, int(ne.value)
+        out.manifold, out.tree_manifold = man, tman
         return out
 
-    def marginal(self, dims) -> "DeviceDensity":
+    def marginal(self, dims, *, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`marginal(p, dims)` (reference src/KDE01.jl:143-153), dims 0-based, built on this density's device
-        (kdehip_density_marginal_device): the same arrays as the host `marginal` of the same density."""
+        (kdehip_density_marginal_device): the same arrays as the host `marginal` of the same density.  `tree_manifold` (one
+        entry per dimension of this density, or "inherit"): the tree is built with tree_manifold[dims]
+        (kdehip_density_marginal_device_tree); the result remembers manifold[dims] and tree_manifold[dims]."""
         from .summary import _marginal_device
-        return _marginal_device(self, dims)
+        return _marginal_device(self, dims, manifold, tree_manifold)
 
-    def getKDEMax(self, N=200, *, values=False):
-        """`getKDEMax(p; N)` (reference src/DualTree01.jl:558-570) on the device (kdehip_density_summary)."""
+    def getKDEMax(self, N=200, *, values=False, manifold=None):
+        """`getKDEMax(p; N)` (reference src/DualTree01.jl:558-570) on the device (kdehip_density_summary[_manifold])."""
         from .summary import getKDEMax
-        return getKDEMax(self, N, values=values)
+        return getKDEMax(self, N, values=values, manifold=manifold)
+
+    def getKDEMean(self, *, manifold=None):
+        """`getKDEMean(p)` on the device; `manifold`: the circular mean (include/kdehip.h section 5e)."""
+        from .summary import getKDEMean
+        return getKDEMean(self, manifold=manifold)
+
+    def getKDEfit(self, *, manifold=None):
+        """`getKDEfit(p)` on the device; `manifold`: the circular mean and wrapped residuals (section 5e)."""
+        from .summary import getKDEfit
+        return getKDEfit(self, manifold=manifold)
+
+    def getKDERange(self, extend=0.1, *, manifold=None):
+        """`getKDERange(p; extend)` on the device; `manifold`: the unwrapped arc of a circular dimension (section 5e)."""
+        from .summary import getKDERange
+        return getKDERange(self, extend, manifold=manifold)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -427,7 +460,7 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tr
         return []
     if seeds is None:
         seeds = [int.from_bytes(os.urandom(8), "little") for _ in range(n)]
-    flags = [bool(addEntropy)] * n if isinstance(addEntropy, (bool, int)) else [bool(f) for f in addEntropy]
+    flags = [bool(addEntropy)] * n if isinstance(addEntropy, (bool, int, np.bool_)) else [bool(f) for f in addEntropy]
     items = (_lib.CMulItem * n)()
     keep = []
     for k, trees in enumerate(products):
@@ -611,6 +644,8 @@ def gibbs1(Ndens, trees, Np, Niter, pts, ind, randU, randN, *, addEntropy=True, 
     if glbs is not None and glbs.recordChoosen:
         labels = np.zeros((Np, Ndens, nlevels(max(Npts(t) for t in trees))), dtype=np.int32)
     man = _manifold_array(manifold, ndims)
+    if man is not None and int(ngpus) != 1:
+        raise ValueError("gibbs1: manifold= runs on one GPU (kdehip_gibbs1_manifold); ngpus must be 1")
     if man is not None:
         _lib.check(_lib.lib.kdehip_gibbs1_manifold(int(Ndens), arr, int(Np), int(Niter), ptr(pts.reshape(-1), f64p),
                                                    ptr(tmp_ind, i64p), ptr(randU, f64p), randU.size, ptr(randN, f64p),

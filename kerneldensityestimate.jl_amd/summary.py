@@ -6,7 +6,12 @@ kdehip_summary_device_batch, kdehip_density_summary, kdehip_kde_max and kdehip_i
 A density's points are its leaf means in original (getPoints) order; `dims` are 0-based.  A BallTreeDensity gets its
 range, mean and fit from numpy -- the sequential sums through np.cumsum, never np.sum, which is pairwise -- and its
 getKDEMax / intersIntgAppxIS from the C entries (the density is uploaded for the call).  A DeviceDensity gets everything
-on its device.  Arguments that mix the two kinds are a TypeError.  Only the Euclidean operators exist (no addop / diffop).
+on its device.  Arguments that mix the two kinds are a TypeError.
+
+`manifold=` (None, a per-dimension sequence of 'euclid' / 'circular' or 0 / 1, or "inherit" = the density's recorded
+`.manifold`) gives the reference's addop / diffop of these functions as the enum of include/kdehip.h: section 5e states what
+each summary means on the circle (tangent offsets wrap(x - a0) at original point 1's angle).  None and all-Euclidean return
+today's bits.
 """
 from __future__ import annotations
 
@@ -15,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import f64p, i32p, ptr
+from ._lib import f64p, i32p, ptr, u8p
 from .density import BallTreeDensity, getBW, getWeights, kde
 
 
@@ -47,6 +52,80 @@ def _leaf_points(p):
     return out
 
 
+_PI, _TWO_PI = np.float64(np.pi), np.float64(2.0 * np.pi)   # circ_wrap's constants (csrc/circ_wrap.hpp)
+
+
+def _wrap(t):
+    """wrap() to [-pi, pi): the one expression of csrc/circ_wrap.hpp, every operation rounded on its own"""
+    t = np.asarray(t, dtype=np.float64)
+    return t - _TWO_PI * np.floor((t + _PI) / _TWO_PI)
+
+
+def _manifold(p, manifold, ndims=None, attr="manifold"):
+    """A `manifold=` / `tree_manifold=` argument as the uint8 enum array or None: "inherit" reads the density's record;
+    a wrong length or a value other than 0 / 1 is a ValueError (before any device is needed); all-Euclidean is None."""
+    from .product import _manifold_array
+    if isinstance(manifold, str):
+        if manifold != "inherit":
+            raise ValueError("manifold: a per-dimension sequence, None or 'inherit'")
+        manifold = getattr(p, attr, None)
+    man = _manifold_array(manifold, _ndim(p) if ndims is None else ndims)
+    if man is None:
+        return None
+    if (man > 1).any():
+        raise ValueError("manifold: every entry is 'euclid' (0) or 'circular' (1)")
+    return man if man.any() else None
+
+
+def _item_manifolds(items, manifold):
+    """the manifold of every item of a batch (`manifold=`: one for all or one per item; an item's own `manifold` key wins),
+    each parsed once per distinct (dimension count, value)"""
+    from .product import _batch_manifolds
+    dims = [it["density"].dims for it in items]
+    if manifold is not None and all(isinstance(m, str) or np.ndim(m) == 0 for m in manifold):
+        shared = [tuple(manifold)] * len(items)   # one for all: parsed below, once per dimension count
+    else:
+        shared = _batch_manifolds(manifold, dims)
+    seen, out = {}, []
+    for it, D, sh in zip(items, dims, shared):
+        m = it["manifold"] if "manifold" in it else sh
+        if m is None or isinstance(m, str):
+            out.append(_manifold(it["density"], m, ndims=D))
+            continue
+        key = (D, tuple(m))
+        if key not in seen:
+            seen[key] = _manifold(it["density"], m, ndims=D)
+        out.append(seen[key])
+    return out
+
+
+def _mp(man):
+    return None if man is None else ptr(man, u8p)
+
+
+def _seqsum(x):
+    """the sequential left-to-right sum of each row from +0.0 (np.sum is pairwise)"""
+    return np.cumsum(np.concatenate([np.zeros((x.shape[0], 1)), x], axis=1), axis=1)[:, -1]
+
+
+def _circ_offsets(pts, man):
+    """(a0, t): per dimension the reference angle (original point 0; 0.0 in a Euclidean dimension) and the tangent offsets
+    wrap(x - a0) (x itself in a Euclidean dimension)"""
+    circ = man.astype(bool)
+    a0 = np.where(circ, pts[:, 0], 0.0)
+    t = pts.copy()
+    t[circ] = _wrap(pts[circ] - a0[circ, None])
+    return a0, t
+
+
+def _circ_mean(pts, man):
+    a0, t = _circ_offsets(pts, man)
+    mu = _seqsum(t) / np.float64(pts.shape[1])
+    circ = man.astype(bool)
+    mu[circ] = _wrap(a0[circ] + mu[circ])
+    return mu
+
+
 def _dims_list(dims, D):
     dims = [dims] if np.isscalar(dims) else list(dims)
     if not 1 <= len(dims) <= _lib.MAX_DIMS:
@@ -72,8 +151,8 @@ def grid(lo, hi, N):
     return x
 
 
-def _summary(p, *, extend=0.1, N=200, range_=False, mean=False, cov=False, argmax=False, values=False):
-    """kdehip_density_summary of a DeviceDensity: the asked-for outputs as numpy arrays."""
+def _summary(p, *, extend=0.1, N=200, range_=False, mean=False, cov=False, argmax=False, values=False, man=None):
+    """kdehip_density_summary[_manifold] of a DeviceDensity: the asked-for outputs as numpy arrays."""
     D = p.dims
     ext = C.c_double(float(extend))
     out = {}
@@ -81,131 +160,198 @@ def _summary(p, *, extend=0.1, N=200, range_=False, mean=False, cov=False, argma
     for name, want, shape in (("range", range_, (2, D)), ("mean", mean, (D,)), ("cov", cov, (D, D)),
                               ("argmax", argmax, (D,)), ("values", values, (D, int(N)))):
         bufs[name] = np.zeros(shape) if want else None
-    _lib.check(_lib.lib.kdehip_density_summary(
-        p._h, C.byref(ext), int(N), *[None if bufs[k] is None else ptr(bufs[k], f64p)
-                                      for k in ("range", "mean", "cov", "argmax", "values")]))
+    args = [None if bufs[k] is None else ptr(bufs[k], f64p) for k in ("range", "mean", "cov", "argmax", "values")]
+    if man is None:
+        _lib.check(_lib.lib.kdehip_density_summary(p._h, C.byref(ext), int(N), *args))
+    else:
+        _lib.check(_lib.lib.kdehip_density_summary_manifold(p._h, C.byref(ext), int(N), *args, ptr(man, u8p)))
     for k, v in bufs.items():
         if v is not None:
             out[k] = v.T.copy() if k == "range" else v  # range: D x 2 column-major
     return out
 
 
-def marginal(p, dims):
+def _sub(man, dl):
+    """the entries of a manifold array at the selected dims; None when none of them is circular"""
+    if man is None or not man[dl].any():
+        return None
+    return np.ascontiguousarray(man[dl])
+
+
+def marginal(p, dims, *, manifold=None, tree_manifold=None):
     """`marginal(p, dims)` (src/KDE01.jl:143-153) = kde(getPoints(p)[dims], getBW(p)[dims, 0], getWeights(p)): the bandwidth
     of ORIGINAL point 0, whose variance comes back as fl(sqrt(v))**2; repeated and reordered dims allowed.  A BallTreeDensity
-    gives a BallTreeDensity (host builder), a DeviceDensity a DeviceDensity (kdehip_density_marginal_device)."""
+    gives a BallTreeDensity (host builder), a DeviceDensity a DeviceDensity (kdehip_density_marginal_device[_tree]).
+    `tree_manifold` (one entry per dimension of p, or "inherit"): the result's tree is built with tree_manifold[dims];
+    `manifold` (likewise) is only recorded: the result remembers manifold[dims] and tree_manifold[dims]."""
     if _is_device(p):
-        return p.marginal(dims)
-    dims = _dims_list(dims, p.bt.dims)
-    return kde(_leaf_points(p)[dims, :], getBW(p)[dims, 0], getWeights(p))
+        return p.marginal(dims, manifold=manifold, tree_manifold=tree_manifold)
+    dl = _dims_list(dims, p.bt.dims)
+    tman = _sub(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
+    _manifold(p, manifold)   # (validated; a BallTreeDensity has no manifold record)
+    return kde(_leaf_points(p)[dl, :], getBW(p)[dl, 0], getWeights(p), tree_manifold=tman)
 
 
-def getKDERange(p, extend=0.1):
+def _circ_range(pts, man, extend):
+    """section 5e: per circular dimension the arc (a0 + lo_t - dr, a0 + hi_t + dr), unwrapped, at most one turn"""
+    a0, t = _circ_offsets(pts, man)
+    lo, hi = t.min(axis=1), t.max(axis=1)
+    dr = np.float64(extend) * (hi - lo)
+    alo, ahi = a0 + lo, a0 + hi    # (only read in the circular dimensions)
+    rlo, rhi = alo - dr, ahi + dr
+    circ = man.astype(bool)
+    rlo = np.where(circ, rlo, lo - dr)
+    rhi = np.where(circ, rhi, hi + dr)
+    with np.errstate(invalid="ignore"):
+        turn = circ & (rhi - rlo > _TWO_PI)
+    mid = np.float64(0.5) * (alo + ahi)
+    return np.stack([np.where(turn, mid - _PI, rlo), np.where(turn, mid + _PI, rhi)], axis=1)
+
+
+def getKDERange(p, extend=0.1, *, manifold=None):
     """`getKDERange(p; extend)` (src/DualTree01.jl:512-540): (D, 2), per dimension (lo - dr, hi + dr) with lo / hi the
-    min / max over the points and dr = extend * (hi - lo).  A list of densities: the element-wise union (:542-553)."""
+    min / max over the points and dr = extend * (hi - lo).  A list of densities: the element-wise union (:542-553).
+    `manifold`: in a circular dimension the arc through the tangent offsets, left unwrapped (section 5e)."""
     if isinstance(p, (list, tuple)):
         if not p:
             raise ValueError("getKDERange: no densities")
         _same_kind(p)
         if len({_ndim(x) for x in p}) > 1:
             raise ValueError("getKDERange: densities of different dimensions")
-        out = getKDERange(p[0], extend)
+        out = getKDERange(p[0], extend, manifold=manifold)
         for x in p[1:]:
-            r = getKDERange(x, extend)
+            r = getKDERange(x, extend, manifold=manifold)
             out[:, 0] = np.where(out[:, 0] < r[:, 0], out[:, 0], r[:, 0])
             out[:, 1] = np.where(out[:, 1] > r[:, 1], out[:, 1], r[:, 1])
         return out
+    man = _manifold(p, manifold)
     if _is_device(p):
-        return _summary(p, extend=extend, range_=True)["range"]
+        return _summary(p, extend=extend, range_=True, man=man)["range"]
     pts = _leaf_points(p)
+    if man is not None:
+        return _circ_range(pts, man, extend)
     lo, hi = pts.min(axis=1), pts.max(axis=1)
     dr = np.float64(extend) * (hi - lo)
     return np.stack([lo - dr, hi + dr], axis=1)
 
 
-def getKDERangeLinspace(p, extend=0.1, N=200):
+def getKDERangeLinspace(p, extend=0.1, N=200, *, manifold=None):
     """`getKDERangeLinspace(p; extend, N)` (src/DualTree01.jl:552-556): the grid over getKDERange(p, extend).  1-D densities
-    only: for D > 1 the reference's (v[1], v[2]) would be (lo_1, lo_2)."""
+    only: for D > 1 the reference's (v[1], v[2]) would be (lo_1, lo_2).  `manifold`: the grid over the circular range,
+    unwrapped (monotone; wrap its points to read them as angles)."""
     if _ndim(p) != 1:
         raise ValueError("getKDERangeLinspace: 1-D densities only")
-    v = getKDERange(p, extend)
+    v = getKDERange(p, extend, manifold=manifold)
     return grid(v[0, 0], v[0, 1], N)
 
 
-def getKDEMax(p, N=200, *, values=False, device=0):
+def getKDEMax(p, N=200, *, values=False, device=0, manifold=None):
     """`getKDEMax(p; N)` (src/DualTree01.jl:558-570): per dimension, the grid point of the FIRST maximum of the 1-D marginal
-    on the N-point grid over its range with extend 0.1.  values=True also returns the (D, N) grid values."""
+    on the N-point grid over its range with extend 0.1.  values=True also returns the (D, N) grid values.
+    `manifold`: the circular range, wrapped differences on the grid, the argmax wrapped to [-pi, pi) (section 5e)."""
     N = int(N)
+    man = _manifold(p, manifold)
     if _is_device(p):
-        r = _summary(p, N=N, argmax=True, values=values)
+        r = _summary(p, N=N, argmax=True, values=values, man=man)
         return (r["argmax"], r["values"]) if values else r["argmax"]
     D = p.bt.dims
     m = np.zeros(D)
     vals = np.zeros((D, max(N, 0))) if values else None
-    _lib.check(_lib.lib.kdehip_kde_max(C.byref(p._cstruct()), N, ptr(m, f64p), None if vals is None else ptr(vals, f64p),
-                                       int(device)))
+    vp = None if vals is None else ptr(vals, f64p)
+    if man is None:
+        _lib.check(_lib.lib.kdehip_kde_max(C.byref(p._cstruct()), N, ptr(m, f64p), vp, int(device)))
+    else:
+        _lib.check(_lib.lib.kdehip_kde_max_manifold(C.byref(p._cstruct()), N, ptr(m, f64p), vp, int(device), ptr(man, u8p)))
     return (m, vals) if values else m
 
 
-def getKDEMean(p):
+def getKDEMean(p, *, manifold=None):
     """`getKDEMean(p)` (src/DualTree01.jl:572-575) = mean(getPoints(p), dims=2): unweighted, per dimension the sequential
-    sum in original order from +0.0, then / N."""
+    sum in original order from +0.0, then / N.  `manifold`: in a circular dimension wrap(a0 + mean of the tangent offsets)
+    (section 5e)."""
+    man = _manifold(p, manifold)
     if _is_device(p):
-        return _summary(p, mean=True)["mean"]
+        return _summary(p, mean=True, man=man)["mean"]
     pts = _leaf_points(p)
+    if man is not None:
+        return _circ_mean(pts, man)
     s = np.cumsum(np.concatenate([np.zeros((pts.shape[0], 1)), pts], axis=1), axis=1)[:, -1]
     return s / np.float64(pts.shape[1])
 
 
-def getKDEfit(p):
+def getKDEfit(p, *, manifold=None):
     """`getKDEfit(p)` (src/DualTree01.jl:576-578) = fit(MvNormal, getPoints(p)): (mu, Sigma) with mu = getKDEMean(p) and
-    Sigma = (1/N) sum (x - mu)(x - mu)^T."""
+    Sigma = (1/N) sum (x - mu)(x - mu)^T.  `manifold`: the circular mean and wrapped residuals (section 5e)."""
+    man = _manifold(p, manifold)
     if _is_device(p):
-        r = _summary(p, mean=True, cov=True)
+        r = _summary(p, mean=True, cov=True, man=man)
         return r["mean"], r["cov"]
-    mu = getKDEMean(p)
+    mu = getKDEMean(p, manifold=man)
     X = _leaf_points(p) - mu[:, None]
+    if man is not None:
+        X[man.astype(bool)] = _wrap(X[man.astype(bool)])
     return mu, (X @ X.T) / np.float64(X.shape[1])
 
 
-def intersIntgAppxIS(p, q, N=201, *, device=0):
+def intersIntgAppxIS(p, q, N=201, *, device=0, manifold=None):
     """`intersIntgAppxIS(p, q; N)` (src/DualTree01.jl:581-618), 1-D and 2-D: p and q evaluated by the direct sum on the
-    grid over p's marginal ranges with extend 0.3, sum of p q times the cell size (rows in order in 2-D)."""
+    grid over p's marginal ranges with extend 0.3, sum of p q times the cell size (rows in order in 2-D).
+    `manifold`: p's circular range, p and q evaluated as `evaluateDualTree(..., manifold=)` (section 5e)."""
     dev = _same_kind([p, q])
+    man = _manifold(p, manifold)
     out = C.c_double(0.0)
     if dev:
-        _lib.check(_lib.lib.kdehip_inters_intg_appx_is_device(p._h, q._h, int(N), C.byref(out)))
+        _lib.check(_lib.lib.kdehip_inters_intg_appx_is_device_manifold(p._h, q._h, int(N), C.byref(out), _mp(man)))
     else:
-        _lib.check(_lib.lib.kdehip_inters_intg_appx_is(C.byref(p._cstruct()), C.byref(q._cstruct()), int(N), C.byref(out),
-                                                       int(device)))
+        _lib.check(_lib.lib.kdehip_inters_intg_appx_is_manifold(C.byref(p._cstruct()), C.byref(q._cstruct()), int(N),
+                                                                C.byref(out), int(device), _mp(man)))
     return float(out.value)
 
 
-def summary_device_batch(items, stream=None):
-    """Summaries of many DeviceDensity in ONE call (kdehip_summary_device_batch): `items` = dicts with `density` and
-    optionally `extend` (0.1), `Ngrid` (200) and the device outputs (torch tensors or addresses, float64) `range` (2D,
-    D x 2 column-major), `mean` (D), `cov` (D*D), `argmax` (D), `values` (D*Ngrid).  Enqueues on `stream` and returns."""
+def summary_device_batch(items, stream=None, *, manifold=None):
+    """Summaries of many DeviceDensity in ONE call (kdehip_summary_device_batch[_manifold]): `items` = dicts with `density`
+    and optionally `extend` (0.1), `Ngrid` (200), `manifold` and the device outputs (torch tensors or addresses, float64)
+    `range` (2D, D x 2 column-major), `mean` (D), `cov` (D*D), `argmax` (D), `values` (D*Ngrid).  `manifold=`: one manifold
+    for all items or one per item (None = Euclidean), as `mul_device_batch` takes it; an item's own `manifold` wins.
+    Euclidean and circular items may be mixed.  Enqueues on `stream` and returns."""
     from .product import DeviceDensity, ProductPlan
     items = list(items)
     n = len(items)
-    arr = (_lib.CSummaryItem * max(1, n))()
-    for k, it in enumerate(items):
+    for it in items:
         if not isinstance(it["density"], DeviceDensity):
             raise TypeError("summary_device_batch: items of DeviceDensity")
-        a = arr[k]
+    circular = False
+    if manifold is not None or any("manifold" in it for it in items):   # (a call without any manifold pays for none)
+        mans = _item_manifolds(items, manifold)
+        circular = any(m is not None for m in mans)
+    arr = ((_lib.CSummaryManifoldItem if circular else _lib.CSummaryItem) * max(1, n))()
+    for k, it in enumerate(items):
+        a = arr[k].item if circular else arr[k]
         a.density = it["density"]._h
         a.extend = float(it.get("extend", 0.1))
         a.Ngrid = int(it.get("Ngrid", 200))
         a.d_range, a.d_mean, a.d_cov = (ProductPlan._addr(it.get(x)) for x in ("range", "mean", "cov"))
         a.d_argmax, a.d_values = ProductPlan._addr(it.get("argmax")), ProductPlan._addr(it.get("values"))
-    _lib.check(_lib.lib.kdehip_summary_device_batch(n, arr, ProductPlan._addr(stream)))
+        if circular and mans[k] is not None:
+            arr[k].circular_mask = sum(1 << d for d in range(len(mans[k])) if mans[k][d])
+    if circular:
+        _lib.check(_lib.lib.kdehip_summary_device_batch_manifold(n, arr, ProductPlan._addr(stream)))
+    else:
+        _lib.check(_lib.lib.kdehip_summary_device_batch(n, arr, ProductPlan._addr(stream)))
 
 
-def _marginal_device(p, dims):
-    """kdehip_density_marginal_device (DeviceDensity.marginal)."""
+def _marginal_device(p, dims, manifold=None, tree_manifold=None):
+    """kdehip_density_marginal_device[_tree] (DeviceDensity.marginal)."""
     from .product import DeviceDensity
     dl = _dims_list(dims, p.dims)
+    man = _sub(_manifold(p, manifold), dl)
+    tman = _sub(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
     d = np.array([x + 1 for x in dl], dtype=np.int32)
     h = C.c_void_p()
-    _lib.check(_lib.lib.kdehip_density_marginal_device(C.byref(h), p._h, len(dl), ptr(d, i32p)))
-    return DeviceDensity(device=p.device, _handle=h)
+    if tman is None:
+        _lib.check(_lib.lib.kdehip_density_marginal_device(C.byref(h), p._h, len(dl), ptr(d, i32p)))
+    else:
+        _lib.check(_lib.lib.kdehip_density_marginal_device_tree(C.byref(h), p._h, len(dl), ptr(d, i32p), ptr(tman, u8p)))
+    out = DeviceDensity(device=p.device, _handle=h)
+    out.manifold, out.tree_manifold = man, tman
+    return out
