@@ -151,6 +151,30 @@ typedef struct kdehip_product_info_t {
 /* precision: 64 (reference arithmetic) or 32.  mask as in kdehip_gibbs1. */
 int kdehip_product_create(kdehip_product **out, int Ndens, const kdehip_density *trees, int ndims,
                           const uint8_t *partialDimMask, int precision, int device);
+/* The same on a manifold (`manifold`: ndims bytes of KDEHIP_MANIFOLD_EUCLIDEAN / KDEHIP_MANIFOLD_CIRCULAR or NULL, the
+ * operators of "manifolds" above): a resident plan whose runs apply the circular operators.  The plan chooses its arithmetic
+ * as kdehip_prod_philox_device_manifold (2c) does: the sampler's circular fast mode when the node values qualify for the fast
+ * forms, the generic arithmetic of kdehip_gibbs1_manifold otherwise; no conditional tables and no fp32 screens in either.
+ * CONTRACT: kdehip_product_sample_philox(seed, sample_offset) on such a plan returns, bit for bit, what
+ * kdehip_prod_philox_device_manifold returns for the same densities, mask, manifold, seed and offset.  Every entry that takes
+ * a plan works on a circular one: kdehip_product_sample_streams (caller streams, d_labels), kdehip_product_info
+ * (fast_math_path as it is), kdehip_product_kernel_name ("gibbs_product_kernel"), kdehip_product_screen_stats (0 levels),
+ * kdehip_product_set_variant, kdehip_product_launch_geometry, kdehip_product_fallback_count.
+ *   - manifold == NULL or all zeros IS kdehip_product_create, bit for bit (it forwards here with NULL);
+ *   - a manifold byte above 1 is KDEHIP_ERR_ARG, ndims above KDEHIP_MAX_DIMS KDEHIP_ERR_UNSUPPORTED, a circular dimension with
+ *     precision 32 KDEHIP_ERR_UNSUPPORTED -- all checked before any device is touched. */
+int kdehip_product_create_manifold(kdehip_product **out, int Ndens, const kdehip_density *trees, int ndims,
+                                   const uint8_t *partialDimMask, const uint8_t *manifold /* ndims bytes or NULL */,
+                                   int precision, int device);
+/* kdehip_prod_philox on a manifold: the one-shot form of such a plan (pack, upload, run with sample offset 0, copy back), on
+ * one or several GPUs -- bit for bit the plan's result, so the same for every ngpus (chains in contiguous ranges, Philox
+ * keyed by the global sample index).  Unlike kdehip_gibbs1_manifold it runs the circular fast mode where the plan would: its
+ * labels are that entry's on the host twin of the Philox streams, its points agree to rounding (1e-12).  manifold == NULL or
+ * all zeros IS kdehip_prod_philox; errors as above. */
+int kdehip_prod_philox_manifold(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, double *pts, int64_t *ind,
+                                uint64_t seed, int addEntropy, int ndims, const uint8_t *partialDimMask,
+                                const uint8_t *manifold /* ndims bytes or NULL */, int precision, int device, int ngpus,
+                                int32_t *labels);
 /* (waits for the device first if runs were enqueued through the device-pointer entry points below) */
 void kdehip_product_destroy(kdehip_product *plan);
 int kdehip_product_info(const kdehip_product *plan, kdehip_product_info_t *info);
@@ -233,6 +257,13 @@ const char *kdehip_product_kernel_name(const kdehip_product *plan, int64_t Np);
 typedef struct kdehip_product_multi kdehip_product_multi;
 int kdehip_product_multi_create(kdehip_product_multi **out, int Ndens, const kdehip_density *trees, int ndims,
                                 const uint8_t *partialDimMask, int precision, int first_device, int ngpus);
+/* The same on a manifold: the circular plan of kdehip_product_create_manifold replicated per device (same mode selection,
+ * same errors, all checked before any device is touched).  The fused peer-store epilogue applies unchanged -- the circular
+ * mode is an arithmetic mode of the same kernel --, and the result is the single plan's for every ngpus.  manifold == NULL
+ * or all zeros IS the entry above. */
+int kdehip_product_multi_create_manifold(kdehip_product_multi **out, int Ndens, const kdehip_density *trees, int ndims,
+                                         const uint8_t *partialDimMask, const uint8_t *manifold /* ndims bytes or NULL */,
+                                         int precision, int first_device, int ngpus);
 void kdehip_product_multi_destroy(kdehip_product_multi *mp);
 int kdehip_product_multi_ngpus(const kdehip_product_multi *mp);
 kdehip_product *kdehip_product_multi_plan(kdehip_product_multi *mp, int g); /* the plan on device g (owned by mp) */
@@ -346,8 +377,8 @@ int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, kdehip_devi
                             int32_t *nevals);
 /* The same with a manifold per item: manifolds == NULL, or nprod rows of KDEHIP_MAX_DIMS bytes (as bw_out has nprod rows of
  * KDEHIP_MAX_DIMS doubles), row i holding the manifold of item i in its first ndims bytes.  Items without a
- * circular dimension take the batched sampler as above; circular items are sampled one by one inside the same call (as
- * masked products are in kdehip_prod_philox_batch), and the bandwidth searches of the circular items of one (ndims, size,
+ * circular dimension take the batched sampler as above; circular items are sampled by kdehip_prod_philox_batch_manifold
+ * (2e: one launch per dimension count for those in the circular fast mode), and the bandwidth searches of the circular items of one (ndims, size,
  * manifold) advance in shared launches with their likelihoods wrapped.  out[i] is bit for bit what
  * kdehip_mul_device_manifold(items[i], row i) returns; manifolds == NULL IS the entry above. */
 int kdehip_mul_device_batch_manifold(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
@@ -400,6 +431,23 @@ typedef struct kdehip_batch_item {
   int32_t *d_labels;                    /* device, optional          */
 } kdehip_batch_item;
 int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int precision, void *stream);
+/* The same with a manifold per item: manifolds == NULL, or nprod rows of KDEHIP_MAX_DIMS bytes (the shape
+ * kdehip_mul_device_batch_manifold takes), row i holding the manifold of item i in its first ndims bytes and zeros behind
+ * them.  Euclidean items ride exactly as above.  Circular fp64 items whose plans reach the sampler's circular fast mode ride
+ * ONE launch per dimension count -- any density count, masked ones included: a batched instantiation of the general kernel,
+ * 8 chains per workgroup --; circular items on the generic arithmetic are enqueued one by one inside the call.  Every item's
+ * result is bit for bit that of kdehip_prod_philox_device_manifold with the same arguments.  manifolds == NULL or all zeros
+ * IS the entry above.  A row byte above 1, or a circular byte at or beyond the item's ndims, is KDEHIP_ERR_ARG; a circular
+ * item with precision 32, or more than KDEHIP_MAX_DIMS dimensions, KDEHIP_ERR_UNSUPPORTED -- before any device is touched.
+ * kdehip_mul_device_batch_manifold and _tree (2d) sample their circular items through this path.
+ * Environment, read once per process: KDEHIP_BATCH_CIRC=0 enqueues the circular items one by one instead (the route before
+ * the batched instantiation existed; the same bits -- a switch for timing one route against the other). */
+int kdehip_prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items, const uint8_t *manifolds, int precision,
+                                      void *stream);
+/* Diagnostic: of the calling thread's last kdehip_prod_philox_batch / _manifold call that reached its launches, how many
+ * batched sampling launches it made (one per group) and how many items it enqueued one by one.  Either pointer may be NULL.
+ * (kdehip_mul_device_batch* call the batch on the calling thread too.) */
+void kdehip_prod_philox_batch_launches(int32_t *batched, int32_t *singles);
 
 /* ---- (2f) drawing from a density: sample, rand, resample ---------------------------------------------------------
  * `sample(p, Npts)` (reference src/KDE01.jl:164-183):  w = the leaf weights in ORIGINAL point order (getWeights);

@@ -103,6 +103,10 @@ SIGNATURES = {
                                      C.c_int, u8p, C.c_int, C.c_int, C.c_int, i32p]),
     "kdehip_product_multi_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CDensity), C.c_int, u8p,
                                               C.c_int, C.c_int, C.c_int]),
+    "kdehip_product_multi_create_manifold": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CDensity), C.c_int, u8p,
+                                                       u8p, C.c_int, C.c_int, C.c_int]),
+    "kdehip_prod_philox_manifold": (C.c_int, [C.c_int, C.POINTER(CDensity), C.c_int64, C.c_int, f64p, i64p, C.c_uint64,
+                                              C.c_int, C.c_int, u8p, u8p, C.c_int, C.c_int, C.c_int, i32p]),
     "kdehip_product_multi_destroy": (None, [C.c_void_p]),
     "kdehip_product_multi_ngpus": (C.c_int, [C.c_void_p]),
     "kdehip_product_multi_plan": (C.c_void_p, [C.c_void_p, C.c_int]),
@@ -112,6 +116,8 @@ SIGNATURES = {
     "kdehip_product_multi_transfers_per_product": (C.c_int, [C.c_void_p]),
     "kdehip_product_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CDensity), C.c_int, u8p,
                                         C.c_int, C.c_int]),
+    "kdehip_product_create_manifold": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CDensity), C.c_int, u8p, u8p,
+                                                 C.c_int, C.c_int]),
     "kdehip_product_destroy": (None, [C.c_void_p]),
     "kdehip_product_info": (C.c_int, [C.c_void_p, C.POINTER(CProductInfo)]),
     "kdehip_product_randu_per_sample": (C.c_int64, [C.c_void_p, C.c_int]),
@@ -189,6 +195,8 @@ SIGNATURES = {
     "kdehip_density_download": (C.c_int, [C.c_void_p, f64p, f64p, f64p, i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p,
                                           f64p, f64p]),
     "kdehip_prod_philox_batch": (C.c_int, [C.c_int, C.POINTER(CBatchItem), C.c_int, C.c_void_p]),
+    "kdehip_prod_philox_batch_manifold": (C.c_int, [C.c_int, C.POINTER(CBatchItem), u8p, C.c_int, C.c_void_p]),
+    "kdehip_prod_philox_batch_launches": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kdehip_sample": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int]),
     "kdehip_sample_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),

@@ -56,7 +56,8 @@ int lean_waves(int64_t Np, int variant) {
   int launch_lean_batch_d##d(int, const PlanDev &, const RunArgs &, void *);            \
   int launch_tables_batch_d##d(const PlanDev &, const RunArgs &, void *);               \
   int launch_lean_f32_d##d(int, int, const PlanDev &, const RunArgs &, void *);  \
-  int launch_gibbs_circ_d##d(const PlanDev &, const RunArgs &, void *);
+  int launch_gibbs_circ_d##d(const PlanDev &, const RunArgs &, void *);           \
+  int launch_gibbs_circ_batch_d##d(const PlanDev &, const RunArgs &, void *);
 KDEHIP_DECL(1) KDEHIP_DECL(2) KDEHIP_DECL(3) KDEHIP_DECL(4) KDEHIP_DECL(5) KDEHIP_DECL(6) KDEHIP_DECL(7) KDEHIP_DECL(8)
 #undef KDEHIP_DECL
 
@@ -151,6 +152,22 @@ int launch_tables_batch(int D, const PlanDev &plan, const RunArgs &args, void *s
     case 6: return launch_tables_batch_d6(plan, args, stream);
     case 7: return launch_tables_batch_d7(plan, args, stream);
     case 8: return launch_tables_batch_d8(plan, args, stream);
+    default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  }
+}
+
+// One launch for a group of fp64 products in the circular fast mode (kdehip_prod_philox_batch_manifold): the BATCH sampling
+// instantiation of gibbs_kernel.hip's circular translation units, any density count, kCircBatchWaves chains per workgroup.
+int launch_gibbs_circ_batch(int D, const PlanDev &plan, const RunArgs &args, void *stream) {
+  switch (D) {
+    case 1: return launch_gibbs_circ_batch_d1(plan, args, stream);
+    case 2: return launch_gibbs_circ_batch_d2(plan, args, stream);
+    case 3: return launch_gibbs_circ_batch_d3(plan, args, stream);
+    case 4: return launch_gibbs_circ_batch_d4(plan, args, stream);
+    case 5: return launch_gibbs_circ_batch_d5(plan, args, stream);
+    case 6: return launch_gibbs_circ_batch_d6(plan, args, stream);
+    case 7: return launch_gibbs_circ_batch_d7(plan, args, stream);
+    case 8: return launch_gibbs_circ_batch_d8(plan, args, stream);
     default: return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   }
 }

@@ -53,11 +53,13 @@ namespace kdehip {
 // TBL: the instantiation that only fills the conditional tables (a.table_build) -- the same code, but without the
 // 120 KiB tile pool in its LDS footprint, so that a CU holds many more of its wavefronts (one wavefront per table row,
 // ~19,000 rows at config 3: 45 us with the sampler's one-workgroup-per-CU footprint, every one-shot call pays it).
-// BATCH (with TBL only): the tables of MANY products in one launch (kdehip_prod_philox_batch) -- workgroup b fills rows of
-// product batch_map[b], whose plan it fetches through the scalar cache (LaunchView, gibbs_device.hpp).
+// BATCH: MANY products in one launch (kdehip_prod_philox_batch) -- workgroup b works for product batch_map[b], whose plan and
+// run parameters it fetches through the scalar cache (LaunchView, gibbs_device.hpp).  With TBL it fills that product's table
+// rows; without, in the circular fast mode only (the batched sampling launches of the other modes are gibbs_lean.hip's), it
+// runs chains of that product, numbered from the product's first workgroup (kdehip_prod_philox_batch_manifold).
 template <typename T, int D, int MODE, int WAVES, bool TBL = false, bool BATCH = false>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_product_kernel(PlanDev plan_, RunArgs a_) {
-  static_assert(!BATCH || TBL, "batched launches of this kernel fill tables only");
+  static_assert(!BATCH || TBL || MODE == kModeFastCirc, "batched launches of this kernel fill tables, or sample in the circular fast mode");
   const LaunchView<BATCH> view(plan_, a_);
   const PlanDev &plan = view.plan;
   const auto &a = view.a;
@@ -598,7 +600,7 @@ static int launch_one(const PlanDev &plan, const RunArgs &args, hipStream_t stre
 // This file is compiled once per dimension count (-DKDEHIP_DIM=1..8, see the Makefile) so the 24 kernel
 // variants of each dimension (2 precisions x 3 arithmetic modes x 4 workgroup widths) build in parallel.
 // With -DKDEHIP_CIRC_TU it is the translation unit of the circular fast mode of that dimension count instead (fp64, three
-// workgroup widths): the instantiations above are not part of it, and theirs hold none of its code.
+// workgroup widths and the batched form): the instantiations above are not part of it, and theirs hold none of its code.
 #ifndef KDEHIP_DIM
 #error "compile gibbs_kernel.hip with -DKDEHIP_DIM=<1..8>"
 #endif
@@ -609,6 +611,18 @@ static int launch_one(const PlanDev &plan, const RunArgs &args, hipStream_t stre
 int KDEHIP_CAT(launch_gibbs_circ_d, KDEHIP_DIM)(const PlanDev &plan, const RunArgs &args, void *stream) {
   if (plan.circ_bits == 0u) return set_error(KDEHIP_ERR_ARG, "the circular mode needs a circular dimension");
   return launch_one<double, KDEHIP_DIM, kModeFastCirc>(plan, args, static_cast<hipStream_t>(stream));
+}
+
+// kdehip_prod_philox_batch_manifold: the chains of a group of circular products in one launch, kCircBatchWaves per
+// workgroup; args.Np = workgroups x kCircBatchWaves (every workgroup takes its own plan from args.batch)
+int KDEHIP_CAT(launch_gibbs_circ_batch_d, KDEHIP_DIM)(const PlanDev &plan, const RunArgs &args, void *stream) {
+  if (args.Np <= 0) return KDEHIP_OK;
+  hipLaunchKernelGGL((gibbs_product_kernel<double, KDEHIP_DIM, kModeFastCirc, kCircBatchWaves, false, true>),
+                     dim3(static_cast<unsigned>(args.Np / kCircBatchWaves)), dim3(kCircBatchWaves * 64), 0,
+                     static_cast<hipStream_t>(stream), plan, args);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(KDEHIP_ERR_HIP, std::string("batched circular launch failed: ") + hipGetErrorString(e));
+  return KDEHIP_OK;
 }
 #else
 

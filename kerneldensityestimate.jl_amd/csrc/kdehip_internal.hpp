@@ -243,7 +243,9 @@ struct BatchRun {
 struct BatchFlags {
   int32_t Niter, addEntropy, use_tables;
   int32_t first_block;   // the product's first workgroup in the launch
-  int32_t pad_[12];
+  uint32_t circ_bits;    // PlanDev::circ_bits of the product (0 for everything but the batched circular fast mode); the
+                         // per-density active-dimension masks travel in the level table head.levels points to
+  int32_t pad_[11];
 };
 struct BatchEntry {
   BatchPlanHead head;
@@ -336,6 +338,10 @@ int launch_gibbs(int precision, int mode, const PlanDev &plan, const RunArgs &ar
 // a group of fp64 products of M (2..4) densities in one launch (gibbs_dispatch.cpp; RunArgs.batch / batch_map)
 int launch_gibbs_batch(int D, int M, const PlanDev &plan, const RunArgs &args, void *stream);
 int launch_tables_batch(int D, const PlanDev &plan, const RunArgs &args, void *stream);
+// a group of fp64 products in the circular fast mode (kModeFastCirc), D dimensions and any density count, in one launch of
+// the general kernel: kCircBatchWaves chains per workgroup; args.Np = workgroups x kCircBatchWaves
+constexpr int kCircBatchWaves = 8;
+int launch_gibbs_circ_batch(int D, const PlanDev &plan, const RunArgs &args, void *stream);
 
 // kde!(points)'s LOOCV bandwidth search (loocv.hip) on `stream` of the current device, from the host's copy of the
 // D x N matrix and/or a copy that already lives in HBM (`d_points`: nothing is uploaded then).  Blocking.

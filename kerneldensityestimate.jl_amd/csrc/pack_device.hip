@@ -748,8 +748,8 @@ extern "C" int kdehip_mul_device_batch(int nprod, const kdehip_mul_item *items, 
   return kdehip_mul_device_batch_manifold(nprod, items, nullptr, out, bw_out, nevals);
 }
 // manifolds: NULL, or nprod rows of KDEHIP_MAX_DIMS bytes (row i: the manifold of item i in its first ndims bytes).  Items without a circular dimension take the batched
-// sampler as before; circular items are sampled one by one inside the same call (kModeFastCirc is outside the batched
-// kernel's domain, like a mask), and their bandwidth searches run in the shared launches of their (D, N, manifold) group.
+// sampler as before; circular items in the circular fast mode ride the general kernel's batched launch, one per dimension
+// count (prod_philox_batch_manifold), and their bandwidth searches run in the shared launches of their (D, N, manifold) group.
 extern "C" int kdehip_mul_device_batch_manifold(int nprod, const kdehip_mul_item *items, const uint8_t *manifolds,
                                                 kdehip_device_density **out, double *bw_out, int32_t *nevals) {
   return kdehip_mul_device_batch_tree(nprod, items, manifolds, nullptr, out, bw_out, nevals);

@@ -331,11 +331,28 @@ void bind_plan(kdehip_product *p, size_t off_lev, size_t off_count, size_t off_t
       if (sc.stage_mode == kStageScreenChunked) p->dev.screened = 2;  // (selects the sampler build that knows chunked screens)
 }
 
+// The manifold of an entry that takes host trees (ndims bytes or NULL) as circular bits, with the argument errors every
+// circular entry has: ndims above KDEHIP_MAX_DIMS is KDEHIP_ERR_UNSUPPORTED, an enum value above 1 KDEHIP_ERR_ARG, a circular
+// dimension in fp32 KDEHIP_ERR_UNSUPPORTED (the circular operators exist in fp64 only).  Touches no device.
+int manifold_circ_bits(const uint8_t *manifold, int ndims, int precision, uint32_t *bits) {
+  *bits = 0;
+  if (!manifold) return KDEHIP_OK;
+  if (ndims < 1 || ndims > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
+  for (int d = 0; d < ndims; ++d) {
+    if (manifold[d] > KDEHIP_MANIFOLD_CIRCULAR) return set_error(KDEHIP_ERR_ARG, "manifold: 0 (Euclidean) or 1 (circular) per dimension");
+    if (manifold[d] == KDEHIP_MANIFOLD_CIRCULAR) *bits |= 1u << d;
+  }
+  if (*bits != 0u && precision == 32) return set_error(KDEHIP_ERR_UNSUPPORTED, "circular dimensions need precision 64");
+  return KDEHIP_OK;
+}
+
 // A plan on `device` from an image: one device allocation, one DMA transfer (hipMalloc / hipFree cost tens of
 // microseconds each and would dominate a one-shot small product; blocks come from the library's cache).
 // wait = false (one-shot calls, whose image outlives the work they enqueue): the upload is left in flight on the
 // calling thread's stream (call_stream); everything the caller enqueues there afterwards is ordered behind it.
-int instantiate(const PlanImage &im, int device, kdehip_product **out, bool wait = true) {
+// circ_bits != 0: the plan runs the circular operators, its arithmetic chosen as layout_resident chooses it for resident
+// densities -- the circular fast mode (kModeFastCirc) when the image was packed in the fast form, else the generic one.
+int instantiate(const PlanImage &im, int device, kdehip_product **out, bool wait = true, uint32_t circ_bits = 0) {
   *out = nullptr;
   kdehip_product *p = new (std::nothrow) kdehip_product();
   if (!p) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
@@ -347,6 +364,8 @@ int instantiate(const PlanImage &im, int device, kdehip_product **out, bool wait
   p->host = im.host;  // descriptors (the frontier ids were released by build_image)
   p->fast = p->host.fast;
   p->mode = !p->host.fast ? kModeGeneric : (p->host.all_active ? kModeFast : kModeFastMasked);
+  p->circ_bits = circ_bits;
+  if (circ_bits != 0u && p->host.fast) p->mode = kModeFastCirc;
   hipError_t e = cached_malloc(&p->d_blob, im.total);
   if (e == hipSuccess) p->blob_bytes = im.total;
   if (e == hipSuccess) e = hipMemcpyAsync(p->d_blob, im.h_blob, im.off_tables, hipMemcpyHostToDevice, call_stream());
@@ -404,12 +423,23 @@ int kdehip_device_count(void) {
 
 int kdehip_product_create(kdehip_product **out, int Ndens, const kdehip_density *trees, int ndims,
                           const uint8_t *partialDimMask, int precision, int device) {
+  return kdehip_product_create_manifold(out, Ndens, trees, ndims, partialDimMask, nullptr, precision, device);
+}
+
+// The same on a manifold: the tiles are the Euclidean plan's, the sampler runs the circular operators (the fast forms,
+// kModeFastCirc, when the node values qualify, else the generic arithmetic; no conditional tables, no fp32 screens).  NULL or
+// all zeros IS the entry above.
+int kdehip_product_create_manifold(kdehip_product **out, int Ndens, const kdehip_density *trees, int ndims,
+                                   const uint8_t *partialDimMask, const uint8_t *manifold, int precision, int device) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
-  PlanImage im;
-  int rc = build_image(im, Ndens, trees, ndims, partialDimMask, precision);
+  uint32_t circ_bits = 0;
+  int rc = manifold_circ_bits(manifold, ndims, precision, &circ_bits);
   if (rc != KDEHIP_OK) return rc;
-  return instantiate(im, device, out);
+  PlanImage im;
+  rc = build_image(im, Ndens, trees, ndims, partialDimMask, precision);
+  if (rc != KDEHIP_OK) return rc;
+  return instantiate(im, device, out, /*wait=*/true, circ_bits);
 }
 
 void kdehip_product_destroy(kdehip_product *plan) {
@@ -581,17 +611,14 @@ struct Shard {
 int one_shot(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, double *pts, int64_t *ind,
              const double *randU, int64_t nU, const double *randN, int64_t nN, uint64_t seed, int addEntropy,
              int ndims, const uint8_t *partialDimMask, int precision, int device, int ngpus, int32_t *labels,
-             const uint8_t *manifold = nullptr) {
-  // the enumerated manifolds (kdehip.h "manifolds"): bit d of circ_bits = dimension d is circular
+             const uint8_t *manifold = nullptr, bool circ_fast = false) {
+  // the enumerated manifolds (kdehip.h "manifolds"): bit d of circ_bits = dimension d is circular.  circ_fast: the
+  // arithmetic of a circular product is chosen as a plan's is (kdehip_prod_philox_manifold); otherwise it is the generic one
+  // (kdehip_gibbs1_manifold: the reference's own accumulation)
   uint32_t circ_bits = 0;
-  if (manifold) {
-    if (ndims < 1 || ndims > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-    for (int d = 0; d < ndims; ++d) {
-      if (manifold[d] > KDEHIP_MANIFOLD_CIRCULAR) return set_error(KDEHIP_ERR_ARG, "manifold: 0 (Euclidean) or 1 (circular) per dimension");
-      if (manifold[d] == KDEHIP_MANIFOLD_CIRCULAR) circ_bits |= 1u << d;
-    }
-  }
-  int rc = check_devices(device, ngpus);
+  int rc = manifold_circ_bits(manifold, ndims, precision, &circ_bits);
+  if (rc != KDEHIP_OK) return rc;
+  rc = check_devices(device, ngpus);
   if (rc != KDEHIP_OK) {
     // argument errors of the product itself take precedence over "no device" only when they are detectable
     // without one: validate the densities first so that hosts without a GPU still get the reference's messages
@@ -612,7 +639,7 @@ int one_shot(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, doub
       for (int d : devs) if (g.enter(d) == KDEHIP_OK) (void)hipStreamSynchronize(call_stream());
     }
   };
-  rc = build_image(im, Ndens, trees, ndims, partialDimMask, precision, /*force_generic=*/circ_bits != 0u);
+  rc = build_image(im, Ndens, trees, ndims, partialDimMask, precision, /*force_generic=*/circ_bits != 0u && !circ_fast);
   if (rc != KDEHIP_OK) return rc;
   const double us_pack = us_since(t_begin);
   if (Np < 0) return set_error(KDEHIP_ERR_ARG, "Np must be >= 0");
@@ -646,9 +673,8 @@ int one_shot(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, doub
     S.hi = share_begin(Np, g + 1, ngpus);
     const int64_t n = S.hi - S.lo;
     drain.devs.push_back(S.device);
-    rc = instantiate(im, S.device, &S.plan, /*wait=*/false);  // the upload overlaps the host side of the launches
+    rc = instantiate(im, S.device, &S.plan, /*wait=*/false, circ_bits);  // the upload overlaps the host side of the launches
     if (rc != KDEHIP_OK) return rc;
-    S.plan->dev.circ_bits = circ_bits;
     rc = guard.enter(S.device);
     if (rc != KDEHIP_OK) return rc;
     const int64_t useU = streams ? ((nU - S.lo * K < n * K) ? nU - S.lo * K : n * K) : 0, useN = streams ? n * R : 0;
@@ -744,6 +770,15 @@ int kdehip_prod_philox(int Ndens, const kdehip_density *trees, int64_t Np, int N
                        int device, int ngpus, int32_t *labels) {
   return one_shot(Ndens, trees, Np, Niter, pts, ind, nullptr, 0, nullptr, 0, seed, addEntropy, ndims, partialDimMask,
                   precision, device, ngpus, labels);
+}
+
+// The same on a manifold, on one or several GPUs: a circular plan per device (kdehip_product_create_manifold's mode
+// selection), chains in contiguous ranges, Philox keyed by the global sample index.  NULL or all zeros IS the entry above.
+int kdehip_prod_philox_manifold(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, double *pts, int64_t *ind,
+                                uint64_t seed, int addEntropy, int ndims, const uint8_t *partialDimMask,
+                                const uint8_t *manifold, int precision, int device, int ngpus, int32_t *labels) {
+  return one_shot(Ndens, trees, Np, Niter, pts, ind, nullptr, 0, nullptr, 0, seed, addEntropy, ndims, partialDimMask,
+                  precision, device, ngpus, labels, manifold, /*circ_fast=*/true);
 }
 
 // ---- products of densities that live in HBM (pack_device.hip) ------------------------------------------------------
@@ -913,14 +948,7 @@ int describe_resident(kdehip_product *p, kdehip_device_density *const *trees, co
 int resident_circ_bits(const uint8_t *manifold, int Ndens, kdehip_device_density *const *trees, int precision, uint32_t *bits) {
   *bits = 0;
   if (!manifold || Ndens < 1 || !trees || !trees[0]) return KDEHIP_OK;
-  const int ndims = trees[0]->D;
-  if (ndims < 1 || ndims > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  for (int d = 0; d < ndims; ++d) {
-    if (manifold[d] > KDEHIP_MANIFOLD_CIRCULAR) return set_error(KDEHIP_ERR_ARG, "manifold: 0 (Euclidean) or 1 (circular) per dimension");
-    if (manifold[d] == KDEHIP_MANIFOLD_CIRCULAR) *bits |= 1u << d;
-  }
-  if (*bits != 0u && precision == 32) return set_error(KDEHIP_ERR_UNSUPPORTED, "circular dimensions need precision 64");
-  return KDEHIP_OK;
+  return manifold_circ_bits(manifold, trees[0]->D, precision, bits);
 }
 
 // own_prep: prepare on the library's stream (an asynchronous caller: the next product's preparation overlaps this
@@ -982,6 +1010,9 @@ bool batchable(const kdehip_product *p) {
   const int M = p->host.M, L = p->host.L, D = p->host.D;
   return p->precision == 64 && p->mode == kModeFast && M >= 2 && M <= 4 && D * (L + 1) <= 128;
 }
+// ... or in one of the general sampler's circular fast mode (gibbs_kernel.hip, the BATCH sampling instantiation of its
+// circular translation units: fp64, any density count, masks included)
+bool circ_batchable(const kdehip_product *p) { return p->precision == 64 && p->mode == kModeFastCirc; }
 
 }  // namespace
 
@@ -991,12 +1022,42 @@ bool batchable(const kdehip_product *p) {
 // chain block), every workgroup fetching its product's plan through the scalar cache.  Each product's result is bit for
 // bit what kdehip_prod_philox_device gives for it (same layout, same kernel code, same Philox keys).  Products outside
 // the batched kernel's domain (fp32, masks, 1 or more than 4 densities) are enqueued one by one inside the same call.
+// kdehip_prod_philox_batch_launches: of the calling thread's last batch call that got as far as launching, [batched sampling
+// launches, items enqueued one by one]
+static thread_local int32_t t_batch_launches[2] = {0, 0};
+void kdehip_prod_philox_batch_launches(int32_t *batched, int32_t *singles) {
+  if (batched) *batched = t_batch_launches[0];
+  if (singles) *singles = t_batch_launches[1];
+}
+
 int kdehip_prod_philox_batch(int nprod, const kdehip_batch_item *items, int precision, void *stream) {
   return kdehip::prod_philox_batch_manifold(nprod, items, nullptr, precision, stream);
 }
+
+// The same with a manifold per item: manifolds == NULL, or nprod rows of KDEHIP_MAX_DIMS bytes (row i: the manifold of item i
+// in its first ndims bytes, zeros behind them).  The rows are checked before any density or device is looked at.
+int kdehip_prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items, const uint8_t *manifolds, int precision,
+                                      void *stream) {
+  if (!manifolds) return kdehip::prod_philox_batch_manifold(nprod, items, nullptr, precision, stream);
+  if (nprod < 0 || (nprod > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "kdehip_prod_philox_batch: bad item list");
+  // (the WHOLE row here, an item's own ndims bytes again where its plan is laid out: a row can be refused without a density)
+  std::vector<const uint8_t *> rows(static_cast<size_t>(nprod), nullptr);
+  for (int i = 0; i < nprod; ++i) {
+    const uint8_t *row = manifolds + static_cast<size_t>(i) * KDEHIP_MAX_DIMS;
+    uint32_t bits = 0;
+    const int rc = manifold_circ_bits(row, KDEHIP_MAX_DIMS, precision, &bits);
+    if (rc != KDEHIP_OK) return rc;
+    const kdehip_batch_item &it = items[i];
+    const int D = (it.Ndens >= 1 && it.trees && it.trees[0]) ? it.trees[0]->D : KDEHIP_MAX_DIMS;
+    if (D >= 0 && D < KDEHIP_MAX_DIMS && (bits >> D) != 0u)
+      return set_error(KDEHIP_ERR_ARG, "manifold: a circular dimension beyond the item's ndims");
+    if (bits != 0u) rows[i] = row;
+  }
+  return kdehip::prod_philox_batch_manifold(nprod, items, rows.data(), precision, stream);
+}
 }  // extern "C"
-// (manifolds: NULL, or per item a manifold of its ndims bytes or NULL; an item with a circular dimension is outside the
-// batched kernel's domain and is enqueued on its own, like a masked one)
+// (manifolds: NULL, or per item a manifold of its ndims bytes or NULL.  Circular items whose plans reach the circular fast
+// mode ride one launch per dimension count; those on the generic arithmetic are enqueued one by one, like masked Euclidean ones)
 int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items, const uint8_t *const *manifolds, int precision,
                                        void *stream) {
   if (nprod < 0 || (nprod > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "kdehip_prod_philox_batch: bad item list");
@@ -1035,7 +1096,8 @@ int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items
   if (device < 0 || device >= kMaxDevices) return set_error(KDEHIP_ERR_UNSUPPORTED, "device ordinal beyond the library's bookkeeping (64)");
   // groups of batchable products by (D, M); everything else runs one by one
   struct Group {
-    int D, M;
+    int D, M;           // (M = 0: a group of the circular fast mode, any density count)
+    int waves = 16;     // chains per workgroup of the group's batched instantiation
     std::vector<int> members;
     int64_t blocks = 0;
     size_t ent_at = 0, map_at = 0;
@@ -1048,16 +1110,26 @@ int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items
   constexpr int kTabWaves = 4;
   std::vector<Group> groups;
   std::vector<int> singles;
-  constexpr int kBatchWaves = 16;  // chains per workgroup of the batched instantiations
+  constexpr int kBatchWaves = 16;  // chains per workgroup of gibbs_lean.hip's batched instantiations
   for (int i = 0; i < nprod; ++i) {
     if (items[i].Np == 0) continue;
     kdehip_product *p = plans[i];
-    if (!batchable(p)) { singles.push_back(i); continue; }
+    // KDEHIP_BATCH_CIRC=0 (read once per process, like KDEHIP_BATCH_TABLES below; include/kdehip.h section 2e): circular items one
+    // by one, the route before the batched instantiation existed -- the baseline of scripts/circular_batch_timing.py and of
+    // DESIGN section 17's table; the results are the same bits either way (tests/test_gpu_circular_batch.py runs both)
+    static const bool circ_batch_on = [] { const char *e = std::getenv("KDEHIP_BATCH_CIRC"); return !(e && e[0] == '0'); }();
+    const bool circ = circ_batch_on && circ_batchable(p);
+    if (!circ && !batchable(p)) { singles.push_back(i); continue; }
+    const int gM = circ ? 0 : p->host.M;
     Group *g = nullptr;
-    for (Group &c : groups) if (c.D == p->host.D && c.M == p->host.M) g = &c;
-    if (!g) { groups.emplace_back(); g = &groups.back(); g->D = p->host.D; g->M = p->host.M; }
+    for (Group &c : groups) if (c.D == p->host.D && c.M == gM) g = &c;
+    if (!g) {
+      groups.emplace_back();
+      g = &groups.back();
+      g->D = p->host.D; g->M = gM; g->waves = circ ? kCircBatchWaves : kBatchWaves;
+    }
     g->members.push_back(i);
-    g->blocks += (items[i].Np + kBatchWaves - 1) / kBatchWaves;
+    g->blocks += (items[i].Np + g->waves - 1) / g->waves;
   }
   for (size_t k = 0; k < groups.size();)  // a group of one gains nothing from the batched kernel
     if (groups[k].members.size() == 1) { singles.push_back(groups[k].members[0]); groups.erase(groups.begin() + k); } else ++k;
@@ -1068,7 +1140,7 @@ int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items
   static const int force_tables = [] { const char *e = std::getenv("KDEHIP_BATCH_TABLES"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
   auto has_tables = [&](int i) {
     const kdehip_product *p = plans[i];
-    if (p->mode == kModeGeneric || p->host.Lt <= 0 || p->host.tab_rows <= 0 || items[i].Np < kTabMinChains) return false;
+    if (p->mode == kModeGeneric || p->mode == kModeFastCirc || p->host.Lt <= 0 || p->host.tab_rows <= 0 || items[i].Np < kTabMinChains) return false;
     if (force_tables >= 0) return force_tables == 1;
     const double saved = static_cast<double>(items[i].Np) * p->host.Lt * items[i].Niter * p->host.M;
     return saved >= 6.5 * static_cast<double>(p->host.tab_rows);
@@ -1118,8 +1190,9 @@ int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items
       be.run.points = it.d_points; be.run.indices = it.d_indices; be.run.labels = it.d_labels;
       be.flags.Niter = it.Niter; be.flags.addEntropy = it.addEntropy ? 1 : 0; be.flags.use_tables = has_tables(i) ? 1 : 0;
       be.flags.first_block = block;
+      be.flags.circ_bits = pd.circ_bits;
       ent[k] = be;
-      const int32_t nb = static_cast<int32_t>((it.Np + kBatchWaves - 1) / kBatchWaves);
+      const int32_t nb = static_cast<int32_t>((it.Np + g.waves - 1) / g.waves);
       for (int32_t q = 0; q < nb; ++q) map[block + q] = static_cast<int32_t>(k);
       block += nb;
     }
@@ -1140,6 +1213,8 @@ int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items
   if (blk.upload(head_bytes, st) != hipSuccess) return set_error(KDEHIP_ERR_HIP, "batched products: descriptor upload failed");
   rc = launch_fill_tiles(precision, reinterpret_cast<const FillJob *>(db + off_jobs), static_cast<int>(njobs), maxB, st);
   if (rc != KDEHIP_OK) return rc;
+  t_batch_launches[0] = static_cast<int32_t>(groups.size());
+  t_batch_launches[1] = static_cast<int32_t>(singles.size());
   for (const Group &g : groups) {
     if (g.tab_blocks > 0) {  // one launch fills the conditional tables of every member that has them
       RunArgs t{};
@@ -1154,8 +1229,9 @@ int kdehip::prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items
     a.rng_philox = 1;
     a.batch = reinterpret_cast<const BatchEntry *>(db + g.ent_at);
     a.batch_map = reinterpret_cast<const int32_t *>(db + g.map_at);
-    a.Np = g.blocks * kBatchWaves;  // (the launcher's grid: g.blocks workgroups)
-    rc = launch_gibbs_batch(g.D, g.M, plans[g.members[0]]->dev, a, st);
+    a.Np = g.blocks * g.waves;  // (the launcher's grid: g.blocks workgroups)
+    rc = g.M == 0 ? launch_gibbs_circ_batch(g.D, plans[g.members[0]]->dev, a, st)
+                  : launch_gibbs_batch(g.D, g.M, plans[g.members[0]]->dev, a, st);
     if (rc != KDEHIP_OK) return rc;
   }
   for (int i : singles) {
@@ -1317,9 +1393,20 @@ bool peer_can_store(const void *p, int writer) {
 
 int kdehip_product_multi_create(kdehip_product_multi **out, int Ndens, const kdehip_density *trees, int ndims,
                                 const uint8_t *partialDimMask, int precision, int first_device, int ngpus) {
+  return kdehip_product_multi_create_manifold(out, Ndens, trees, ndims, partialDimMask, nullptr, precision, first_device, ngpus);
+}
+
+// The same on a manifold: the circular plan of kdehip_product_create_manifold on every device (the fused peer-store epilogue
+// is the kernel's, whatever its arithmetic mode).  NULL or all zeros IS the entry above.
+int kdehip_product_multi_create_manifold(kdehip_product_multi **out, int Ndens, const kdehip_density *trees, int ndims,
+                                         const uint8_t *partialDimMask, const uint8_t *manifold, int precision,
+                                         int first_device, int ngpus) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
-  int rc = check_devices(first_device, ngpus);
+  uint32_t circ_bits = 0;
+  int rc = manifold_circ_bits(manifold, ndims, precision, &circ_bits);
+  if (rc != KDEHIP_OK) return rc;
+  rc = check_devices(first_device, ngpus);
   if (rc != KDEHIP_OK) return rc;
   PlanImage im;
   rc = build_image(im, Ndens, trees, ndims, partialDimMask, precision);
@@ -1332,7 +1419,7 @@ int kdehip_product_multi_create(kdehip_product_multi **out, int Ndens, const kde
   DeviceGuard guard;
   for (int g = 0; g < ngpus && rc == KDEHIP_OK; ++g) {
     kdehip_product *p = nullptr;
-    rc = instantiate(im, phys(first_device + g), &p);
+    rc = instantiate(im, phys(first_device + g), &p, /*wait=*/true, circ_bits);
     if (rc != KDEHIP_OK) break;
     mp->plans.push_back(p);
     rc = guard.enter(phys(first_device + g));

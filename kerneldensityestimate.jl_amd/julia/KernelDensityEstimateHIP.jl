@@ -306,6 +306,36 @@ function mul_batch(products::Vector{Vector{DeviceDensity}}; addEntropy::Bool=tru
 end
 
 """
+    hip_prod_manifold(trees::Vector{BallTreeDensity}, manifold; Np, Niter=3, addEntropy=true, partialDimMask=nothing,
+                      seed=nothing, device=0, ngpus=1) -> (points, indices)
+
+`prodAppxMSGibbsS` without caller streams on a manifold, on one or several GPUs (`kdehip_prod_philox_manifold`,
+include/kdehip.h section 2): device Philox keyed by `seed`, the sampler's circular fast mode where the densities qualify,
+the same numbers for every `ngpus`.  Labels are those of `gibbs1` with the enum manifold on the host twin of the Philox
+streams; points agree with it to rounding (1e-12, on the circle in the circular dimensions).  `manifold`: as `hip_mul`.
+The plan and batch entries of sections 2, 2b and 2e (`kdehip_product_create_manifold`, `kdehip_product_multi_create_manifold`,
+`kdehip_prod_philox_batch_manifold`) have no wrapper here, as their Euclidean forms have none: this shim binds no plans.
+"""
+function hip_prod_manifold(trees::Vector{BallTreeDensity}, manifold; Np::Int, Niter::Int=3, addEntropy::Bool=true,
+                           partialDimMask=nothing, seed::Union{Nothing,UInt64}=nothing, device::Int=0, ngpus::Int=1)
+  Ndens = length(trees)
+  ndims = trees[1].bt.dims
+  cds = CDensity[CDensity(t) for t in trees]
+  mask = maskbytes(partialDimMask, Ndens, ndims)
+  man = manifold_bytes(manifold, ndims)
+  points = zeros(ndims * Np)
+  indices = ones(Int64, Ndens, Np)
+  s = seed === nothing ? rand(UInt64) : seed
+  GC.@preserve trees cds mask man begin
+    check(ccall((:kdehip_prod_philox_manifold, libkdehip), Cint,
+                (Cint, Ptr{CDensity}, Int64, Cint, Ptr{Float64}, Ptr{Int64}, UInt64, Cint, Cint, Ptr{UInt8}, Ptr{UInt8}, Cint,
+                 Cint, Cint, Ptr{Int32}),
+                Ndens, cds, Np, Niter, points, indices, s, addEntropy ? 1 : 0, ndims, mask, man, 64, device, ngpus, C_NULL))
+  end
+  return reshape(points, ndims, Np), indices
+end
+
+"""
     hip_mul(trees::Vector{DeviceDensity}, manifold; addEntropy=true, seed=nothing) -> DeviceDensity
 
 `*` on resident densities on a manifold (`kdehip_mul_device_manifold`, include/kdehip.h section 2d): the circular product,

@@ -25,6 +25,14 @@ def _mask_array(partialDimMask, Ndens, ndims):
     return m
 
 
+def _plan_manifold(manifold, ndims):
+    """the `manifold=` of a plan as the enum array: a wrong length or a name outside the enum is a ValueError"""
+    try:
+        return _manifold_array(manifold, ndims)
+    except KeyError as e:
+        raise ValueError(f"manifold: {e.args[0]!r} is not 'euclid' or 'circular'") from None
+
+
 def nlevels(maxNp: int) -> int:
     """floor(Int, log(maxNp)/log(2) + 1) (reference src/MSGibbs01.jl:568, :660)."""
     return int(math.floor(math.log(float(maxNp)) / math.log(2.0) + 1.0))
@@ -35,19 +43,23 @@ class ProductPlan:
 
     Keeps inputs on the device across calls: the timed region of bench.py and repeated products on
     the same densities start from HBM-resident data.
+    `manifold`: the per-dimension enum of `gibbs1` -- every run of the plan applies the circular operators
+    (kdehip_product_create_manifold; precision 64 only), with the numbers of `prodAppxMSGibbsS_device(manifold=)`.
     """
 
-    def __init__(self, trees, partialDimMask=None, precision=64, device=0, ndims=None):
+    def __init__(self, trees, partialDimMask=None, precision=64, device=0, ndims=None, manifold=None):
         trees = list(trees)
         self.Ndens = len(trees)
         self.ndims = int(ndims) if ndims is not None else max(Ndim(t) for t in trees)
         self._keep = trees  # arrays must outlive the create call only; kept for introspection
+        self.manifold = _plan_manifold(manifold, self.ndims)   # the uint8 enum array, or None
         arr = (_lib.CDensity * self.Ndens)(*[t._cstruct() for t in trees])
         mask = _mask_array(partialDimMask, self.Ndens, self.ndims)
         h = C.c_void_p()
-        _lib.check(_lib.lib.kdehip_product_create(C.byref(h), self.Ndens, arr, self.ndims,
-                                                  None if mask is None else ptr(mask, u8p),
-                                                  int(precision), int(device)))
+        _lib.check(_lib.lib.kdehip_product_create_manifold(C.byref(h), self.Ndens, arr, self.ndims,
+                                                           None if mask is None else ptr(mask, u8p),
+                                                           None if self.manifold is None else ptr(self.manifold, u8p),
+                                                           int(precision), int(device)))
         self._h = h
         info = _lib.CProductInfo()
         _lib.check(_lib.lib.kdehip_product_info(self._h, C.byref(info)))
@@ -156,18 +168,21 @@ class ProductPlan:
 class MultiProductPlan:
     """One resident plan per GPU of a node, one process (kdehip_product_multi_*): chains in contiguous ranges, Philox
     counters keyed by the global sample index, one all-gather of [pGM | indices] fused into the sampling kernel (peer
-    stores over xGMI), after which every device holds the complete result."""
+    stores over xGMI), after which every device holds the complete result.  `manifold`: as `ProductPlan`
+    (kdehip_product_multi_create_manifold): the circular plan on every device, the same result for every `ngpus`."""
 
-    def __init__(self, trees, partialDimMask=None, precision=64, first_device=0, ngpus=1, ndims=None):
+    def __init__(self, trees, partialDimMask=None, precision=64, first_device=0, ngpus=1, ndims=None, manifold=None):
         trees = list(trees)
         self.Ndens = len(trees)
         self.ndims = int(ndims) if ndims is not None else max(Ndim(t) for t in trees)
+        self.manifold = _plan_manifold(manifold, self.ndims)
         arr = (_lib.CDensity * self.Ndens)(*[t._cstruct() for t in trees])
         mask = _mask_array(partialDimMask, self.Ndens, self.ndims)
         h = C.c_void_p()
-        _lib.check(_lib.lib.kdehip_product_multi_create(C.byref(h), self.Ndens, arr, self.ndims,
-                                                        None if mask is None else ptr(mask, u8p), int(precision),
-                                                        int(first_device), int(ngpus)))
+        _lib.check(_lib.lib.kdehip_product_multi_create_manifold(C.byref(h), self.Ndens, arr, self.ndims,
+                                                                 None if mask is None else ptr(mask, u8p),
+                                                                 None if self.manifold is None else ptr(self.manifold, u8p),
+                                                                 int(precision), int(first_device), int(ngpus)))
         self._h = h
         self.first_device = int(first_device)
         self.ngpus = int(_lib.lib.kdehip_product_multi_ngpus(self._h))
@@ -451,7 +466,8 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tr
     `DeviceDensity` per product, each bit for bit what `mul_device(products[i], addEntropy=..., seed=seeds[i])` returns --
     batched sampler, the LOOCV searches of all results of one size in shared launches, trees built under them.
     `addEntropy`: one flag or one per product.  `manifold`: one for all products or one per product (None = Euclidean);
-    circular products are sampled one by one inside the call, their searches share launches (kdehip_mul_device_batch_manifold).
+    circular products ride the batched launch of the sampler's circular fast mode (`prodAppxMSGibbsS_batch(manifold=)`), their
+    searches share launches (kdehip_mul_device_batch_manifold).
     `tree_manifold`: the tree builders' operators, one for all products or one per product like `manifold`
     (kdehip_mul_device_batch_tree); products with and without a circular tree may be mixed."""
     products = [list(p) for p in products]
@@ -494,10 +510,22 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tr
 
 class ProductBatch:
     """The argument block of one `kdehip_prod_philox_batch` call, built once: a host that issues the same set of products
-    sweep after sweep (only seeds / sample offsets change) does not pay the Python-side marshalling per call."""
+    sweep after sweep (only seeds / sample offsets change) does not pay the Python-side marshalling per call.
+    `manifold`: one for all products or one per product (None = Euclidean), by the convention of `mul_device_batch`; a
+    product's own "manifold" key takes precedence (kdehip_prod_philox_batch_manifold)."""
 
-    def __init__(self, products, precision=64):
+    def __init__(self, products, precision=64, manifold=None):
         n = len(products)
+        dims = [list(pr["trees"])[0].dims for pr in products]
+        mans = _batch_manifolds(manifold, dims)
+        self.manifolds = [(_manifold_array(pr["manifold"], d) if pr.get("manifold") is not None else m)
+                          for pr, d, m in zip(products, dims, mans)]
+        self._marr = None   # nprod rows of MAX_DIMS bytes, or None when every product is Euclidean
+        if any(m is not None and m.any() for m in self.manifolds):
+            self._marr = np.zeros((n, _lib.MAX_DIMS), dtype=np.uint8)
+            for k, m in enumerate(self.manifolds):
+                if m is not None:
+                    self._marr[k, :len(m)] = m
         self.n = n
         self.precision = int(precision)
         self.items = (_lib.CBatchItem * max(1, n))()
@@ -525,16 +553,31 @@ class ProductBatch:
         if sample_offset is not None:
             for k in range(self.n):
                 self.items[k].sample_offset = int(sample_offset)
-        _lib.check(_lib.lib.kdehip_prod_philox_batch(self.n, self.items, self.precision, ProductPlan._addr(stream)))
+        if self._marr is None:
+            _lib.check(_lib.lib.kdehip_prod_philox_batch(self.n, self.items, self.precision, ProductPlan._addr(stream)))
+        else:
+            _lib.check(_lib.lib.kdehip_prod_philox_batch_manifold(self.n, self.items, ptr(self._marr, u8p), self.precision,
+                                                                  ProductPlan._addr(stream)))
 
 
-def prodAppxMSGibbsS_batch(products, *, precision=64, stream=None):
+def batch_launches() -> dict:
+    """Diagnostic (kdehip_prod_philox_batch_launches): of this thread's last `prodAppxMSGibbsS_batch` / `ProductBatch.enqueue`
+    / `mul_device_batch`, the batched sampling launches (one per group) and the products enqueued one by one."""
+    b, s = C.c_int32(0), C.c_int32(0)
+    _lib.lib.kdehip_prod_philox_batch_launches(C.byref(b), C.byref(s))
+    return {"batched": int(b.value), "singles": int(s.value)}
+
+
+def prodAppxMSGibbsS_batch(products, *, precision=64, stream=None, manifold=None):
     """Many `prodAppxMSGibbsS` calls on `DeviceDensity` inputs in ONE library call (kdehip_prod_philox_batch): one device
     block, one gather launch, and one sampling launch per (dimension count, density count) group of fp64 products of 2..4
     densities.  `products`: dicts with the keywords of `prodAppxMSGibbsS_device` (trees, d_points, d_indices, Np, and
     optionally Niter=3, seed=0, sample_offset=0, addEntropy=True, partialDimMask, d_labels).  Every product gets the
-    numbers the single call would give it.  Enqueues on `stream` and returns."""
-    ProductBatch(products, precision).enqueue(stream)
+    numbers the single call would give it.  Enqueues on `stream` and returns.
+    `manifold`: one for all products or one per product (or a "manifold" key in a product's dict): circular products whose
+    densities qualify for the fast forms ride one launch per dimension count, each with the numbers of
+    `prodAppxMSGibbsS_device(manifold=)` (kdehip_prod_philox_batch_manifold)."""
+    ProductBatch(products, precision, manifold).enqueue(stream)
 
 
 def prodAppxMSGibbsS_device(trees, d_points, d_indices, *, Np, Niter=3, seed=0, sample_offset=0, addEntropy=True,
@@ -670,7 +713,7 @@ def gibbs1(Ndens, trees, Np, Niter, pts, ind, randU, randN, *, addEntropy=True, 
 def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter, Niter=3, addEntropy=True, ndims=None,
                      Ndens=None, Np=None, maxNp=None, Nlevels=None, randU=None, randN=None, partialDimMask=None,
                      addop=None, diffop=None, getMu=None, getLambda=None, glbs=None,
-                     seed=None, device=0, precision=64, ngpus=1, manifold=None):
+                     seed=None, device=0, precision=64, ngpus=1, manifold=None, fast_circular=False):
     """`prodAppxMSGibbsS` (reference src/MSGibbs01.jl:645-703).
 
     npd0 only supplies Np = Npts(npd0) (:658); anFcns/anParams are ignored as in the reference
@@ -684,6 +727,11 @@ def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter,
     positional `Niter` (:632-643).
     The returned matrices are column-major (Fortran-ordered) VIEWS of the flat result buffers, like Julia's: pass them
     through `np.ascontiguousarray` before handing their `.ctypes` pointer to C code that expects row-major data.
+    `manifold` without caller streams: on one GPU the host twin of the Philox streams goes through `gibbs1(manifold=)` -- the
+    generic arithmetic, byte for byte the explicit-stream call.  With `ngpus > 1`, or with `fast_circular=True` on any number
+    of GPUs, the call takes kdehip_prod_philox_manifold instead: device Philox and the sampler's circular fast mode, the
+    numbers of `ProductPlan(manifold=).sample(seed)` and the same for every `ngpus`.  The two routes return identical labels;
+    their points differ by rounding only (within 1e-12, compared on the circle in the circular dimensions).
     """
     if deprecated_niter:
         if len(deprecated_niter) > 1:
@@ -703,7 +751,8 @@ def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter,
         Np = Npts(npd0)
     if (randU is None) != (randN is None):
         raise ValueError("give both randU and randN, or neither")
-    if manifold is not None and randU is None:
+    philox_manifold = manifold is not None and randU is None and (bool(fast_circular) or int(ngpus) != 1)
+    if manifold is not None and randU is None and not philox_manifold:
         # the manifold entry consumes caller streams: the host twin of the device stream gives the run the numbers the
         # Philox path would have drawn for `seed`
         if seed is None:
@@ -725,10 +774,12 @@ def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter,
     pts = np.empty(ndims * Np)   # (every element is written by the call)
     ind = np.empty(Ndens * Np, dtype=np.int64)
     labels = np.zeros((Np, Ndens, nlevels(max(Npts(t) for t in trees))), dtype=np.int32) if trace else None
-    _lib.check(_lib.lib.kdehip_prod_philox(int(Ndens), arr, int(Np), int(Niter), ptr(pts, f64p), ptr(ind, i64p),
-                                           C.c_uint64(int(seed) & (2 ** 64 - 1)), int(bool(addEntropy)), int(ndims),
-                                           None if mask is None else ptr(mask, u8p), int(precision), int(device),
-                                           int(ngpus), None if labels is None else ptr(labels, i32p)))
+    man = _manifold_array(manifold, ndims) if philox_manifold else None
+    _lib.check(_lib.lib.kdehip_prod_philox_manifold(int(Ndens), arr, int(Np), int(Niter), ptr(pts, f64p), ptr(ind, i64p),
+                                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), int(bool(addEntropy)), int(ndims),
+                                                    None if mask is None else ptr(mask, u8p),
+                                                    None if man is None else ptr(man, u8p), int(precision), int(device),
+                                                    int(ngpus), None if labels is None else ptr(labels, i32p)))
     if trace:
         glbs._fill(labels, Niter)
     # (ndims, Np) and (Ndens, Np) as the reference returns them: column-major matrices -- views of the flat buffers
