@@ -51,7 +51,8 @@ class CSampleItem(C.Structure):
 
 
 class CSampleManifoldItem(C.Structure):
-    """struct kdehip_sample_manifold_item"""
+    """struct kdehip_sample_manifold_item (the item's fields are reachable on the outer struct: no nested access per item)"""
+    _anonymous_ = ("item",)
     _fields_ = [("item", CSampleItem), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
@@ -72,7 +73,8 @@ class CSummaryItem(C.Structure):
 
 
 class CSummaryManifoldItem(C.Structure):
-    """struct kdehip_summary_manifold_item"""
+    """struct kdehip_summary_manifold_item (likewise)"""
+    _anonymous_ = ("item",)
     _fields_ = [("item", CSummaryItem), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
@@ -289,3 +291,30 @@ def check(rc: int):
 
 def ptr(a, t):
     return a.ctypes.data_as(t)
+
+
+def optr(a, t):
+    """an optional array argument: NULL for None"""
+    return None if a is None else a.ctypes.data_as(t)
+
+
+def addr(x):
+    """a device address (or a stream) for the ABI: a torch tensor, an integer, or None = NULL"""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        return C.c_void_p(x.data_ptr())
+    return C.c_void_p(int(x))
+
+
+SEED_MASK = 2 ** 64 - 1   # a seed is the 64 bits the Philox key takes: `int(seed) & SEED_MASK` in a struct field
+
+
+def u64(seed):
+    """... and as a uint64_t argument"""
+    return C.c_uint64(int(seed) & SEED_MASK)
+
+
+def random_seed() -> int:
+    """the seed of a call that was given none: 64 bits from the operating system"""
+    return int.from_bytes(os.urandom(8), "little")

@@ -7,17 +7,16 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import f64p, ptr, u8p
+from . import _lib, manifold as _mf
+from ._lib import f64p, ptr
 from .density import BallTreeDensity, kde
 
 
 def _man_ptr(manifold, ndims):
     """(array kept alive, ctypes pointer or None) of a `manifold=` keyword: None, or one 'euclid' / 'circular' / 0 / 1 per
     dimension (include/kdehip.h section 5d)"""
-    from .product import _manifold_array
-    man = _manifold_array(manifold, ndims)
-    return man, (None if man is None else ptr(man, u8p))
+    man = _mf.parse(manifold, ndims)
+    return man, _mf.pointer(man)
 
 
 def auto_bandwidth(points, device=0, return_evals=False, manifold=None):

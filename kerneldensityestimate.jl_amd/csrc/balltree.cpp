@@ -23,7 +23,7 @@
 #include "device_density.hpp"
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
-#include "tree_manifold.hpp"
+#include "manifold_arg.hpp"
 
 namespace kdehip {
 namespace {
@@ -328,7 +328,7 @@ extern "C" int kdehip_make_density_tree(int64_t D, int64_t N, const double *poin
       !lowest_leaf || !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin ||
       !bandwidthMax)
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_density: null pointer");
-  if (tree_manifold_mask(tree_manifold, D, nullptr) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  if (manifold_arg(tree_manifold, D, nullptr, kHostTreeManifold) != KDEHIP_OK) return KDEHIP_ERR_ARG;
 
   const size_t nd = static_cast<size_t>(2 * N * D);
   std::memset(centers, 0, nd * sizeof(double));

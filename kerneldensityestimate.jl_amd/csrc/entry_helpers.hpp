@@ -70,17 +70,4 @@ struct DevBuf {
 // (scratch = 64 * Nq doubles).
 constexpr int kEvalMaxGroups = 64;
 
-// The per-dimension manifold enum of include/kdehip.h as a mask (bit k = dimension k is circular); NULL = all Euclidean.
-// Checked before any device is touched: a byte other than 0 / 1 is KDEHIP_ERR_ARG.
-inline int manifold_mask(const uint8_t *manifold, int64_t D, unsigned *mask) {
-  *mask = 0;
-  if (!manifold || D < 1 || D > KDEHIP_MAX_DIMS) return KDEHIP_OK;  // (a bad D is the caller's own refusal)
-  for (int64_t k = 0; k < D; ++k) {
-    if (manifold[k] == KDEHIP_MANIFOLD_CIRCULAR) *mask |= 1u << k;
-    else if (manifold[k] != KDEHIP_MANIFOLD_EUCLIDEAN)
-      return set_error(KDEHIP_ERR_ARG, "manifold: every entry is KDEHIP_MANIFOLD_EUCLIDEAN or KDEHIP_MANIFOLD_CIRCULAR");
-  }
-  return KDEHIP_OK;
-}
-
 }  // namespace kdehip

@@ -32,6 +32,7 @@
 #include "device_density.hpp"
 #include "call_block.hpp"
 #include "entry_helpers.hpp"
+#include "manifold_arg.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
@@ -404,8 +405,8 @@ extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
   if (D < 1 || D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  unsigned circ = 0;
-  if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (N < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
     return set_error(KDEHIP_ERR_ARG, "malformed density");
   if (leave_one_out) Nq = N;
@@ -481,8 +482,8 @@ extern "C" int kdehip_eval_avg_logl_manifold(const kdehip_density *bd, const kde
     for (int k = 0; k < D; ++k)
       if (bd->bandwidth[(N + i) * D + k] != bw[k])
         return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
-  unsigned circ = 0;
-  if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -567,8 +568,8 @@ extern "C" int kdehip_eval_avg_logl_device_manifold(const kdehip_device_density 
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
   int rc = check_pair(bd, at, leave_one_out);
   if (rc != KDEHIP_OK) return rc;
-  unsigned circ = 0;
-  if (manifold_mask(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;
@@ -595,8 +596,8 @@ extern "C" int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, 
   if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
   int rc = check_pair(bd, bd, 0);
   if (rc != KDEHIP_OK) return rc;
-  unsigned circ = 0;
-  if (manifold_mask(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
   rc = guard.enter(bd->device);
@@ -621,8 +622,8 @@ extern "C" int kdehip_evaluate_device_at_manifold(const kdehip_device_density *b
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   int rc = check_pair(bd, at, at == bd);
   if (rc != KDEHIP_OK) return rc;
-  unsigned circ = 0;
-  if (manifold_mask(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;

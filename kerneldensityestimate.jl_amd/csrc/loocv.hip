@@ -26,7 +26,7 @@
 #include "kdehip_internal.hpp"
 #include "loocv_search.hpp"
 #include "phase_timer.hpp"
-#include "tree_manifold.hpp"
+#include "manifold_arg.hpp"
 
 using namespace kdehip;
 
@@ -955,8 +955,8 @@ extern "C" int kdehip_auto_bandwidth_manifold(int64_t D64, int64_t N, const doub
   if (!points || !bw_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   if (D64 < 1 || D64 > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   if (N < 2) return set_error(KDEHIP_ERR_ARG, "kde!(points) needs at least two points");
-  unsigned circ = 0;
-  if (manifold_mask(manifold, D64, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, D64, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
   const int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -1000,9 +1000,9 @@ extern "C" int kdehip_make_density_auto_tree(int64_t D, int64_t N, const double 
                                              const uint8_t *tree_manifold) {
   using namespace kdehip;
   if (D < 1 || N < 2) return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_auto: need D >= 1 and N >= 2");
-  unsigned circ = 0;  // (checked here too: before the tree build starts)
-  if (manifold_mask(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (tree_manifold_mask(tree_manifold, D, nullptr) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  // (checked here too: before the tree build starts)
+  if (manifold_arg(manifold, D, nullptr) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  if (manifold_arg(tree_manifold, D, nullptr, kHostTreeManifold) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (!points || !bw_out || !centers || !ranges || !weights || !left_child || !right_child || !lowest_leaf ||
       !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin || !bandwidthMax)
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_auto: null pointer");

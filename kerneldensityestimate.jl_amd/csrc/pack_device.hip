@@ -31,7 +31,7 @@
 #include "host_pool.hpp"
 #include "kdehip_internal.hpp"
 #include "loocv_search.hpp"
-#include "tree_manifold.hpp"
+#include "manifold_arg.hpp"
 
 using namespace kdehip;
 
@@ -385,14 +385,6 @@ extern "C" int kdehip_density_from_device_points_manifold(kdehip_device_density 
   return kdehip_density_from_device_points_tree(out, d_points, D, N, device, stream, bw_out, nevals, manifold, nullptr);
 }
 
-// A tree_manifold byte other than 0 or 1 is KDEHIP_ERR_ARG (tree_manifold.hpp); all zeros becomes NULL (the Euclidean builder).
-static int tree_manifold_arg(const uint8_t *&tree_manifold, int64_t D) {
-  uint32_t mask = 0;
-  const int rc = tree_manifold_mask(tree_manifold, D < KDEHIP_MAX_DIMS ? D : KDEHIP_MAX_DIMS, &mask);
-  if (rc == KDEHIP_OK && mask == 0) tree_manifold = nullptr;
-  return rc;
-}
-
 // (tree_manifold: the host builder's operators, kdehip_make_density_tree -- kde!(points, addop, diffop), src/KDE01.jl:24)
 extern "C" int kdehip_density_from_device_points_tree(kdehip_device_density **out, const double *d_points, int64_t D,
                                                       int64_t N, int device, void *stream, double *bw_out, int32_t *nevals,
@@ -403,13 +395,10 @@ extern "C" int kdehip_density_from_device_points_tree(kdehip_device_density **ou
   int rc = check_shape(N, D);
   if (rc != KDEHIP_OK) return rc;
   if (N < 2) return set_error(KDEHIP_ERR_ARG, "kde!(points) needs at least two points");
-  unsigned circ = 0;
-  for (int64_t k = 0; manifold && k < D && k < KDEHIP_MAX_DIMS; ++k) {
-    if (manifold[k] == KDEHIP_MANIFOLD_CIRCULAR) circ |= 1u << k;
-    else if (manifold[k] != KDEHIP_MANIFOLD_EUCLIDEAN)
-      return set_error(KDEHIP_ERR_ARG, "manifold: every entry is KDEHIP_MANIFOLD_EUCLIDEAN or KDEHIP_MANIFOLD_CIRCULAR");
-  }
-  rc = tree_manifold_arg(tree_manifold, D);
+  uint32_t circ = 0;
+  rc = manifold_arg(manifold, D, &circ, {"manifold", ManifoldDims::kClamp});
+  if (rc != KDEHIP_OK) return rc;
+  rc = manifold_arg_or_null(tree_manifold, D, nullptr, kTreeManifold);  // (all zeros: the Euclidean builder)
   if (rc != KDEHIP_OK) return rc;
   DeviceGuard guard;
   rc = guard.enter(device);
@@ -579,7 +568,7 @@ extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, 
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   if (nsel < 1 || nsel > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_ARG, "marginal: nsel outside 1..KDEHIP_MAX_DIMS");
-  const int trc = tree_manifold_arg(tree_manifold, nsel);
+  const int trc = manifold_arg_or_null(tree_manifold, nsel, nullptr, kTreeManifold);
   if (trc != KDEHIP_OK) return trc;
   if (!dims) return set_error(KDEHIP_ERR_ARG, "marginal: null dims");
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
@@ -642,15 +631,6 @@ extern "C" int kdehip_mul_device(kdehip_device_density **out, int Ndens, kdehip_
   return kdehip_mul_device_manifold(out, Ndens, trees, seed, addEntropy, bw_out, nevals, nullptr);
 }
 
-// The manifold of a `*` on handles: an enum value above 1 is KDEHIP_ERR_ARG, more than KDEHIP_MAX_DIMS dimensions
-// KDEHIP_ERR_UNSUPPORTED (as the one-shot entries); NULL and all zeros are the Euclidean `*`.
-static int mul_manifold_mask(const uint8_t *manifold, int D, unsigned *mask) {
-  *mask = 0;
-  if (!manifold) return KDEHIP_OK;
-  if (D < 1 || D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  return manifold_mask(manifold, D, mask);
-}
-
 // The same on a manifold: the circular product, then kde!(pGM) with the same manifold (the bandwidth search's likelihoods
 // wrap; the tree is the Euclidean builder's).
 extern "C" int kdehip_mul_device_manifold(kdehip_device_density **out, int Ndens, kdehip_device_density *const *trees,
@@ -672,11 +652,11 @@ extern "C" int kdehip_mul_device_tree(kdehip_device_density **out, int Ndens, kd
     if (trees[j]->device != trees[0]->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
   }
   const int D = trees[0]->D, device = trees[0]->device;
-  unsigned circ = 0;
-  const int mrc = mul_manifold_mask(manifold, D, &circ);
+  // (the manifold of a `*`: more than KDEHIP_MAX_DIMS dimensions are KDEHIP_ERR_UNSUPPORTED, as the one-shot entries; NULL and
+  // all zeros are the Euclidean `*`)
+  const int mrc = manifold_arg_or_null(manifold, D, nullptr, product_manifold(64));
   if (mrc != KDEHIP_OK) return mrc;
-  if (circ == 0) manifold = nullptr;
-  const int trc = tree_manifold_arg(tree_manifold, D);
+  const int trc = manifold_arg_or_null(tree_manifold, D, nullptr, kTreeManifold);
   if (trc != KDEHIP_OK) return trc;
   DeviceGuard guard;
   int rc = guard.enter(device);
@@ -721,7 +701,7 @@ namespace {
 
 struct MulPlan {   // what one item of the batch becomes
   int D = 0, M = 0;
-  unsigned circ = 0;                     // bit d: dimension d is circular (0: the Euclidean `*`)
+  uint32_t circ = 0;                     // bit d: dimension d is circular (0: the Euclidean `*`)
   const uint8_t *manifold = nullptr;     // the item's manifold when circ != 0
   const uint8_t *tree_manifold = nullptr;  // the operators of its tree build (NULL: the Euclidean builder)
   int64_t N = 0;          // points of the result (Np of the product, or the density's own count for the shortcut)
@@ -787,11 +767,11 @@ static int mul_device_batch_impl(int nprod, const kdehip_mul_item *items, const 
     MulPlan &m = mp[i];
     m.D = it.trees[0]->D; m.M = it.Ndens;
     const uint8_t *man = manifolds ? manifolds + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr;
-    const int mrc = mul_manifold_mask(man, m.D, &m.circ);
+    m.manifold = man;
+    const int mrc = manifold_arg_or_null(m.manifold, m.D, &m.circ, product_manifold(64));
     if (mrc != KDEHIP_OK) return mrc;
-    m.manifold = m.circ ? man : nullptr;
     m.tree_manifold = tree_manifolds ? tree_manifolds + static_cast<size_t>(i) * KDEHIP_MAX_DIMS : nullptr;
-    const int trc = tree_manifold_arg(m.tree_manifold, m.D);
+    const int trc = manifold_arg_or_null(m.tree_manifold, m.D, nullptr, kTreeManifold);
     if (trc != KDEHIP_OK) return trc;
     m.shortcut = it.Ndens == 1 && !it.addEntropy;  // the "hack fix for #70" (:713-716)
     if (m.shortcut) m.N = it.trees[0]->N;

@@ -17,6 +17,7 @@
 #include "call_block.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
+#include "manifold_arg.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
 
@@ -331,21 +332,6 @@ void bind_plan(kdehip_product *p, size_t off_lev, size_t off_count, size_t off_t
       if (sc.stage_mode == kStageScreenChunked) p->dev.screened = 2;  // (selects the sampler build that knows chunked screens)
 }
 
-// The manifold of an entry that takes host trees (ndims bytes or NULL) as circular bits, with the argument errors every
-// circular entry has: ndims above KDEHIP_MAX_DIMS is KDEHIP_ERR_UNSUPPORTED, an enum value above 1 KDEHIP_ERR_ARG, a circular
-// dimension in fp32 KDEHIP_ERR_UNSUPPORTED (the circular operators exist in fp64 only).  Touches no device.
-int manifold_circ_bits(const uint8_t *manifold, int ndims, int precision, uint32_t *bits) {
-  *bits = 0;
-  if (!manifold) return KDEHIP_OK;
-  if (ndims < 1 || ndims > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  for (int d = 0; d < ndims; ++d) {
-    if (manifold[d] > KDEHIP_MANIFOLD_CIRCULAR) return set_error(KDEHIP_ERR_ARG, "manifold: 0 (Euclidean) or 1 (circular) per dimension");
-    if (manifold[d] == KDEHIP_MANIFOLD_CIRCULAR) *bits |= 1u << d;
-  }
-  if (*bits != 0u && precision == 32) return set_error(KDEHIP_ERR_UNSUPPORTED, "circular dimensions need precision 64");
-  return KDEHIP_OK;
-}
-
 // A plan on `device` from an image: one device allocation, one DMA transfer (hipMalloc / hipFree cost tens of
 // microseconds each and would dominate a one-shot small product; blocks come from the library's cache).
 // wait = false (one-shot calls, whose image outlives the work they enqueue): the upload is left in flight on the
@@ -434,7 +420,7 @@ int kdehip_product_create_manifold(kdehip_product **out, int Ndens, const kdehip
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   uint32_t circ_bits = 0;
-  int rc = manifold_circ_bits(manifold, ndims, precision, &circ_bits);
+  int rc = manifold_arg(manifold, ndims, &circ_bits, product_manifold(precision));
   if (rc != KDEHIP_OK) return rc;
   PlanImage im;
   rc = build_image(im, Ndens, trees, ndims, partialDimMask, precision);
@@ -616,7 +602,7 @@ int one_shot(int Ndens, const kdehip_density *trees, int64_t Np, int Niter, doub
   // arithmetic of a circular product is chosen as a plan's is (kdehip_prod_philox_manifold); otherwise it is the generic one
   // (kdehip_gibbs1_manifold: the reference's own accumulation)
   uint32_t circ_bits = 0;
-  int rc = manifold_circ_bits(manifold, ndims, precision, &circ_bits);
+  int rc = manifold_arg(manifold, ndims, &circ_bits, product_manifold(precision));
   if (rc != KDEHIP_OK) return rc;
   rc = check_devices(device, ngpus);
   if (rc != KDEHIP_OK) {
@@ -942,13 +928,12 @@ int describe_resident(kdehip_product *p, kdehip_device_density *const *trees, co
   return maxB;
 }
 
-// The manifold of a resident entry (ndims bytes or NULL) as circular bits, with one_shot's argument errors: an enum value
-// above 1 is KDEHIP_ERR_ARG, ndims above KDEHIP_MAX_DIMS is KDEHIP_ERR_UNSUPPORTED; and the circular operators exist in
-// fp64 only.  (The densities themselves are validated by layout_resident.)
+// The manifold of a resident entry (ndims bytes or NULL) as circular bits, with one_shot's argument errors (product_manifold).
+// Without a first density there is no ndims to read it by: the densities themselves are refused by layout_resident.
 int resident_circ_bits(const uint8_t *manifold, int Ndens, kdehip_device_density *const *trees, int precision, uint32_t *bits) {
   *bits = 0;
-  if (!manifold || Ndens < 1 || !trees || !trees[0]) return KDEHIP_OK;
-  return manifold_circ_bits(manifold, trees[0]->D, precision, bits);
+  if (Ndens < 1 || !trees || !trees[0]) return KDEHIP_OK;
+  return manifold_arg(manifold, trees[0]->D, bits, product_manifold(precision));
 }
 
 // own_prep: prepare on the library's stream (an asynchronous caller: the next product's preparation overlaps this
@@ -1045,7 +1030,7 @@ int kdehip_prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items,
   for (int i = 0; i < nprod; ++i) {
     const uint8_t *row = manifolds + static_cast<size_t>(i) * KDEHIP_MAX_DIMS;
     uint32_t bits = 0;
-    const int rc = manifold_circ_bits(row, KDEHIP_MAX_DIMS, precision, &bits);
+    const int rc = manifold_arg(row, KDEHIP_MAX_DIMS, &bits, product_manifold(precision));
     if (rc != KDEHIP_OK) return rc;
     const kdehip_batch_item &it = items[i];
     const int D = (it.Ndens >= 1 && it.trees && it.trees[0]) ? it.trees[0]->D : KDEHIP_MAX_DIMS;
@@ -1404,7 +1389,7 @@ int kdehip_product_multi_create_manifold(kdehip_product_multi **out, int Ndens, 
   if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
   *out = nullptr;
   uint32_t circ_bits = 0;
-  int rc = manifold_circ_bits(manifold, ndims, precision, &circ_bits);
+  int rc = manifold_arg(manifold, ndims, &circ_bits, product_manifold(precision));
   if (rc != KDEHIP_OK) return rc;
   rc = check_devices(first_device, ngpus);
   if (rc != KDEHIP_OK) return rc;

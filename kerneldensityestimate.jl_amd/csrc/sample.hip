@@ -27,7 +27,7 @@
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "philox.hpp"
-#include "tree_manifold.hpp"
+#include "manifold_arg.hpp"
 
 using namespace kdehip;
 
@@ -329,14 +329,6 @@ SampleItem item_of(const kdehip_device_density *h, int64_t Npts, uint64_t seed, 
 
 bool weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }
 
-// the circular bits of a draw's manifold (a bad D is the entry's own refusal)
-int sample_mask(const uint8_t *manifold, int64_t D, uint32_t *circ) {
-  unsigned m = 0;
-  KDEHIP_CHECK_RC(manifold_mask(manifold, D, &m));
-  *circ = m;
-  return KDEHIP_OK;
-}
-
 }  // namespace
 
 extern "C" int kdehip_sample(const kdehip_density *p, int64_t Npts, uint64_t seed, int64_t sample_offset,
@@ -351,7 +343,7 @@ extern "C" int kdehip_sample_manifold(const kdehip_density *p, int64_t Npts, uin
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
   if (Npts < 0) return set_error(KDEHIP_ERR_ARG, "sample: Npts < 0");
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(sample_mask(manifold, p->ndim, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->ndim, &circ));
   if (Npts == 0) return KDEHIP_OK;
   const int64_t N = p->npts, D = p->ndim;
   if (D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims above KDEHIP_MAX_DIMS");
@@ -425,7 +417,7 @@ extern "C" int kdehip_sample_device_manifold(kdehip_device_density *p, int64_t N
   if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
   if (Npts < 0) return set_error(KDEHIP_ERR_ARG, "sample: Npts < 0");
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(sample_mask(manifold, p->D, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->D, &circ));
   if (Npts == 0) return KDEHIP_OK;
   if (p->D < 1 || p->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   if (!d_pts || !d_ind) return set_error(KDEHIP_ERR_ARG, "null output buffer");
@@ -536,8 +528,8 @@ extern "C" int kdehip_resample_device_manifold(kdehip_device_density **out, kdeh
   if (Np <= 0) Np = p->N;
   if (Np < 2) return set_error(KDEHIP_ERR_ARG, "resample: kde!(points) needs at least two points");
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(sample_mask(manifold, p->D, &circ));
-  KDEHIP_CHECK_RC(tree_manifold_mask(tree_manifold, p->D < KDEHIP_MAX_DIMS ? p->D : KDEHIP_MAX_DIMS, nullptr));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->D, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(tree_manifold, p->D, nullptr, kTreeManifold));
   DeviceGuard guard;
   int rc = guard.enter(p->device);
   if (rc != KDEHIP_OK) return rc;

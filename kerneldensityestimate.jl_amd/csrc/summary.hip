@@ -30,6 +30,7 @@
 #include "call_block.hpp"
 #include "circ_wrap.hpp"
 #include "entry_helpers.hpp"
+#include "manifold_arg.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
 
@@ -622,14 +623,6 @@ int summary_batch(int n, Item item, Mask mask, void *stream) {
   return run.defer(device);
 }
 
-// the circular bits of a host entry's manifold for a density of D dimensions (a bad D is check_resident / check_host's)
-int summary_mask(const uint8_t *manifold, int64_t D, uint32_t *circ) {
-  unsigned m = 0;
-  KDEHIP_CHECK_RC(manifold_mask(manifold, D, &m));
-  *circ = m;
-  return KDEHIP_OK;
-}
-
 }  // namespace
 
 extern "C" int kdehip_summary_device_batch(int n, const kdehip_summary_item *items, void *stream) {
@@ -654,7 +647,7 @@ extern "C" int kdehip_density_summary_manifold(const kdehip_device_density *p, c
   KDEHIP_CHECK_RC(check_resident(p));
   KDEHIP_CHECK_RC(check_grid(Ngrid));
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(summary_mask(manifold, p->D, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->D, &circ));
   const int64_t D = p->D;
   DeviceGuard guard;
   KDEHIP_CHECK_RC(guard.enter(p->device));
@@ -693,7 +686,7 @@ extern "C" int kdehip_kde_max_manifold(const kdehip_density *p, int64_t Ngrid, d
   KDEHIP_CHECK_RC(check_host(p));
   KDEHIP_CHECK_RC(check_grid(Ngrid));
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(summary_mask(manifold, p->ndim, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->ndim, &circ));
   Uploaded up;
   KDEHIP_CHECK_RC(kdehip_density_upload(&up.h, p, device));
   return kdehip_density_summary_manifold(up.h, nullptr, Ngrid, nullptr, nullptr, nullptr, out, grid_values, manifold);
@@ -711,7 +704,7 @@ extern "C" int kdehip_inters_intg_appx_is_device_manifold(const kdehip_device_de
   KDEHIP_CHECK_RC(check_resident(q));
   KDEHIP_CHECK_RC(check_inters_shapes(p->D, q->D, Ngrid));
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(summary_mask(manifold, p->D, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->D, &circ));
   if (p->device != q->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
   if (!leaves_share_bandwidth(p) || !leaves_share_bandwidth(q))
     return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
@@ -730,7 +723,7 @@ extern "C" int kdehip_inters_intg_appx_is_manifold(const kdehip_density *p, cons
   KDEHIP_CHECK_RC(check_host(q));
   KDEHIP_CHECK_RC(check_inters_shapes(p->ndim, q->ndim, Ngrid));
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(summary_mask(manifold, p->ndim, &circ));
+  KDEHIP_CHECK_RC(manifold_arg(manifold, p->ndim, &circ));
   for (const kdehip_density *d : {p, q}) {
     const int64_t N = d->npts, D = d->ndim;
     for (int64_t i = 0; i < N; ++i)

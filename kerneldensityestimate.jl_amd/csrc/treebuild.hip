@@ -41,7 +41,7 @@
 #include "entry_helpers.hpp"
 #include "kdehip_internal.hpp"
 #include "phase_timer.hpp"
-#include "tree_manifold.hpp"
+#include "manifold_arg.hpp"
 
 namespace kdehip {
 namespace {
@@ -467,7 +467,7 @@ extern "C" int kdehip_make_densities_device_tree(int nb, int64_t D, const int64_
     return set_error(KDEHIP_ERR_ARG, "kdehip_make_densities_device: null pointer");
   if (nks != 1 && nks != D) return set_error(KDEHIP_ERR_ARG, "kdehip_make_densities_device: ks must have 1 or D entries");
   uint32_t circ_bits = 0;
-  if (tree_manifold_mask(tree_manifold, D < KDEHIP_MAX_DIMS ? D : KDEHIP_MAX_DIMS, &circ_bits) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  if (manifold_arg(tree_manifold, D, &circ_bits, kTreeManifold) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   int64_t maxN = 0;
   for (int j = 0; j < nb; ++j) {
     if (!kdehip_make_density_device_supported(D, Ns[j]))

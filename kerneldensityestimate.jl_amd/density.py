@@ -9,8 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
-from ._lib import f64p, i64p, ptr, u8p
+from . import _lib, manifold as _mf
+from ._lib import f64p, i64p, optr, ptr
 
 
 class BallTree:
@@ -129,22 +129,17 @@ def kde(points, ks=None, weights=None, device=None, manifold=None, tree_manifold
     if device is not None:
         return kde_batch([(points, ks, weights)], device=device, tree_manifold=tree_manifold)[0]
     D, N, flat, ks, w = _prepare(points, ks, weights)
-    tman = _tree_manifold_array(tree_manifold, D)
+    tman = _mf.parse(tree_manifold, D)
     bd = _empty_density(D, N)
     bt = bd.bt
     _lib.check(_lib.lib.kdehip_make_density_tree(
-        D, N, ptr(flat, f64p), ptr(ks, f64p), ks.size, None if w is None else ptr(w, f64p),
+        D, N, ptr(flat, f64p), ptr(ks, f64p), ks.size, optr(w, f64p),
         ptr(bt.centers, f64p), ptr(bt.ranges, f64p), ptr(bt.weights, f64p), ptr(bt.left_child, i64p),
         ptr(bt.right_child, i64p), ptr(bt.lowest_leaf, i64p), ptr(bt.highest_leaf, i64p),
         ptr(bt.permutation, i64p), ptr(bd.means, f64p), ptr(bd.bandwidth, f64p),
-        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), None if tman is None else ptr(tman, u8p)))
+        ptr(bd.bandwidthMin, f64p), ptr(bd.bandwidthMax, f64p), _mf.pointer(tman)))
     bd.tree_manifold = tman
     return bd
-
-
-def _tree_manifold_array(tree_manifold, ndims):
-    from .product import _manifold_array
-    return _manifold_array(tree_manifold, ndims)
 
 
 def kde_batch(items, device=0, tree_manifold=None):
@@ -163,7 +158,7 @@ def kde_batch(items, device=0, tree_manifold=None):
     tmans = {}
     for idx, (D, N, flat, ks, w) in enumerate(prepared):
         if D not in tmans:
-            tmans[D] = _tree_manifold_array(tree_manifold, D)
+            tmans[D] = _mf.parse(tree_manifold, D)
         if N >= 2 and _lib.lib.kdehip_make_density_device_supported(D, N):
             groups.setdefault((D, ks.size), []).append(idx)
         else:
@@ -188,7 +183,7 @@ def kde_batch(items, device=0, tree_manifold=None):
                 arr(lambda k: dens[k].bt.lowest_leaf), arr(lambda k: dens[k].bt.highest_leaf),
                 arr(lambda k: dens[k].bt.permutation), arr(lambda k: dens[k].means), arr(lambda k: dens[k].bandwidth),
                 arr(lambda k: dens[k].bandwidthMin), arr(lambda k: dens[k].bandwidthMax), int(device),
-                None if tman is None else ptr(tman, u8p)))
+                _mf.pointer(tman)))
             for k, i in enumerate(chunk):
                 dens[k].tree_manifold = tman
                 out[i] = dens[k]

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, manifold as _mf
 from .density import BallTreeDensity
 
 
@@ -30,11 +30,6 @@ def _dims(d):
     return d.bt.dims if isinstance(d, BallTreeDensity) else d.dims
 
 
-def _man(manifold, ndims):
-    from .product import _manifold_array
-    return _manifold_array(manifold, ndims)
-
-
 def _mask(man):
     return 0 if man is None else int(sum(int(v) << k for k, v in enumerate(man)))
 
@@ -47,8 +42,8 @@ def evalAvgLogL(bd1, bd2, *, device=0, manifold=None) -> float:
         raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
     out = C.c_double(0.0)
     loo = 1 if bd1 is bd2 else 0
-    man = _man(manifold, _dims(bd1))  # (circular differences in those dimensions: include/kdehip.h section 5d)
-    mp = None if man is None else _lib.ptr(man, _lib.u8p)
+    man = _mf.parse(manifold, _dims(bd1))  # (circular differences in those dimensions: include/kdehip.h section 5d)
+    mp = _mf.pointer(man)
     if kind == "host":
         c1 = bd1._cstruct()
         c2 = c1 if loo else bd2._cstruct()
@@ -83,7 +78,7 @@ def eval_avg_logl_device_batch(pairs, d_out, stream=None, manifolds=None):
     """evalAvgLogL of many (bd, at) DeviceDensity pairs in ONE call (kdehip_eval_avg_logl_device_batch): d_out[i] (a
     float64 device tensor or address of len(pairs) doubles) = evalAvgLogL(bd_i, at_i), leave-one-out where `bd_i is
     at_i`.  `manifolds`: None, or one manifold (or None) per pair.  Enqueues on `stream` and returns."""
-    from .product import DeviceDensity, ProductPlan
+    from .product import DeviceDensity
     pairs = list(pairs)
     n = len(pairs)
     if manifolds is not None and len(manifolds) != n:
@@ -93,9 +88,8 @@ def eval_avg_logl_device_batch(pairs, d_out, stream=None, manifolds=None):
         if not (isinstance(bd, DeviceDensity) and isinstance(at, DeviceDensity)):
             raise TypeError("eval_avg_logl_device_batch: pairs of DeviceDensity")
         arr[k].bd, arr[k].at, arr[k].leave_one_out = bd._h, at._h, 1 if bd is at else 0
-        arr[k].circular_mask = 0 if manifolds is None else _mask(_man(manifolds[k], bd.dims))
-    _lib.check(_lib.lib.kdehip_eval_avg_logl_device_batch_manifold(n, arr, ProductPlan._addr(d_out),
-                                                                   ProductPlan._addr(stream)))
+        arr[k].circular_mask = 0 if manifolds is None else _mask(_mf.parse(manifolds[k], bd.dims))
+    _lib.check(_lib.lib.kdehip_eval_avg_logl_device_batch_manifold(n, arr, _lib.addr(d_out), _lib.addr(stream)))
 
 
 def kld_batch(pairs, manifold=None, manifolds=None):

@@ -9,13 +9,16 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 
 import numpy as np
 
-from . import _lib
-from ._lib import f64p, i64p, i32p, u8p, ptr
+from . import _lib, manifold as _mf
+from ._lib import SEED_MASK, addr, f64p, i64p, i32p, optr, ptr, u8p, u64
 from .density import BallTreeDensity, Ndim, Npts
+
+
+# the names manifold.parse / manifold.per_product had while they lived here (tests and scripts import them from this module)
+_manifold_array, _batch_manifolds = _mf.parse, _mf.per_product
 
 
 def _mask_array(partialDimMask, Ndens, ndims):
@@ -23,14 +26,6 @@ def _mask_array(partialDimMask, Ndens, ndims):
         return None
     m = np.ascontiguousarray(np.asarray(partialDimMask, dtype=bool).reshape(Ndens, ndims).astype(np.uint8))
     return m
-
-
-def _plan_manifold(manifold, ndims):
-    """the `manifold=` of a plan as the enum array: a wrong length or a name outside the enum is a ValueError"""
-    try:
-        return _manifold_array(manifold, ndims)
-    except KeyError as e:
-        raise ValueError(f"manifold: {e.args[0]!r} is not 'euclid' or 'circular'") from None
 
 
 def nlevels(maxNp: int) -> int:
@@ -52,13 +47,12 @@ class ProductPlan:
         self.Ndens = len(trees)
         self.ndims = int(ndims) if ndims is not None else max(Ndim(t) for t in trees)
         self._keep = trees  # arrays must outlive the create call only; kept for introspection
-        self.manifold = _plan_manifold(manifold, self.ndims)   # the uint8 enum array, or None
+        self.manifold = _mf.parse(manifold, self.ndims, unknown_name=ValueError)   # the uint8 enum array, or None
         arr = (_lib.CDensity * self.Ndens)(*[t._cstruct() for t in trees])
         mask = _mask_array(partialDimMask, self.Ndens, self.ndims)
         h = C.c_void_p()
         _lib.check(_lib.lib.kdehip_product_create_manifold(C.byref(h), self.Ndens, arr, self.ndims,
-                                                           None if mask is None else ptr(mask, u8p),
-                                                           None if self.manifold is None else ptr(self.manifold, u8p),
+                                                           optr(mask, u8p), _mf.pointer(self.manifold),
                                                            int(precision), int(device)))
         self._h = h
         info = _lib.CProductInfo()
@@ -126,27 +120,19 @@ class ProductPlan:
         return {"waves": int(w.value), "team": int(t.value)}
 
     # ---- device-pointer runs (torch tensors or raw addresses) -----------------------------------
-    @staticmethod
-    def _addr(x):
-        if x is None:
-            return None
-        if hasattr(x, "data_ptr"):
-            return C.c_void_p(x.data_ptr())
-        return C.c_void_p(int(x))
+    _addr = staticmethod(addr)   # (kept for the scripts and tests that call it)
 
     def sample_philox_device(self, Np, Niter, seed, sample_offset, addEntropy, d_points, d_indices,
                              d_labels=None, stream=None):
         _lib.check(_lib.lib.kdehip_product_sample_philox(
-            self._h, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset),
-            int(bool(addEntropy)), self._addr(d_points), self._addr(d_indices), self._addr(d_labels),
-            self._addr(stream)))
+            self._h, int(Np), int(Niter), u64(seed), int(sample_offset), int(bool(addEntropy)), addr(d_points),
+            addr(d_indices), addr(d_labels), addr(stream)))
 
     def sample_streams_device(self, Np, Niter, d_randU, nU, d_randN, nN, addEntropy, d_points, d_indices,
                               d_labels=None, stream=None):
         _lib.check(_lib.lib.kdehip_product_sample_streams(
-            self._h, int(Np), int(Niter), self._addr(d_randU), int(nU), self._addr(d_randN), int(nN),
-            int(bool(addEntropy)), self._addr(d_points), self._addr(d_indices), self._addr(d_labels),
-            self._addr(stream)))
+            self._h, int(Np), int(Niter), addr(d_randU), int(nU), addr(d_randN), int(nN),
+            int(bool(addEntropy)), addr(d_points), addr(d_indices), addr(d_labels), addr(stream)))
 
     # ---- host-buffer run -------------------------------------------------------------------------
     def sample(self, Np, Niter=3, seed=0, sample_offset=0, addEntropy=True, want_labels=False):
@@ -156,9 +142,8 @@ class ProductPlan:
         ind = np.ones(M * Np, dtype=np.int64)
         labels = np.zeros(Np * M * L, dtype=np.int32) if want_labels else None
         _lib.check(_lib.lib.kdehip_product_sample_philox_host(
-            self._h, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset),
-            int(bool(addEntropy)), ptr(pts, f64p), ptr(ind, i64p),
-            None if labels is None else ptr(labels, i32p)))
+            self._h, int(Np), int(Niter), u64(seed), int(sample_offset), int(bool(addEntropy)), ptr(pts, f64p),
+            ptr(ind, i64p), optr(labels, i32p)))
         out = (pts.reshape(Np, D).T.copy(), ind.reshape(Np, M).T.copy())
         if want_labels:
             out = out + (labels.reshape(Np, M, L),)
@@ -175,13 +160,12 @@ class MultiProductPlan:
         trees = list(trees)
         self.Ndens = len(trees)
         self.ndims = int(ndims) if ndims is not None else max(Ndim(t) for t in trees)
-        self.manifold = _plan_manifold(manifold, self.ndims)
+        self.manifold = _mf.parse(manifold, self.ndims, unknown_name=ValueError)
         arr = (_lib.CDensity * self.Ndens)(*[t._cstruct() for t in trees])
         mask = _mask_array(partialDimMask, self.Ndens, self.ndims)
         h = C.c_void_p()
         _lib.check(_lib.lib.kdehip_product_multi_create_manifold(C.byref(h), self.Ndens, arr, self.ndims,
-                                                                 None if mask is None else ptr(mask, u8p),
-                                                                 None if self.manifold is None else ptr(self.manifold, u8p),
+                                                                 optr(mask, u8p), _mf.pointer(self.manifold),
                                                                  int(precision), int(first_device), int(ngpus)))
         self._h = h
         self.first_device = int(first_device)
@@ -217,11 +201,11 @@ class MultiProductPlan:
         """d_points / d_indices: one device array (torch tensor or address) per GPU, each holding the COMPLETE result
         afterwards (the all-gather is part of the run); enqueue only."""
         G = self.ngpus
-        P = (C.c_void_p * G)(*[ProductPlan._addr(x) for x in d_points])
-        I = (C.c_void_p * G)(*[ProductPlan._addr(x) for x in d_indices])
-        S = None if streams is None else (C.c_void_p * G)(*[ProductPlan._addr(x) for x in streams])
+        P = (C.c_void_p * G)(*[addr(x) for x in d_points])
+        I = (C.c_void_p * G)(*[addr(x) for x in d_indices])
+        S = None if streams is None else (C.c_void_p * G)(*[addr(x) for x in streams])
         _lib.check(_lib.lib.kdehip_product_multi_sample_philox(self._h, int(Np), int(Niter),
-                                                               C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset),
+                                                               u64(seed), int(sample_offset),
                                                                int(bool(addEntropy)), P, I, S))
 
 
@@ -250,6 +234,13 @@ class DeviceDensity:
         self.tree_manifold = getattr(tree, "tree_manifold", None) if _handle is None else None
 
     @classmethod
+    def _built(cls, handle, device, bw=None, nevals=None, manifold=None, tree_manifold=None):
+        """a handle the library has just built, with the records of how: bandwidth, search evaluations, manifolds"""
+        out = cls(device=device, _handle=handle)
+        out.bw, out.nevals, out.manifold, out.tree_manifold = bw, nevals, manifold, tree_manifold
+        return out
+
+    @classmethod
     def from_device_points(cls, d_points, D, N, device=0, stream=None, manifold=None, tree_manifold=None):
         """`kde!(points)` (reference src/KDE01.jl:3-27) of a D x N column-major matrix that lives in HBM (a torch tensor or
         an address; `stream` = the stream that produced it): LOOCV bandwidth search on the device matrix, ball tree from one
@@ -259,15 +250,12 @@ class DeviceDensity:
         h = C.c_void_p()
         bw = np.empty(int(D))
         ne = C.c_int32(0)
-        man = _manifold_array(manifold, int(D))
-        tman = _manifold_array(tree_manifold, int(D))
+        man = _mf.parse(manifold, int(D))
+        tman = _mf.parse(tree_manifold, int(D))
         _lib.check(_lib.lib.kdehip_density_from_device_points_tree(
-            C.byref(h), ProductPlan._addr(d_points), int(D), int(N), int(device), ProductPlan._addr(stream), ptr(bw, f64p),
-            C.byref(ne), None if man is None else ptr(man, u8p), None if tman is None else ptr(tman, u8p)))
-        out = cls(device=device, _handle=h)
-        out.bw, out.nevals = bw, int(ne.value)
-        out.manifold, out.tree_manifold = man, tman
-        return out
+            C.byref(h), addr(d_points), int(D), int(N), int(device), addr(stream), ptr(bw, f64p),
+            C.byref(ne), _mf.pointer(man), _mf.pointer(tman)))
+        return cls._built(h, device, bw, int(ne.value), man, tman)
 
     def download(self) -> BallTreeDensity:
         """The reference's arrays of a density that was built on the device (kdehip_density_download)."""
@@ -296,8 +284,8 @@ class DeviceDensity:
         (include/kdehip.h section 5d)."""
         import torch
         dev = torch.device("cuda", self.device)
-        man = _manifold_array(manifold, self.dims)
-        mp = None if man is None else ptr(man, u8p)
+        man = _mf.parse(manifold, self.dims)
+        mp = _mf.pointer(man)
         if lvFlag:
             pos = self
         if pos is None:
@@ -308,8 +296,8 @@ class DeviceDensity:
                 if pos.dims != self.dims:
                     raise ValueError("bd and pos must have the same dimension")
                 out = torch.empty(max(1, pos.num_points), dtype=torch.float64, device=dev)
-                _lib.check(_lib.lib.kdehip_evaluate_device_at_manifold(self._h, pos._h, ProductPlan._addr(out),
-                                                                       ProductPlan._addr(st.cuda_stream), mp))
+                _lib.check(_lib.lib.kdehip_evaluate_device_at_manifold(self._h, pos._h, addr(out),
+                                                                       addr(st.cuda_stream), mp))
                 st.synchronize()
                 return out.cpu().numpy()[:pos.num_points].copy()
             tensor = hasattr(pos, "data_ptr")
@@ -322,8 +310,8 @@ class DeviceDensity:
             # column-major D x Nq = the (Nq, D) row-major array
             flat = P.t().contiguous().to(dev, torch.float64) if tensor else torch.from_numpy(np.ascontiguousarray(P.T)).to(dev)
             out = torch.empty(max(1, Nq), dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib.kdehip_evaluate_device_manifold(self._h, ProductPlan._addr(flat), Nq, 0, ProductPlan._addr(out),
-                                                                ProductPlan._addr(st.cuda_stream), mp))
+            _lib.check(_lib.lib.kdehip_evaluate_device_manifold(self._h, addr(flat), Nq, 0, addr(out),
+                                                                addr(st.cuda_stream), mp))
             if tensor:
                 return out[:Nq]
             st.synchronize()
@@ -338,14 +326,9 @@ class DeviceDensity:
         device int64[Npts] of given labels.  The first call on the density builds its table and blocks; later calls only
         enqueue on `stream` (kdehip_sample_device).  `manifold` (a sequence or "inherit"): circular coordinates are stored
         wrapped to [-pi, pi) (kdehip_sample_device_manifold)."""
-        from .summary import _manifold
-        man = _manifold(self, manifold)
-        args = (self._h, int(Npts), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset), ProductPlan._addr(ind),
-                ProductPlan._addr(d_pts), ProductPlan._addr(d_ind), ProductPlan._addr(stream))
-        if man is None:
-            _lib.check(_lib.lib.kdehip_sample_device(*args))
-        else:
-            _lib.check(_lib.lib.kdehip_sample_device_manifold(*args, ptr(man, u8p)))
+        man = _mf.resolve(self, manifold, self.dims)
+        _lib.check(_lib.lib.kdehip_sample_device_manifold(self._h, int(Npts), u64(seed), int(sample_offset), addr(ind),
+                                                          addr(d_pts), addr(d_ind), addr(stream), _mf.pointer(man)))
 
     def resample(self, Np=None, *, seed=None, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`resample(p, Np, :lcv)` (reference src/BallTreeDensity01.jl:312-334) without leaving the device: Np samples
@@ -353,24 +336,16 @@ class DeviceDensity:
         for a density that remembers a manifold; `manifold` / `tree_manifold` (sequences or "inherit"): the wrapped draw,
         then `from_device_points(manifold=, tree_manifold=)` on it (kdehip_resample_device_manifold) -- the result
         remembers both."""
-        from .summary import _manifold
-        man, tman = _manifold(self, manifold), _manifold(self, tree_manifold, attr="tree_manifold")
+        man = _mf.resolve(self, manifold, self.dims)
+        tman = _mf.resolve(self, tree_manifold, self.dims, attr="tree_manifold")
         if seed is None:
-            seed = int.from_bytes(os.urandom(8), "little")
+            seed = _lib.random_seed()
         h = C.c_void_p()
         bw = np.empty(self.dims)
         ne = C.c_int32(0)
-        args = (C.byref(h), self._h, 0 if Np is None else int(Np), C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(bw, f64p),
-                C.byref(ne))
-        if man is None and tman is None:
-            _lib.check(_lib.lib.kdehip_resample_device(*args))
-        else:
-            _lib.check(_lib.lib.kdehip_resample_device_manifold(*args, None if man is None else ptr(man, u8p),
-                                                                None if tman is None else ptr(tman, u8p)))
-        out = DeviceDensity(device=self.device, _handle=h)
-        out.bw, out.nevals = bw, int(ne.value)
-        out.manifold, out.tree_manifold = man, tman
-        return out
+        _lib.check(_lib.lib.kdehip_resample_device_manifold(C.byref(h), self._h, 0 if Np is None else int(Np), u64(seed),
+                                                            ptr(bw, f64p), C.byref(ne), _mf.pointer(man), _mf.pointer(tman)))
+        return self._built(h, self.device, bw, int(ne.value), man, tman)
 
     def marginal(self, dims, *, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`marginal(p, dims)` (reference src/KDE01.jl:143-153), dims 0-based, built on this density's device
@@ -426,39 +401,19 @@ def mul_device(trees, *, addEntropy=True, seed=None, manifold=None, tree_manifol
     matrix (kdehip_mul_device_manifold); the result remembers it.  `tree_manifold`: the operators of the result's tree
     build, as `from_device_points(tree_manifold=)` (kdehip_mul_device_tree)."""
     trees = list(trees)
-    man = _manifold_array(manifold, trees[0].dims)
-    tman = _manifold_array(tree_manifold, trees[0].dims)
+    man = _mf.parse(manifold, trees[0].dims)
+    tman = _mf.parse(tree_manifold, trees[0].dims)
     if seed is None:
-        seed = int.from_bytes(os.urandom(8), "little")
+        seed = _lib.random_seed()
     M = len(trees)
     arr = (C.c_void_p * M)(*[t._h for t in trees])
     h = C.c_void_p()
     bw = np.empty(trees[0].dims)
     ne = C.c_int32(0)
-    _lib.check(_lib.lib.kdehip_mul_device_tree(C.byref(h), M, arr, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+    _lib.check(_lib.lib.kdehip_mul_device_tree(C.byref(h), M, arr, u64(seed),
                                                int(bool(addEntropy)), ptr(bw, f64p), C.byref(ne),
-                                               None if man is None else ptr(man, u8p),
-                                               None if tman is None else ptr(tman, u8p)))
-    out = DeviceDensity(device=trees[0].device, _handle=h)
-    out.bw, out.nevals = bw, int(ne.value)
-    out.manifold, out.tree_manifold = man, tman
-    return out
-
-
-def _batch_manifolds(manifold, dims):
-    """The `manifold=` argument of a batch as one enum array (or None) per product: None; ONE manifold for all products (a
-    flat sequence of enum values, every product then has that many dimensions); or one entry per product (each None or a
-    manifold of that product's dimensions).  `dims`: the products' dimension counts."""
-    n = len(dims)
-    if manifold is None:
-        return [None] * n
-    manifold = list(manifold)
-    shared = len(manifold) > 0 and all(m is not None and (isinstance(m, str) or np.ndim(m) == 0) for m in manifold)
-    if shared:
-        return [_manifold_array(manifold, d) for d in dims]
-    if len(manifold) != n:
-        raise ValueError("manifold: one manifold for all products, or one entry per product")
-    return [_manifold_array(m, d) for m, d in zip(manifold, dims)]
+                                               _mf.pointer(man), _mf.pointer(tman)))
+    return DeviceDensity._built(h, trees[0].device, bw, int(ne.value), man, tman)
 
 
 def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tree_manifold=None):
@@ -475,7 +430,7 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tr
     if n == 0:
         return []
     if seeds is None:
-        seeds = [int.from_bytes(os.urandom(8), "little") for _ in range(n)]
+        seeds = [_lib.random_seed() for _ in range(n)]
     flags = [bool(addEntropy)] * n if isinstance(addEntropy, (bool, int, np.bool_)) else [bool(f) for f in addEntropy]
     items = (_lib.CMulItem * n)()
     keep = []
@@ -483,17 +438,10 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tr
         arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
         keep.append(arr)
         items[k].Ndens, items[k].addEntropy, items[k].trees = len(trees), int(flags[k]), arr
-        items[k].seed = int(seeds[k]) & (2 ** 64 - 1)
-    mans = _batch_manifolds(manifold, [p[0].dims if p else 0 for p in products])   # (an empty product: the library refuses it)
-    marr = np.zeros((n, _lib.MAX_DIMS), dtype=np.uint8)   # row k: product k's manifold (zeros = Euclidean)
-    for k, m in enumerate(mans):
-        if m is not None:
-            marr[k, :len(m)] = m
-    tmans = _batch_manifolds(tree_manifold, [p[0].dims if p else 0 for p in products])
-    tarr = np.zeros((n, _lib.MAX_DIMS), dtype=np.uint8)   # row k: the operators of product k's tree build
-    for k, m in enumerate(tmans):
-        if m is not None:
-            tarr[k, :len(m)] = m
+        items[k].seed = int(seeds[k]) & SEED_MASK
+    dims = [p[0].dims if p else 0 for p in products]   # (an empty product: the library refuses it)
+    mans, tmans = _mf.per_product(manifold, dims), _mf.per_product(tree_manifold, dims)
+    marr, tarr = _mf.matrix(mans), _mf.matrix(tmans)   # row k: product k's manifold / the operators of its tree build
     out = (C.c_void_p * n)()
     bw = np.zeros((n, _lib.MAX_DIMS))
     ne = np.zeros(n, dtype=np.int32)
@@ -501,10 +449,8 @@ def mul_device_batch(products, *, addEntropy=True, seeds=None, manifold=None, tr
                                                      ptr(ne, _lib.i32p)))
     res = []
     for k in range(n):
-        d = DeviceDensity(device=products[k][0].device, _handle=C.c_void_p(out[k]))
-        d.bw, d.nevals = bw[k, :d.dims].copy(), int(ne[k])
-        d.manifold, d.tree_manifold = mans[k], tmans[k]
-        res.append(d)
+        res.append(DeviceDensity._built(C.c_void_p(out[k]), products[k][0].device, bw[k, :dims[k]].copy(), int(ne[k]),
+                                        mans[k], tmans[k]))
     return res
 
 
@@ -517,15 +463,10 @@ class ProductBatch:
     def __init__(self, products, precision=64, manifold=None):
         n = len(products)
         dims = [list(pr["trees"])[0].dims for pr in products]
-        mans = _batch_manifolds(manifold, dims)
-        self.manifolds = [(_manifold_array(pr["manifold"], d) if pr.get("manifold") is not None else m)
-                          for pr, d, m in zip(products, dims, mans)]
-        self._marr = None   # nprod rows of MAX_DIMS bytes, or None when every product is Euclidean
-        if any(m is not None and m.any() for m in self.manifolds):
-            self._marr = np.zeros((n, _lib.MAX_DIMS), dtype=np.uint8)
-            for k, m in enumerate(self.manifolds):
-                if m is not None:
-                    self._marr[k, :len(m)] = m
+        self.manifolds = _mf.per_product(manifold, dims, own=[pr.get("manifold") for pr in products])
+        # nprod rows of MAX_DIMS bytes, or None (the library's NULL) when every product is Euclidean
+        self._marr = _mf.matrix(self.manifolds) if any(m is not None and m.any() for m in self.manifolds) else None
+        self._mptr = _mf.pointer(self._marr)
         self.n = n
         self.precision = int(precision)
         self.items = (_lib.CBatchItem * max(1, n))()
@@ -540,24 +481,20 @@ class ProductBatch:
             it.Ndens, it.Niter = M, int(pr.get("Niter", 3))
             it.trees = arr
             it.Np = int(pr["Np"])
-            it.seed = int(pr.get("seed", 0)) & (2 ** 64 - 1)
+            it.seed = int(pr.get("seed", 0)) & SEED_MASK
             it.sample_offset = int(pr.get("sample_offset", 0))
             it.addEntropy = int(bool(pr.get("addEntropy", True)))
-            it.partialDimMask = None if mask is None else ptr(mask, u8p)
-            it.d_points = ProductPlan._addr(pr["d_points"])
-            it.d_indices = ProductPlan._addr(pr["d_indices"])
-            it.d_labels = ProductPlan._addr(pr.get("d_labels"))
+            it.partialDimMask = optr(mask, u8p)
+            it.d_points = addr(pr["d_points"])
+            it.d_indices = addr(pr["d_indices"])
+            it.d_labels = addr(pr.get("d_labels"))
 
     def enqueue(self, stream=None, sample_offset=None):
         """one library call for all products (enqueue only); `sample_offset` (optional) replaces every product's"""
         if sample_offset is not None:
             for k in range(self.n):
                 self.items[k].sample_offset = int(sample_offset)
-        if self._marr is None:
-            _lib.check(_lib.lib.kdehip_prod_philox_batch(self.n, self.items, self.precision, ProductPlan._addr(stream)))
-        else:
-            _lib.check(_lib.lib.kdehip_prod_philox_batch_manifold(self.n, self.items, ptr(self._marr, u8p), self.precision,
-                                                                  ProductPlan._addr(stream)))
+        _lib.check(_lib.lib.kdehip_prod_philox_batch_manifold(self.n, self.items, self._mptr, self.precision, addr(stream)))
 
 
 def batch_launches() -> dict:
@@ -592,11 +529,11 @@ def prodAppxMSGibbsS_device(trees, d_points, d_indices, *, Np, Niter=3, seed=0, 
     arr = (C.c_void_p * M)(*[t._h for t in trees])
     ndims = trees[0].dims
     mask = _mask_array(partialDimMask, M, ndims)
-    man = _manifold_array(manifold, ndims)
+    man = _mf.parse(manifold, ndims)
     _lib.check(_lib.lib.kdehip_prod_philox_device_manifold(
-        M, arr, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(sample_offset), int(bool(addEntropy)),
-        None if mask is None else ptr(mask, u8p), None if man is None else ptr(man, u8p), int(precision),
-        ProductPlan._addr(d_points), ProductPlan._addr(d_indices), ProductPlan._addr(d_labels), ProductPlan._addr(stream)))
+        M, arr, int(Np), int(Niter), u64(seed), int(sample_offset), int(bool(addEntropy)),
+        optr(mask, u8p), _mf.pointer(man), int(precision),
+        addr(d_points), addr(d_indices), addr(d_labels), addr(stream)))
 
 
 def prodAppxMSGibbsS_resident(trees, *, Np, Niter=3, seed=0, addEntropy=True, partialDimMask=None, precision=64,
@@ -608,13 +545,12 @@ def prodAppxMSGibbsS_resident(trees, *, Np, Niter=3, seed=0, addEntropy=True, pa
     M, D = len(trees), trees[0].dims
     arr = (C.c_void_p * M)(*[t._h for t in trees])
     mask = _mask_array(partialDimMask, M, D)
-    man = _manifold_array(manifold, D)
+    man = _mf.parse(manifold, D)
     pts = np.empty(D * Np)   # (every element is written by the call)
     ind = np.empty(M * Np, dtype=np.int64)
     _lib.check(_lib.lib.kdehip_prod_philox_resident_manifold(
-        M, arr, int(Np), int(Niter), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(bool(addEntropy)),
-        None if mask is None else ptr(mask, u8p), None if man is None else ptr(man, u8p), int(precision), ptr(pts, f64p),
-        ptr(ind, i64p)))
+        M, arr, int(Np), int(Niter), u64(seed), int(bool(addEntropy)),
+        optr(mask, u8p), _mf.pointer(man), int(precision), ptr(pts, f64p), ptr(ind, i64p)))
     return pts.reshape(Np, D).T, ind.reshape(Np, M).T
 
 
@@ -623,7 +559,7 @@ def philox_streams(seed, sample_begin, nsamples, K, R):
     (kdehip_philox_fill_uniform / _normal)."""
     u = np.empty(nsamples * K)
     n = np.empty(nsamples * R)
-    s = C.c_uint64(int(seed) & (2 ** 64 - 1))
+    s = u64(seed)
     _lib.lib.kdehip_philox_fill_uniform(s, int(sample_begin), int(nsamples), int(K), ptr(u, f64p))
     _lib.lib.kdehip_philox_fill_normal(s, int(sample_begin), int(nsamples), int(R), ptr(n, f64p))
     return u, n
@@ -651,17 +587,6 @@ def makeEmptyGbGlb(recordChoosen=False):
     return GbGlb(recordChoosen)
 
 
-def _manifold_array(manifold, ndims):
-    """per-dimension manifold enum of include/kdehip.h "manifolds": None, or a sequence of 0 / 'euclid' / 1 / 'circular'"""
-    if manifold is None:
-        return None
-    names = {"euclid": 0, "euclidean": 0, "circular": 1, "circ": 1}
-    vals = [names[m.lower()] if isinstance(m, str) else int(m) for m in manifold]
-    if len(vals) != ndims:
-        raise ValueError("manifold needs one entry per dimension")
-    return np.ascontiguousarray(vals, dtype=np.uint8)
-
-
 def gibbs1(Ndens, trees, Np, Niter, pts, ind, randU, randN, *, addEntropy=True, ndims=None,
            partialDimMask=None, glbs=None, device=0, ngpus=1, manifold=None):
     """`gibbs1` (reference src/MSGibbs01.jl:527-537): fills the caller's `pts` (length ndims*Np,
@@ -686,21 +611,19 @@ def gibbs1(Ndens, trees, Np, Niter, pts, ind, randU, randN, *, addEntropy=True, 
     labels = None
     if glbs is not None and glbs.recordChoosen:
         labels = np.zeros((Np, Ndens, nlevels(max(Npts(t) for t in trees))), dtype=np.int32)
-    man = _manifold_array(manifold, ndims)
+    man = _mf.parse(manifold, ndims)
     if man is not None and int(ngpus) != 1:
         raise ValueError("gibbs1: manifold= runs on one GPU (kdehip_gibbs1_manifold); ngpus must be 1")
     if man is not None:
         _lib.check(_lib.lib.kdehip_gibbs1_manifold(int(Ndens), arr, int(Np), int(Niter), ptr(pts.reshape(-1), f64p),
                                                    ptr(tmp_ind, i64p), ptr(randU, f64p), randU.size, ptr(randN, f64p),
                                                    randN.size, int(bool(addEntropy)), int(ndims),
-                                                   None if mask is None else ptr(mask, u8p), ptr(man, u8p), int(device),
-                                                   None if labels is None else ptr(labels, i32p)))
+                                                   optr(mask, u8p), ptr(man, u8p), int(device), optr(labels, i32p)))
     else:
         _lib.check(_lib.lib.kdehip_gibbs1_multi(int(Ndens), arr, int(Np), int(Niter), ptr(pts.reshape(-1), f64p),
                                                 ptr(tmp_ind, i64p), ptr(randU, f64p), randU.size, ptr(randN, f64p),
                                                 randN.size, int(bool(addEntropy)), int(ndims),
-                                                None if mask is None else ptr(mask, u8p), int(device), int(ngpus),
-                                                None if labels is None else ptr(labels, i32p)))
+                                                optr(mask, u8p), int(device), int(ngpus), optr(labels, i32p)))
     if labels is not None:
         glbs._fill(labels, Niter)
     if ind.ndim == 2:
@@ -756,7 +679,7 @@ def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter,
         # the manifold entry consumes caller streams: the host twin of the device stream gives the run the numbers the
         # Philox path would have drawn for `seed`
         if seed is None:
-            seed = int.from_bytes(os.urandom(8), "little")
+            seed = _lib.random_seed()
         L = nlevels(max(Npts(t) for t in trees[:Ndens]))
         randU, randN = philox_streams(seed, 0, Np, Ndens * (1 + L * (Niter + 1)), ndims * (L + 1))
     if randU is not None:
@@ -766,7 +689,7 @@ def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter,
                partialDimMask=partialDimMask, glbs=glbs, device=device, ngpus=ngpus, manifold=manifold)
         return points.reshape(Np, ndims).T.copy(), indices
     if seed is None:
-        seed = int.from_bytes(os.urandom(8), "little")
+        seed = _lib.random_seed()
     trace = glbs is not None and glbs.recordChoosen
     trees = trees[:Ndens]
     arr = (_lib.CDensity * Ndens)(*[t._cstruct() for t in trees])
@@ -774,12 +697,11 @@ def prodAppxMSGibbsS(npd0, trees, anFcns=None, anParams=None, *deprecated_niter,
     pts = np.empty(ndims * Np)   # (every element is written by the call)
     ind = np.empty(Ndens * Np, dtype=np.int64)
     labels = np.zeros((Np, Ndens, nlevels(max(Npts(t) for t in trees))), dtype=np.int32) if trace else None
-    man = _manifold_array(manifold, ndims) if philox_manifold else None
+    man = _mf.parse(manifold, ndims) if philox_manifold else None
     _lib.check(_lib.lib.kdehip_prod_philox_manifold(int(Ndens), arr, int(Np), int(Niter), ptr(pts, f64p), ptr(ind, i64p),
-                                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), int(bool(addEntropy)), int(ndims),
-                                                    None if mask is None else ptr(mask, u8p),
-                                                    None if man is None else ptr(man, u8p), int(precision), int(device),
-                                                    int(ngpus), None if labels is None else ptr(labels, i32p)))
+                                                    u64(seed), int(bool(addEntropy)), int(ndims),
+                                                    optr(mask, u8p), _mf.pointer(man), int(precision), int(device),
+                                                    int(ngpus), optr(labels, i32p)))
     if trace:
         glbs._fill(labels, Niter)
     # (ndims, Np) and (Ndens, Np) as the reference returns them: column-major matrices -- views of the flat buffers
@@ -800,7 +722,7 @@ def mul(trees, *, glbs=None, addEntropy=True, seed=None, device=0):
             raise ValueError("kdes must have same dimension")
     numpts = int(round(float(np.mean([Npts(t) for t in trees]))))
     if seed is None:
-        seed = int.from_bytes(os.urandom(8), "little")
+        seed = _lib.random_seed()
     pGM, _ = prodAppxMSGibbsS(None, trees, None, None, Niter=5, addEntropy=addEntropy, Np=numpts, glbs=glbs,
                               seed=seed, device=device)
     return kde_auto(pGM, device=device)

@@ -15,19 +15,17 @@ manifold returns; labels and the other dimensions are unchanged (include/kdehip.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _lib
-from ._lib import f64p, i64p, ptr, u8p
+from . import _lib, manifold as _mf
+from ._lib import SEED_MASK, addr, f64p, i64p, optr, ptr
 from .density import BallTreeDensity, getBW, getPoints, kde
+from .summary import _manifold as _man
 
 
 def _seed(seed):
-    if seed is None:
-        seed = int.from_bytes(os.urandom(8), "little")
-    return int(seed) & (2 ** 64 - 1)
+    return int(_lib.random_seed() if seed is None else seed) & SEED_MASK
 
 
 def _labels(ind, Npts):
@@ -35,11 +33,6 @@ def _labels(ind, Npts):
     if a.size != Npts:
         raise ValueError("ind must hold Npts labels")
     return a
-
-
-def _man(p, manifold, attr="manifold"):
-    from .summary import _manifold
-    return _manifold(p, manifold, attr=attr)
 
 
 def sample(p, Npts, ind=None, *, seed=None, sample_offset=0, device=0, manifold=None):
@@ -70,12 +63,8 @@ def sample(p, Npts, ind=None, *, seed=None, sample_offset=0, device=0, manifold=
     pts = np.empty(D * n)
     out = np.empty(n, dtype=np.int64)
     lab = None if ind is None else _labels(ind, n)
-    args = (C.byref(p._cstruct()), Npts, C.c_uint64(s), int(sample_offset), None if lab is None else ptr(lab, i64p),
-            ptr(pts, f64p), ptr(out, i64p), int(device))
-    if man is None:
-        _lib.check(_lib.lib.kdehip_sample(*args))
-    else:
-        _lib.check(_lib.lib.kdehip_sample_manifold(*args, ptr(man, u8p)))
+    _lib.check(_lib.lib.kdehip_sample_manifold(C.byref(p._cstruct()), Npts, C.c_uint64(s), int(sample_offset), optr(lab, i64p),
+                                               ptr(pts, f64p), ptr(out, i64p), int(device), _mf.pointer(man)))
     return pts.reshape(n, D).T.copy(), out
 
 
@@ -119,27 +108,21 @@ def sample_device_batch(items, stream=None, *, manifold=None):
     that have none yet, one draw launch per dimension count; every item gets what `DeviceDensity.sample_device` gives it.
     `manifold=`: one manifold for all items or one per item (None = Euclidean); an item's own `manifold` wins
     (kdehip_sample_device_batch_manifold).  Enqueues on `stream` and returns."""
-    from .product import ProductPlan
-    from .summary import _item_manifolds
     items = list(items)
     n = len(items)
-    circular = False
-    if manifold is not None or any("manifold" in it for it in items):   # (a call without any manifold pays for none)
-        mans = _item_manifolds(items, manifold)
-        circular = any(m is not None for m in mans)
-    arr = ((_lib.CSampleManifoldItem if circular else _lib.CSampleItem) * max(1, n))()
+    mans = None
+    if manifold is not None or any("manifold" in it for it in items):   # (a call without any manifold parses none)
+        mans = _mf.per_item(items, manifold)
+    arr = (_lib.CSampleManifoldItem * max(1, n))()
     for k, it in enumerate(items):
-        a = arr[k].item if circular else arr[k]
-        if circular and mans[k] is not None:
-            arr[k].circular_mask = sum(1 << d for d in range(len(mans[k])) if mans[k][d])
+        a = arr[k]
+        if mans is not None:
+            a.circular_mask = _mf.mask(mans[k])
         a.density = it["density"]._h
         a.Npts = int(it["Npts"])
-        a.seed = int(it.get("seed", 0)) & (2 ** 64 - 1)
+        a.seed = int(it.get("seed", 0)) & SEED_MASK
         a.sample_offset = int(it.get("sample_offset", 0))
-        a.d_ind_in = ProductPlan._addr(it.get("ind"))
-        a.d_pts = ProductPlan._addr(it["d_pts"])
-        a.d_ind = ProductPlan._addr(it["d_ind"])
-    if circular:
-        _lib.check(_lib.lib.kdehip_sample_device_batch_manifold(n, arr, ProductPlan._addr(stream)))
-    else:
-        _lib.check(_lib.lib.kdehip_sample_device_batch(n, arr, ProductPlan._addr(stream)))
+        a.d_ind_in = addr(it.get("ind"))
+        a.d_pts = addr(it["d_pts"])
+        a.d_ind = addr(it["d_ind"])
+    _lib.check(_lib.lib.kdehip_sample_device_batch_manifold(n, arr, addr(stream)))

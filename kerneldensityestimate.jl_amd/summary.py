@@ -19,8 +19,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import f64p, i32p, ptr, u8p
+from . import _lib, manifold as _mf
+from ._lib import addr, f64p, i32p, optr, ptr
 from .density import BallTreeDensity, getBW, getWeights, kde
 
 
@@ -61,46 +61,9 @@ def _wrap(t):
     return t - _TWO_PI * np.floor((t + _PI) / _TWO_PI)
 
 
-def _manifold(p, manifold, ndims=None, attr="manifold"):
-    """A `manifold=` / `tree_manifold=` argument as the uint8 enum array or None: "inherit" reads the density's record;
-    a wrong length or a value other than 0 / 1 is a ValueError (before any device is needed); all-Euclidean is None."""
-    from .product import _manifold_array
-    if isinstance(manifold, str):
-        if manifold != "inherit":
-            raise ValueError("manifold: a per-dimension sequence, None or 'inherit'")
-        manifold = getattr(p, attr, None)
-    man = _manifold_array(manifold, _ndim(p) if ndims is None else ndims)
-    if man is None:
-        return None
-    if (man > 1).any():
-        raise ValueError("manifold: every entry is 'euclid' (0) or 'circular' (1)")
-    return man if man.any() else None
-
-
-def _item_manifolds(items, manifold):
-    """the manifold of every item of a batch (`manifold=`: one for all or one per item; an item's own `manifold` key wins),
-    each parsed once per distinct (dimension count, value)"""
-    from .product import _batch_manifolds
-    dims = [it["density"].dims for it in items]
-    if manifold is not None and all(isinstance(m, str) or np.ndim(m) == 0 for m in manifold):
-        shared = [tuple(manifold)] * len(items)   # one for all: parsed below, once per dimension count
-    else:
-        shared = _batch_manifolds(manifold, dims)
-    seen, out = {}, []
-    for it, D, sh in zip(items, dims, shared):
-        m = it["manifold"] if "manifold" in it else sh
-        if m is None or isinstance(m, str):
-            out.append(_manifold(it["density"], m, ndims=D))
-            continue
-        key = (D, tuple(m))
-        if key not in seen:
-            seen[key] = _manifold(it["density"], m, ndims=D)
-        out.append(seen[key])
-    return out
-
-
-def _mp(man):
-    return None if man is None else ptr(man, u8p)
+def _manifold(p, manifold, attr="manifold"):
+    """the `manifold=` / `tree_manifold=` of a call on the density p (manifold.resolve)"""
+    return _mf.resolve(p, manifold, _ndim(p), attr)
 
 
 def _seqsum(x):
@@ -160,22 +123,12 @@ def _summary(p, *, extend=0.1, N=200, range_=False, mean=False, cov=False, argma
     for name, want, shape in (("range", range_, (2, D)), ("mean", mean, (D,)), ("cov", cov, (D, D)),
                               ("argmax", argmax, (D,)), ("values", values, (D, int(N)))):
         bufs[name] = np.zeros(shape) if want else None
-    args = [None if bufs[k] is None else ptr(bufs[k], f64p) for k in ("range", "mean", "cov", "argmax", "values")]
-    if man is None:
-        _lib.check(_lib.lib.kdehip_density_summary(p._h, C.byref(ext), int(N), *args))
-    else:
-        _lib.check(_lib.lib.kdehip_density_summary_manifold(p._h, C.byref(ext), int(N), *args, ptr(man, u8p)))
+    args = [optr(bufs[k], f64p) for k in ("range", "mean", "cov", "argmax", "values")]
+    _lib.check(_lib.lib.kdehip_density_summary_manifold(p._h, C.byref(ext), int(N), *args, _mf.pointer(man)))
     for k, v in bufs.items():
         if v is not None:
             out[k] = v.T.copy() if k == "range" else v  # range: D x 2 column-major
     return out
-
-
-def _sub(man, dl):
-    """the entries of a manifold array at the selected dims; None when none of them is circular"""
-    if man is None or not man[dl].any():
-        return None
-    return np.ascontiguousarray(man[dl])
 
 
 def marginal(p, dims, *, manifold=None, tree_manifold=None):
@@ -187,7 +140,7 @@ def marginal(p, dims, *, manifold=None, tree_manifold=None):
     if _is_device(p):
         return p.marginal(dims, manifold=manifold, tree_manifold=tree_manifold)
     dl = _dims_list(dims, p.bt.dims)
-    tman = _sub(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
+    tman = _mf.select(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
     _manifold(p, manifold)   # (validated; a BallTreeDensity has no manifold record)
     return kde(_leaf_points(p)[dl, :], getBW(p)[dl, 0], getWeights(p), tree_manifold=tman)
 
@@ -257,11 +210,8 @@ def getKDEMax(p, N=200, *, values=False, device=0, manifold=None):
     D = p.bt.dims
     m = np.zeros(D)
     vals = np.zeros((D, max(N, 0))) if values else None
-    vp = None if vals is None else ptr(vals, f64p)
-    if man is None:
-        _lib.check(_lib.lib.kdehip_kde_max(C.byref(p._cstruct()), N, ptr(m, f64p), vp, int(device)))
-    else:
-        _lib.check(_lib.lib.kdehip_kde_max_manifold(C.byref(p._cstruct()), N, ptr(m, f64p), vp, int(device), ptr(man, u8p)))
+    _lib.check(_lib.lib.kdehip_kde_max_manifold(C.byref(p._cstruct()), N, ptr(m, f64p), optr(vals, f64p), int(device),
+                                                _mf.pointer(man)))
     return (m, vals) if values else m
 
 
@@ -301,10 +251,10 @@ def intersIntgAppxIS(p, q, N=201, *, device=0, manifold=None):
     man = _manifold(p, manifold)
     out = C.c_double(0.0)
     if dev:
-        _lib.check(_lib.lib.kdehip_inters_intg_appx_is_device_manifold(p._h, q._h, int(N), C.byref(out), _mp(man)))
+        _lib.check(_lib.lib.kdehip_inters_intg_appx_is_device_manifold(p._h, q._h, int(N), C.byref(out), _mf.pointer(man)))
     else:
         _lib.check(_lib.lib.kdehip_inters_intg_appx_is_manifold(C.byref(p._cstruct()), C.byref(q._cstruct()), int(N),
-                                                                C.byref(out), int(device), _mp(man)))
+                                                                C.byref(out), int(device), _mf.pointer(man)))
     return float(out.value)
 
 
@@ -314,44 +264,34 @@ def summary_device_batch(items, stream=None, *, manifold=None):
     `range` (2D, D x 2 column-major), `mean` (D), `cov` (D*D), `argmax` (D), `values` (D*Ngrid).  `manifold=`: one manifold
     for all items or one per item (None = Euclidean), as `mul_device_batch` takes it; an item's own `manifold` wins.
     Euclidean and circular items may be mixed.  Enqueues on `stream` and returns."""
-    from .product import DeviceDensity, ProductPlan
+    from .product import DeviceDensity
     items = list(items)
     n = len(items)
     for it in items:
         if not isinstance(it["density"], DeviceDensity):
             raise TypeError("summary_device_batch: items of DeviceDensity")
-    circular = False
-    if manifold is not None or any("manifold" in it for it in items):   # (a call without any manifold pays for none)
-        mans = _item_manifolds(items, manifold)
-        circular = any(m is not None for m in mans)
-    arr = ((_lib.CSummaryManifoldItem if circular else _lib.CSummaryItem) * max(1, n))()
+    mans = None
+    if manifold is not None or any("manifold" in it for it in items):   # (a call without any manifold parses none)
+        mans = _mf.per_item(items, manifold)
+    arr = (_lib.CSummaryManifoldItem * max(1, n))()
     for k, it in enumerate(items):
-        a = arr[k].item if circular else arr[k]
+        a = arr[k]
         a.density = it["density"]._h
         a.extend = float(it.get("extend", 0.1))
         a.Ngrid = int(it.get("Ngrid", 200))
-        a.d_range, a.d_mean, a.d_cov = (ProductPlan._addr(it.get(x)) for x in ("range", "mean", "cov"))
-        a.d_argmax, a.d_values = ProductPlan._addr(it.get("argmax")), ProductPlan._addr(it.get("values"))
-        if circular and mans[k] is not None:
-            arr[k].circular_mask = sum(1 << d for d in range(len(mans[k])) if mans[k][d])
-    if circular:
-        _lib.check(_lib.lib.kdehip_summary_device_batch_manifold(n, arr, ProductPlan._addr(stream)))
-    else:
-        _lib.check(_lib.lib.kdehip_summary_device_batch(n, arr, ProductPlan._addr(stream)))
+        a.d_range, a.d_mean, a.d_cov = (addr(it.get(x)) for x in ("range", "mean", "cov"))
+        a.d_argmax, a.d_values = addr(it.get("argmax")), addr(it.get("values"))
+        if mans is not None:
+            a.circular_mask = _mf.mask(mans[k])
+    _lib.check(_lib.lib.kdehip_summary_device_batch_manifold(n, arr, addr(stream)))
 
 
 def _marginal_device(p, dims, manifold=None, tree_manifold=None):
-    """kdehip_density_marginal_device[_tree] (DeviceDensity.marginal)."""
-    from .product import DeviceDensity
+    """kdehip_density_marginal_device_tree (DeviceDensity.marginal)."""
     dl = _dims_list(dims, p.dims)
-    man = _sub(_manifold(p, manifold), dl)
-    tman = _sub(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
+    man = _mf.select(_manifold(p, manifold), dl)
+    tman = _mf.select(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
     d = np.array([x + 1 for x in dl], dtype=np.int32)
     h = C.c_void_p()
-    if tman is None:
-        _lib.check(_lib.lib.kdehip_density_marginal_device(C.byref(h), p._h, len(dl), ptr(d, i32p)))
-    else:
-        _lib.check(_lib.lib.kdehip_density_marginal_device_tree(C.byref(h), p._h, len(dl), ptr(d, i32p), ptr(tman, u8p)))
-    out = DeviceDensity(device=p.device, _handle=h)
-    out.manifold, out.tree_manifold = man, tman
-    return out
+    _lib.check(_lib.lib.kdehip_density_marginal_device_tree(C.byref(h), p._h, len(dl), ptr(d, i32p), _mf.pointer(tman)))
+    return type(p)._built(h, p.device, manifold=man, tree_manifold=tman)
