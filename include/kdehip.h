@@ -900,6 +900,47 @@ int kdehip_resample_device_manifold(kdehip_device_density **out, kdehip_device_d
                                     double *bw_out, int32_t *nevals, const uint8_t *manifold /* ndims bytes or NULL */,
                                     const uint8_t *tree_manifold /* ndims bytes or NULL */);
 
+/* ---- (5f) log-domain evaluation: evaluate_log, log-domain evalAvgLogL / entropy / kld / minkld ----------------------------
+ * The entries of 5 / 5b / 5d form p(x) = sum_i w_i exp(a_i) / norm in the linear domain, as the reference does: once every
+ * a_i is below about -745 (a query some 38 standard deviations from the nearest kernel) p is exactly 0, evalAvgLogL is -Inf
+ * and kld is +-Inf or NaN.  Those entries keep that behaviour, bit for bit.  The entries below return log p(x) itself, by
+ * log-sum-exp in the evaluation kernel, and the log-likelihoods built on it; they are this library's own, the reference has
+ * no counterpart.  Semantic, for a density bd with leaves i, weights w_i and ONE bandwidth vector v_k (section 5), a query x
+ * and a per-dimension `manifold` as in 5d (NULL = Euclidean; no Euclidean twins):
+ *   a_i     = sum_k d_ik^2 * (-0.5 / v_k), d_ik = x_k - c_ik, through wrap() first in a circular dimension: the expression,
+ *             fma order and -0.5 / v_k of the direct kernel
+ *   S       = { i : w_i > 0 } (leave-one-out: and i != q).  A leaf of weight zero takes no part in the maximum: a near,
+ *             weightless point would otherwise push every real term into underflow
+ *   m       = max_{i in S} a_i
+ *   log p   = m + log( sum_{i in S} w_i exp(a_i - m) ) - log(norm)   [- log(1 - w_q) for leave-one-out],
+ *             norm = (2 pi)^(D/2) * prod_k sqrt(v_k) as in section 5; S empty gives -Inf
+ *   evalAvgLogL(bd, at) = sum over { q : W_q != 0 } of W_q * log p(x_q), in the block order and the fixed 256-wide tree of
+ *             5b; -Inf only if some such log p is -Inf
+ *   entropy, kld, minkld: the compositions of 5b, leave_one_out exactly where the arguments are the same object.
+ * The sum is split as in 5b: consecutive 128-leaf chunks in groups that depend on (N, Nq) alone; a group carries (m, s), the
+ * carried s rescaled by exp(m_old - m_new) once per chunk, and the groups are combined in group order with M = max m_g,
+ * sum_g s_g exp(m_g - M).  So the host entry, a single resident call and any batch return the same bits, run after run.
+ * Where nothing underflows log p agrees with log of the direct entry to rounding (1e-12 relative), not bit for bit.
+ * Arguments: those of 5 / 5b / 5d, checked before a device is touched -- NULLs (KDEHIP_ERR_ARG), ndims mismatch
+ * (KDEHIP_ERR_DIM_MISMATCH), D above KDEHIP_MAX_DIMS or per-point bandwidths (KDEHIP_ERR_UNSUPPORTED), a manifold byte above
+ * 1 or a mask bit at or beyond ndims in a batch (KDEHIP_ERR_ARG).  fp64 only. */
+/* Host arrays, blocking: logp_out as p_out of kdehip_evaluate (leave_one_out: npts values in the ORIGINAL point order). */
+int kdehip_evaluate_log(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *logp_out,
+                        int device, const uint8_t *manifold);
+/* Resident, enqueue only on `stream`: as kdehip_evaluate_device / kdehip_evaluate_device_at (original point order of `at`,
+ * leave-one-out when at == bd). */
+int kdehip_evaluate_log_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,
+                               double *d_out, void *stream, const uint8_t *manifold);
+int kdehip_evaluate_log_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out,
+                                  void *stream, const uint8_t *manifold);
+/* Log-domain evalAvgLogL: host arrays; resident and blocking; resident batch, enqueue only (every item log-domain, Euclidean
+ * and circular items of any D mixed, each result bit for bit the single call's). */
+int kdehip_eval_avg_logl_log(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out, int device,
+                             const uint8_t *manifold);
+int kdehip_eval_avg_logl_log_device(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                    double *out, const uint8_t *manifold);
+int kdehip_eval_avg_logl_log_device_batch(int n, const kdehip_logl_manifold_item *items, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,12 @@ SIGNATURES = {
     "kdehip_eval_avg_logl_manifold": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int, f64p, C.c_int, u8p]),
     "kdehip_eval_avg_logl_device_manifold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p, u8p]),
     "kdehip_eval_avg_logl_device_batch_manifold": (C.c_int, [C.c_int, C.POINTER(CLoglManifoldItem), C.c_void_p, C.c_void_p]),
+    "kdehip_evaluate_log": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_evaluate_log_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_evaluate_log_device_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_eval_avg_logl_log": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_eval_avg_logl_log_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p, u8p]),
+    "kdehip_eval_avg_logl_log_device_batch": (C.c_int, [C.c_int, C.POINTER(CLoglManifoldItem), C.c_void_p, C.c_void_p]),
     "kdehip_auto_bandwidth_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, u8p]),
     "kdehip_make_density_auto_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p,
                                                     i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),

@@ -67,16 +67,31 @@ def kde_auto(points, device=0, overlap=None, manifold=None, tree_manifold=None) 
     return bd
 
 
+def evaluate_log(bd, pos=None, lvFlag=False, manifold=None, device=0):
+    """log of `evaluateDualTree(bd, pos, lvFlag)` by log-sum-exp in the kernel (kdehip_evaluate_log, include/kdehip.h
+    section 5f): finite where the density itself underflows to 0.  Same shapes as `evaluateDualTree`; host densities only
+    (a DeviceDensity has `.evaluate_log`)."""
+    from .product import DeviceDensity
+    if not isinstance(bd, BallTreeDensity) or isinstance(pos, DeviceDensity):
+        raise TypeError("evaluate_log: a BallTreeDensity at host points or a BallTreeDensity (a DeviceDensity has "
+                        ".evaluate_log)")
+    return _evaluate(_lib.lib.kdehip_evaluate_log, bd, pos, lvFlag, device, manifold)
+
+
 def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, device=0, manifold=None):
     """`evaluateDualTree(bd, pos, lvFlag)` (src/DualTree01.jl:370-421) with FORCE_EVAL_DIRECT = true
     (errTol is then unused, as in the reference).  pos: (D, Nq) matrix, a vector of 1-D positions, or a
     BallTreeDensity whose points are used; lvFlag=True (or pos is bd) evaluates leave-one-out at bd's
     own points and returns the values in the original point order."""
+    return _evaluate(_lib.lib.kdehip_evaluate_manifold, bd, pos, lvFlag, device, manifold)
+
+
+def _evaluate(entry, bd, pos, lvFlag, device, manifold):
     cd = bd._cstruct()
     man, mp = _man_ptr(manifold, bd.bt.dims)  # (manifold: circular differences in those dimensions, kdehip.h section 5d)
     if lvFlag or pos is bd:
         out = np.zeros(bd.bt.num_points)
-        _lib.check(_lib.lib.kdehip_evaluate_manifold(C.byref(cd), None, 0, 1, ptr(out, f64p), int(device), mp))
+        _lib.check(entry(C.byref(cd), None, 0, 1, ptr(out, f64p), int(device), mp))
         return out
     if isinstance(pos, BallTreeDensity):
         from .density import getPoints
@@ -88,6 +103,5 @@ def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, d
         raise ValueError("bd and pos must have the same dimension")
     flat = np.ascontiguousarray(pos.T).ravel()
     out = np.zeros(pos.shape[1])
-    _lib.check(_lib.lib.kdehip_evaluate_manifold(C.byref(cd), ptr(flat, f64p), pos.shape[1], 0, ptr(out, f64p), int(device),
-                                                 mp))
+    _lib.check(entry(C.byref(cd), ptr(flat, f64p), pos.shape[1], 0, ptr(out, f64p), int(device), mp))
     return out

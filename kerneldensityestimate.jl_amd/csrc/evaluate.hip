@@ -18,6 +18,8 @@
 //                           instead of adding -Inf;
 //   logl_reduce_kernel      only when an item asks for a log-likelihood: per item, the block shares summed in block order
 //                           (or -Inf if a flag is up) into one double.
+// Log-domain items (kdehip.h section 5f: log p by log-sum-exp, finite where p underflows) run eval_partial_log_kernel<D> and
+// eval_finish_log_kernel in launches of their own, with the same mapping, split and reduction.
 // The group split (split_chunks(N, Nq, 1)) depends on the item's (N, Nq) alone, so nothing depends on the launch or the
 // batch: the host entry, a single device call and any batch give the same bits.
 #include <hip/hip_runtime.h>
@@ -77,6 +79,7 @@ struct EvalItem {
   double norm0;         // (2 pi)^(D/2) as the host's libm rounds it
   int64_t N, Nq, chunks_per_group;
   int32_t ngroups, nfb, D, loo;
+  int32_t logdom, pad_;  // log-domain item (kdehip.h section 5f): partial is [2][ngroups][Nq], the maxima m then the sums s
 };
 
 // partial[g][q] = sum over the source chunks c of group g, in chunk order, of
@@ -154,6 +157,96 @@ __global__ __launch_bounds__(kEvalThreads) void eval_partial_kernel(const EvalIt
   if (q < pb.Nq) pb.partial[grp * pb.Nq + q] = total;
 }
 
+// The log-domain twin (kdehip.h section 5f): the same items, block mapping, LDS double buffer and a_i (same fma order, same
+// nhib[k]) as eval_partial_kernel, but the block carries (m, s) with
+//   m = max a_i,  s = sum w_i exp(a_i - m)   over S = { i in the group : w_i > 0, (i != q if loo) }
+// instead of the plain sum, so nothing underflows that matters to log p.  Per staged chunk: pass one takes the chunk's
+// maximum over S (D fmas per source, no exp), the carried s is rescaled ONCE by exp_nonpos(m_old - m_new), pass two
+// recomputes a_i and adds w_i exp_nonpos(a_i - m_new): one exp per pair, as the direct kernel.  A source outside S takes no
+// part in the maximum (a near, weightless point would push every real term into underflow) and adds nothing.  A group
+// with S empty leaves (m, s) = (-Inf, 0).  Every lane, those beyond Nq included, walks the same chunks and barriers.
+// partial[g][q] = m, partial[ngroups + g][q] = s.
+template <int D, bool CIRC = false>
+__global__ __launch_bounds__(kEvalThreads) void eval_partial_log_kernel(const EvalItem *__restrict__ items,
+                                                                        const int32_t *__restrict__ first, int n,
+                                                                        const uint32_t *__restrict__ masks = nullptr) {
+  __shared__ double sSrc[2][kEvalChunk * (D + 1)];
+  __shared__ double sExpTab[32];
+  if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
+  const int b = static_cast<int>(blockIdx.x) + first[0];
+  const int i = item_of_block(first, n, b);
+  const EvalItem pb = items[i];
+  unsigned circ = 0;
+  if constexpr (CIRC) circ = __builtin_amdgcn_readfirstlane(masks[i]);
+  const int64_t qblocks = (pb.Nq + kEvalThreads - 1) / kEvalThreads;
+  const int64_t kb = b - first[i];
+  const int64_t qb = kb % qblocks, grp = kb / qblocks;
+  const int64_t q = qb * kEvalThreads + threadIdx.x;
+  const int64_t c_begin = grp * pb.chunks_per_group;
+  int64_t c_end = c_begin + pb.chunks_per_group;
+  const int64_t nchunks = (pb.N + kEvalChunk - 1) / kEvalChunk;
+  if (c_end > nchunks) c_end = nchunks;
+  if (c_begin >= c_end) return;  // block-uniform
+  double nhib[D];  // -1/(2 bw_k)
+#pragma unroll
+  for (int k = 0; k < D; ++k) nhib[k] = -0.5 / pb.bw[k];
+  double x[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = (q < pb.Nq) ? pb.qry[q * D + k] : 0.0;
+  auto stage = [&](int64_t c, int buf) {
+    const int64_t i0 = c * kEvalChunk;
+    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
+    for (int t = threadIdx.x; t < cnt * (D + 1); t += kEvalThreads) {
+      const int i = t / (D + 1), f = t % (D + 1);
+      sSrc[buf][t] = (f < D) ? pb.src[(i0 + i) * D + f] : pb.w[i0 + i];
+    }
+  };
+  auto exponent = [&](const double *s) {  // a_i
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double d = x[k] - s[k];
+      if constexpr (CIRC) {
+        if ((circ >> k) & 1u) d = circ_wrap(d);
+      }
+      acc = fma(d * d, nhib[k], acc);
+    }
+    return acc;
+  };
+  const int64_t skip = pb.loo ? q : -1;  // leave-one-out: the self term is not in S
+  stage(c_begin, 0);
+  double m = -INFINITY, total = 0.0;
+  for (int64_t c = c_begin; c < c_end; ++c) {
+    const int buf = static_cast<int>((c - c_begin) & 1);
+    __syncthreads();  // chunk c is staged; the other buffer is free again
+    if (c + 1 < c_end) stage(c + 1, buf ^ 1);
+    const int64_t i0 = c * kEvalChunk;
+    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
+    double cm = -INFINITY;
+    for (int i = 0; i < cnt; ++i) {
+      const double *s = sSrc[buf] + i * (D + 1);
+      const double acc = exponent(s);
+      cm = (s[D] > 0.0 && i0 + i != skip) ? fmax(cm, acc) : cm;
+    }
+    if (cm > m) {  // (m == -Inf: total is still 0)
+      total *= exp_nonpos(m - cm, sExpTab);
+      m = cm;
+    }
+    double sum = 0.0;
+    for (int i = 0; i < cnt; ++i) {
+      const double *s = sSrc[buf] + i * (D + 1);
+      const double acc = exponent(s);
+      const bool in = s[D] > 0.0 && i0 + i != skip;  // in S: then acc <= m
+      sum += in ? s[D] * exp_nonpos(acc - m, sExpTab) : 0.0;
+    }
+    total += sum;
+  }
+  if (q < pb.Nq) {
+    pb.partial[grp * pb.Nq + q] = m;
+    pb.partial[(pb.ngroups + grp) * pb.Nq + q] = total;
+  }
+}
+
 // p[q] = (sum over the groups, in group order) / norm [/ (1 - w_q)]   (src/DualTree01.jl:325-340), then W log p and the
 // block's share (items [0, n), item i owns blocks [first[i], first[i+1]))
 __global__ __launch_bounds__(kFinishThreads) void eval_finish_kernel(const EvalItem *__restrict__ items,
@@ -197,6 +290,63 @@ __global__ __launch_bounds__(kFinishThreads) void eval_finish_kernel(const EvalI
   }
 }
 
+// The log-domain finish (section 5f), for the items [0, n) with block offsets first[] (first[0] is the launch's first
+// block): the groups combined in group order, M = max m_g, S = sum s_g exp(m_g - M),
+//   log p = M + log S - log norm [- log(1 - w_q)],   -Inf when no group has a source in S;
+// stored and reduced as eval_finish_kernel does, with W log p summed over the W != 0 only and the block's flag raised by a
+// weighted -Inf.
+__global__ __launch_bounds__(kFinishThreads) void eval_finish_log_kernel(const EvalItem *__restrict__ items,
+                                                                       const int32_t *__restrict__ first, int n) {
+  __shared__ double red[kFinishThreads];
+  const int b = static_cast<int>(blockIdx.x) + first[0];
+  const int i = item_of_block(first, n, b);
+  const EvalItem it = items[i];
+  const int fb = b - first[i];
+  const int64_t q = static_cast<int64_t>(fb) * kFinishThreads + threadIdx.x;
+  double norm = it.norm0;  // as eval_finish_kernel
+  for (int k = 0; k < it.D; ++k) norm *= __dsqrt_rn(it.bw[k]);
+  const double lognorm = log(norm);
+  double term = 0.0;
+  int zero = 0;
+  if (q < it.Nq) {
+    const double *pm = it.partial + q, *ps = pm + static_cast<int64_t>(it.ngroups) * it.Nq;
+    double M = -INFINITY;
+    for (int c = 0; c < it.ngroups; ++c) M = fmax(M, pm[static_cast<int64_t>(c) * it.Nq]);
+    double lp = -INFINITY;
+    if (M > -INFINITY) {
+      double S = 0.0;
+      for (int c = 0; c < it.ngroups; ++c) {
+        const double mg = pm[static_cast<int64_t>(c) * it.Nq];
+        if (mg > -INFINITY) S += ps[static_cast<int64_t>(c) * it.Nq] * exp(mg - M);
+      }
+      lp = M + log(S) - lognorm;
+      if (it.loo) lp -= log(1.0 - it.w[q]);
+    }
+    if (it.out) {
+      const int64_t o = it.perm ? it.perm[q] - 1 : q;
+      if (o >= 0 && o < it.Nq) it.out[o] = lp;
+    }
+    if (it.qw) {
+      const double W = it.qw[q];
+      if (W != 0.0) {
+        if (lp == -INFINITY) zero = 1;
+        else term = W * lp;
+      }
+    }
+  }
+  if (!it.logl) return;  // (block-uniform)
+  red[threadIdx.x] = term;
+  const int anyzero = __syncthreads_or(zero);
+  for (int off = kFinishThreads / 2; off > 0; off >>= 1) {
+    if (static_cast<int>(threadIdx.x) < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    it.bpart[fb] = red[0];
+    it.bzero[fb] = anyzero;
+  }
+}
+
 // one thread per item: the block shares in block order
 __global__ void logl_reduce_kernel(const EvalItem *__restrict__ items, int n) {
   const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
@@ -212,13 +362,17 @@ __global__ void logl_reduce_kernel(const EvalItem *__restrict__ items, int n) {
   *it.logl = zero ? -INFINITY : s;
 }
 
-// d_masks: the items' circular masks (all nonzero), or null: Euclidean items
+// d_masks: the items' circular masks (all nonzero), or null: Euclidean items; logdom: log-domain items
 int launch_partial(int D, const EvalItem *d_items, const int32_t *d_first, int n, int blocks, const uint32_t *d_masks,
-                   hipStream_t st) {
+                   bool logdom, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(blocks)), block(kEvalThreads);
   KDEHIP_CHECK_RC(dispatch_dims(D, [&](auto dim) {
     constexpr int kD = decltype(dim)::value;
-    if (d_masks) hipLaunchKernelGGL((eval_partial_kernel<kD, true>), grid, block, 0, st, d_items, d_first, n, d_masks);
+    if (logdom) {
+      if (d_masks) hipLaunchKernelGGL((eval_partial_log_kernel<kD, true>), grid, block, 0, st, d_items, d_first, n, d_masks);
+      else hipLaunchKernelGGL((eval_partial_log_kernel<kD, false>), grid, block, 0, st, d_items, d_first, n,
+                              static_cast<const uint32_t *>(nullptr));
+    } else if (d_masks) hipLaunchKernelGGL((eval_partial_kernel<kD, true>), grid, block, 0, st, d_items, d_first, n, d_masks);
     else hipLaunchKernelGGL((eval_partial_kernel<kD, false>), grid, block, 0, st, d_items, d_first, n,
                             static_cast<const uint32_t *>(nullptr));
   }));
@@ -258,7 +412,7 @@ class EvalRun {
     scratch_.resize(n);
     for (size_t k = 0; k < n; ++k) {
       const EvalItem &it = items[k];
-      scratch_[k] = c.take(sizeof(double) * (it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
+      scratch_[k] = c.take(sizeof(double) * ((it.logdom ? 2 : 1) * it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
     }
     KDEHIP_CHECK(blk_.alloc(c.mark(), o_res_ + sizeof(double) * nres_));
     return KDEHIP_OK;
@@ -272,21 +426,22 @@ class EvalRun {
     KDEHIP_CHECK_RC(upload(st));
     return launch();
   }
-  // scratch pointers, descriptors sorted by D (Euclidean items before circular ones), one upload on `st`
+  // scratch pointers, descriptors sorted (the direct items before the log-domain ones; by D; Euclidean items before circular
+  // ones), one upload on `st`
   int upload(hipStream_t st) {
     const size_t n = items.size();
     for (size_t k = 0; k < n; ++k) {
       EvalItem &it = items[k];
       unsigned char *s = dev() + scratch_[k];
       it.partial = reinterpret_cast<double *>(s);
-      it.bpart = it.partial + static_cast<int64_t>(it.ngroups) * it.Nq;
+      it.bpart = it.partial + static_cast<int64_t>(it.logdom ? 2 : 1) * it.ngroups * it.Nq;
       it.bzero = reinterpret_cast<int32_t *>(it.bpart + it.nfb);
     }
     circ.resize(n, 0u);
     {
       std::vector<size_t> ord(n);
       for (size_t k = 0; k < n; ++k) ord[k] = k;
-      auto key = [&](size_t k) { return 2 * items[k].D + (circ[k] ? 1 : 0); };
+      auto key = [&](size_t k) { return (items[k].logdom ? 1024 : 0) + 2 * items[k].D + (circ[k] ? 1 : 0); };
       std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return key(a) < key(b); });
       std::vector<EvalItem> si(n);
       std::vector<uint32_t> sc(n);
@@ -306,7 +461,8 @@ class EvalRun {
     KDEHIP_CHECK(blk_.upload(o_res_, st));
     return KDEHIP_OK;
   }
-  // the launches behind the upload: two kernels, and the per-item reduce when an item asks for a log-likelihood
+  // the launches behind the upload: two kernels (and their log-domain twins for the log-domain items), and the per-item
+  // reduce when an item asks for a log-likelihood
   int launch() {
     const hipStream_t st = blk_.stream();
     const size_t n = items.size();
@@ -314,19 +470,24 @@ class EvalRun {
     const EvalItem *d_items = reinterpret_cast<const EvalItem *>(dev() + o_items_);
     const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 1);
     const uint32_t *d_masks = reinterpret_cast<const uint32_t *>(dev() + o_masks_);
-    for (size_t a = 0; a < n;) {  // one launch per distinct D, and one more for its items with a circular dimension
+    for (size_t a = 0; a < n;) {  // one launch per distinct D, and one more for its circular and for its log-domain items
       size_t e = a;
-      while (e < n && items[e].D == items[a].D && !circ[e] == !circ[a]) ++e;
+      while (e < n && items[e].D == items[a].D && !circ[e] == !circ[a] && items[e].logdom == items[a].logdom) ++e;
       const int blocks = pfirst[e] - pfirst[a];
       if (blocks > 0) {
         KDEHIP_CHECK_RC(launch_partial(items[a].D, d_items + a, d_pfirst + a, static_cast<int>(e - a), blocks,
-                                       circ[a] ? d_masks + a : nullptr, st));
+                                       circ[a] ? d_masks + a : nullptr, items[a].logdom != 0, st));
       }
       a = e;
     }
-    if (ffirst[n] > 0)
-      hipLaunchKernelGGL(eval_finish_kernel, dim3(static_cast<unsigned>(ffirst[n])), dim3(kFinishThreads), 0, st, d_items,
-                         d_ffirst, static_cast<int>(n));
+    size_t nd = 0;  // the direct items are the first nd
+    while (nd < n && !items[nd].logdom) ++nd;
+    if (ffirst[nd] > 0)
+      hipLaunchKernelGGL(eval_finish_kernel, dim3(static_cast<unsigned>(ffirst[nd])), dim3(kFinishThreads), 0, st, d_items,
+                         d_ffirst, static_cast<int>(nd));
+    if (ffirst[n] > ffirst[nd])
+      hipLaunchKernelGGL(eval_finish_log_kernel, dim3(static_cast<unsigned>(ffirst[n] - ffirst[nd])), dim3(kFinishThreads), 0,
+                         st, d_items + nd, d_ffirst + nd, static_cast<int>(n - nd));
     if (std::any_of(items.begin(), items.end(), [](const EvalItem &it) { return it.logl != nullptr; }))
       hipLaunchKernelGGL(logl_reduce_kernel, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, st, d_items,
                          static_cast<int>(n));
@@ -379,7 +540,7 @@ int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at,
 }
 
 // bd at at's leaf points (tree order; out, if any, through at's permutation), W = at's leaf weights
-EvalItem pair_item(const kdehip_device_density *bd, const kdehip_device_density *at, int loo, bool logl) {
+EvalItem pair_item(const kdehip_device_density *bd, const kdehip_device_density *at, int loo, bool logl, bool logdom) {
   EvalItem it{};
   const int64_t N = bd->N, Nq = at->N;
   const int D = bd->D;
@@ -388,7 +549,7 @@ EvalItem pair_item(const kdehip_device_density *bd, const kdehip_device_density 
   it.qw = logl ? at->weights + Nq : nullptr;
   it.perm = at->perm + Nq;
   it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = Nq; it.D = D; it.loo = loo ? 1 : 0;
+  it.N = N; it.Nq = Nq; it.D = D; it.loo = loo ? 1 : 0; it.logdom = logdom ? 1 : 0;
   return it;
 }
 
@@ -399,8 +560,10 @@ extern "C" int kdehip_evaluate(const kdehip_density *bd, const double *pos, int6
   return kdehip_evaluate_manifold(bd, pos, Nq, leave_one_out, p_out, device, nullptr);
 }
 
-extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,
-                                        double *p_out, int device, const uint8_t *manifold) {
+// The bodies of the entries: `logdom` selects the log-domain kernels (section 5f); everything else -- checks, layout of the
+// call's block, streams -- is shared, so a log-domain entry refuses what its direct twin refuses, with the same words.
+static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out, int device,
+                         const uint8_t *manifold, bool logdom) {
   if (!bd || !p_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
@@ -432,7 +595,7 @@ extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *
   EvalRun run;
   EvalItem it{};
   it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = Nq; it.D = D; it.loo = leave_one_out ? 1 : 0;
+  it.N = N; it.Nq = Nq; it.D = D; it.loo = leave_one_out ? 1 : 0; it.logdom = logdom ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq)));
@@ -464,8 +627,8 @@ extern "C" int kdehip_eval_avg_logl(const kdehip_density *bd, const kdehip_densi
   return kdehip_eval_avg_logl_manifold(bd, at, leave_one_out, out, device, nullptr);
 }
 
-extern "C" int kdehip_eval_avg_logl_manifold(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
-                                             int device, const uint8_t *manifold) {
+static int eval_avg_logl_host(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out, int device,
+                              const uint8_t *manifold, bool logdom) {
   // every check that needs no device comes first
   if (!bd || !out) return set_error(KDEHIP_ERR_ARG, "null argument");
   if (leave_one_out && at && at != bd) return set_error(KDEHIP_ERR_ARG, "leave_one_out needs at == bd (or at == NULL)");
@@ -495,7 +658,7 @@ extern "C" int kdehip_eval_avg_logl_manifold(const kdehip_density *bd, const kde
   EvalRun run;
   EvalItem it{};
   it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = Nq; it.D = static_cast<int32_t>(D); it.loo = leave_one_out ? 1 : 0;
+  it.N = N; it.Nq = Nq; it.D = static_cast<int32_t>(D); it.loo = leave_one_out ? 1 : 0; it.logdom = logdom ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix));
@@ -532,8 +695,7 @@ extern "C" int kdehip_eval_avg_logl_device_batch(int n, const kdehip_logl_item *
   }
 }
 
-extern "C" int kdehip_eval_avg_logl_device_batch_manifold(int n, const kdehip_logl_manifold_item *items, double *d_out,
-                                                          void *stream) {
+static int eval_avg_logl_batch(int n, const kdehip_logl_manifold_item *items, double *d_out, void *stream, bool logdom) {
   if (n < 0 || (n > 0 && (!items || !d_out))) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: bad item list");
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
@@ -549,7 +711,7 @@ extern "C" int kdehip_eval_avg_logl_device_batch_manifold(int n, const kdehip_lo
   if (rc != KDEHIP_OK) return rc;
   EvalRun run;
   for (int i = 0; i < n; ++i) {
-    run.items.push_back(pair_item(items[i].bd, items[i].at, items[i].leave_one_out, true));
+    run.items.push_back(pair_item(items[i].bd, items[i].at, items[i].leave_one_out, true, logdom));
     run.items.back().logl = d_out + i;
     run.circ.push_back(items[i].circular_mask);
   }
@@ -563,8 +725,8 @@ extern "C" int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, cons
   return kdehip_eval_avg_logl_device_manifold(bd, at, leave_one_out, out, nullptr);
 }
 
-extern "C" int kdehip_eval_avg_logl_device_manifold(const kdehip_device_density *bd, const kdehip_device_density *at,
-                                                    int leave_one_out, double *out, const uint8_t *manifold) {
+static int eval_avg_logl_resident(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                  double *out, const uint8_t *manifold, bool logdom) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
   int rc = check_pair(bd, at, leave_one_out);
   if (rc != KDEHIP_OK) return rc;
@@ -574,7 +736,7 @@ extern "C" int kdehip_eval_avg_logl_device_manifold(const kdehip_device_density 
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;
   EvalRun run;
-  run.items.push_back(pair_item(bd, at, leave_one_out, true));
+  run.items.push_back(pair_item(bd, at, leave_one_out, true, logdom));
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   run.items[0].logl = run.result(0);
@@ -589,10 +751,13 @@ extern "C" int kdehip_evaluate_device(const kdehip_device_density *bd, const dou
   return kdehip_evaluate_device_manifold(bd, d_pos, Nq, leave_one_out, d_out, stream, nullptr);
 }
 
-extern "C" int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, const double *d_pos, int64_t Nq,
-                                               int leave_one_out, double *d_out, void *stream, const uint8_t *manifold) {
+static int evaluate_resident_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out, void *stream,
+                                const uint8_t *manifold, bool logdom);
+
+static int evaluate_resident(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out, double *d_out,
+                             void *stream, const uint8_t *manifold, bool logdom) {
   if (!bd || !d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  if (leave_one_out) return kdehip_evaluate_device_at_manifold(bd, bd, d_out, stream, manifold);
+  if (leave_one_out) return evaluate_resident_at(bd, bd, d_out, stream, manifold, logdom);
   if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
   int rc = check_pair(bd, bd, 0);
   if (rc != KDEHIP_OK) return rc;
@@ -603,7 +768,7 @@ extern "C" int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, 
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;
   EvalRun run;
-  EvalItem it = pair_item(bd, bd, 0, false);
+  EvalItem it = pair_item(bd, bd, 0, false, logdom);
   it.qry = d_pos; it.perm = nullptr; it.Nq = Nq; it.out = d_out;
   run.items.push_back(it);
   run.circ.push_back(circ);
@@ -617,8 +782,8 @@ extern "C" int kdehip_evaluate_device_at(const kdehip_device_density *bd, const 
   return kdehip_evaluate_device_at_manifold(bd, at, d_out, stream, nullptr);
 }
 
-extern "C" int kdehip_evaluate_device_at_manifold(const kdehip_device_density *bd, const kdehip_device_density *at,
-                                                  double *d_out, void *stream, const uint8_t *manifold) {
+static int evaluate_resident_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out, void *stream,
+                                const uint8_t *manifold, bool logdom) {
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   int rc = check_pair(bd, at, at == bd);
   if (rc != KDEHIP_OK) return rc;
@@ -628,11 +793,61 @@ extern "C" int kdehip_evaluate_device_at_manifold(const kdehip_device_density *b
   rc = guard.enter(bd->device);
   if (rc != KDEHIP_OK) return rc;
   EvalRun run;
-  EvalItem it = pair_item(bd, at, at == bd, false);
+  EvalItem it = pair_item(bd, at, at == bd, false, logdom);
   it.out = d_out;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
   return run.defer(bd->device);
+}
+
+extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,
+                                        double *p_out, int device, const uint8_t *manifold) {
+  return evaluate_host(bd, pos, Nq, leave_one_out, p_out, device, manifold, false);
+}
+extern "C" int kdehip_eval_avg_logl_manifold(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
+                                             int device, const uint8_t *manifold) {
+  return eval_avg_logl_host(bd, at, leave_one_out, out, device, manifold, false);
+}
+extern "C" int kdehip_eval_avg_logl_device_batch_manifold(int n, const kdehip_logl_manifold_item *items, double *d_out,
+                                                          void *stream) {
+  return eval_avg_logl_batch(n, items, d_out, stream, false);
+}
+extern "C" int kdehip_eval_avg_logl_device_manifold(const kdehip_device_density *bd, const kdehip_device_density *at,
+                                                    int leave_one_out, double *out, const uint8_t *manifold) {
+  return eval_avg_logl_resident(bd, at, leave_one_out, out, manifold, false);
+}
+extern "C" int kdehip_evaluate_device_manifold(const kdehip_device_density *bd, const double *d_pos, int64_t Nq,
+                                               int leave_one_out, double *d_out, void *stream, const uint8_t *manifold) {
+  return evaluate_resident(bd, d_pos, Nq, leave_one_out, d_out, stream, manifold, false);
+}
+extern "C" int kdehip_evaluate_device_at_manifold(const kdehip_device_density *bd, const kdehip_device_density *at,
+                                                  double *d_out, void *stream, const uint8_t *manifold) {
+  return evaluate_resident_at(bd, at, d_out, stream, manifold, false);
+}
+
+// ---- log-domain entries (kdehip.h section 5f): the same bodies with the log-domain kernels
+extern "C" int kdehip_evaluate_log(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *logp_out,
+                                   int device, const uint8_t *manifold) {
+  return evaluate_host(bd, pos, Nq, leave_one_out, logp_out, device, manifold, true);
+}
+extern "C" int kdehip_evaluate_log_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int leave_one_out,
+                                          double *d_out, void *stream, const uint8_t *manifold) {
+  return evaluate_resident(bd, d_pos, Nq, leave_one_out, d_out, stream, manifold, true);
+}
+extern "C" int kdehip_evaluate_log_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out,
+                                             void *stream, const uint8_t *manifold) {
+  return evaluate_resident_at(bd, at, d_out, stream, manifold, true);
+}
+extern "C" int kdehip_eval_avg_logl_log(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, double *out,
+                                        int device, const uint8_t *manifold) {
+  return eval_avg_logl_host(bd, at, leave_one_out, out, device, manifold, true);
+}
+extern "C" int kdehip_eval_avg_logl_log_device(const kdehip_device_density *bd, const kdehip_device_density *at,
+                                               int leave_one_out, double *out, const uint8_t *manifold) {
+  return eval_avg_logl_resident(bd, at, leave_one_out, out, manifold, true);
+}
+extern "C" int kdehip_eval_avg_logl_log_device_batch(int n, const kdehip_logl_manifold_item *items, double *d_out, void *stream) {
+  return eval_avg_logl_batch(n, items, d_out, stream, true);
 }

@@ -589,6 +589,55 @@ hip_minkld(p::BallTreeDensity, q::BallTreeDensity, manifold::AbstractVector; dev
   min(abs(hip_kld(p, q, manifold; device=device)), abs(hip_kld(q, p, manifold; device=device)))
 
 """
+    hip_evaluate_log(bd, pos, lvFlag=false; manifold=nothing, device=0)
+
+`log.(evaluateDualTree(bd, pos, lvFlag))` by log-sum-exp in the kernel (`kdehip_evaluate_log`, include/kdehip.h
+section 5f): finite where the density itself underflows to 0.  `manifold` as in `hip_evaluateDualTree`, `nothing` =
+Euclidean.  The semantic is the library's own (the reference has no counterpart): not installed by `enable!()`.
+"""
+function hip_evaluate_log(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, lvFlag::Bool=false; manifold=nothing, device::Int=0)
+  Ndim(bd) == size(pos, 1) || error("bd and pos must have the same dimension")
+  man = manifold === nothing ? zeros(UInt8, Ndim(bd)) : manifold_bytes(manifold, Ndim(bd))
+  Nq = lvFlag ? Npts(bd) : size(pos, 2)
+  out = zeros(Nq)
+  cd = Ref(CDensity(bd))
+  posd = Matrix{Float64}(pos)
+  GC.@preserve bd posd man begin
+    check(ccall((:kdehip_evaluate_log, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Cint, Ptr{UInt8}),
+                cd, posd, size(pos, 2), lvFlag ? 1 : 0, out, device, man))
+  end
+  return out
+end
+
+"""
+    hip_evalAvgLogL_log(bd1, bd2; manifold=nothing, device=0)
+
+Log-domain `evalAvgLogL` (`kdehip_eval_avg_logl_log`, section 5f): the sum over `W != 0` of `W log p` with `log p` by
+log-sum-exp, `-Inf` only where `bd1` has no weighted point; `hip_entropy_log`, `hip_kld_log` and `hip_minkld_log` are its
+compositions, leave-one-out where the arguments are the same object.  Not installed by `enable!()`.
+"""
+function hip_evalAvgLogL_log(bd1::BallTreeDensity, bd2::BallTreeDensity; manifold=nothing, device::Int=0)
+  Ndim(bd1) == Ndim(bd2) || error("evaluate -- dimensions of two BallTreeDensities must match")
+  man = manifold === nothing ? zeros(UInt8, Ndim(bd1)) : manifold_bytes(manifold, Ndim(bd1))
+  loo = bd1 === bd2
+  c1 = Ref(CDensity(bd1))
+  c2 = loo ? c1 : Ref(CDensity(bd2))
+  out = Ref{Float64}(0.0)
+  GC.@preserve bd1 bd2 man begin
+    check(ccall((:kdehip_eval_avg_logl_log, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Cint, Ptr{Float64}, Cint, Ptr{UInt8}),
+                c1, c2, loo ? 1 : 0, out, device, man))
+  end
+  return out[]
+end
+hip_entropy_log(bd::BallTreeDensity; manifold=nothing, device::Int=0) = -hip_evalAvgLogL_log(bd, bd; manifold=manifold, device=device)
+hip_kld_log(p1::BallTreeDensity, p2::BallTreeDensity; manifold=nothing, device::Int=0) =
+  hip_evalAvgLogL_log(p1, p1; manifold=manifold, device=device) - hip_evalAvgLogL_log(p2, p1; manifold=manifold, device=device)
+hip_minkld_log(p::BallTreeDensity, q::BallTreeDensity; manifold=nothing, device::Int=0) =
+  min(abs(hip_kld_log(p, q; manifold=manifold, device=device)), abs(hip_kld_log(q, p; manifold=manifold, device=device)))
+
+"""
     hip_auto_bandwidth(points, manifold; device=0)
 
 The bandwidth of `kde!(points, addop, diffop)` with the library's circular `diffop` in the marked dimensions

@@ -6,6 +6,9 @@ kernels in csrc/evaluate.hip).
 Leave-one-out is decided by identity, as in the reference (`bd == locations` on a mutable struct, :333): evalAvgLogL(p, p)
 skips the self terms, evalAvgLogL(p, copy_of_p) does not -- so kld(p, p) is not 0.  Both arguments are BallTreeDensity
 (host arrays, evaluated on `device`) or both DeviceDensity (on their own device); mixing the two is a TypeError.
+
+`log_domain=True` (include/kdehip.h section 5f) forms every log p by log-sum-exp in the kernel: where the default returns
+-inf because a p underflowed to 0, the result stays finite and ordered.  The default is the reference's arithmetic.
 """
 from __future__ import annotations
 
@@ -34,9 +37,10 @@ def _mask(man):
     return 0 if man is None else int(sum(int(v) << k for k, v in enumerate(man)))
 
 
-def evalAvgLogL(bd1, bd2, *, device=0, manifold=None) -> float:
+def evalAvgLogL(bd1, bd2, *, device=0, manifold=None, log_domain=False) -> float:
     """`evalAvgLogL(bd1, bd2)` (src/DualTree01.jl:450-470): sum over bd2's points of W log L, L = bd1 at those points
-    (leave-one-out when `bd1 is bd2`), W = bd2's weights; -inf when an L == 0 carries weight."""
+    (leave-one-out when `bd1 is bd2`), W = bd2's weights; -inf when an L == 0 carries weight.  `log_domain=True`: the sum
+    over W != 0 of W log p with log p by log-sum-exp (section 5f), finite wherever bd1 has a weighted point."""
     kind = _kind(bd1, bd2)
     if _dims(bd1) != _dims(bd2):
         raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
@@ -47,18 +51,20 @@ def evalAvgLogL(bd1, bd2, *, device=0, manifold=None) -> float:
     if kind == "host":
         c1 = bd1._cstruct()
         c2 = c1 if loo else bd2._cstruct()
-        _lib.check(_lib.lib.kdehip_eval_avg_logl_manifold(C.byref(c1), C.byref(c2), loo, C.byref(out), int(device), mp))
+        fn = _lib.lib.kdehip_eval_avg_logl_log if log_domain else _lib.lib.kdehip_eval_avg_logl_manifold
+        _lib.check(fn(C.byref(c1), C.byref(c2), loo, C.byref(out), int(device), mp))
     else:
-        _lib.check(_lib.lib.kdehip_eval_avg_logl_device_manifold(bd1._h, bd2._h, loo, C.byref(out), mp))
+        fn = _lib.lib.kdehip_eval_avg_logl_log_device if log_domain else _lib.lib.kdehip_eval_avg_logl_device_manifold
+        _lib.check(fn(bd1._h, bd2._h, loo, C.byref(out), mp))
     return float(out.value)
 
 
-def entropy(bd, *, device=0, manifold=None) -> float:
+def entropy(bd, *, device=0, manifold=None, log_domain=False) -> float:
     """`entropy(bd)` (src/DualTree01.jl:505-508) = -evalAvgLogL(bd, bd)."""
-    return -evalAvgLogL(bd, bd, device=device, manifold=manifold)
+    return -evalAvgLogL(bd, bd, device=device, manifold=manifold, log_domain=log_domain)
 
 
-def kld(p1, p2, method="direct", *, device=0, manifold=None) -> float:
+def kld(p1, p2, method="direct", *, device=0, manifold=None, log_domain=False) -> float:
     """`kld(p1, p2; method=:direct)` (src/DualTree01.jl:477-503) = evalAvgLogL(p1, p1) - evalAvgLogL(p2, p1)."""
     if method != "direct":
         raise ValueError(f"kld: method {method!r} is not supported (only 'direct'; the reference's 'unscented' builds "
@@ -66,18 +72,21 @@ def kld(p1, p2, method="direct", *, device=0, manifold=None) -> float:
     _kind(p1, p2)
     if _dims(p1) != _dims(p2):
         raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
-    return evalAvgLogL(p1, p1, device=device, manifold=manifold) - evalAvgLogL(p2, p1, device=device, manifold=manifold)
+    kw = dict(device=device, manifold=manifold, log_domain=log_domain)
+    return evalAvgLogL(p1, p1, **kw) - evalAvgLogL(p2, p1, **kw)
 
 
-def minkld(p, q, *, device=0, manifold=None) -> float:
+def minkld(p, q, *, device=0, manifold=None, log_domain=False) -> float:
     """`minkld(p, q)` (src/DualTree01.jl:510) = min(|kld(p, q)|, |kld(q, p)|)."""
-    return min(abs(kld(p, q, device=device, manifold=manifold)), abs(kld(q, p, device=device, manifold=manifold)))
+    kw = dict(device=device, manifold=manifold, log_domain=log_domain)
+    return min(abs(kld(p, q, **kw)), abs(kld(q, p, **kw)))
 
 
-def eval_avg_logl_device_batch(pairs, d_out, stream=None, manifolds=None):
+def eval_avg_logl_device_batch(pairs, d_out, stream=None, manifolds=None, log_domain=False):
     """evalAvgLogL of many (bd, at) DeviceDensity pairs in ONE call (kdehip_eval_avg_logl_device_batch): d_out[i] (a
     float64 device tensor or address of len(pairs) doubles) = evalAvgLogL(bd_i, at_i), leave-one-out where `bd_i is
-    at_i`.  `manifolds`: None, or one manifold (or None) per pair.  Enqueues on `stream` and returns."""
+    at_i`.  `manifolds`: None, or one manifold (or None) per pair.  `log_domain=True`: every item in the log domain
+    (kdehip_eval_avg_logl_log_device_batch).  Enqueues on `stream` and returns."""
     from .product import DeviceDensity
     pairs = list(pairs)
     n = len(pairs)
@@ -89,13 +98,14 @@ def eval_avg_logl_device_batch(pairs, d_out, stream=None, manifolds=None):
             raise TypeError("eval_avg_logl_device_batch: pairs of DeviceDensity")
         arr[k].bd, arr[k].at, arr[k].leave_one_out = bd._h, at._h, 1 if bd is at else 0
         arr[k].circular_mask = 0 if manifolds is None else _mask(_mf.parse(manifolds[k], bd.dims))
-    _lib.check(_lib.lib.kdehip_eval_avg_logl_device_batch_manifold(n, arr, _lib.addr(d_out), _lib.addr(stream)))
+    fn = _lib.lib.kdehip_eval_avg_logl_log_device_batch if log_domain else _lib.lib.kdehip_eval_avg_logl_device_batch_manifold
+    _lib.check(fn(n, arr, _lib.addr(d_out), _lib.addr(stream)))
 
 
-def kld_batch(pairs, manifold=None, manifolds=None):
+def kld_batch(pairs, manifold=None, manifolds=None, log_domain=False):
     """kld(p_i, q_i) for many DeviceDensity pairs: ONE batch call of 2n items (evalAvgLogL(p, p), evalAvgLogL(q, p) per
     pair), one synchronisation; returns a numpy array of n values, each bit for bit `kld(p_i, q_i)`.  `manifold`: one for
-    all pairs; `manifolds`: one (or None) per pair."""
+    all pairs; `manifolds`: one (or None) per pair; `log_domain` as in `kld`."""
     from .product import DeviceDensity
     pairs = [(p, q) for p, q in pairs]
     n = len(pairs)
@@ -120,7 +130,7 @@ def kld_batch(pairs, manifold=None, manifolds=None):
     out = torch.empty(2 * n, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev)
-        eval_avg_logl_device_batch(items, out, stream=st.cuda_stream, manifolds=mans)
+        eval_avg_logl_device_batch(items, out, stream=st.cuda_stream, manifolds=mans, log_domain=log_domain)
         st.synchronize()
     v = out.cpu().numpy()
     return v[0::2] - v[1::2]

@@ -274,7 +274,7 @@ class DeviceDensity:
         """the Euclidean `*`, also for densities that remember a manifold: use `mul_device(..., manifold=)` on the circle"""
         return mul_device([self, other])
 
-    def evaluate(self, pos=None, lvFlag=False, manifold=None):
+    def evaluate(self, pos=None, lvFlag=False, manifold=None, *, _log=False):
         """`evaluateDualTree(bd, pos, lvFlag)` (reference src/DualTree01.jl:370-421, FORCE_EVAL_DIRECT) on the device
         (kdehip_evaluate_device / kdehip_evaluate_device_at): every value is bit for bit what `evaluateDualTree` gives on the
         density's host arrays.  `pos`: a (D, Nq) numpy array -- values in query order, as a numpy array --, a float64 (D, Nq)
@@ -296,8 +296,8 @@ class DeviceDensity:
                 if pos.dims != self.dims:
                     raise ValueError("bd and pos must have the same dimension")
                 out = torch.empty(max(1, pos.num_points), dtype=torch.float64, device=dev)
-                _lib.check(_lib.lib.kdehip_evaluate_device_at_manifold(self._h, pos._h, addr(out),
-                                                                       addr(st.cuda_stream), mp))
+                at_entry = _lib.lib.kdehip_evaluate_log_device_at if _log else _lib.lib.kdehip_evaluate_device_at_manifold
+                _lib.check(at_entry(self._h, pos._h, addr(out), addr(st.cuda_stream), mp))
                 st.synchronize()
                 return out.cpu().numpy()[:pos.num_points].copy()
             tensor = hasattr(pos, "data_ptr")
@@ -310,12 +310,20 @@ class DeviceDensity:
             # column-major D x Nq = the (Nq, D) row-major array
             flat = P.t().contiguous().to(dev, torch.float64) if tensor else torch.from_numpy(np.ascontiguousarray(P.T)).to(dev)
             out = torch.empty(max(1, Nq), dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib.kdehip_evaluate_device_manifold(self._h, addr(flat), Nq, 0, addr(out),
-                                                                addr(st.cuda_stream), mp))
+            entry = _lib.lib.kdehip_evaluate_log_device if _log else _lib.lib.kdehip_evaluate_device_manifold
+            _lib.check(entry(self._h, addr(flat), Nq, 0, addr(out), addr(st.cuda_stream), mp))
             if tensor:
                 return out[:Nq]
             st.synchronize()
             return out.cpu().numpy()[:Nq].copy()
+
+    def evaluate_log(self, pos=None, lvFlag=False, manifold=None):
+        """log of `.evaluate(pos, lvFlag, manifold)` by log-sum-exp in the kernel (kdehip_evaluate_log_device /
+        kdehip_evaluate_log_device_at, include/kdehip.h section 5f): finite where the density underflows to 0.  The same
+        shapes and return kinds as `.evaluate`, the `at` form (pos a DeviceDensity) included."""
+        if isinstance(pos, BallTreeDensity):
+            raise TypeError("evaluate_log: a DeviceDensity is evaluated at points or at a DeviceDensity")
+        return self.evaluate(pos, lvFlag, manifold=manifold, _log=True)
 
     def __call__(self, pos=None, lvFlag=False, manifold=None):
         return self.evaluate(pos, lvFlag, manifold=manifold)
