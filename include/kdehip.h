@@ -941,6 +941,52 @@ int kdehip_eval_avg_logl_log_device(const kdehip_device_density *bd, const kdehi
                                     double *out, const uint8_t *manifold);
 int kdehip_eval_avg_logl_log_device_batch(int n, const kdehip_logl_manifold_item *items, double *d_out, void *stream);
 
+/* ---- (5g) exact overlap measures by kernel sums: intersIntg, ise, mmd ------------------------------------------------------
+ * How far apart are two densities?  The log-likelihoods of 5b / 5f are asymmetric, not 0 at p == q and depend on both LOOCV
+ * bandwidths; intersIntgAppxIS (5c) is a grid sum in 1-D and 2-D.  For Gaussian-kernel mixtures the quantities have closed
+ * forms in any dimension, all of them compositions of ONE primitive, a weighted all-pairs Gaussian sum reduced to a scalar
+ * (csrc/ksum.hip; this library's own, the reference has no counterpart):
+ *   S(A, B; v) = sum_{j<M} b_j sum_{i<N} a_i exp(-1/2 sum_k diff_k(y_jk, x_ik)^2 / v_k)
+ * with A = (x_i, a_i) and B = (y_j, b_j) the leaf points and leaf weights of the densities a and b, v a variance vector and
+ * diff_k the plain difference y_jk - x_ik, through wrap() first in a circular dimension (5d).  With normalize != 0 the sum is
+ * divided by prod_k sqrt(2 pi v_k): multiplied by 1 / ((2 pi)^(D/2) * prod_k sqrt(v_k)), the product over k ascending.
+ *   integral p q      = S(p, q; v_p + v_q), normalised                       (`intersIntg`: exact, any D <= KDEHIP_MAX_DIMS)
+ *   integral (p-q)^2  = intersIntg(p,p) - 2 intersIntg(p,q) + intersIntg(q,q)   (`ise`: symmetric, 0 iff p == q)
+ *   MMD^2(p, q; h)    = S(p,p;h^2) - 2 S(p,q;h^2) + S(q,q;h^2)                  (`mmd`: biased, kernel exp(-|x-y|^2 / 2h^2))
+ * var: D explicit variances (a HOST pointer in every entry, the batch items included), or NULL = the sum of the two
+ * densities' leaf variances, a's first leaf's plus b's, added in the kernel.  NULL needs densities whose leaves share one
+ * bandwidth vector (KDEHIP_ERR_UNSUPPORTED otherwise, as kdehip_evaluate); with explicit variances only points and weights
+ * are read, so per-point bandwidths are fine.
+ * The full square is summed: no leave-one-out and no shortcut for a == b, so S(p, p) and S(p, an equal copy of p) are the same
+ * bits and ise(p, p) and mmd(p, p, h) are exactly 0.  Cost: one all-pairs pass, as one kdehip_evaluate of a at b's points.
+ * Arithmetic: the exponent, its fma order, -0.5 / v_k and the exponential are those of kdehip_evaluate; lane j multiplies its
+ * sum over a's leaves by b_j, the 256 lanes of a block are added in a fixed tree, and the blocks in block order.  The split of
+ * the sum depends on the pair's (N, M) alone: each result is the same bits from the host entry, a single device call and any
+ * batch, run after run.  S(a, b) and S(b, a) are sums in different orders: equal to rounding, not bit for bit.
+ * Circular dimensions (5d): circular data in which no pair difference leaves [-pi, pi) gives the Euclidean call's bits; a
+ * circular dimension keeps the Gaussian constant when normalised, as evaluation does -- the library's nearest-image
+ * semantic, the one kdehip_evaluate_manifold uses (the integral over the circle of two wrapped Gaussians it is not).
+ * Errors, all checked before any device is touched: ndims differ -- KDEHIP_ERR_DIM_MISMATCH; D above KDEHIP_MAX_DIMS, or
+ * var == NULL with per-point bandwidths on either side -- KDEHIP_ERR_UNSUPPORTED; a variance that is not finite or not > 0, a
+ * manifold byte above 1 or a mask bit at or above D, a null density or output, densities on different devices within one
+ * batch -- KDEHIP_ERR_ARG. */
+typedef struct kdehip_ksum_item {
+  const kdehip_device_density *a, *b;
+  const double *var;        /* HOST pointer, D variances, each finite and > 0; NULL = a's leaf variances + b's */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+  int32_t normalize;        /* != 0: divide by prod_k sqrt(2 pi v_k) */
+} kdehip_ksum_item;
+/* Resident densities, all on one device: d_out[i] (device, n doubles) = S of item i.  One partial-sum launch per distinct D
+ * (one more for its circular items) and one reduction launch for all items; Euclidean and circular items of any D may be
+ * mixed.  The variances are copied during the call.  Enqueue only, on `stream` (hipStream_t, NULL = the null stream). */
+int kdehip_kernel_sum_device_batch(int n, const kdehip_ksum_item *items, double *d_out, void *stream);
+/* One resident pair, blocking on the calling thread's stream; the result to host memory.  manifold: ndims bytes or NULL. */
+int kdehip_kernel_sum_device(const kdehip_device_density *a, const kdehip_device_density *b, const double *var,
+                             int normalize, double *out, const uint8_t *manifold);
+/* Host densities, one pinned upload, blocking, on hipStreamPerThread. */
+int kdehip_kernel_sum(const kdehip_density *a, const kdehip_density *b, const double *var, int normalize,
+                      double *out, int device, const uint8_t *manifold);
+
 #ifdef __cplusplus
 }
 #endif

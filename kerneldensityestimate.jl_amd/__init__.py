@@ -3,7 +3,7 @@
 This package is the Python host mirror of the reference's interface for that path
 (`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`,
 `sample/rand/resample`, `evalAvgLogL/entropy/kld/minkld`, `evaluate_log`, `marginal`, `getKDERange/getKDEMax/getKDEMean/getKDEfit`,
-`intersIntgAppxIS`)
+`intersIntgAppxIS`, and the library's own exact overlap measures `intersIntg/ise/mmd`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
 """
@@ -16,6 +16,7 @@ from .product import (DeviceDensity, GbGlb, MultiProductPlan, ProductBatch, Prod
                       prodAppxMSGibbsS_resident)
 from .sample import rand, resample, sample, sample_device_batch  # noqa: F401
 from .loglik import entropy, eval_avg_logl_device_batch, evalAvgLogL, kld, kld_batch, minkld  # noqa: F401
+from .overlap import intersIntg, ise, ise_batch, kernel_sum, kernel_sum_device_batch, mmd, mmd_batch  # noqa: F401
 from .summary import (getKDEfit, getKDEMax, getKDEMean, getKDERange, getKDERangeLinspace, intersIntgAppxIS,  # noqa: F401
                       marginal, summary_device_batch)
 

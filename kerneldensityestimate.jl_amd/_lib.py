@@ -66,6 +66,11 @@ class CLoglManifoldItem(C.Structure):
     _fields_ = [("bd", C.c_void_p), ("at", C.c_void_p), ("leave_one_out", C.c_int32), ("circular_mask", C.c_uint32)]
 
 
+class CKsumItem(C.Structure):
+    """struct kdehip_ksum_item (`var` is a HOST pointer or NULL)"""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("var", f64p), ("circular_mask", C.c_uint32), ("normalize", C.c_int32)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -164,6 +169,9 @@ SIGNATURES = {
     "kdehip_eval_avg_logl_log": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int, f64p, C.c_int, u8p]),
     "kdehip_eval_avg_logl_log_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p, u8p]),
     "kdehip_eval_avg_logl_log_device_batch": (C.c_int, [C.c_int, C.POINTER(CLoglManifoldItem), C.c_void_p, C.c_void_p]),
+    "kdehip_kernel_sum": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), f64p, C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_kernel_sum_device": (C.c_int, [C.c_void_p, C.c_void_p, f64p, C.c_int, f64p, u8p]),
+    "kdehip_kernel_sum_device_batch": (C.c_int, [C.c_int, C.POINTER(CKsumItem), C.c_void_p, C.c_void_p]),
     "kdehip_auto_bandwidth_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, u8p]),
     "kdehip_make_density_auto_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p,
                                                     i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),

@@ -70,4 +70,25 @@ struct DevBuf {
 // (scratch = 64 * Nq doubles).
 constexpr int kEvalMaxGroups = 64;
 
+// The mapping of the all-pairs sums of evaluate.hip and ksum.hip: a block owns kEvalThreads queries and one group of
+// consecutive kEvalChunk-point source chunks.
+constexpr int kEvalThreads = 256;  // queries per block
+constexpr int kEvalChunk = 128;    // source points per staged chunk
+
+// Source chunks are dealt to groups of consecutive chunks: as many groups as it takes to give every CU a few
+// blocks (small problems: one chunk per group, the most parallel split), never more than kEvalMaxGroups.
+struct GroupSplit { int64_t chunks_per_group; int ngroups; };
+inline GroupSplit split_chunks(int64_t N, int64_t Nq, int nprob) {
+  const int64_t nchunks = (N + kEvalChunk - 1) / kEvalChunk;
+  const int64_t qblocks = ((Nq + kEvalThreads - 1) / kEvalThreads) * (nprob > 0 ? nprob : 1);
+  int64_t want = (int64_t(8) * device_cu_count() + qblocks - 1) / qblocks;  // groups for ~8 blocks per CU
+  if (want < 1) want = 1;
+  if (want > kEvalMaxGroups) want = kEvalMaxGroups;
+  if (want > nchunks) want = nchunks;
+  GroupSplit g;
+  g.chunks_per_group = (nchunks + want - 1) / want;
+  g.ngroups = static_cast<int>((nchunks + g.chunks_per_group - 1) / g.chunks_per_group);
+  return g;
+}
+
 }  // namespace kdehip

@@ -43,25 +43,8 @@ using namespace kdehip;
 
 namespace {
 
-constexpr int kEvalThreads = 256;    // queries per block
-constexpr int kEvalChunk = 128;      // source points per staged chunk
+// (kEvalThreads, kEvalChunk and split_chunks, the mapping of the all-pairs sum, are in entry_helpers.hpp: ksum.hip shares them)
 constexpr int kFinishThreads = 256;  // queries per finish block
-
-// Source chunks are dealt to groups of consecutive chunks: as many groups as it takes to give every CU a few
-// blocks (small problems: one chunk per group, the most parallel split), never more than kEvalMaxGroups.
-struct GroupSplit { int64_t chunks_per_group; int ngroups; };
-inline GroupSplit split_chunks(int64_t N, int64_t Nq, int nprob) {
-  const int64_t nchunks = (N + kEvalChunk - 1) / kEvalChunk;
-  const int64_t qblocks = ((Nq + kEvalThreads - 1) / kEvalThreads) * (nprob > 0 ? nprob : 1);
-  int64_t want = (int64_t(8) * device_cu_count() + qblocks - 1) / qblocks;  // groups for ~8 blocks per CU
-  if (want < 1) want = 1;
-  if (want > kEvalMaxGroups) want = kEvalMaxGroups;
-  if (want > nchunks) want = nchunks;
-  GroupSplit g;
-  g.chunks_per_group = (nchunks + want - 1) / want;
-  g.ngroups = static_cast<int>((nchunks + g.chunks_per_group - 1) / g.chunks_per_group);
-  return g;
-}
 
 // One evaluation: a density (N source points in tree / leaf order, one bandwidth vector) at Nq query points.
 struct EvalItem {

@@ -731,6 +731,48 @@ hip_minkld(p::BallTreeDensity, q::BallTreeDensity; device::Int=0) =
   min(abs(hip_kld(p, q; device=device)), abs(hip_kld(q, p; device=device)))
 
 """
+    hip_kernel_sum(a, b, var=nothing; normalize=false, manifold=nothing, device=0)
+
+The weighted all-pairs Gaussian sum `S(a, b; var)` over the leaf points and weights of two densities (`kdehip_kernel_sum`,
+include/kdehip.h section 5g): `var` = D variances, or `nothing` = the sum of the two densities' leaf variances;
+`normalize` divides by `prod_k sqrt(2 pi var_k)`.  The full square is summed, whatever the identity of the arguments.
+`hip_intersIntg`, `hip_ise` and `hip_mmd` are its compositions.  The library's own: not installed by `enable!()`.
+"""
+function hip_kernel_sum(a::BallTreeDensity, b::BallTreeDensity, var::Union{Nothing,AbstractVector{Float64}}=nothing;
+                        normalize::Bool=false, manifold=nothing, device::Int=0)
+  Ndim(a) == Ndim(b) || error("kernel sum -- dimensions of two BallTreeDensities must match")
+  var === nothing || length(var) == Ndim(a) || error("var needs one variance per dimension")
+  man = manifold === nothing ? zeros(UInt8, Ndim(a)) : manifold_bytes(manifold, Ndim(a))
+  v = var === nothing ? Float64[] : Vector{Float64}(var)
+  ca = Ref(CDensity(a))
+  cb = a === b ? ca : Ref(CDensity(b))
+  out = Ref{Float64}(0.0)
+  GC.@preserve a b v man begin
+    check(ccall((:kdehip_kernel_sum, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Ptr{UInt8}),
+                ca, cb, var === nothing ? Ptr{Float64}(C_NULL) : pointer(v), normalize ? 1 : 0, out, device, man))
+  end
+  return out[]
+end
+
+"The exact integral of p q (what `intersIntgAppxIS` approximates, in any dimension up to 8): the normalised sum at the summed leaf variances."
+hip_intersIntg(p::BallTreeDensity, q::BallTreeDensity; manifold=nothing, device::Int=0) =
+  hip_kernel_sum(p, q; normalize=true, manifold=manifold, device=device)
+
+"The integrated squared error, integral of (p - q)^2: symmetric, exactly 0 for `hip_ise(p, p)`."
+hip_ise(p::BallTreeDensity, q::BallTreeDensity; manifold=nothing, device::Int=0) =
+  hip_intersIntg(p, p; manifold=manifold, device=device) - 2.0 * hip_intersIntg(p, q; manifold=manifold, device=device) +
+  hip_intersIntg(q, q; manifold=manifold, device=device)
+
+"The biased MMD^2 under the Gaussian kernel of standard deviation `bw` (one entry or one per dimension, squared as `kde!` squares it)."
+function hip_mmd(p::BallTreeDensity, q::BallTreeDensity, bw::AbstractVector{Float64}; manifold=nothing, device::Int=0)
+  length(bw) == 1 || length(bw) == Ndim(p) || error("bw needs 1 or D entries")
+  v = Float64[(length(bw) == 1 ? bw[1] : bw[k])^2 for k in 1:Ndim(p)]
+  s(a, b) = hip_kernel_sum(a, b, v; manifold=manifold, device=device)
+  return s(p, p) - 2.0 * s(p, q) + s(q, q)
+end
+
+"""
     hip_getKDEMax(p; N=200, device=0)
 
 `getKDEMax(p; N)` (src/DualTree01.jl:558-570) on the GPU (`kdehip_kde_max`, include/kdehip.h section 5c): per dimension the

@@ -246,7 +246,8 @@ def getKDEfit(p, *, manifold=None):
 def intersIntgAppxIS(p, q, N=201, *, device=0, manifold=None):
     """`intersIntgAppxIS(p, q; N)` (src/DualTree01.jl:581-618), 1-D and 2-D: p and q evaluated by the direct sum on the
     grid over p's marginal ranges with extend 0.3, sum of p q times the cell size (rows in order in 2-D).
-    `manifold`: p's circular range, p and q evaluated as `evaluateDualTree(..., manifold=)` (section 5e)."""
+    `manifold`: p's circular range, p and q evaluated as `evaluateDualTree(..., manifold=)` (section 5e).
+    The exact integral, in any dimension up to 8, is `intersIntg(p, q)` (overlap.py, section 5g)."""
     dev = _same_kind([p, q])
     man = _manifold(p, manifold)
     out = C.c_double(0.0)
