@@ -70,8 +70,8 @@ struct DevBuf {
 // (scratch = 64 * Nq doubles).
 constexpr int kEvalMaxGroups = 64;
 
-// The mapping of the all-pairs sums of evaluate.hip and ksum.hip: a block owns kEvalThreads queries and one group of
-// consecutive kEvalChunk-point source chunks.
+// The mapping of the all-pairs sum of evaluate.hip and ksum.hip (the sum itself, written once, is pair_sweep.hpp): a block
+// owns kEvalThreads queries and one group of consecutive kEvalChunk-point source chunks.
 constexpr int kEvalThreads = 256;  // queries per block
 constexpr int kEvalChunk = 128;    // source points per staged chunk
 

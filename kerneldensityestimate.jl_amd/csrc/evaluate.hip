@@ -10,8 +10,7 @@
 // all of them: any number of items (a density, a set of query points, what to compute) of any sizes, described in device
 // memory by EvalItem and driven by EvalRun:
 //   eval_partial_kernel<D>  one launch per distinct D (one more for its items with a circular dimension): the all-pairs
-//                           Gaussian sum, one lane per query point, source points staged through LDS in chunks and read as
-//                           broadcasts, one partial sum per (group of source chunks, query);
+//                           Gaussian sum of pair_sweep.hpp, one partial sum per (group of source chunks, query);
 //   eval_finish_kernel      the groups summed in a fixed order (deterministic, no atomics), / norm, / (1 - w) for
 //                           leave-one-out, the value stored (through the item's permutation, if any) when asked for, then
 //                           W_q log p_q and the block's share in a fixed LDS tree; a weighted zero raises the block's flag
@@ -19,7 +18,7 @@
 //   logl_reduce_kernel      only when an item asks for a log-likelihood: per item, the block shares summed in block order
 //                           (or -Inf if a flag is up) into one double.
 // Log-domain items (kdehip.h section 5f: log p by log-sum-exp, finite where p underflows) run eval_partial_log_kernel<D> and
-// eval_finish_log_kernel in launches of their own, with the same mapping, split and reduction.
+// eval_finish_log_kernel in launches of their own, with the same sweep, split and reduction.
 // The group split (split_chunks(N, Nq, 1)) depends on the item's (N, Nq) alone, so nothing depends on the launch or the
 // batch: the host entry, a single device call and any batch give the same bits.
 #include <hip/hip_runtime.h>
@@ -30,28 +29,25 @@
 #include <string>
 #include <vector>
 
-#include "circ_wrap.hpp"
 #include "device_density.hpp"
-#include "call_block.hpp"
 #include "entry_helpers.hpp"
 #include "manifold_arg.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
+#include "pair_sweep.hpp"
 #include "phase_timer.hpp"
 
 using namespace kdehip;
 
 namespace {
 
-// (kEvalThreads, kEvalChunk and split_chunks, the mapping of the all-pairs sum, are in entry_helpers.hpp: ksum.hip shares them)
+// (kEvalThreads, kEvalChunk and split_chunks, the mapping of the all-pairs sum, are in entry_helpers.hpp; the sum itself is
+// pair_sweep.hpp: ksum.hip shares them)
 constexpr int kFinishThreads = 256;  // queries per finish block
 
 // One evaluation: a density (N source points in tree / leaf order, one bandwidth vector) at Nq query points.
-struct EvalItem {
-  const double *src;    // [N][D] leaf means of the evaluated density (tree order)
-  const double *w;      // [N] its leaf weights
-  const double *bw;     // [D] its first leaf's variances (every leaf has them: checked on the host)
-  const double *qry;    // [Nq][D] query points
+struct EvalItem : PairHead {
+  const double *bw;     // [D] the density's first leaf's variances (every leaf has them: checked on the host)
   const double *qw;     // [Nq] query weights (the `at` density's leaf weights), or null: no log-likelihood
   const int64_t *perm;  // [Nq] 1-based output position of query q, or null: query order
   double *out;          // [Nq] p, or null
@@ -60,7 +56,6 @@ struct EvalItem {
   int32_t *bzero;       // [nfb] the finish block met a p == 0 with W != 0
   double *logl;         // the result, or null
   double norm0;         // (2 pi)^(D/2) as the host's libm rounds it
-  int64_t N, Nq, chunks_per_group;
   int32_t ngroups, nfb, D, loo;
   int32_t logdom, pad_;  // log-domain item (kdehip.h section 5f): partial is [2][ngroups][Nq], the maxima m then the sums s
 };
@@ -68,12 +63,9 @@ struct EvalItem {
 // partial[g][q] = sum over the source chunks c of group g, in chunk order, of
 //   sum_{i in chunk c, (i != q if loo)} w_i exp(-1/2 sum_k (x_qk - c_ik)^2 / bw_k)
 // (the kernel value of distGauss!, src/DualTree01.jl:14-47, with leaf ranges 0 and uniform bandwidth), for the items [0, n)
-// of one D: item i owns blocks [first[i], first[i+1]) - first[0], its block k is query block k % qblocks of source group
-// k / qblocks.  A block owns kEvalThreads queries and ONE group of consecutive 128-point source chunks, which it walks in
-// order with the running sum in a register: the scratch is [ngroups][Nq] with ngroups <= kEvalMaxGroups whatever N is,
-// and the summation order is fixed by (N, ngroups).
-// CIRC: bit k of masks[i] (uniform over the block) makes dimension k of item i circular -- its difference goes through
-// circ_wrap before it is squared (diffop inside distGauss!); nothing else changes, so data in which no difference wraps
+// of one D, by the sweep of pair_sweep.hpp with the running sum in a register: the scratch is [ngroups][Nq] with
+// ngroups <= kEvalMaxGroups whatever N is, and the summation order is fixed by (N, ngroups).
+// CIRC: bit k of masks[i] makes dimension k of item i circular; nothing else changes, so data in which no difference wraps
 // gives the bits of the Euclidean instantiation (circ_wrap(t) == t for -pi <= t < pi).  The host launches the items that
 // have a circular dimension with this instantiation and all others with the Euclidean one.
 template <int D, bool CIRC = false>
@@ -83,71 +75,35 @@ __global__ __launch_bounds__(kEvalThreads) void eval_partial_kernel(const EvalIt
   __shared__ double sSrc[2][kEvalChunk * (D + 1)];
   __shared__ double sExpTab[32];
   if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
-  const int b = static_cast<int>(blockIdx.x) + first[0];
-  const int i = item_of_block(first, n, b);
-  const EvalItem pb = items[i];
-  unsigned circ = 0;
-  if constexpr (CIRC) circ = __builtin_amdgcn_readfirstlane(masks[i]);
-  const int64_t qblocks = (pb.Nq + kEvalThreads - 1) / kEvalThreads;
-  const int64_t kb = b - first[i];
-  const int64_t qb = kb % qblocks, grp = kb / qblocks;
-  const int64_t q = qb * kEvalThreads + threadIdx.x;
-  const int64_t c_begin = grp * pb.chunks_per_group;
-  int64_t c_end = c_begin + pb.chunks_per_group;
-  const int64_t nchunks = (pb.N + kEvalChunk - 1) / kEvalChunk;
-  if (c_end > nchunks) c_end = nchunks;
-  if (c_begin >= c_end) return;  // block-uniform
+  const ItemBlock ib = item_block(first, n);
+  const EvalItem pb = items[ib.item];
+  const unsigned circ = circ_mask<CIRC>(masks, ib.item);
+  const PairPlace at = pair_place(pb, ib.k);
+  if (at.c_begin >= at.c_end) return;  // block-uniform
   double nhib[D];  // -1/(2 bw_k)
 #pragma unroll
   for (int k = 0; k < D; ++k) nhib[k] = -0.5 / pb.bw[k];
-  double x[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) x[k] = (q < pb.Nq) ? pb.qry[q * D + k] : 0.0;
-  auto stage = [&](int64_t c, int buf) {
-    const int64_t i0 = c * kEvalChunk;
-    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
-    for (int t = threadIdx.x; t < cnt * (D + 1); t += kEvalThreads) {
-      const int i = t / (D + 1), f = t % (D + 1);
-      sSrc[buf][t] = (f < D) ? pb.src[(i0 + i) * D + f] : pb.w[i0 + i];
-    }
-  };
-  stage(c_begin, 0);
   double total = 0.0;
-  for (int64_t c = c_begin; c < c_end; ++c) {
-    const int buf = static_cast<int>((c - c_begin) & 1);
-    __syncthreads();  // chunk c is staged; the other buffer is free again
-    if (c + 1 < c_end) stage(c + 1, buf ^ 1);
-    const int64_t i0 = c * kEvalChunk;
-    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
+  pair_sweep<D, CIRC>(pb, at, circ, nhib, sSrc, [&](auto &&each) {
     double sum = 0.0;
-    for (int i = 0; i < cnt; ++i) {
-      const double *s = sSrc[buf] + i * (D + 1);
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        double d = x[k] - s[k];
-        if constexpr (CIRC) {
-          if ((circ >> k) & 1u) d = circ_wrap(d);
-        }
-        acc = fma(d * d, nhib[k], acc);
-      }
-      double v = s[D] * exp_nonpos(acc, sExpTab);  // acc <= 0
-      if (pb.loo && i0 + i == q) v = 0.0;  // leave-one-out: skip the self term (:141)
+    each([&](int64_t i, double w, double a) {
+      double v = w * exp_nonpos(a, sExpTab);
+      if (pb.loo && i == at.q) v = 0.0;  // leave-one-out: skip the self term (:141)
       sum += v;
-    }
+    });
     total += sum;
-  }
-  if (q < pb.Nq) pb.partial[grp * pb.Nq + q] = total;
+  });
+  if (at.q < pb.Nq) pb.partial[at.grp * pb.Nq + at.q] = total;
 }
 
-// The log-domain twin (kdehip.h section 5f): the same items, block mapping, LDS double buffer and a_i (same fma order, same
-// nhib[k]) as eval_partial_kernel, but the block carries (m, s) with
+// The log-domain step on the same sweep (kdehip.h section 5f): the same items, mapping and a_i, but the block carries
+// (m, s) with
 //   m = max a_i,  s = sum w_i exp(a_i - m)   over S = { i in the group : w_i > 0, (i != q if loo) }
 // instead of the plain sum, so nothing underflows that matters to log p.  Per staged chunk: pass one takes the chunk's
 // maximum over S (D fmas per source, no exp), the carried s is rescaled ONCE by exp_nonpos(m_old - m_new), pass two
 // recomputes a_i and adds w_i exp_nonpos(a_i - m_new): one exp per pair, as the direct kernel.  A source outside S takes no
 // part in the maximum (a near, weightless point would push every real term into underflow) and adds nothing.  A group
-// with S empty leaves (m, s) = (-Inf, 0).  Every lane, those beyond Nq included, walks the same chunks and barriers.
+// with S empty leaves (m, s) = (-Inf, 0).
 // partial[g][q] = m, partial[ngroups + g][q] = s.
 template <int D, bool CIRC = false>
 __global__ __launch_bounds__(kEvalThreads) void eval_partial_log_kernel(const EvalItem *__restrict__ items,
@@ -156,146 +112,102 @@ __global__ __launch_bounds__(kEvalThreads) void eval_partial_log_kernel(const Ev
   __shared__ double sSrc[2][kEvalChunk * (D + 1)];
   __shared__ double sExpTab[32];
   if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
-  const int b = static_cast<int>(blockIdx.x) + first[0];
-  const int i = item_of_block(first, n, b);
-  const EvalItem pb = items[i];
-  unsigned circ = 0;
-  if constexpr (CIRC) circ = __builtin_amdgcn_readfirstlane(masks[i]);
-  const int64_t qblocks = (pb.Nq + kEvalThreads - 1) / kEvalThreads;
-  const int64_t kb = b - first[i];
-  const int64_t qb = kb % qblocks, grp = kb / qblocks;
-  const int64_t q = qb * kEvalThreads + threadIdx.x;
-  const int64_t c_begin = grp * pb.chunks_per_group;
-  int64_t c_end = c_begin + pb.chunks_per_group;
-  const int64_t nchunks = (pb.N + kEvalChunk - 1) / kEvalChunk;
-  if (c_end > nchunks) c_end = nchunks;
-  if (c_begin >= c_end) return;  // block-uniform
+  const ItemBlock ib = item_block(first, n);
+  const EvalItem pb = items[ib.item];
+  const unsigned circ = circ_mask<CIRC>(masks, ib.item);
+  const PairPlace at = pair_place(pb, ib.k);
+  if (at.c_begin >= at.c_end) return;  // block-uniform
   double nhib[D];  // -1/(2 bw_k)
 #pragma unroll
   for (int k = 0; k < D; ++k) nhib[k] = -0.5 / pb.bw[k];
-  double x[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) x[k] = (q < pb.Nq) ? pb.qry[q * D + k] : 0.0;
-  auto stage = [&](int64_t c, int buf) {
-    const int64_t i0 = c * kEvalChunk;
-    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
-    for (int t = threadIdx.x; t < cnt * (D + 1); t += kEvalThreads) {
-      const int i = t / (D + 1), f = t % (D + 1);
-      sSrc[buf][t] = (f < D) ? pb.src[(i0 + i) * D + f] : pb.w[i0 + i];
-    }
-  };
-  auto exponent = [&](const double *s) {  // a_i
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      double d = x[k] - s[k];
-      if constexpr (CIRC) {
-        if ((circ >> k) & 1u) d = circ_wrap(d);
-      }
-      acc = fma(d * d, nhib[k], acc);
-    }
-    return acc;
-  };
-  const int64_t skip = pb.loo ? q : -1;  // leave-one-out: the self term is not in S
-  stage(c_begin, 0);
+  const int64_t skip = pb.loo ? at.q : -1;  // leave-one-out: the self term is not in S
   double m = -INFINITY, total = 0.0;
-  for (int64_t c = c_begin; c < c_end; ++c) {
-    const int buf = static_cast<int>((c - c_begin) & 1);
-    __syncthreads();  // chunk c is staged; the other buffer is free again
-    if (c + 1 < c_end) stage(c + 1, buf ^ 1);
-    const int64_t i0 = c * kEvalChunk;
-    const int cnt = static_cast<int>((pb.N - i0 < kEvalChunk) ? (pb.N - i0) : kEvalChunk);
+  pair_sweep<D, CIRC>(pb, at, circ, nhib, sSrc, [&](auto &&each) {
     double cm = -INFINITY;
-    for (int i = 0; i < cnt; ++i) {
-      const double *s = sSrc[buf] + i * (D + 1);
-      const double acc = exponent(s);
-      cm = (s[D] > 0.0 && i0 + i != skip) ? fmax(cm, acc) : cm;
-    }
+    each([&](int64_t i, double w, double a) { cm = (w > 0.0 && i != skip) ? fmax(cm, a) : cm; });
     if (cm > m) {  // (m == -Inf: total is still 0)
       total *= exp_nonpos(m - cm, sExpTab);
       m = cm;
     }
     double sum = 0.0;
-    for (int i = 0; i < cnt; ++i) {
-      const double *s = sSrc[buf] + i * (D + 1);
-      const double acc = exponent(s);
-      const bool in = s[D] > 0.0 && i0 + i != skip;  // in S: then acc <= m
-      sum += in ? s[D] * exp_nonpos(acc - m, sExpTab) : 0.0;
-    }
+    each([&](int64_t i, double w, double a) {
+      const bool in = w > 0.0 && i != skip;  // in S: then a <= m
+      sum += in ? w * exp_nonpos(a - m, sExpTab) : 0.0;
+    });
     total += sum;
-  }
-  if (q < pb.Nq) {
-    pb.partial[grp * pb.Nq + q] = m;
-    pb.partial[(pb.ngroups + grp) * pb.Nq + q] = total;
+  });
+  if (at.q < pb.Nq) {
+    pb.partial[at.grp * pb.Nq + at.q] = m;
+    pb.partial[(pb.ngroups + at.grp) * pb.Nq + at.q] = total;
   }
 }
 
-// p[q] = (sum over the groups, in group order) / norm [/ (1 - w_q)]   (src/DualTree01.jl:325-340), then W log p and the
-// block's share (items [0, n), item i owns blocks [first[i], first[i+1]))
-__global__ __launch_bounds__(kFinishThreads) void eval_finish_kernel(const EvalItem *__restrict__ items,
-                                                                   const int32_t *__restrict__ first, int n) {
-  __shared__ double red[kFinishThreads];
-  const int b = static_cast<int>(blockIdx.x);
-  const int i = item_of_block(first, n, b);
-  const EvalItem it = items[i];
-  const int fb = b - first[i];
-  const int64_t q = static_cast<int64_t>(fb) * kFinishThreads + threadIdx.x;
-  double norm = it.norm0;  // (2 pi)^(D/2) * prod_k sqrt(bw_k)   (src/DualTree01.jl:325-330)
-  for (int k = 0; k < it.D; ++k) norm *= __dsqrt_rn(it.bw[k]);
-  const double inv_norm = 1.0 / norm;
-  double term = 0.0;
-  int zero = 0;
-  if (q < it.Nq) {
-    double s = 0.0;
-    for (int c = 0; c < it.ngroups; ++c) s += it.partial[static_cast<int64_t>(c) * it.Nq + q];
-    double p = s * inv_norm;
-    if (it.loo) p = p / (1.0 - it.w[q]);
-    if (it.out) {
-      const int64_t o = it.perm ? it.perm[q] - 1 : q;
-      if (o >= 0 && o < it.Nq) it.out[o] = p;  // (an uploaded density's permutation is the caller's)
-    }
-    if (it.qw) {  // evalAvgLogL (:456-466): L == 0 counts as 1 when its weight is 0, and makes the result -Inf otherwise
-      const double W = it.qw[q];
-      if (p == 0.0) { zero = W != 0.0; p = 1.0; }
-      term = log(p) * W;
-    }
+__device__ __forceinline__ double eval_norm(const EvalItem &it) {
+  return gauss_norm(it.norm0, it.D, [&](int k) { return it.bw[k]; });
+}
+
+// The tail of both finish kernels, for query q of finish block fb (q < Nq: a live lane): the value stored (through the
+// item's permutation, if any) when the item asks for values; when it asks for a log-likelihood, the lanes' terms summed in
+// a fixed LDS tree into bpart[fb], and bzero[fb] raised if any lane's `zero` is.
+__device__ __forceinline__ void finish_tail(const EvalItem &it, int fb, int64_t q, double value, double term, int zero,
+                                            double *red /* LDS [kFinishThreads] */) {
+  if (q < it.Nq && it.out) {
+    const int64_t o = it.perm ? it.perm[q] - 1 : q;
+    if (o >= 0 && o < it.Nq) it.out[o] = value;  // (an uploaded density's permutation is the caller's)
   }
   if (!it.logl) return;  // (block-uniform)
   red[threadIdx.x] = term;
   const int anyzero = __syncthreads_or(zero);
-  for (int off = kFinishThreads / 2; off > 0; off >>= 1) {
-    if (static_cast<int>(threadIdx.x) < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
+  const double share = block_tree_sum<kFinishThreads>(red);
   if (threadIdx.x == 0) {
-    it.bpart[fb] = red[0];
+    it.bpart[fb] = share;
     it.bzero[fb] = anyzero;
   }
 }
 
-// The log-domain finish (section 5f), for the items [0, n) with block offsets first[] (first[0] is the launch's first
-// block): the groups combined in group order, M = max m_g, S = sum s_g exp(m_g - M),
+// p[q] = (sum over the groups, in group order) / norm [/ (1 - w_q)]   (src/DualTree01.jl:325-340), then W log p and the
+// block's share (items [0, n), item i owns blocks [first[i], first[i+1]), first[0] the launch's first block)
+__global__ __launch_bounds__(kFinishThreads) void eval_finish_kernel(const EvalItem *__restrict__ items,
+                                                                   const int32_t *__restrict__ first, int n) {
+  __shared__ double red[kFinishThreads];
+  const ItemBlock ib = item_block(first, n);
+  const EvalItem it = items[ib.item];
+  const int64_t q = static_cast<int64_t>(ib.k) * kFinishThreads + threadIdx.x;
+  const double inv_norm = 1.0 / eval_norm(it);
+  double p = 0.0, term = 0.0;
+  int zero = 0;
+  if (q < it.Nq) {
+    double s = 0.0;
+    for (int c = 0; c < it.ngroups; ++c) s += it.partial[static_cast<int64_t>(c) * it.Nq + q];
+    p = s * inv_norm;
+    if (it.loo) p = p / (1.0 - it.w[q]);
+    if (it.qw) {  // evalAvgLogL (:456-466): L == 0 counts as 1 when its weight is 0, and makes the result -Inf otherwise
+      const double W = it.qw[q];
+      double L = p;
+      if (L == 0.0) { zero = W != 0.0; L = 1.0; }
+      term = log(L) * W;
+    }
+  }
+  finish_tail(it, ib.k, q, p, term, zero, red);
+}
+
+// The log-domain finish (section 5f): the groups combined in group order, M = max m_g, S = sum s_g exp(m_g - M),
 //   log p = M + log S - log norm [- log(1 - w_q)],   -Inf when no group has a source in S;
 // stored and reduced as eval_finish_kernel does, with W log p summed over the W != 0 only and the block's flag raised by a
 // weighted -Inf.
 __global__ __launch_bounds__(kFinishThreads) void eval_finish_log_kernel(const EvalItem *__restrict__ items,
                                                                        const int32_t *__restrict__ first, int n) {
   __shared__ double red[kFinishThreads];
-  const int b = static_cast<int>(blockIdx.x) + first[0];
-  const int i = item_of_block(first, n, b);
-  const EvalItem it = items[i];
-  const int fb = b - first[i];
-  const int64_t q = static_cast<int64_t>(fb) * kFinishThreads + threadIdx.x;
-  double norm = it.norm0;  // as eval_finish_kernel
-  for (int k = 0; k < it.D; ++k) norm *= __dsqrt_rn(it.bw[k]);
-  const double lognorm = log(norm);
-  double term = 0.0;
+  const ItemBlock ib = item_block(first, n);
+  const EvalItem it = items[ib.item];
+  const int64_t q = static_cast<int64_t>(ib.k) * kFinishThreads + threadIdx.x;
+  const double lognorm = log(eval_norm(it));
+  double lp = -INFINITY, term = 0.0;
   int zero = 0;
   if (q < it.Nq) {
     const double *pm = it.partial + q, *ps = pm + static_cast<int64_t>(it.ngroups) * it.Nq;
     double M = -INFINITY;
     for (int c = 0; c < it.ngroups; ++c) M = fmax(M, pm[static_cast<int64_t>(c) * it.Nq]);
-    double lp = -INFINITY;
     if (M > -INFINITY) {
       double S = 0.0;
       for (int c = 0; c < it.ngroups; ++c) {
@@ -305,10 +217,6 @@ __global__ __launch_bounds__(kFinishThreads) void eval_finish_log_kernel(const E
       lp = M + log(S) - lognorm;
       if (it.loo) lp -= log(1.0 - it.w[q]);
     }
-    if (it.out) {
-      const int64_t o = it.perm ? it.perm[q] - 1 : q;
-      if (o >= 0 && o < it.Nq) it.out[o] = lp;
-    }
     if (it.qw) {
       const double W = it.qw[q];
       if (W != 0.0) {
@@ -317,17 +225,7 @@ __global__ __launch_bounds__(kFinishThreads) void eval_finish_log_kernel(const E
       }
     }
   }
-  if (!it.logl) return;  // (block-uniform)
-  red[threadIdx.x] = term;
-  const int anyzero = __syncthreads_or(zero);
-  for (int off = kFinishThreads / 2; off > 0; off >>= 1) {
-    if (static_cast<int>(threadIdx.x) < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    it.bpart[fb] = red[0];
-    it.bzero[fb] = anyzero;
-  }
+  finish_tail(it, ib.k, q, lp, term, zero, red);
 }
 
 // one thread per item: the block shares in block order
@@ -345,66 +243,32 @@ __global__ void logl_reduce_kernel(const EvalItem *__restrict__ items, int n) {
   *it.logl = zero ? -INFINITY : s;
 }
 
-// d_masks: the items' circular masks (all nonzero), or null: Euclidean items; logdom: log-domain items
-int launch_partial(int D, const EvalItem *d_items, const int32_t *d_first, int n, int blocks, const uint32_t *d_masks,
-                   bool logdom, hipStream_t st) {
-  const dim3 grid(static_cast<unsigned>(blocks)), block(kEvalThreads);
-  KDEHIP_CHECK_RC(dispatch_dims(D, [&](auto dim) {
-    constexpr int kD = decltype(dim)::value;
-    if (logdom) {
-      if (d_masks) hipLaunchKernelGGL((eval_partial_log_kernel<kD, true>), grid, block, 0, st, d_items, d_first, n, d_masks);
-      else hipLaunchKernelGGL((eval_partial_log_kernel<kD, false>), grid, block, 0, st, d_items, d_first, n,
-                              static_cast<const uint32_t *>(nullptr));
-    } else if (d_masks) hipLaunchKernelGGL((eval_partial_kernel<kD, true>), grid, block, 0, st, d_items, d_first, n, d_masks);
-    else hipLaunchKernelGGL((eval_partial_kernel<kD, false>), grid, block, 0, st, d_items, d_first, n,
-                            static_cast<const uint32_t *>(nullptr));
-  }));
-  KDEHIP_CHECK(hipGetLastError());
-  return KDEHIP_OK;
-}
-
-// The blocks of one call: ONE device block [caller's data | descriptors | first[] | results | per item: partial, shares,
-// flags] and ONE pinned image of everything up to and including the results; what precedes the results goes up in one copy.
-// Protocol: fill `items` (sizes, D, loo, what to compute) -> alloc(prefix bytes of caller data) -> the caller writes its
-// data into host() and points the items at dev() -> enqueue(stream) (= upload + launch) -> wait() (blocking calls) or
-// defer(stream) (enqueue-only calls).  The results are one double per item (an item's log-likelihood), or as many as a
-// blocking caller asks alloc for (the host evaluation's Nq values): wait() brings them back in one copy.
-class EvalRun {
+// The run of one call (pair_sweep.hpp PairRun) with the evaluation's scratch, per item [partial | shares | flags], and its
+// launches.  Protocol: fill `items` (sizes, D, loo, what to compute) and `circ` (may be shorter: 0 for the rest) ->
+// alloc(prefix bytes of caller data) -> the caller writes its data into host() and points the items at dev() ->
+// enqueue(stream) (= upload + launch) -> wait() or defer(device).  The results are one double per item (an item's
+// log-likelihood), or as many as a blocking caller asks alloc for (the host evaluation's Nq values).
+class EvalRun : public PairRun<EvalItem> {
  public:
-  std::vector<EvalItem> items;
-  std::vector<uint32_t> circ;  // per item: its circular dimensions (bit k = dimension k); shorter than `items`: 0 for the rest
   int alloc(size_t prefix, size_t nresults = 0) {  // nresults == 0: one per item
     const size_t n = items.size();
     int64_t pblocks = 0, fblocks = 0;
     for (EvalItem &it : items) {
-      const GroupSplit gs = split_chunks(it.N, it.Nq, 1);
-      it.chunks_per_group = gs.chunks_per_group;
-      it.ngroups = it.Nq > 0 ? gs.ngroups : 0;
+      pblocks += split(it);
       it.nfb = static_cast<int32_t>((it.Nq + kFinishThreads - 1) / kFinishThreads);
-      pblocks += ((it.Nq + kEvalThreads - 1) / kEvalThreads) * it.ngroups;
       fblocks += it.nfb;
     }
     if (pblocks > INT32_MAX || fblocks > INT32_MAX) return set_error(KDEHIP_ERR_UNSUPPORTED, "evaluation too large for one launch");
     Carve c;
-    c.take(prefix);
-    o_items_ = c.take(sizeof(EvalItem) * n);
-    o_first_ = c.take(sizeof(int32_t) * 2 * (n + 1) + sizeof(uint32_t) * n);  // first[] of both kernels, then the masks
-    o_masks_ = o_first_ + sizeof(int32_t) * 2 * (n + 1);
-    nres_ = nresults ? nresults : n;
-    o_res_ = c.take(sizeof(double) * nres_);
+    carve_head(c, prefix, 2, 0, nresults ? nresults : n);  // first[] of both kernels
     scratch_.resize(n);
     for (size_t k = 0; k < n; ++k) {
       const EvalItem &it = items[k];
       scratch_[k] = c.take(sizeof(double) * ((it.logdom ? 2 : 1) * it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
     }
-    KDEHIP_CHECK(blk_.alloc(c.mark(), o_res_ + sizeof(double) * nres_));
+    KDEHIP_CHECK(alloc_block(c));
     return KDEHIP_OK;
   }
-  unsigned char *dev() const { return blk_.dev(); }
-  unsigned char *host() const { return blk_.host(); }
-  double *result(size_t k) const { return reinterpret_cast<double *>(dev() + o_res_) + k; }  // (device) result k: item k's own slot
-  double *host_result(size_t k) const { return reinterpret_cast<double *>(host() + o_res_) + k; }
-
   int enqueue(hipStream_t st) {
     KDEHIP_CHECK_RC(upload(st));
     return launch();
@@ -415,86 +279,54 @@ class EvalRun {
     const size_t n = items.size();
     for (size_t k = 0; k < n; ++k) {
       EvalItem &it = items[k];
-      unsigned char *s = dev() + scratch_[k];
-      it.partial = reinterpret_cast<double *>(s);
+      it.partial = reinterpret_cast<double *>(dev() + scratch_[k]);
       it.bpart = it.partial + static_cast<int64_t>(it.logdom ? 2 : 1) * it.ngroups * it.Nq;
       it.bzero = reinterpret_cast<int32_t *>(it.bpart + it.nfb);
     }
-    circ.resize(n, 0u);
-    {
-      std::vector<size_t> ord(n);
-      for (size_t k = 0; k < n; ++k) ord[k] = k;
-      auto key = [&](size_t k) { return (items[k].logdom ? 1024 : 0) + 2 * items[k].D + (circ[k] ? 1 : 0); };
-      std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return key(a) < key(b); });
-      std::vector<EvalItem> si(n);
-      std::vector<uint32_t> sc(n);
-      for (size_t k = 0; k < n; ++k) { si[k] = items[ord[k]]; sc[k] = circ[ord[k]]; }
-      items.swap(si);
-      circ.swap(sc);
-    }
-    if (n) std::memcpy(host() + o_masks_, circ.data(), sizeof(uint32_t) * n);
-    int32_t *pfirst = reinterpret_cast<int32_t *>(host() + o_first_), *ffirst = pfirst + (n + 1);
-    pfirst[0] = ffirst[0] = 0;
-    for (size_t k = 0; k < n; ++k) {
-      const EvalItem &it = items[k];
-      pfirst[k + 1] = pfirst[k] + static_cast<int32_t>(((it.Nq + kEvalThreads - 1) / kEvalThreads) * it.ngroups);
-      ffirst[k + 1] = ffirst[k] + it.nfb;
-    }
-    if (n) std::memcpy(host() + o_items_, items.data(), sizeof(EvalItem) * n);
-    KDEHIP_CHECK(blk_.upload(o_res_, st));
+    prepare([&](size_t k) { return (items[k].logdom ? 1024 : 0) + 2 * items[k].D + (circ[k] ? 1 : 0); });
+    int32_t *ffirst = first(1);
+    ffirst[0] = 0;
+    for (size_t k = 0; k < n; ++k) ffirst[k + 1] = ffirst[k] + items[k].nfb;
+    KDEHIP_CHECK(send(st));
     return KDEHIP_OK;
   }
   // the launches behind the upload: two kernels (and their log-domain twins for the log-domain items), and the per-item
   // reduce when an item asks for a log-likelihood
   int launch() {
-    const hipStream_t st = blk_.stream();
+    const hipStream_t st = stream();
     const size_t n = items.size();
-    const int32_t *pfirst = reinterpret_cast<const int32_t *>(host() + o_first_), *ffirst = pfirst + (n + 1);
-    const EvalItem *d_items = reinterpret_cast<const EvalItem *>(dev() + o_items_);
-    const int32_t *d_pfirst = reinterpret_cast<const int32_t *>(dev() + o_first_), *d_ffirst = d_pfirst + (n + 1);
-    const uint32_t *d_masks = reinterpret_cast<const uint32_t *>(dev() + o_masks_);
-    for (size_t a = 0; a < n;) {  // one launch per distinct D, and one more for its circular and for its log-domain items
-      size_t e = a;
-      while (e < n && items[e].D == items[a].D && !circ[e] == !circ[a] && items[e].logdom == items[a].logdom) ++e;
-      const int blocks = pfirst[e] - pfirst[a];
-      if (blocks > 0) {
-        KDEHIP_CHECK_RC(launch_partial(items[a].D, d_items + a, d_pfirst + a, static_cast<int>(e - a), blocks,
-                                       circ[a] ? d_masks + a : nullptr, items[a].logdom != 0, st));
-      }
-      a = e;
-    }
+    // one launch per distinct D, and one more for its circular and for its log-domain items
+    KDEHIP_CHECK_RC(for_each_run([&](const EvalItem &it, const EvalItem *d_it, const int32_t *d_pfirst, int cnt, int blocks,
+                                     const uint32_t *d_masks) -> int {
+      KDEHIP_CHECK_RC(dispatch_dims(it.D, [&](auto dim) {
+        constexpr int kD = decltype(dim)::value;
+        if (it.logdom)
+          launch_pair<EvalItem>(eval_partial_log_kernel<kD, false>, eval_partial_log_kernel<kD, true>, blocks, st, d_it, d_pfirst,
+                                cnt, d_masks);
+        else
+          launch_pair<EvalItem>(eval_partial_kernel<kD, false>, eval_partial_kernel<kD, true>, blocks, st, d_it, d_pfirst, cnt,
+                                d_masks);
+      }));
+      KDEHIP_CHECK(hipGetLastError());
+      return KDEHIP_OK;
+    }));
+    const int32_t *ffirst = first(1);
     size_t nd = 0;  // the direct items are the first nd
     while (nd < n && !items[nd].logdom) ++nd;
     if (ffirst[nd] > 0)
-      hipLaunchKernelGGL(eval_finish_kernel, dim3(static_cast<unsigned>(ffirst[nd])), dim3(kFinishThreads), 0, st, d_items,
-                         d_ffirst, static_cast<int>(nd));
+      hipLaunchKernelGGL(eval_finish_kernel, dim3(static_cast<unsigned>(ffirst[nd])), dim3(kFinishThreads), 0, st, d_items(),
+                         d_first(1), static_cast<int>(nd));
     if (ffirst[n] > ffirst[nd])
       hipLaunchKernelGGL(eval_finish_log_kernel, dim3(static_cast<unsigned>(ffirst[n] - ffirst[nd])), dim3(kFinishThreads), 0,
-                         st, d_items + nd, d_ffirst + nd, static_cast<int>(n - nd));
+                         st, d_items() + nd, d_first(1) + nd, static_cast<int>(n - nd));
     if (std::any_of(items.begin(), items.end(), [](const EvalItem &it) { return it.logl != nullptr; }))
-      hipLaunchKernelGGL(logl_reduce_kernel, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, st, d_items,
+      hipLaunchKernelGGL(logl_reduce_kernel, dim3(static_cast<unsigned>((n + 63) / 64)), dim3(64), 0, st, d_items(),
                          static_cast<int>(n));
     KDEHIP_CHECK(hipGetLastError());
     return KDEHIP_OK;
   }
-  // blocking calls: the results come back to host_result()
-  int wait() {
-    hipError_t e = hipSuccess;
-    if (nres_) e = blk_.download(o_res_, sizeof(double) * nres_, blk_.stream());
-    const hipError_t se = blk_.wait();
-    KDEHIP_CHECK(e);
-    KDEHIP_CHECK(se);
-    return KDEHIP_OK;
-  }
-  // enqueue-only calls: both blocks go back once the work on the stream is done
-  int defer(int device) {
-    reap_deferred(device);
-    return blk_.defer(device);
-  }
 
  private:
-  CallBlock blk_;
-  size_t o_items_ = 0, o_first_ = 0, o_masks_ = 0, o_res_ = 0, nres_ = 0;
   std::vector<size_t> scratch_;
 };
 
@@ -510,6 +342,8 @@ bool kdehip::leaves_share_bandwidth(const kdehip_device_density *h) {
 
 namespace {
 
+const char kOneBandwidth[] = "per-point bandwidths are not supported (the reference's kde! never builds them)";
+
 // the checks every resident entry makes; `at` may be bd
 int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at, int loo) {
   if (!bd || !at) return set_error(KDEHIP_ERR_ARG, "null density");
@@ -517,8 +351,7 @@ int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at,
   if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   if (at->D != bd->D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "evaluate -- dimensions of two BallTreeDensities must match");
   if (at->device != bd->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
-  if (!leaves_share_bandwidth(bd))
-    return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  if (!leaves_share_bandwidth(bd)) return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
   return KDEHIP_OK;
 }
 
@@ -558,12 +391,7 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   if (leave_one_out) Nq = N;
   else if (!pos || Nq < 0) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
   if (Nq == 0) return KDEHIP_OK;
-  // the reference's evalDirect reads ONE bandwidth vector (bandwidthMin[1..D], BallTreeDensity01.jl:98)
-  const double *bw = bd->bandwidth + N * D;
-  for (int64_t i = 0; i < N; ++i)
-    for (int k = 0; k < D; ++k)
-      if (bd->bandwidth[(N + i) * D + k] != bw[k])
-        return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));  // (the reference's evalDirect reads bandwidthMin[1..D])
   DeviceGuard guard;
   int rc = guard.enter(device);
   if (rc != KDEHIP_OK) return rc;
@@ -573,7 +401,7 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   // order].  ONE pinned image goes up in one DMA and the Nq results come back in one; everything is enqueued on the
   // calling thread's stream and the host waits once (pageable hipMemcpy calls, one per array, cost more than the kernel
   // for anything below ~10^8 kernel evaluations).
-  const size_t o_w = sizeof(double) * N * D, o_bw = o_w + sizeof(double) * N, o_q = o_bw + sizeof(double) * D;
+  const size_t o_bw = sizeof(double) * N * (D + 1), o_q = o_bw + sizeof(double) * D;
   const size_t prefix = o_q + (leave_one_out ? sizeof(int64_t) * N : sizeof(double) * Nq * D);
   EvalRun run;
   EvalItem it{};
@@ -583,14 +411,13 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq)));
   unsigned char *h = run.host(), *d = run.dev();
-  std::memcpy(h, bd->means + N * D, sizeof(double) * N * D);
-  std::memcpy(h + o_w, bd->weights + N, sizeof(double) * N);
-  std::memcpy(h + o_bw, bw, sizeof(double) * D);
+  const LeafArrays src = pack_leaves(run, 0, bd);
+  std::memcpy(h + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
   if (leave_one_out) std::memcpy(h + o_q, bd->permutation + N, sizeof(int64_t) * N);
   else std::memcpy(h + o_q, pos, sizeof(double) * Nq * D);
   EvalItem &ri = run.items[0];
-  ri.src = reinterpret_cast<const double *>(d);
-  ri.w = reinterpret_cast<const double *>(d + o_w);
+  ri.src = src.means;
+  ri.w = src.weights;
   ri.bw = reinterpret_cast<const double *>(d + o_bw);
   ri.qry = leave_one_out ? ri.src : reinterpret_cast<const double *>(d + o_q);
   ri.perm = leave_one_out ? reinterpret_cast<const int64_t *>(d + o_q) : nullptr;
@@ -623,11 +450,7 @@ static int eval_avg_logl_host(const kdehip_density *bd, const kdehip_density *at
   if (at->ndim != D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "evaluate -- dimensions of two BallTreeDensities must match");
   if (N < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation) return set_error(KDEHIP_ERR_ARG, "malformed density");
   if (Nq < 0 || (Nq > 0 && (!at->means || !at->weights))) return set_error(KDEHIP_ERR_ARG, "malformed density");
-  const double *bw = bd->bandwidth + N * D;
-  for (int64_t i = 0; i < N; ++i)
-    for (int k = 0; k < D; ++k)
-      if (bd->bandwidth[(N + i) * D + k] != bw[k])
-        return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
@@ -636,8 +459,8 @@ static int eval_avg_logl_host(const kdehip_density *bd, const kdehip_density *at
   hipStream_t st = hipStreamPerThread;
   const bool self = at == bd;
   // caller data: [bd leaf means | bd leaf weights | bd leaf bandwidth | at leaf means | at leaf weights] (at == bd: none)
-  const size_t o_w = sizeof(double) * N * D, o_bw = o_w + sizeof(double) * N, o_q = o_bw + sizeof(double) * D;
-  const size_t o_qw = o_q + (self ? 0 : sizeof(double) * Nq * D), prefix = o_qw + (self ? 0 : sizeof(double) * Nq);
+  const size_t o_bw = sizeof(double) * N * (D + 1), o_q = o_bw + sizeof(double) * D;
+  const size_t prefix = o_q + (self ? 0 : sizeof(double) * Nq * (D + 1));
   EvalRun run;
   EvalItem it{};
   it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
@@ -645,20 +468,14 @@ static int eval_avg_logl_host(const kdehip_density *bd, const kdehip_density *at
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix));
-  unsigned char *h = run.host(), *d = run.dev();
-  std::memcpy(h, bd->means + N * D, sizeof(double) * N * D);
-  std::memcpy(h + o_w, bd->weights + N, sizeof(double) * N);
-  std::memcpy(h + o_bw, bw, sizeof(double) * D);
-  if (!self) {
-    std::memcpy(h + o_q, at->means + Nq * D, sizeof(double) * Nq * D);
-    std::memcpy(h + o_qw, at->weights + Nq, sizeof(double) * Nq);
-  }
+  const LeafArrays src = pack_leaves(run, 0, bd), qry = self ? src : pack_leaves(run, o_q, at);
+  std::memcpy(run.host() + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
   EvalItem &ri = run.items[0];
-  ri.src = reinterpret_cast<const double *>(d);
-  ri.w = reinterpret_cast<const double *>(d + o_w);
-  ri.bw = reinterpret_cast<const double *>(d + o_bw);
-  ri.qry = self ? ri.src : reinterpret_cast<const double *>(d + o_q);
-  ri.qw = self ? ri.w : reinterpret_cast<const double *>(d + o_qw);
+  ri.src = src.means;
+  ri.w = src.weights;
+  ri.bw = reinterpret_cast<const double *>(run.dev() + o_bw);
+  ri.qry = qry.means;
+  ri.qw = qry.weights;
   ri.logl = run.result(0);
   KDEHIP_CHECK_RC(run.enqueue(st));
   KDEHIP_CHECK_RC(run.wait());

@@ -24,26 +24,29 @@ def normalise(weights, N):
     return w / w.sum()
 
 
-def eval_direct(points, weights, bw, pos=None, manifold=None, loo=False):
+def eval_direct(points, weights, bw, pos=None, manifold=None, loo=False, rows=None):
     """evalDirect -> maxDistKer! -> distGauss! (src/DualTree01.jl:14-47, 130-162) with the normalisation of evaluate
     (:325-335, untouched by the operators): p[q] = sum_i w_i exp(-1/2 sum_k diffop_k(x_qk, c_ik)^2 / bw_k) / norm; loo:
-    at the density's own points without the self term (:141), divided by (1 - w_q) (:335)."""
+    at the density's own points without the self term (:141), divided by (1 - w_q) (:335).  rows: a slice of the queries --
+    the values of those alone (a large leave-one-out is evaluated block by block, never as one N x N array)."""
     points = np.asarray(points, dtype=np.float64)
     D, N = points.shape
     w = normalise(weights, N)
     bw = np.asarray(bw, dtype=np.float64)
     man = [0] * D if manifold is None else list(manifold)
     pos = points if loo else np.asarray(pos, dtype=np.float64).reshape(D, -1)
+    q = np.arange(pos.shape[1])[slice(None) if rows is None else rows]
+    pos = pos[:, q]
     acc = np.zeros((pos.shape[1], N))
     for k in range(D):
         d = diff(pos[k][:, None], points[k][None, :], man[k])
         acc += d * d * (-0.5 / bw[k])
     K = np.exp(acc) * w[None, :]
     if loo:
-        K[np.arange(N), np.arange(N)] = 0.0
+        K[np.arange(q.size), q] = 0.0
     norm = (2.0 * math.pi) ** (D / 2.0) * np.prod(np.sqrt(bw))
     p = K.sum(axis=1) / norm
-    return p / (1.0 - w) if loo else p
+    return p / (1.0 - w[q]) if loo else p
 
 
 def avg_logl(L, W):

@@ -25,27 +25,30 @@ def exponents(points, bw, pos, manifold=None):
     return a
 
 
-def eval_log(points, weights, bw, pos=None, manifold=None, loo=False):
+def eval_log(points, weights, bw, pos=None, manifold=None, loo=False, rows=None):
     """log p[q] = m + log(sum_{i in S} w_i exp(a_i - m)) - log(norm) [- log(1 - w_q)], m = max_{i in S} a_i,
-    S = {i : w_i > 0} (loo: and i != q); S empty gives -inf"""
+    S = {i : w_i > 0} (loo: and i != q); S empty gives -inf.  rows: a slice of the queries -- the values of those alone (a
+    large leave-one-out is evaluated block by block, never as one N x N array)."""
     points = np.asarray(points, dtype=np.float64)
     D, N = points.shape
     w = normalise(weights, N)
     bw = np.asarray(bw, dtype=np.float64)
-    a = exponents(points, bw, points if loo else pos, manifold)
+    pos = points if loo else np.asarray(pos, dtype=np.float64).reshape(D, -1)
+    qs = np.arange(pos.shape[1])[slice(None) if rows is None else rows]
+    a = exponents(points, bw, pos[:, qs], manifold)
     inS = np.broadcast_to(w[None, :] > 0.0, a.shape).copy()
     if loo:
-        inS[np.arange(N), np.arange(N)] = False
+        inS[np.arange(qs.size), qs] = False
     lognorm = math.log((2.0 * math.pi) ** (D / 2.0) * np.prod(np.sqrt(bw)))
     out = np.full(a.shape[0], -np.inf)
-    for q in range(a.shape[0]):
-        s = inS[q]
+    for r, q in enumerate(qs):
+        s = inS[r]
         if not s.any():
             continue
-        m = a[q, s].max()
-        out[q] = m + math.log(float(np.sum(w[s] * np.exp(a[q, s] - m)))) - lognorm
+        m = a[r, s].max()
+        out[r] = m + math.log(float(np.sum(w[s] * np.exp(a[r, s] - m)))) - lognorm
         if loo:
-            out[q] -= math.log(1.0 - w[q])
+            out[r] -= math.log(1.0 - w[q])
     return out
 
 

@@ -11,6 +11,7 @@ import pytest
 
 import kdehip
 from kdehip import _lib
+from tests import circular_model as cm
 from tests import ksum_model as km
 
 pytestmark = pytest.mark.gpu
@@ -323,3 +324,48 @@ def test_resident_arguments_are_refused_before_the_device_is_used():
         assert L.kdehip_kernel_sum_device_batch(2, items, C.c_void_p(256), None) == _lib.ERR_DIM_MISMATCH
         with pytest.raises(ValueError):
             kdehip.ise(p2, p3)
+
+
+# Groups of SEVERAL source chunks, the only part of the all-pairs sweep (csrc/pair_sweep.hpp) that really double-buffers.
+# split_chunks (csrc/entry_helpers.hpp) deals the ceil(N / 128) chunks to at most 64 groups (kEvalMaxGroups), and on the
+# 256 CUs of an MI355X it wants all 64 for any M up to a few thousand: a group holds more than one chunk only when
+# N > 128 * 64.
+#   N = 128 * 64 + 1:  65 chunks, 2 per group, 33 groups; the last group is ONE chunk of ONE point, every other group prefetches
+#   N = 128 * 128 + 1: 129 chunks, 3 per group: both buffer parities inside a group; the last chunk holds one point
+# M = 257: a second query block with one live lane.  One case has a circular dimension.
+SWEEP_M = 257
+SWEEP_CASES = [(1, 128 * 64 + 1, None), (6, 128 * 64 + 1, None), (1, 128 * 128 + 1, None), (6, 128 * 128 + 1, None),
+               (6, 128 * 64 + 1, [0, 0, 1, 0, 0, 0])]
+
+
+@pytest.mark.parametrize("D,N,man", SWEEP_CASES)
+def test_groups_of_several_chunks_against_the_model(D, N, man):
+    import torch
+    rng = np.random.default_rng(7 * N + D)
+    if man is None:
+        a, b = _density(rng, D, N), _density(rng, D, SWEEP_M, shift=0.4)
+    else:
+        pa, _, ks, pb = cm.circular_case(7 * N + D, D, N, SWEEP_M, man, False)
+        a, b = kdehip.kde(pa, ks, _weights(rng, N)), kdehip.kde(pb, ks[::-1].copy(), _weights(rng, SWEEP_M))
+    sd = rng.uniform(0.3, 0.9, size=D)
+    v = sd * sd
+    A, B = _arrays(a), _arrays(b)
+    got_v = kdehip.kernel_sum(a, b, v, manifold=man)
+    _close(got_v, km.kernel_sum(A, B, v, False, man))            # explicit variances
+    got_sum = kdehip.kernel_sum(a, b, manifold=man)
+    _close(got_sum, km.kernel_sum(A, B, None, False, man))       # the summed leaf variances
+    # normalised = sum_j b_j p(y_j) with p = kde(a's points, sqrt(v), a's weights), by evaluateDualTree
+    p = kdehip.kde(A[0], sd, A[1])  # its variances are sd * sd == v, bit for bit
+    want = math.fsum((B[1] * kdehip.evaluateDualTree(p, B[0], manifold=man)).tolist())
+    _close(kdehip.kernel_sum(a, b, v, normalize=True, manifold=man), want)
+    # host entry == resident entry == a batch whose first item is a small 1-D Euclidean one: the launch of a 6-D or circular
+    # item then starts at a block offset (first[0] != 0), and a Euclidean 1-D item is the second of its launch
+    small = kdehip.kde(np.array([[0.1, 0.4, -0.3]]), [0.3])
+    with kdehip.DeviceDensity(a) as da, kdehip.DeviceDensity(b) as db, kdehip.DeviceDensity(small) as ds:
+        assert kdehip.kernel_sum(da, db, v, manifold=man) == got_v
+        assert kdehip.kernel_sum(da, db, manifold=man) == got_sum
+        out = torch.full((3,), np.nan, dtype=torch.float64, device="cuda:0")
+        kdehip.kernel_sum_device_batch([dict(a=ds, b=ds), dict(a=da, b=db, var=v, manifold=man),
+                                        dict(a=da, b=db, manifold=man)], out)
+        torch.cuda.synchronize()
+        assert out.cpu().numpy().tolist() == [kdehip.kernel_sum(small, small), got_v, got_sum]

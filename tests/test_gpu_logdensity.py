@@ -224,3 +224,67 @@ def test_a_batch_mask_bit_beyond_ndims_is_refused():
         _lib.check(_lib.lib.kdehip_eval_avg_logl_log_device_batch(1, arr, out.data_ptr(), None))
         torch.cuda.synchronize()
         assert out.item() == kdehip.evalAvgLogL(dq, dq, manifold=[0, 1], log_domain=True)
+
+
+# Groups of SEVERAL chunks (the shape in SHAPES has 3 queries): the double-buffered walk of csrc/pair_sweep.hpp with the
+# carried (m, s) rescaled inside a group.  On the 256 CUs of an MI355X split_chunks wants all MAX_GROUPS groups for any query
+# count up to a few thousand, so a group holds more than one chunk only when N > 128 * MAX_GROUPS.
+#   N = 128 * 64 + 1:  65 chunks, 2 per group, 33 groups; the last group is ONE chunk of ONE point, every other group prefetches
+#   N = 128 * 128 + 1: 129 chunks, 3 per group: both buffer parities inside a group; the last chunk holds one point
+# 257 queries: a second query block with one live lane.  One case has a circular dimension.
+SWEEP_NQ = 257
+SWEEP_CASES = [(1, 128 * MAX_GROUPS + 1, None), (6, 128 * MAX_GROUPS + 1, None), (1, 256 * MAX_GROUPS + 1, None),
+               (6, 256 * MAX_GROUPS + 1, None), (6, 128 * MAX_GROUPS + 1, [0, 0, 1, 0, 0, 0])]
+
+
+def _sweep_case(D, N, man):
+    """points, weights (with exact zeros), standard deviations and SWEEP_NQ queries"""
+    if man is None:
+        pts, w, sd, pos = _case(5 * N + D, D, N, SWEEP_NQ, True)
+    else:
+        pts, w, sd, pos = cm.circular_case(5 * N + D, D, N, SWEEP_NQ, man, True)
+    w[::5] = 0.0
+    return pts, w, sd, pos
+
+
+@pytest.mark.parametrize("D,N,man", SWEEP_CASES)
+def test_groups_of_several_chunks_against_the_model(D, N, man):
+    import torch
+    pts, w, sd, pos = _sweep_case(D, N, man)
+    p, q = kdehip.kde(pts, sd, w), kdehip.kde(pos, [0.3])
+    want = lm.eval_log(pts, w, _var(p), pos, man)
+    host = kdehip.evaluate_log(p, pos, manifold=man)
+    _close(host, want, "evaluate_log")
+    want_ll, _ = lm.avg_logl_log(want, np.full(SWEEP_NQ, 1.0 / SWEEP_NQ))  # (q's weights are uniform; a sum has no order)
+    e = kdehip.evalAvgLogL(p, q, manifold=man, log_domain=True)
+    _close(e, want_ll, "evalAvgLogL")
+    # host entry == resident entry == a batch whose first item is a small 1-D Euclidean one: the launch of a 6-D or circular
+    # item then starts at a block offset (first[0] != 0), and a Euclidean 1-D item is the second of its launch
+    small = kdehip.kde(np.array([[0.1, 0.4, -0.3, 0.9, 0.5]]), [0.3])
+    with kdehip.DeviceDensity(p) as dp, kdehip.DeviceDensity(q) as dq, kdehip.DeviceDensity(small) as ds:
+        assert np.array_equal(dp.evaluate_log(pos, manifold=man), host)
+        assert np.array_equal(dp.evaluate_log(dq, manifold=man), kdehip.evaluate_log(p, kdehip.getPoints(q), manifold=man))
+        assert kdehip.evalAvgLogL(dp, dq, manifold=man, log_domain=True) == e
+        out = torch.full((2,), np.nan, dtype=torch.float64, device="cuda:0")
+        kdehip.eval_avg_logl_device_batch([(ds, ds), (dp, dq)], out, manifolds=[None, man], log_domain=True)
+        torch.cuda.synchronize()
+        assert out[1].item() == e and out[0].item() == kdehip.evalAvgLogL(small, small, log_domain=True)
+
+
+def test_leave_one_out_with_the_self_term_in_a_groups_second_chunk():
+    """N = Nq = 128 * 64 + 1 in 1-D: 33 query blocks, 33 groups of 2 chunks; for half the queries the self term is a point of
+    the second chunk its block walks.  The model is evaluated in row blocks (never an N x N array)."""
+    N = 128 * MAX_GROUPS + 1
+    pts, w, sd, _ = _case(N, 1, N, 1, True)
+    w[::5] = 0.0
+    p = kdehip.kde(pts, sd, w)
+    want = np.concatenate([lm.eval_log(pts, w, _var(p), loo=True, rows=slice(r, r + 1024)) for r in range(0, N, 1024)])
+    assert want.shape == (N,)
+    loo = kdehip.evaluate_log(p, lvFlag=True)
+    _close(loo, want, "leave-one-out")
+    want_ll, _ = lm.avg_logl_log(want, cm.normalise(w, N))
+    e = kdehip.evalAvgLogL(p, p, log_domain=True)
+    _close(e, want_ll, "evalAvgLogL(p, p)")
+    with kdehip.DeviceDensity(p) as dp:
+        assert kdehip.evalAvgLogL(dp, dp, log_domain=True) == e
+        assert np.array_equal(dp.evaluate_log(dp), loo)

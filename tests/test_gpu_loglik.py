@@ -10,6 +10,7 @@ import pytest
 
 import kdehip
 from oracle import oracle
+from tests import circular_model as cm
 
 pytestmark = pytest.mark.gpu
 
@@ -208,3 +209,81 @@ def test_kld_batch_equals_single_calls_and_is_deterministic():
     for p, q in devs:
         p.close()
         q.close()
+
+
+# Shapes at which a block walks MORE than one source chunk, the only part of the all-pairs sweep (csrc/pair_sweep.hpp) that
+# really double-buffers.  split_chunks (csrc/entry_helpers.hpp) deals the ceil(N / 128) chunks to at most 64 groups
+# (kEvalMaxGroups), and on the 256 CUs of an MI355X it wants all 64 for any query count up to a few thousand: a group holds
+# more than one chunk only when N > 128 * 64.
+#   N = 128 * 64 + 1:  65 chunks, 2 per group, 33 groups; the last group is ONE chunk of ONE point, every other group prefetches
+#   N = 128 * 128 + 1: 129 chunks, 3 per group: both buffer parities inside a group; the last chunk holds one point
+# 257 queries: a second query block with one live lane.  One case has a circular dimension.
+SWEEP_NQ = 257
+SWEEP_CASES = [(1, 128 * 64 + 1, None), (6, 128 * 64 + 1, None), (1, 128 * 128 + 1, None), (6, 128 * 128 + 1, None),
+               (6, 128 * 64 + 1, [0, 0, 1, 0, 0, 0])]
+
+
+def _sweep_case(D, N, man):
+    """points, weights (with exact zeros), standard deviations and SWEEP_NQ queries"""
+    if man is None:
+        rng = np.random.default_rng(3 * N + D)
+        pts, w, sd, pos = _pts(rng, D, N), rng.uniform(0.05, 1.0, size=N), rng.uniform(0.2, 0.6, size=D), _pts(rng, D, SWEEP_NQ)
+    else:
+        pts, w, sd, pos = cm.circular_case(3 * N + D, D, N, SWEEP_NQ, man, True)
+    w[::5] = 0.0
+    return pts, w, sd, pos
+
+
+def _var(p):
+    """the variances the library holds for p (its first leaf's)"""
+    N, D = p.bt.num_points, p.bt.dims
+    return np.array(p.bandwidth[N * D:N * D + D])
+
+
+@pytest.mark.parametrize("D,N,man", SWEEP_CASES)
+def test_groups_of_several_chunks_against_the_model(D, N, man):
+    import torch
+    pts, w, sd, pos = _sweep_case(D, N, man)
+    p, q = kdehip.kde(pts, sd, w), kdehip.kde(pos, [0.3])
+    want = cm.eval_direct(pts, w, _var(p), pos, man)
+    assert np.all(want > 0.0)
+    host = kdehip.evaluateDualTree(p, pos, manifold=man)
+    print("evaluate: max relative error", np.max(np.abs(host - want) / want))
+    assert np.allclose(host, want, rtol=1e-12, atol=1e-300)
+    want_ll, scale = cm.avg_logl(want, np.full(SWEEP_NQ, 1.0 / SWEEP_NQ))  # (q's weights are uniform; a sum has no order)
+    e = kdehip.evalAvgLogL(p, q, manifold=man)
+    print("evalAvgLogL", e, want_ll, abs(e - want_ll), 1e-12 * scale)
+    _close(e, want_ll, scale)
+    # host entry == resident entry == a batch whose first item is a small 1-D Euclidean one: the launch of a 6-D or circular
+    # item then starts at a block offset (first[0] != 0), and a Euclidean 1-D item is the second of its launch
+    small = kdehip.kde(np.array([[0.1, 0.4, -0.3, 0.9, 0.5]]), [0.3])
+    with kdehip.DeviceDensity(p) as dp, kdehip.DeviceDensity(q) as dq, kdehip.DeviceDensity(small) as ds:
+        assert np.array_equal(dp.evaluate(pos, manifold=man), host)
+        assert np.array_equal(dp.evaluate(dq, manifold=man), kdehip.evaluateDualTree(p, kdehip.getPoints(q), manifold=man))
+        assert kdehip.evalAvgLogL(dp, dq, manifold=man) == e
+        out = torch.full((2,), np.nan, dtype=torch.float64, device="cuda:0")
+        kdehip.eval_avg_logl_device_batch([(ds, ds), (dp, dq)], out, manifolds=[None, man])
+        torch.cuda.synchronize()
+        assert out[1].item() == e and out[0].item() == kdehip.evalAvgLogL(small, small)
+
+
+def test_leave_one_out_with_the_self_term_in_a_groups_second_chunk():
+    """N = Nq = 128 * 64 + 1 in 1-D: 33 query blocks, 33 groups of 2 chunks; for half the queries the self term is a point of
+    the second chunk its block walks.  The model is evaluated in row blocks (never an N x N array)."""
+    N = 128 * 64 + 1
+    rng = np.random.default_rng(N)
+    pts, w, sd = _pts(rng, 1, N), rng.uniform(0.05, 1.0, size=N), rng.uniform(0.2, 0.6, size=1)
+    w[::5] = 0.0
+    p = kdehip.kde(pts, sd, w)
+    want = np.concatenate([cm.eval_direct(pts, w, _var(p), loo=True, rows=slice(r, r + 1024)) for r in range(0, N, 1024)])
+    assert want.shape == (N,) and np.all(want > 0.0)
+    loo = kdehip.evaluateDualTree(p, lvFlag=True)
+    print("leave-one-out: max relative error", np.max(np.abs(loo - want) / want))
+    assert np.allclose(loo, want, rtol=1e-12, atol=1e-300)
+    want_ll, scale = cm.avg_logl(want, cm.normalise(w, N))
+    e = kdehip.evalAvgLogL(p, p)
+    print("evalAvgLogL(p, p)", e, want_ll, abs(e - want_ll), 1e-12 * scale)
+    _close(e, want_ll, scale)
+    with kdehip.DeviceDensity(p) as dp:
+        assert kdehip.evalAvgLogL(dp, dp) == e
+        assert np.array_equal(dp.evaluate(dp), loo)
