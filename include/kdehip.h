@@ -987,6 +987,72 @@ int kdehip_kernel_sum_device(const kdehip_device_density *a, const kdehip_device
 int kdehip_kernel_sum(const kdehip_density *a, const kdehip_density *b, const double *var, int normalize,
                       double *out, int device, const uint8_t *manifold);
 
+/* ---- (5h) the gradient of the density and its joint modes by mean shift ---------------------------------------------------
+ * Where is a belief, jointly?  getKDEMax (5c) is the reference's answer: the grid argmax of every 1-D marginal, taken
+ * independently -- for a multimodal density a point that may belong to no mode; getKDEMean / getKDEfit are moments.  The
+ * entries below give the gradient of (log) p and the fixed points of the mean-shift iteration, the joint modes
+ * (csrc/modes.hip; this library's own, the reference has no counterpart).  For a density bd with leaves i, weights w_i and
+ * ONE bandwidth vector v_k (section 5), a query x and a per-dimension `manifold` as in 5d (NULL = Euclidean):
+ *   d_ik    = x_k - c_ik, through wrap() first in a circular dimension
+ *   a_i     = sum_k d_ik^2 * (-0.5 / v_k): the expression and fma order of the direct kernel
+ *   S       = { i : w_i > 0 }, m = max_{i in S} a_i (the rule of 5f: a weightless leaf neither sets the maximum nor adds)
+ *   S_0     = sum_{i in S} w_i exp(a_i - m),  S_k = sum_{i in S} w_i exp(a_i - m) d_ik
+ *   log p   = m + log S_0 - log norm,  p = exp(m) S_0 / norm,  norm = (2 pi)^(D/2) prod_k sqrt(v_k) as in section 5
+ *   grad log p (x)_k = -S_k / (S_0 v_k),  grad p = p * grad log p
+ *   the mean-shift step: x_k <- x_k - S_k / S_0, through wrap() in a circular dimension.
+ * S empty: log p = -Inf, p = 0 and the gradient is 0; such a start does not move (0 steps).  The ratio S_k / S_0 is formed
+ * from sums scaled by exp(-m), so it is defined wherever some a_i is finite -- far beyond where p underflows.
+ * The sum is split as in 5b / 5f: consecutive 128-leaf chunks in groups that depend on (npts, Nq) alone; a group carries
+ * (m, s_0, .., s_D), rescaled by exp(m_old - m_new) once per chunk, and the groups are combined in group order with
+ * M = max m_g, sum_g s_jg exp(m_g - M).  No atomics.  So the host entry, a resident call and any batch return the same bits,
+ * run after run; a start's trajectory depends on the density, the start, tol and that split alone -- not on what else is in
+ * the call, nor on how the sweeps are grouped between the host's checks.
+ * Mean shift: every start takes steps until max_k |S_k / S_0| / sqrt(v_k) <= tol (the step just taken is the last: the
+ * point is frozen and never written again) or until it has taken maxiter steps.  iters[q] = the steps taken, negative when
+ * the last of them was still above tol; logp[q] = log p at the returned x[q], from one closing evaluation.  Query blocks
+ * (256 starts) whose starts are all frozen cost nothing in later sweeps.
+ * Not here: leave-one-out gradients, per-point bandwidths, kernels other than the Gaussian.
+ * Errors, all checked before any device is touched: null arguments (val and grad both NULL included), Nq / nstart < 0,
+ * start == NULL with nstart != npts, tol negative or not finite, maxiter / niter < 0, a manifold byte above 1 or a mask bit
+ * at or above D, densities on different devices within one batch -- KDEHIP_ERR_ARG; D outside 1..KDEHIP_MAX_DIMS or per-point
+ * bandwidths -- KDEHIP_ERR_UNSUPPORTED.  Nq == 0, n == 0 and maxiter == 0 are KDEHIP_OK (maxiter == 0: the starts and their
+ * log p).  fp64 only. */
+/* Host density, blocking: pos as kdehip_evaluate takes it (Nq points, D values each); val [Nq] (log p, or p with
+ * log_domain == 0) or NULL; grad [Nq][D] (of log p, or of p with log_domain == 0) or NULL. */
+int kdehip_evaluate_grad(const kdehip_density *bd, const double *pos, int64_t Nq, int log_domain, double *val, double *grad,
+                         int device, const uint8_t *manifold);
+/* Resident density, device arrays, enqueue only on `stream`. */
+int kdehip_evaluate_grad_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int log_domain,
+                                double *d_val, double *d_grad, const uint8_t *manifold, void *stream);
+/* tol is a HOST pointer to ONE value in every entry (this ABI passes integers and pointers only, so that every binding of it
+ * can be checked against this header type by type); NULL is KDEHIP_ERR_ARG.
+ * Host density, blocking.  start: nstart points, or NULL = the density's own points in their ORIGINAL order (nstart must be
+ * npts).  x [nstart][D], logp [nstart], iters [nstart]: host arrays.  The sweeps run in rounds with one read of the number
+ * of live starts between them; the round length changes no bit of the result. */
+int kdehip_meanshift(const kdehip_density *bd, const double *start, int64_t nstart, const double *tol, int maxiter, double *x,
+                     double *logp, int32_t *iters, int device, const uint8_t *manifold);
+/* The same for a resident density: d_start a device array or NULL, the results to HOST arrays; blocking. */
+int kdehip_meanshift_device(const kdehip_device_density *bd, const double *d_start, int64_t nstart, const double *tol,
+                            int maxiter, double *x, double *logp, int32_t *iters, const uint8_t *manifold);
+typedef struct kdehip_meanshift_item {
+  const kdehip_device_density *bd;
+  const double *d_start;    /* device, [nstart][D], or NULL = bd's own points in original order (nstart == npts) */
+  int64_t nstart;
+  double *d_x;              /* device, [nstart][D]; may be d_start */
+  double *d_logp;           /* device, [nstart] */
+  int32_t *d_iters;         /* device, [nstart] */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+  uint32_t reserved_;
+} kdehip_meanshift_item;
+/* Resident densities, all on one device.  Enqueue only on `stream`: exactly niter step sweeps and the closing evaluation,
+ * one launch per distinct (D, circular) per sweep for all items together, and no read-back -- so the call can be captured
+ * in a HIP graph.  The descriptor and scratch blocks of a captured call (a device and a pinned block, some tens of KB plus
+ * (D + 2) * groups * nstart doubles per item) are kept until kdehip_clear_cache, because the graph's nodes use them at every
+ * replay: every capture adds a pair, so capture once and replay, and kdehip_clear_cache INVALIDATES every graph captured
+ * from this entry -- destroy those graphs first, or do not replay them afterwards.  Every item's results are bit for bit
+ * those of kdehip_meanshift_device with maxiter == niter. */
+int kdehip_meanshift_device_batch(int n, const kdehip_meanshift_item *items, const double *tol, int niter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,12 @@ class CKsumItem(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("var", f64p), ("circular_mask", C.c_uint32), ("normalize", C.c_int32)]
 
 
+class CMeanshiftItem(C.Structure):
+    """struct kdehip_meanshift_item"""
+    _fields_ = [("bd", C.c_void_p), ("d_start", C.c_void_p), ("nstart", C.c_int64), ("d_x", C.c_void_p), ("d_logp", C.c_void_p),
+                ("d_iters", C.c_void_p), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -172,6 +178,11 @@ SIGNATURES = {
     "kdehip_kernel_sum": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), f64p, C.c_int, f64p, C.c_int, u8p]),
     "kdehip_kernel_sum_device": (C.c_int, [C.c_void_p, C.c_void_p, f64p, C.c_int, f64p, u8p]),
     "kdehip_kernel_sum_device_batch": (C.c_int, [C.c_int, C.POINTER(CKsumItem), C.c_void_p, C.c_void_p]),
+    "kdehip_evaluate_grad": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, f64p, f64p, C.c_int, u8p]),
+    "kdehip_evaluate_grad_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, u8p, C.c_void_p]),
+    "kdehip_meanshift": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, C.c_int, u8p]),
+    "kdehip_meanshift_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, u8p]),
+    "kdehip_meanshift_device_batch": (C.c_int, [C.c_int, C.POINTER(CMeanshiftItem), f64p, C.c_int, C.c_void_p]),
     "kdehip_auto_bandwidth_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, u8p]),
     "kdehip_make_density_auto_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p,
                                                     i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),

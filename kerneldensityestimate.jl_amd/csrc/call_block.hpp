@@ -33,6 +33,9 @@ void reap_deferred(int device, hipStream_t mine = nullptr, size_t limit = 0);
 // everything is released at once (KDEHIP_ERR_HIP).
 int defer_release(int device, hipStream_t stream, void *d, size_t dbytes, void *h, size_t hbytes, ReleaseHook hook = nullptr,
                   void *ctx = nullptr);
+// Keeps a device and a pinned block (either may be null) until kdehip_clear_cache: the blocks of a call that was captured into
+// a graph, whose nodes use them at every replay.  No event, no stream operation.
+int keep_until_clear(int device, void *d, size_t dbytes, void *h, size_t hbytes);
 // Waits for and releases everything parked for `device` (which is current), or for every device (-1: kdehip_clear_cache).
 void drain_deferred(int device = -1);
 
@@ -95,6 +98,13 @@ class CallBlock {
     d_ = h_ = nullptr;
     n_ = 0;
     return defer_release(device, st, d, dbytes_, h, hbytes_, hook, ctx);
+  }
+  // a call captured into a graph: both blocks are kept until kdehip_clear_cache, and the object is disarmed
+  int keep(int device) {
+    void *d = d_, *h = h_;
+    d_ = h_ = nullptr;
+    n_ = 0;
+    return keep_until_clear(device, d, dbytes_, h, hbytes_);
   }
 
  private:

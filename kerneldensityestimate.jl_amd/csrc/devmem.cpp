@@ -204,6 +204,31 @@ int defer_release(int device, hipStream_t stream, void *d, size_t dbytes, void *
   return KDEHIP_OK;
 }
 
+namespace {
+std::mutex g_kept_mu;
+std::vector<Deferred> g_kept;  // blocks of captured calls: no event, released by kdehip_clear_cache
+}  // namespace
+
+int keep_until_clear(int device, void *d, size_t dbytes, void *h, size_t hbytes) {
+  Deferred f;
+  f.device = device;
+  f.d = d; f.dbytes = dbytes; f.h = h; f.hbytes = hbytes;
+  std::lock_guard<std::mutex> lock(g_kept_mu);
+  g_kept.push_back(f);
+  return KDEHIP_OK;
+}
+
+static void release_kept() {
+  std::vector<Deferred> kept;
+  {
+    std::lock_guard<std::mutex> lock(g_kept_mu);
+    kept.swap(g_kept);
+  }
+  DeviceGuard guard;
+  for (Deferred &f : kept)
+    if (guard.enter(f.device) == KDEHIP_OK) release_deferred(f);
+}
+
 void drain_deferred(int device) {
   if (device >= 0) { reap(device, true, nullptr, 0); return; }
   int n = 0;
@@ -251,6 +276,7 @@ extern "C" void kdehip_clear_cache(void) {
   using namespace kdehip;
   g_peer_epoch.fetch_add(1, std::memory_order_relaxed);  // verdicts cached per raw pointer do not survive a cache reset
   drain_deferred();  // blocks (and plans) of enqueue-only calls still waiting for their work
+  release_kept();    // blocks of calls that were captured into a graph
   int cur = 0;
   const bool have_cur = hipGetDevice(&cur) == hipSuccess;
   int n = 0;

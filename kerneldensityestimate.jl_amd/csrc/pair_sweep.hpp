@@ -9,12 +9,15 @@
 //   a_i = -1/2 sum_k diff_k(x_qk, c_ik)^2 / v_k     (k ascending, one fma per dimension; diff_k is the plain difference,
 //                                                    or circ_wrap of it in a circular dimension)
 // and hands (i, w_i, a_i) to the kernel's own step: the plain sum, the sum without the self term, or a running maximum and
-// a rescaled sum.  What the variances v_k are is the kernel's business: it passes nhib[k] = -1/(2 v_k).
+// a rescaled sum.  A step that also takes the D differences, f(i, w_i, a_i, d) with d[k] = diff_k -- the values a_i was
+// formed from --, gets them (modes.hip: the first moments); the others compile to what they were without them.
+// What the variances v_k are is the kernel's business: it passes nhib[k] = -1/(2 v_k).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "call_block.hpp"
@@ -62,7 +65,8 @@ __device__ __forceinline__ PairPlace pair_place(const PairHead &h, int64_t kb) {
 }
 
 // The walk over the chunks of the block's group.  Per staged chunk, in chunk order, step(each) is called once; each(f)
-// calls f(i, w_i, a_i) for the chunk's sources in order and may be called more than once (a second pass recomputes a_i).
+// calls f(i, w_i, a_i) -- or f(i, w_i, a_i, d), d the D differences, if f takes four arguments -- for the chunk's sources in
+// order and may be called more than once (a second pass recomputes a_i).
 // Every lane, those at or beyond Nq included (their x is 0), walks the same chunks and barriers.
 template <int D, bool CIRC, typename Step>
 __device__ __forceinline__ void pair_sweep(const PairHead &h, const PairPlace &at, unsigned circ, const double (&nhib)[D],
@@ -88,18 +92,22 @@ __device__ __forceinline__ void pair_sweep(const PairHead &h, const PairPlace &a
     const int64_t i0 = c * kEvalChunk;
     const int cnt = static_cast<int>((N - i0 < kEvalChunk) ? (N - i0) : kEvalChunk);
     step([&](auto &&f) {
+      constexpr bool kDiffs = std::is_invocable_v<decltype(f), int64_t, double, double, const double (&)[D]>;
       for (int i = 0; i < cnt; ++i) {
         const double *s = sSrc[buf] + i * (D + 1);
         double acc = 0.0;
+        [[maybe_unused]] double diff[kDiffs ? D : 1];
 #pragma unroll
         for (int k = 0; k < D; ++k) {
           double d = x[k] - s[k];
           if constexpr (CIRC) {
             if ((circ >> k) & 1u) d = circ_wrap(d);
           }
+          if constexpr (kDiffs) diff[k] = d;
           acc = fma(d * d, nhib[k], acc);
         }
-        f(i0 + i, s[D], acc);  // acc <= 0
+        if constexpr (kDiffs) f(i0 + i, s[D], acc, diff);
+        else f(i0 + i, s[D], acc);  // acc <= 0
       }
     });
   }
@@ -166,6 +174,9 @@ class PairRun {
     return blk_.defer(device);
   }
 
+  // enqueue-only calls on a stream that is being captured into a graph: both blocks stay until kdehip_clear_cache
+  int keep(int device) { return blk_.keep(device); }
+
  protected:
   // the item's group split (a function of its sizes alone); returns its number of sweep blocks
   static int64_t split(Item &it) {
@@ -214,6 +225,7 @@ class PairRun {
   hipStream_t stream() const { return blk_.stream(); }
   const Item *d_items() const { return reinterpret_cast<const Item *>(dev() + o_items_); }
   const int32_t *d_first(int which = 0) const { return reinterpret_cast<const int32_t *>(dev() + o_first_) + which * (items.size() + 1); }
+  const uint32_t *d_masks() const { return reinterpret_cast<const uint32_t *>(dev() + o_masks_); }  // one word per item
   // launch(first item of the run, its descriptors, its first[], items, blocks, its masks or null) per run of equal key
   template <typename Launch>
   int for_each_run(Launch launch) {

@@ -773,6 +773,109 @@ function hip_mmd(p::BallTreeDensity, q::BallTreeDensity, bw::AbstractVector{Floa
 end
 
 """
+    hip_evaluate_grad(bd, pos; log=true, manifold=nothing, device=0)
+
+`(val, grad)` at the columns of `pos` (`kdehip_evaluate_grad`, include/kdehip.h section 5h): `log p` and its gradient
+`-S_k / (S_0 v_k)`, or with `log=false` `p` and its gradient; `val` has `Nq` entries, `grad` is `D x Nq`.  `log p` and its
+gradient stay finite where `p` underflows to 0.  The library's own (the reference has no gradient): not installed by
+`enable!()`.
+"""
+function hip_evaluate_grad(bd::BallTreeDensity, pos::AbstractMatrix{Float64}; log::Bool=true, manifold=nothing, device::Int=0)
+  Ndim(bd) == size(pos, 1) || error("bd and pos must have the same dimension")
+  man = manifold === nothing ? zeros(UInt8, Ndim(bd)) : manifold_bytes(manifold, Ndim(bd))
+  Nq = size(pos, 2)
+  val = zeros(Nq)
+  grad = zeros(Ndim(bd), Nq)
+  cd = Ref(CDensity(bd))
+  posd = Matrix{Float64}(pos)
+  GC.@preserve bd posd man begin
+    check(ccall((:kdehip_evaluate_grad, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{UInt8}),
+                cd, posd, Nq, log ? 1 : 0, val, grad, device, man))
+  end
+  return val, grad
+end
+
+"""
+    hip_meanshift(bd, starts=nothing; tol=1e-9, maxiter=500, manifold=nothing, device=0)
+
+`(x, logp, iters)` (`kdehip_meanshift`, include/kdehip.h section 5h): every column of `starts` -- `nothing`: the density's
+own points, in `getPoints` order -- moved by mean-shift steps `x_k <- x_k - S_k / S_0` (wrapped to `[-pi, pi)` in a circular
+dimension) on the device until a step is at most `tol` bandwidths long in every dimension, or for `maxiter` steps; `iters` =
+the steps taken, negative where the last was still above `tol`; `logp` = `log p` at `x`.  Not installed by `enable!()`.
+"""
+function hip_meanshift(bd::BallTreeDensity, starts::Union{Nothing,AbstractMatrix{Float64}}=nothing; tol::Float64=1e-9,
+                       maxiter::Int=500, manifold=nothing, device::Int=0)
+  D = Ndim(bd)
+  starts === nothing || D == size(starts, 1) || error("bd and starts must have the same dimension")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  K = starts === nothing ? Npts(bd) : size(starts, 2)
+  x = zeros(D, K)
+  logp = zeros(K)
+  iters = zeros(Int32, K)
+  cd = Ref(CDensity(bd))
+  sd = starts === nothing ? zeros(0, 0) : Matrix{Float64}(starts)
+  tolv = Float64[tol]
+  GC.@preserve bd sd tolv man begin
+    check(ccall((:kdehip_meanshift, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Cint, Ptr{UInt8}),
+                cd, starts === nothing ? Ptr{Float64}(C_NULL) : pointer(sd), K, tolv, maxiter, x, logp, iters, device, man))
+  end
+  return x, logp, iters
+end
+
+"""
+    hip_modes(bd, starts=nothing; tol=1e-9, maxiter=500, merge=1e-3, manifold=nothing, device=0)
+
+`(modes, logp, mass, labels)`: `hip_meanshift`, then the converged points merged greedily -- in descending `logp`, ties by
+index, a point joins the first kept mode within `merge` bandwidths (`max_k |diff_k| / sd_k`, wrapped where circular), else it
+founds a new one.  `mass` = the summed weights of the starts labelled to a mode when the starts are the density's own points
+(shares of the starts otherwise); an unconverged start is labelled 0 and belongs to no mode; labels are 1-based.
+"""
+function hip_modes(bd::BallTreeDensity, starts::Union{Nothing,AbstractMatrix{Float64}}=nothing; tol::Float64=1e-9,
+                   maxiter::Int=500, merge::Float64=1e-3, manifold=nothing, device::Int=0)
+  D = Ndim(bd)
+  own = starts === nothing
+  x, logp, iters = hip_meanshift(bd, starts; tol=tol, maxiter=maxiter, manifold=manifold, device=device)
+  circ = manifold === nothing ? falses(D) : (manifold_bytes(manifold, D) .== 0x01)
+  sd = getBW(bd)[:, 1]
+  K = size(x, 2)
+  labels = zeros(Int, K)
+  kept = Int[]
+  order = sort([q for q in 1:K if iters[q] >= 0]; by = q -> (-logp[q], q))
+  for q in order
+    home = 0
+    for (j, f) in enumerate(kept)
+      d = x[:, q] .- x[:, f]
+      for k in 1:D
+        circ[k] && (d[k] = d[k] - 2pi * floor((d[k] + pi) / 2pi))
+      end
+      if maximum(abs.(d) ./ sd) <= merge
+        home = j
+        break
+      end
+    end
+    if home == 0
+      push!(kept, q)
+      home = length(kept)
+    end
+    labels[q] = home
+  end
+  w = own ? getWeights(bd) : fill(1.0 / max(K, 1), K)
+  mass = Float64[sum(w[labels .== j]) for j in 1:length(kept)]
+  return x[:, kept], logp[kept], mass, labels
+end
+
+"""
+    hip_getKDEMode(bd; kwargs...)
+
+The joint mode of the density: the highest of `hip_modes(bd; kwargs...)`, a local maximum of the D-dimensional density
+itself.  `getKDEMax` is the grid argmax of every 1-D marginal on its own: for a multimodal density its coordinates may come
+from different modes.
+"""
+hip_getKDEMode(bd::BallTreeDensity; kwargs...) = hip_modes(bd; kwargs...)[1][:, 1]
+
+"""
     hip_getKDEMax(p; N=200, device=0)
 
 `getKDEMax(p; N)` (src/DualTree01.jl:558-570) on the GPU (`kdehip_kde_max`, include/kdehip.h section 5c): per dimension the

@@ -222,6 +222,10 @@ class DeviceDensity:
         else:
             h = _handle
         self._h = h
+        # An uploaded density's arrays stay the caller's (`download` serves built densities only): `modes` reads the bandwidth
+        # and the weights for its host-side merge from this object.  It is a reference, not a copy: a caller who changes the
+        # host density after the upload makes the merge disagree with what the device iterates on.
+        self._host = tree if _handle is None else None
         self.device = int(device)
         self.num_points = int(_lib.lib.kdehip_density_npts(h))
         self.dims = int(_lib.lib.kdehip_density_ndim(h))
@@ -327,6 +331,12 @@ class DeviceDensity:
 
     def __call__(self, pos=None, lvFlag=False, manifold=None):
         return self.evaluate(pos, lvFlag, manifold=manifold)
+
+    def evaluate_grad(self, pos, *, log=True, manifold=None):
+        """(log p, its gradient) -- or (p, its gradient) with log=False -- at the columns of `pos` (kdehip_evaluate_grad_device,
+        include/kdehip.h section 5h): `kdehip.evaluate_grad` of this density."""
+        from .modes import evaluate_grad
+        return evaluate_grad(self, pos, log=log, manifold=manifold)
 
     def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None, manifold=None):
         """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):

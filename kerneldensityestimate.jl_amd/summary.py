@@ -201,7 +201,10 @@ def getKDERangeLinspace(p, extend=0.1, N=200, *, manifold=None):
 def getKDEMax(p, N=200, *, values=False, device=0, manifold=None):
     """`getKDEMax(p; N)` (src/DualTree01.jl:558-570): per dimension, the grid point of the FIRST maximum of the 1-D marginal
     on the N-point grid over its range with extend 0.1.  values=True also returns the (D, N) grid values.
-    `manifold`: the circular range, wrapped differences on the grid, the argmax wrapped to [-pi, pi) (section 5e)."""
+    `manifold`: the circular range, wrapped differences on the grid, the argmax wrapped to [-pi, pi) (section 5e).
+    Every dimension is taken on its own, as the reference does: for a multimodal density the coordinates may come from
+    different modes, so the point need not lie near any of them.  `getKDEMode` is the joint mode -- a local maximum of the
+    D-dimensional density itself, by mean shift (section 5h)."""
     N = int(N)
     man = _manifold(p, manifold)
     if _is_device(p):
