@@ -1053,6 +1053,87 @@ typedef struct kdehip_meanshift_item {
  * those of kdehip_meanshift_device with maxiter == niter. */
 int kdehip_meanshift_device_batch(int n, const kdehip_meanshift_item *items, const double *tol, int niter, void *stream);
 
+/* ---- (5i) conditioning a density on some of its dimensions: weights, moments and draws ------------------------------------
+ * What does a joint belief say about these coordinates, given those?  `marginal` (5c) drops dimensions; the entries below
+ * fix them (csrc/conditional.hip; this library's own, the reference has no counterpart).  For a density bd of dimension D
+ * with leaves i in LEAF ORDER, centres c_i, weights w_i and ONE bandwidth vector v (the rule of section 5):
+ *   given_mask  bit d set = dimension d is given.  G = the given dimensions, ascending, ng = |G|; F = the others, ascending,
+ *               nf = D - ng.  Required: 1 <= ng <= D - 1 and no bit at or above D, otherwise KDEHIP_ERR_ARG -- in particular
+ *               a 1-D density can never be conditioned.
+ *   a query     y[q]: ng values in the order of G.  `manifold` as in 5d (NULL = Euclidean).
+ * Per query:
+ *   d_ik    = y_k - c_ik (k in G), through wrap() first in a circular dimension
+ *   a_i     = sum_{k in G, ascending} d_ik^2 * (-0.5 / v_k): the expression and fma order of the direct kernel
+ *   S       = { i : w_i > 0 },  m = max_{i in S} a_i,  t_i = w_i exp(a_i - m),  S_0 = sum_{i in S} t_i
+ *   logz    = m + log S_0 - log((2 pi)^(ng/2) prod_{k in G} sqrt(v_k))     (= the log of the G-marginal at y)
+ *   omega_i = t_i / S_0                                                    (0 outside S)
+ *   mean_k  = sum_{i in S} omega_i c_ik                                    (k in F)
+ *   var_k   = v_k + sum_{i in S} omega_i (c_ik - mean_k)^2                 (k in F; the diagonal only; never below v_k)
+ * Moments: the first and second moments of c_ik - r_k about ONE fixed reference point r inside the data's hull (the root
+ * node's mean) are accumulated in one pass beside S_0; mean_k = r_k + S1_k / S_0 and the excess S2_k / S_0 - (S1_k / S_0)^2
+ * is clamped at 0.  Consequence: var_k is accurate to an absolute error proportional to R_k^2, R_k the data's range in
+ * dimension k -- a conditional far narrower than the data loses relative digits.  When mean or var is asked for while a FREE
+ * dimension is circular the call returns KDEHIP_ERR_UNSUPPORTED; circular GIVEN dimensions are fully supported (wrapped
+ * differences).
+ * The draw (ONE per query): the global index is g = sample_offset + q and the random numbers are those kdehip_sample (2f)
+ * uses for index g of an nf-dimensional density, u = kdehip_philox_fill_uniform(seed, g, 1, K = 1) and
+ * n[j] = kdehip_philox_fill_normal(seed, g, 1, R = nf)[j].  With C_i = sum_{j <= i, j in S} t_j in leaf order the label is
+ * the first i in S with C_i > u * S_0; if rounding leaves none, the last leaf of S.  ind[q] = the 1-based ORIGINAL index of
+ * that leaf (through the permutation); pts[q][j] = c_{i,F_j} + sqrt(v_{F_j}) * n[j], the multiply and the add rounded
+ * separately as in 2f, wrapped to [-pi, pi) where F_j is circular.
+ * The C_i are defined in exact arithmetic.  The implementation forms them in the group split of 5b / 5f / 5h, so a u * S_0
+ * within a relative 1e-9 of some C_i may resolve to the neighbouring leaf of S.  Everything else about the label is exact,
+ * and host, resident and batched calls return the same bits run after run.
+ * S empty: logz = -Inf, mean and var are NaN, ind = 0 and the point is NaN.  No entry reads out of bounds.
+ * The sum is split as in 5b / 5f / 5h (128-leaf chunks in groups that depend on (npts, Nq) alone, combined in group order);
+ * no atomics; a full call evaluates at most two exp per (query, leaf) pair: one sweep for (m, S_0, moments), one -- only
+ * in the (256-query block, group) pairs some query's draw fell into -- for the label.
+ * Errors, all checked before any device is touched: null arguments (all outputs NULL included; pts and ind are given
+ * together or not at all), Nq < 0, a bad given_mask, a manifold byte above 1 or a circular_mask bit at or above D,
+ * densities on different devices within a batch -- KDEHIP_ERR_ARG; D outside 1..KDEHIP_MAX_DIMS, per-point bandwidths, or
+ * moments over a circular free dimension -- KDEHIP_ERR_UNSUPPORTED.  Nq == 0 and n == 0 are KDEHIP_OK.  fp64 only.
+ * Not here: the full conditional covariance, moments on circular free dimensions, more than one draw per query (use
+ * kdehip_density_condition_device / `condition`, then sample), per-point bandwidths, kernels other than the Gaussian. */
+/* Host density, host arrays, blocking.  given [Nq][ng]; logz [Nq], mean / var [Nq][nf], pts [Nq][nf] with ind [Nq]: any may
+ * be NULL (not all; pts and ind together). */
+int kdehip_conditional(const kdehip_density *bd, uint32_t given_mask, const double *given, int64_t Nq, uint64_t seed,
+                       int64_t sample_offset, double *logz, double *mean, double *var, double *pts, int64_t *ind, int device,
+                       const uint8_t *manifold);
+/* Resident density, device arrays, enqueue only on `stream` (hipStream_t, NULL = the null stream). */
+int kdehip_conditional_device(const kdehip_device_density *bd, uint32_t given_mask, const double *d_given, int64_t Nq,
+                              uint64_t seed, int64_t sample_offset, double *d_logz, double *d_mean, double *d_var,
+                              double *d_pts, int64_t *d_ind, const uint8_t *manifold, void *stream);
+typedef struct kdehip_conditional_item {
+  const kdehip_device_density *bd;
+  const double *d_given;    /* device, [Nq][ng] */
+  int64_t Nq;
+  uint64_t seed;
+  int64_t sample_offset;
+  double *d_logz;           /* device, [Nq], or NULL */
+  double *d_mean;           /* device, [Nq][nf], or NULL */
+  double *d_var;            /* device, [Nq][nf], or NULL */
+  double *d_pts;            /* device, [Nq][nf], or NULL (then d_ind is NULL too) */
+  int64_t *d_ind;           /* device, [Nq] */
+  uint32_t given_mask;      /* bit d = dimension d is given */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+} kdehip_conditional_item;
+/* Many resident items (mixed D, N, Nq and masks) on one device, enqueue only on `stream`.  Launches per pass are one per
+ * distinct (D, circular) for all items together.  Every item's results are bit for bit those of kdehip_conditional_device. */
+int kdehip_conditional_device_batch(int n, const kdehip_conditional_item *items, void *stream);
+/* The weights themselves: w_out[q][o] = omega of ORIGINAL point o, o = 0..npts-1 (what kde(points[F], ks[F], w) takes);
+ * logz [Nq] or NULL.  Host density, blocking. */
+int kdehip_condition_weights(const kdehip_density *bd, uint32_t given_mask, const double *given, int64_t Nq, double *w_out,
+                             double *logz, int device, const uint8_t *manifold);
+/* Resident density, device arrays, enqueue only on `stream`. */
+int kdehip_condition_weights_device(const kdehip_device_density *bd, uint32_t given_mask, const double *d_given, int64_t Nq,
+                                    double *d_w_out, double *d_logz, const uint8_t *manifold, void *stream);
+/* p(x_F | x_G = y) as a resident density, by the route of kdehip_density_marginal_device (5c): F and the weights omega
+ * gathered on the device, one copy down, the host builder with ks = the bandwidth of ORIGINAL point 0 in F (marginal's rule)
+ * and those weights, the block back up.  Blocking, on the calling thread's stream.  y: a HOST array of ng doubles;
+ * tree_manifold: nf bytes (the operators of the result's tree, 5e) or NULL.  logz = -Inf (no leaf in S) is KDEHIP_ERR_ARG. */
+int kdehip_density_condition_device(kdehip_device_density **out, const kdehip_device_density *p, uint32_t given_mask,
+                                    const double *y, const uint8_t *manifold, const uint8_t *tree_manifold);
+
 #ifdef __cplusplus
 }
 #endif

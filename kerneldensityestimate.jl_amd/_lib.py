@@ -77,6 +77,13 @@ class CMeanshiftItem(C.Structure):
                 ("d_iters", C.c_void_p), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class CConditionalItem(C.Structure):
+    """struct kdehip_conditional_item"""
+    _fields_ = [("bd", C.c_void_p), ("d_given", C.c_void_p), ("Nq", C.c_int64), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
+                ("d_logz", C.c_void_p), ("d_mean", C.c_void_p), ("d_var", C.c_void_p), ("d_pts", C.c_void_p), ("d_ind", C.c_void_p),
+                ("given_mask", C.c_uint32), ("circular_mask", C.c_uint32)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -183,6 +190,15 @@ SIGNATURES = {
     "kdehip_meanshift": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, C.c_int, u8p]),
     "kdehip_meanshift_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, u8p]),
     "kdehip_meanshift_device_batch": (C.c_int, [C.c_int, C.POINTER(CMeanshiftItem), f64p, C.c_int, C.c_void_p]),
+    "kdehip_conditional": (C.c_int, [C.POINTER(CDensity), C.c_uint32, f64p, C.c_int64, C.c_uint64, C.c_int64, f64p, f64p, f64p,
+                                     f64p, i64p, C.c_int, u8p]),
+    "kdehip_conditional_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u8p, C.c_void_p]),
+    "kdehip_conditional_device_batch": (C.c_int, [C.c_int, C.POINTER(CConditionalItem), C.c_void_p]),
+    "kdehip_condition_weights": (C.c_int, [C.POINTER(CDensity), C.c_uint32, f64p, C.c_int64, f64p, f64p, C.c_int, u8p]),
+    "kdehip_condition_weights_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, u8p,
+                                                  C.c_void_p]),
+    "kdehip_density_condition_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, f64p, u8p, u8p]),
     "kdehip_auto_bandwidth_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, u8p]),
     "kdehip_make_density_auto_manifold": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i64p,
                                                     i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),

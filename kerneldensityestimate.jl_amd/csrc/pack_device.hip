@@ -554,35 +554,16 @@ extern "C" int kdehip_density_from_device_points_tree(kdehip_device_density **ou
   return KDEHIP_OK;
 }
 
-// marginal(p, dims) (src/KDE01.jl:143-153) of a resident density = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims],
-// getWeights(p)): the gather kernel above, ONE copy down, the host builder with explicit ks and weights (the path of
-// kdehip_density_from_device_points without the bandwidth search), the block back up.  The sqrt of getBW is the host's.
-extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
-                                              const int32_t *dims) {
-  return kdehip_density_marginal_device_tree(out, p, nsel, dims, nullptr);
-}
-
-// ... with the operators of tree_manifold (the nsel selected dimensions') in the builder (section 5e)
-extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
-                                                   const int32_t *dims, const uint8_t *tree_manifold) {
-  if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
-  *out = nullptr;
-  if (nsel < 1 || nsel > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_ARG, "marginal: nsel outside 1..KDEHIP_MAX_DIMS");
-  const int trc = manifold_arg_or_null(tree_manifold, nsel, nullptr, kTreeManifold);
-  if (trc != KDEHIP_OK) return trc;
-  if (!dims) return set_error(KDEHIP_ERR_ARG, "marginal: null dims");
-  if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
+// The density over the dimensions md of a resident p, built by the host builder from ONE copy down: the points gathered in
+// original order, ks = the bandwidth of original point 0 in those dimensions, and the weights of p -- or, with `on`, the
+// conditional weights omega of kdehip_condition_weights_device for the query on->y (then no leaf in S is KDEHIP_ERR_ARG).
+struct ConditionOn { uint32_t given_mask; const double *y; const uint8_t *manifold; };
+static int subdensity_device(kdehip_device_density **out, const kdehip_device_density *p, int nsel, const MarginalDims &md,
+                             const uint8_t *tree_manifold, const ConditionOn *on) {
   const int64_t N = p->N;
   const int D = p->D;
-  int rc = check_shape(N, D);
-  if (rc != KDEHIP_OK) return rc;
-  MarginalDims md{};
-  for (int s = 0; s < nsel; ++s) {
-    if (dims[s] < 1 || dims[s] > D) return set_error(KDEHIP_ERR_ARG, "marginal: dims outside 1..ndims");
-    md.d[s] = dims[s] - 1;
-  }
   DeviceGuard guard;
-  rc = guard.enter(p->device);
+  int rc = guard.enter(p->device);
   if (rc != KDEHIP_OK) return rc;
   hipStream_t cs = hipStreamPerThread;
   struct Cleanup {  // (the handle, until it is the caller's)
@@ -593,7 +574,9 @@ extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, 
       delete h;
     }
   } cl;
-  const size_t bytes = sizeof(double) * (N * nsel + N + D);
+  // [points (N nsel) | weights (N) | the bandwidth of original point 0 (D) | logz (1) | y (D - nsel)]: the last two with `on`
+  const size_t o_logz = static_cast<size_t>(N) * nsel + N + D, o_y = o_logz + 1;
+  const size_t bytes = sizeof(double) * (on ? o_y + (D - nsel) : o_logz);
   CallBlock gathered;
   KDEHIP_CHECK(gathered.alloc(bytes, bytes));
   gathered.touch(cs);
@@ -601,8 +584,17 @@ extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, 
   hipLaunchKernelGGL(gather_marginal_kernel, dim3(static_cast<unsigned>((N * nsel + 255) / 256)), dim3(256), 0, cs, p->means,
                      p->bandwidth, p->weights, p->perm, N, D, nsel, md, d_blk);
   KDEHIP_CHECK(hipGetLastError());
+  if (on) {  // (after the gather on the same stream: omega replaces the weights it wrote)
+    std::memcpy(blk + o_y, on->y, sizeof(double) * (D - nsel));
+    KDEHIP_CHECK(hipMemcpyAsync(d_blk + o_y, blk + o_y, sizeof(double) * (D - nsel), hipMemcpyHostToDevice, cs));
+    rc = kdehip_condition_weights_device(p, on->given_mask, d_blk + o_y, 1, d_blk + static_cast<size_t>(N) * nsel, d_blk + o_logz,
+                                         on->manifold, cs);
+    if (rc != KDEHIP_OK) return rc;
+  }
   KDEHIP_CHECK(gathered.download(0, bytes, cs));
   KDEHIP_CHECK(gathered.wait());
+  if (on && !(blk[o_logz] > -INFINITY))
+    return set_error(KDEHIP_ERR_ARG, "condition: no point of the density has a positive weight at y (logz = -Inf)");
   double ks[KDEHIP_MAX_DIMS];
   for (int s = 0; s < nsel; ++s) ks[s] = std::sqrt(blk[N * nsel + N + md.d[s]]);  // getBW(p, [1])[dims]
   kdehip_device_density *h = new (std::nothrow) kdehip_device_density();
@@ -622,6 +614,59 @@ extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, 
   cl.h = nullptr;
   *out = h;
   return KDEHIP_OK;
+}
+
+// marginal(p, dims) (src/KDE01.jl:143-153) of a resident density = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims],
+// getWeights(p)): the gather kernel above, ONE copy down, the host builder with explicit ks and weights (the path of
+// kdehip_density_from_device_points without the bandwidth search), the block back up.  The sqrt of getBW is the host's.
+extern "C" int kdehip_density_marginal_device(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
+                                              const int32_t *dims) {
+  return kdehip_density_marginal_device_tree(out, p, nsel, dims, nullptr);
+}
+
+// ... with the operators of tree_manifold (the nsel selected dimensions') in the builder (section 5e)
+extern "C" int kdehip_density_marginal_device_tree(kdehip_device_density **out, const kdehip_device_density *p, int nsel,
+                                                   const int32_t *dims, const uint8_t *tree_manifold) {
+  if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
+  *out = nullptr;
+  if (nsel < 1 || nsel > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_ARG, "marginal: nsel outside 1..KDEHIP_MAX_DIMS");
+  const int trc = manifold_arg_or_null(tree_manifold, nsel, nullptr, kTreeManifold);
+  if (trc != KDEHIP_OK) return trc;
+  if (!dims) return set_error(KDEHIP_ERR_ARG, "marginal: null dims");
+  if (!p) return set_error(KDEHIP_ERR_ARG, "null density");
+  const int rc = check_shape(p->N, p->D);
+  if (rc != KDEHIP_OK) return rc;
+  MarginalDims md{};
+  for (int s = 0; s < nsel; ++s) {
+    if (dims[s] < 1 || dims[s] > p->D) return set_error(KDEHIP_ERR_ARG, "marginal: dims outside 1..ndims");
+    md.d[s] = dims[s] - 1;
+  }
+  return subdensity_device(out, p, nsel, md, tree_manifold, nullptr);
+}
+
+// p(x_F | x_G = y) of a resident density (include/kdehip.h section 5i): the marginal over F with the weights omega
+extern "C" int kdehip_density_condition_device(kdehip_device_density **out, const kdehip_device_density *p, uint32_t given_mask,
+                                               const double *y, const uint8_t *manifold, const uint8_t *tree_manifold) {
+  if (!out) return set_error(KDEHIP_ERR_ARG, "null out pointer");
+  *out = nullptr;
+  if (!p || !y) return set_error(KDEHIP_ERR_ARG, "null argument");
+  const int rc = check_shape(p->N, p->D);
+  if (rc != KDEHIP_OK) return rc;
+  const int D = p->D;
+  if (D < 2 || (given_mask >> D) || given_mask == 0u || given_mask == (1u << D) - 1u)
+    return set_error(KDEHIP_ERR_ARG, "condition: between 1 and ndims - 1 of the density's dimensions can be given");
+  const int mrc = manifold_arg(manifold, D, nullptr);
+  if (mrc != KDEHIP_OK) return mrc;
+  MarginalDims md{};
+  int nf = 0;
+  for (int k = 0; k < D; ++k)
+    if (!((given_mask >> k) & 1u)) md.d[nf++] = k;
+  const int trc = manifold_arg_or_null(tree_manifold, nf, nullptr, kTreeManifold);
+  if (trc != KDEHIP_OK) return trc;
+  if (!leaves_share_bandwidth(p))
+    return set_error(KDEHIP_ERR_UNSUPPORTED, "per-point bandwidths are not supported (the reference's kde! never builds them)");
+  const ConditionOn on{given_mask, y, manifold};
+  return subdensity_device(out, p, nf, md, tree_manifold, &on);
 }
 
 // `*(trees; addEntropy)` (src/MSGibbs01.jl:707-726) on handles: Np = round(mean Npts), Niter = 5, then kde!(pGM) -- and

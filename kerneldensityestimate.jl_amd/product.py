@@ -373,6 +373,27 @@ class DeviceDensity:
         from .summary import _marginal_device
         return _marginal_device(self, dims, manifold, tree_manifold)
 
+    def condition(self, dims, values, *, manifold=None, tree_manifold=None) -> "DeviceDensity":
+        """p(x_F | x_dims = values) as a density over the other dimensions, built on this density's device
+        (kdehip_density_condition_device, include/kdehip.h section 5i): the same arrays as the host `condition`."""
+        from .conditional import condition
+        return condition(self, dims, values, manifold=manifold, tree_manifold=tree_manifold)
+
+    def conditional_weights(self, dims, Y, *, manifold=None):
+        """`kdehip.conditional_weights` of this density (kdehip_condition_weights_device)."""
+        from .conditional import conditional_weights
+        return conditional_weights(self, dims, Y, manifold=manifold)
+
+    def conditional_moments(self, dims, Y, *, manifold=None):
+        """`kdehip.conditional_moments` of this density (kdehip_conditional_device)."""
+        from .conditional import conditional_moments
+        return conditional_moments(self, dims, Y, manifold=manifold)
+
+    def sample_conditional(self, dims, Y, seed=0, sample_offset=0, *, manifold=None):
+        """`kdehip.sample_conditional` of this density (kdehip_conditional_device)."""
+        from .conditional import sample_conditional
+        return sample_conditional(self, dims, Y, seed, sample_offset, manifold=manifold)
+
     def getKDEMax(self, N=200, *, values=False, manifold=None):
         """`getKDEMax(p; N)` (reference src/DualTree01.jl:558-570) on the device (kdehip_density_summary[_manifold])."""
         from .summary import getKDEMax
