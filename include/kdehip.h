@@ -533,6 +533,26 @@ int kdehip_profile_phase_read(int which, double *total_ms, int64_t *count);
  * hardware's result for it.  tests/test_gpu_ulp.py sweeps the screen's whole input ranges with it.  Blocking. */
 int kdehip_selftest_fp32(int which, uint32_t first_bits, uint64_t count, int device, double *max_err,
                          uint32_t *worst_bits, uint32_t *worst_result_bits);
+/* The fp64 exponentials every density kernel calls once per pair (csrc/fastexp.hpp), MEASURED on `device` against a
+ * double-double reference (csrc/expdd.hpp, relative error <= 2^-80).  which = 0: exp_nonpos (32-entry table), 1:
+ * exp256_nonpos (256-entry table); each is evaluated through its _begin / _end halves and through the one-call form, with
+ * the table staged in LDS as the kernels stage it, and *form_mismatches (optional) counts the inputs at which the two forms
+ * differ in any bit.  The inputs are generated on the device: input i (first <= i < first + count) of `family` is
+ *   0 dense       upper word 0xBE100000 + i / 16 (-2^-30 .. -708), lower word 0, 0xFFFFFFFF or mix(i) (i % 16 = 0, 1, else)
+ *   1 half-way    the double nearest -(n + 1/2) c, c = ln2/32 (which 0) or ln2/256 (which 1), n = i / 129, moved by
+ *                 i % 129 - 64 places in the order of the doubles: where the reduction's rounding flips
+ *   2 whole       the same about -(n + 1) c, n = i / 129: where the reduced argument cancels
+ *   3 range       2^26 + 1 arguments spread over [-745.2, -708.3] (results below the smallest normal number)
+ *   4 range       2^24 + 1 arguments spread over [-1000.0 (which 1) or -800.0 (which 0), -745.2] (results that round to 0)
+ *   5 near zero   biased exponent 993 - i / 8 (2^-30 down to the subnormals), 8 mantissas each, negative
+ *   6 raw         the bit pattern `first + i` itself (single inputs, neighbourhoods, non-finite values)
+ * (the exact maps are kdehip::exp64_input, csrc/selftest.hip, repeated in tests/test_gpu_exp64.py).  One error unit for
+ * all: |got - ref| / ulp(ref), ulp(ref) = 2^(e-52) for 2^e <= ref < 2^(e+1), floored at 2^-1074 (below the normal range it
+ * counts spacings of the subnormal grid); an argument below -770 has ref = 0; a NaN on either side counts as 2^60.
+ * Returns the largest error, the 64 bits of its input and of the device's result (the lowest such i on a tie).  count <=
+ * 2^40.  Blocking. */
+int kdehip_selftest_exp64(int which, int family, uint64_t first, uint64_t count, int device, double *max_err,
+                          uint64_t *worst_bits, uint64_t *worst_result_bits, uint64_t *form_mismatches);
 
 /* ---- (3) host twin of the device RNG ----------------------------------------------------------
  * Fills the arrays a caller would pass as randU / randN so that a streams-run (or the Julia
@@ -1130,9 +1150,22 @@ int kdehip_condition_weights_device(const kdehip_device_density *bd, uint32_t gi
 /* p(x_F | x_G = y) as a resident density, by the route of kdehip_density_marginal_device (5c): F and the weights omega
  * gathered on the device, one copy down, the host builder with ks = the bandwidth of ORIGINAL point 0 in F (marginal's rule)
  * and those weights, the block back up.  Blocking, on the calling thread's stream.  y: a HOST array of ng doubles;
- * tree_manifold: nf bytes (the operators of the result's tree, 5e) or NULL.  logz = -Inf (no leaf in S) is KDEHIP_ERR_ARG. */
+ * tree_manifold: nf bytes (the operators of the result's tree, 5e) or NULL.  logz = -Inf (no leaf in S) or NaN (a NaN in y) is
+ * KDEHIP_ERR_ARG. */
 int kdehip_density_condition_device(kdehip_device_density **out, const kdehip_device_density *p, uint32_t given_mask,
                                     const double *y, const uint8_t *manifold, const uint8_t *tree_manifold);
+
+/* ---- (5j) non-finite positions from the caller ----------------------------------------------------------------------------
+ * For the entries that take an array of positions -- kdehip_evaluate[_manifold] and kdehip_evaluate_log with pos,
+ * kdehip_evaluate_grad, kdehip_meanshift with start, kdehip_conditional, kdehip_condition_weights,
+ * kdehip_density_condition_device, and the resident and batched forms of each:
+ *   a NaN in any coordinate of a query (for the conditionals: in any given value) makes every floating-point output of THAT
+ *   query NaN -- p, log p, every gradient component, logz, mean, var, the whole row of w_out, the drawn point -- with ind = 0;
+ *   a mean-shift start with a NaN is returned as given with iters = 0 and logp = NaN, and never counts as live;
+ *   kdehip_density_condition_device fails with KDEHIP_ERR_ARG.  No other query's outputs change by a bit.
+ *   +-Inf in a coordinate is infinitely far from every leaf: p = 0, log p = logz = -Inf, and everything else as for "S empty"
+ *   in 5h / 5i (gradient 0, the start returned with iters = 0, mean / var / the point NaN, ind = 0, the row of w_out all 0).
+ * NaN or Inf INSIDE a density (points, weights, bandwidths) is outside this contract. */
 
 #ifdef __cplusplus
 }

@@ -219,6 +219,7 @@ SIGNATURES = {
     "kdehip_profile_phase_read": (C.c_int, [C.c_int, f64p, i64p]),
     "kdehip_selftest_fp32": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_int, f64p, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32)]),
+    "kdehip_selftest_exp64": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, f64p] + [C.POINTER(C.c_uint64)] * 3),
     "kdehip_profile_sampler_read": (C.c_int, [C.c_int, C.c_void_p, f64p, i64p]),
     "kdehip_product_multi_timing": (C.c_int, [C.c_void_p, f64p, f64p]),
     "kdehip_density_from_device_points": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int64, C.c_int,

@@ -162,7 +162,7 @@ def condition(p, dims, values, *, device=0, manifold=None, tree_manifold=None):
         return type(p)._built(h, p.device, manifold=_mf.select(man, free), tree_manifold=tman)
     W, logz = conditional_weights(p, dl, np.asarray(values, dtype=np.float64).reshape(-1, 1), device=device, manifold=man)
     if not logz[0] > -np.inf:
-        raise _lib.KdeHipError(_lib.ERR_ARG, "condition: no point of the density has a positive weight at y (logz = -Inf)")
+        raise _lib.KdeHipError(_lib.ERR_ARG, "condition: no point of the density has a positive weight at y (logz = -Inf), or y holds a NaN")
     return kde(_leaf_points(p)[free, :], getBW(p)[free, 0], W[0], tree_manifold=tman)
 
 

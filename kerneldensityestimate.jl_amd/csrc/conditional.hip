@@ -161,7 +161,8 @@ __global__ __launch_bounds__(kEvalThreads) void cond_partial_kernel(const CondIt
 
 // Items [0, n), item i owns blocks [first[i], first[i+1]).  The groups in group order: M = max m_g, S_j = sum_g s_jg
 // exp(m_g - M); logz = M + log S_0 - log norm_G; mean_k = r_k - S1_k / S_0, var_k = v_k + max(0, S2_k / S_0 - (S1_k / S_0)^2)
-// (k in F).  No leaf in S: logz = -Inf, mean and var NaN, the draw's point NaN and ind = 0.  The draw: T = u S_0, the first
+// (k in F).  No leaf in S: logz = -Inf, mean and var NaN, the draw's point NaN and ind = 0.  A NaN among the given values:
+// logz NaN as well, the rest likewise, and no group marked as chosen.  The draw: T = u S_0, the first
 // group whose running total (the very additions that formed S_0) exceeds T, the residual T - (the total before it) divided
 // by exp(m_g - M); none: the last group with s_0g > 0 and an infinite residual.
 __global__ __launch_bounds__(kFinishThreads) void cond_finish_kernel(const CondItem *__restrict__ items,
@@ -181,6 +182,8 @@ __global__ __launch_bounds__(kFinishThreads) void cond_finish_kernel(const CondI
     const double *pm = it.partial + q;
     double M = -INFINITY;
     for (int g = 0; g < it.ngroups; ++g) M = fmax(M, pm[static_cast<int64_t>(g) * it.Nq]);
+    bool bad = false;  // a NaN among the given values (the sweep drops it: pair_sweep.hpp): every output of the query is NaN
+    for (int k = 0; k < D; ++k) bad = bad || (is_given(it, k) && it.xq[q * D + k] != it.xq[q * D + k]);
     const bool some = M > -INFINITY;
     const int nsum = it.mom ? 1 + 2 * D : 1;
     double S[2 * KDEHIP_MAX_DIMS + 1];
@@ -198,14 +201,14 @@ __global__ __launch_bounds__(kFinishThreads) void cond_finish_kernel(const CondI
     it.ms[it.Nq + q] = S[0];
     if (it.logz) {
       const double norm = gauss_norm(it.norm0, D, [&](int k) { return is_given(it, k) ? it.bw[k] : 1.0; });
-      it.logz[q] = some ? M + log(S[0]) - log(norm) : -INFINITY;
+      it.logz[q] = bad ? __builtin_nan("") : some ? M + log(S[0]) - log(norm) : -INFINITY;
     }
     if (it.mom) {
       int j = 0;
       for (int k = 0; k < D; ++k) {
         if (is_given(it, k)) continue;
         double mu = __builtin_nan(""), va = __builtin_nan("");
-        if (some) {
+        if (some && !bad) {
           const double a1 = S[1 + k] / S[0], a2 = S[1 + D + k] / S[0];
           mu = it.ref[k] - a1;
           va = it.bw[k] + fmax(a2 - a1 * a1, 0.0);
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(kFinishThreads) void cond_finish_kernel(const CondI
     if (draw) {
       int cg = -1;
       double res = INFINITY;
-      if (some) {
+      if (some && !bad) {  // (a NaN query chooses no group)
         const double T = philox_uniform(it.seed, static_cast<uint64_t>(it.offset + q), 1u) * S[0];
         double run = 0.0;
         int last = -1;
@@ -318,7 +321,8 @@ __global__ __launch_bounds__(kEvalThreads) void cond_select_kernel(const CondIte
 }
 
 // ONE item; thread t is (query t / N, leaf t % N): omega = w_i exp_nonpos(a_i - M) / S_0 -- a_i by the sweep's expression
-// over the given dimensions (the free ones add +0 there) -- to w_out[q][original index of the leaf]; a leaf outside S: 0.
+// over the given dimensions (the free ones add +0 there) -- to w_out[q][original index of the leaf]; a leaf outside S: 0;
+// a query whose S_0 is 0 (an infinite given value): 0; a query with a NaN among its given values: NaN.
 __global__ __launch_bounds__(256) void cond_weights_kernel(const CondItem *__restrict__ items, uint32_t circ) {
   __shared__ double sExpTab[32];
   if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
@@ -330,8 +334,10 @@ __global__ __launch_bounds__(256) void cond_weights_kernel(const CondItem *__res
   const int64_t o = it.perm[i] - 1;
   if (o < 0 || o >= it.N) return;  // (an uploaded density's permutation is the caller's)
   const double w = it.w[i];
-  double om = 0.0;
-  if (w > 0.0) {
+  bool bad = false;  // a NaN among the given values: the whole row is NaN
+  for (int k = 0; k < it.D; ++k) bad = bad || (is_given(it, k) && it.xq[q * it.D + k] != it.xq[q * it.D + k]);
+  double om = bad ? __builtin_nan("") : 0.0;
+  if (!bad && w > 0.0 && it.ms[it.Nq + q] > 0.0) {  // (S_0 == 0: no leaf of S in reach of an infinite value -- the row is 0)
     double acc = 0.0;
     for (int k = 0; k < it.D; ++k) {
       if (!is_given(it, k)) continue;

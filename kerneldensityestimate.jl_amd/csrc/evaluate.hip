@@ -14,7 +14,7 @@
 //   eval_finish_kernel      the groups summed in a fixed order (deterministic, no atomics), / norm, / (1 - w) for
 //                           leave-one-out, the value stored (through the item's permutation, if any) when asked for, then
 //                           W_q log p_q and the block's share in a fixed LDS tree; a weighted zero raises the block's flag
-//                           instead of adding -Inf;
+//                           instead of adding -Inf; a query with a NaN coordinate gets NaN;
 //   logl_reduce_kernel      only when an item asks for a log-likelihood: per item, the block shares summed in block order
 //                           (or -Inf if a flag is up) into one double.
 // Log-domain items (kdehip.h section 5f: log p by log-sum-exp, finite where p underflows) run eval_partial_log_kernel<D> and
@@ -181,6 +181,7 @@ __global__ __launch_bounds__(kFinishThreads) void eval_finish_kernel(const EvalI
     for (int c = 0; c < it.ngroups; ++c) s += it.partial[static_cast<int64_t>(c) * it.Nq + q];
     p = s * inv_norm;
     if (it.loo) p = p / (1.0 - it.w[q]);
+    if (query_has_nan(it.qry, q, it.D)) p = __builtin_nan("");  // (the sweep drops a NaN: pair_sweep.hpp)
     if (it.qw) {  // evalAvgLogL (:456-466): L == 0 counts as 1 when its weight is 0, and makes the result -Inf otherwise
       const double W = it.qw[q];
       double L = p;
@@ -217,6 +218,7 @@ __global__ __launch_bounds__(kFinishThreads) void eval_finish_log_kernel(const E
       lp = M + log(S) - lognorm;
       if (it.loo) lp -= log(1.0 - it.w[q]);
     }
+    if (query_has_nan(it.qry, q, it.D)) lp = __builtin_nan("");  // (the sweep drops a NaN: pair_sweep.hpp)
     if (it.qw) {
       const double W = it.qw[q];
       if (W != 0.0) {

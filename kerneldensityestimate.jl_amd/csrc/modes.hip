@@ -73,8 +73,10 @@ __global__ __launch_bounds__(kFinishThreads) void moments_init_kernel(const Mome
   const ItemBlock ib = item_block(first, n);
   const MomentItem it = items[ib.item];
   const int64_t q = static_cast<int64_t>(ib.k) * kFinishThreads + threadIdx.x;
+  bool bad = false;  // a start with a NaN coordinate is frozen from the outset: it never counts as live
   if (q < it.Nq) {
     if (it.start) {
+      bad = query_has_nan(it.start, q, it.D);
       if (it.start != it.x)
         for (int k = 0; k < it.D; ++k) it.x[q * it.D + k] = it.start[q * it.D + k];
     } else {  // (Nq == N) leaf q is original point perm[q]
@@ -83,12 +85,10 @@ __global__ __launch_bounds__(kFinishThreads) void moments_init_kernel(const Mome
         for (int k = 0; k < it.D; ++k) it.x[o * it.D + k] = it.src[q * it.D + k];
     }
     it.iters[q] = 0;
-    it.frozen[q] = 0;
+    it.frozen[q] = bad ? 1 : 0;
   }
-  if (threadIdx.x == 0) {
-    const int64_t left = it.Nq - static_cast<int64_t>(ib.k) * kFinishThreads;
-    it.live[ib.k] = static_cast<int32_t>(left < kFinishThreads ? left : kFinishThreads);
-  }
+  const int cnt = __syncthreads_count(q < it.Nq && !bad);
+  if (threadIdx.x == 0) it.live[ib.k] = cnt;
 }
 
 // partial[0][g][q] = m, partial[1][g][q] = s_0, partial[2 + k][g][q] = s_{k+1} over the source chunks of group g in chunk
@@ -150,10 +150,11 @@ __global__ __launch_bounds__(kEvalThreads) void moments_partial_kernel(const Mom
 // Items [0, n) of one mode, item i owns blocks [first[i], first[i+1]).  The groups in group order: M = max m_g,
 // S_j = sum_g s_jg exp(m_g - M); then
 //   evaluate: val = log p = M + log S_0 - log norm (or p = exp(M) S_0 / norm), grad_k = -S_k / (S_0 v_k) (times p); no
-//             source in S: -Inf (0) and 0
+//             source in S: -Inf (0) and 0; a query with a NaN coordinate: NaN, all of them
 //   step:     val = log p HERE, then x_k <- x_k - S_k / S_0 (wrapped in a circular dimension), one more step counted, and the
 //             query frozen once max_k |S_k / S_0| / sqrt(v_k) <= tol; no source in S: frozen where it is.  A frozen query
-//             is not touched.  live[block] = the block's queries that still move.
+//             is not touched, and a start with a NaN coordinate is frozen by moments_init_kernel: it stays where it is with
+//             0 steps, and the closing evaluation gives it log p = NaN.  live[block] = the block's queries that still move.
 __global__ __launch_bounds__(kFinishThreads) void moments_finish_kernel(const MomentItem *__restrict__ items,
                                                                       const int32_t *__restrict__ first, int n,
                                                                       const uint32_t *__restrict__ masks) {
@@ -181,14 +182,18 @@ __global__ __launch_bounds__(kFinishThreads) void moments_finish_kernel(const Mo
       }
     }
     const double lp = (M > -INFINITY) ? M + log(S[0]) - log(moment_norm(it)) : -INFINITY;
+    const bool bad = query_has_nan(it.qry, q, D);  // (the sweep drops a NaN: pair_sweep.hpp)
     if (!step) {
       const double p = (M > -INFINITY) ? exp(M) * S[0] / moment_norm(it) : 0.0;
-      if (it.val) it.val[q] = it.logdom ? lp : p;
+      if (it.val) it.val[q] = bad ? __builtin_nan("") : it.logdom ? lp : p;
       if (it.grad)
         for (int k = 0; k < D; ++k) {
           const double g = (M > -INFINITY) ? -S[k + 1] / (S[0] * it.bw[k]) : 0.0;
-          it.grad[q * D + k] = it.logdom ? g : g * p;
+          it.grad[q * D + k] = bad ? __builtin_nan("") : it.logdom ? g : g * p;
         }
+    } else if (bad) {  // (a start is caught by moments_init_kernel; this is a query that has become NaN on its way)
+      it.val[q] = __builtin_nan("");
+      it.frozen[q] = 1;
     } else if (M > -INFINITY) {
       it.val[q] = lp;
       double reach = 0.0;

@@ -594,7 +594,7 @@ static int subdensity_device(kdehip_device_density **out, const kdehip_device_de
   KDEHIP_CHECK(gathered.download(0, bytes, cs));
   KDEHIP_CHECK(gathered.wait());
   if (on && !(blk[o_logz] > -INFINITY))
-    return set_error(KDEHIP_ERR_ARG, "condition: no point of the density has a positive weight at y (logz = -Inf)");
+    return set_error(KDEHIP_ERR_ARG, "condition: no point of the density has a positive weight at y (logz = -Inf), or y holds a NaN");
   double ks[KDEHIP_MAX_DIMS];
   for (int s = 0; s < nsel; ++s) ks[s] = std::sqrt(blk[N * nsel + N + md.d[s]]);  // getBW(p, [1])[dims]
   kdehip_device_density *h = new (std::nothrow) kdehip_device_density();

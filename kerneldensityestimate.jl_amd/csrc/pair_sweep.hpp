@@ -113,6 +113,15 @@ __device__ __forceinline__ void pair_sweep(const PairHead &h, const PairPlace &a
   }
 }
 
+// A query with a NaN in one of its D coordinates.  The sweep cannot tell: exp_nonpos's clamp and the running maxima (fmax)
+// drop a NaN, so such a query comes out of it like one with no source in reach.  The kernels that finish a query (one thread
+// per query) ask this of the position itself and answer NaN.
+__device__ __forceinline__ bool query_has_nan(const double *__restrict__ qry, int64_t q, int D) {
+  bool bad = false;
+  for (int k = 0; k < D; ++k) bad = bad || (qry[q * D + k] != qry[q * D + k]);
+  return bad;
+}
+
 // The sum of red[0 .. W) in a fixed tree (halving strides), for a block of W threads; red[t] was written by thread t and a
 // barrier has passed since.  Every thread returns the sum.
 template <int W>

@@ -95,7 +95,8 @@ def _iteration(tol, maxiter):
 def meanshift(p, starts=None, *, tol=1e-9, maxiter=500, device=0, manifold=None):
     """(x (D, K), logp (K,), iters (K,)): every column of `starts` (D, K) -- None: the density's own points, in getPoints
     order -- moved by mean-shift steps until a step is at most `tol` bandwidths long in every dimension, or for `maxiter`
-    steps.  iters = the steps taken, negative where the last of them was still above tol; logp = log p at x."""
+    steps.  iters = the steps taken, negative where the last of them was still above tol; logp = log p at x.  A start with a
+    NaN coordinate stays where it is: iters = 0 and logp = NaN."""
     kind, D = _kind(p), _dims(p)
     tol, maxiter = _iteration(tol, maxiter)
     man = _mf.resolve(p, manifold, D)
@@ -166,10 +167,11 @@ def _bandwidth_sd(h):
 def merge_modes(x, logp, iters, sd, merge, man=None):
     """The greedy merge of converged points: in descending logp (ties by index) a point joins the first kept mode within
     `merge` in max_k |diff_k| / sd_k (the difference wrapped where circular), else it founds one.  Returns (indices of the
-    founders, labels (K,)); an unconverged point (iters < 0) is labelled -1."""
+    founders, labels (K,)); an unconverged point (iters < 0) and a point whose logp is NaN (a start with a NaN coordinate)
+    are labelled -1."""
     K = x.shape[1]
     labels = np.full(K, -1, dtype=np.int64)
-    order = sorted((k for k in range(K) if iters[k] >= 0), key=lambda k: (-logp[k], k))
+    order = sorted((k for k in range(K) if iters[k] >= 0 and logp[k] == logp[k]), key=lambda k: (-logp[k], k))
     kept = []
     circ = None if man is None else np.asarray(man, dtype=bool)
     for k in order:
@@ -192,8 +194,9 @@ def modes(p, starts=None, *, tol=1e-9, maxiter=500, merge=1e-3, device=0, manifo
     within `merge` bandwidths (max_k |diff_k| / sqrt(v_k), wrapped where circular), else it founds a new one.  The modes
     come in descending logp.  mass = the summed weights of the starts labelled to each mode when the starts are the
     density's own points, and the share of the starts (counts / K) otherwise.  Unconverged starts are labelled -1 and belong
-    to no mode.  For a DeviceDensity the merge reads the bandwidth and the weights from the host density it was uploaded
-    from (or from its download if it was built on the device): do not change that host density after the upload."""
+    to no mode, and so are starts with a NaN coordinate.  For a DeviceDensity the merge reads the bandwidth and the weights
+    from the host density it was uploaded from (or from its download if it was built on the device): do not change that host
+    density after the upload."""
     kind, D = _kind(p), _dims(p)
     man = _mf.resolve(p, manifold, D)
     x, logp, iters = meanshift(p, starts, tol=tol, maxiter=maxiter, device=device, manifold=man)
