@@ -394,8 +394,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   unsigned long long sstamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool sstamp_on = false;
 #endif
-  // (chunked screen tiles, step_screen_chunked below) The fp32 evaluator and the error-bound coefficients of a screened
-  // step, from the screen tile's header values (lanes = dimensions) and the chain's leave-one-out product; body(ev, ok):
+  // (chunked screen tiles, step_screen_chunked below) The fp32 evaluator and the error bound's per-dimension terms of a
+  // screened step, from the screen tile's header values (lanes = dimensions) and the chain's leave-one-out product; body(ev, ok):
   // ok = the step is inside the ranges the bound assumes (wave-uniform; with !ok the evaluator must not be used for a
   // decision -- every wavefront still has to walk the chunks: their barriers).  step_screen spells the same set-up out
   // itself: written through these two helpers it was 1.2 % slower on config 3 (A/B of development libraries, round 5).
@@ -408,17 +408,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
     // (a2 <= kScreenMaxA2 in every dimension keeps na <= 2^-11, the regime the bound is linearised for: screen_device.hpp)
     const bool inr = (acen <= kScreenMaxAbsMean) && (covf <= static_cast<float>(kScreenMaxVar)) && (a2 <= kScreenMaxA2);  // (false for a NaN)
     const bool ok = valid != 0.0f && __ballot(lane < D && !inr) == 0ull;
-    a2 += dpp_fetch<0x111, 0xF>(a2);  // row_shr:1, 2, 4: lane 7 holds the sum over the (at most 8) dimension lanes
-    a2 += dpp_fetch<0x112, 0xF>(a2);
-    a2 += dpp_fetch<0x114, 0xF>(a2);
-    const float na = __builtin_sqrtf(lane_read(a2, 7)) * (kScreenU * kScreenSqrtC0 * 1.01f);
-    using SC = ScreenConst<D>;
-    const float Bc = (kScreenLn2 * 1.01f) * (na + (ds.uniform_bw ? SC::kx_uni : SC::kx_node) * kScreenU);
-    const float A = (kScreenLn2 * 1.01f) * na +
-                    (static_cast<float>(((ds.B + 1) >> 1) + 9) + (ds.uniform_bw ? SC::vc_uni : SC::vc_node)) * kScreenU;
     if (ds.uniform_bw) {
       ScreenEval<D, true> ev;
-      ev.A = A; ev.Bc = Bc;
+      ev.a2 = a2; ev.nsum = (ds.B + 1) >> 1;
       const float ninv = -kScreenC0 * __builtin_amdgcn_rcpf(cf);
       float pr = 1.0f;
 #pragma unroll
@@ -431,7 +423,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       return body(ev, ok);
     } else {
       ScreenEval<D, false> ev;
-      ev.A = A; ev.Bc = Bc; ev.scale = 1.0f;
+      ev.a2 = a2; ev.nsum = (ds.B + 1) >> 1; ev.scale = 1.0f;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         ev.cen[d] = lane_read(cen, d);
@@ -566,18 +558,10 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       int pos = -1;
       const T *hdrg = data + ds.hdr_off();
       if (valid != 0.0f && __ballot(lane < D && !inr) == 0ull) {
-        a2 += dpp_fetch<0x111, 0xF>(a2);  // row_shr:1, 2, 4: lane 7 holds the sum over the (at most 8) dimension lanes
-        a2 += dpp_fetch<0x112, 0xF>(a2);
-        a2 += dpp_fetch<0x114, 0xF>(a2);
-        const float na = __builtin_sqrtf(lane_read(a2, 7)) * (kScreenU * kScreenSqrtC0 * 1.01f);
-        using SC = ScreenConst<D>;
-        const float Bc = (kScreenLn2 * 1.01f) * (na + (ds.uniform_bw ? SC::kx_uni : SC::kx_node) * kScreenU);
-        const float A = (kScreenLn2 * 1.01f) * na +
-                        (static_cast<float>(((ds.B + 1) >> 1) + 9) + (ds.uniform_bw ? SC::vc_uni : SC::vc_node)) * kScreenU;
         const LdsPtr<float> rows32 = h32 + kScreenHeaderFloats;
         if (ds.uniform_bw) {
           ScreenEval<D, true> ev;
-          ev.A = A; ev.Bc = Bc;
+          ev.a2 = a2; ev.nsum = (ds.B + 1) >> 1;
           const float ninv = -kScreenC0 * __builtin_amdgcn_rcpf(cf);
           float pr = 1.0f;
 #pragma unroll
@@ -590,7 +574,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
           pos = screen_draw<D, true>(rows32, ds.n, ds.B, ds.F, lane, ev, u SSTAMP_ARGS);
         } else {
           ScreenEval<D, false> ev;
-          ev.A = A; ev.Bc = Bc; ev.scale = 1.0f;
+          ev.a2 = a2; ev.nsum = (ds.B + 1) >> 1; ev.scale = 1.0f;
 #pragma unroll
           for (int d = 0; d < D; ++d) {
             ev.cen[d] = lane_read(cen, d);
@@ -686,7 +670,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
         }
         KDEHIP_PRIO_CHAIN();
         if (!ok) return -1;
-        return screen_decide<D, Ev::kUni, true>(grows, ds.n, ds.B, RS, lane, ev, u, q.values(), q.errors() SSTAMP_ARGS);
+        return screen_decide<D, Ev::kUni, true>(grows, ds.n, ds.B, RS, lane, ev, u, q.values(), q.moments() SSTAMP_ARGS);
       }));
       if constexpr (kCoop) {
         ++n_screened;

@@ -33,7 +33,17 @@
 //     pass's scan is shorter) are within (ceil(B / 2) + 7) u of the exact sums of the computed values.
 // So |v~_i - v_i| <= v_i (A + Bc |x_i|) with the wave-uniform A = ln2 na + (ceil(B / 2) + 9 + vc) u, Bc = ln2 (na + kx u)
 // (each with a 1 % allowance for the second-order terms), every cumulative sum is within E = sum_i v~_i (A + Bc |x~_i|)
-// of its fp64 value, and so is the target u * total.  (Rounds 5a-5o ran with the cruder kx = 32, vc = 24, B + 16 for the
+// of its fp64 value, and so is the target u * total.
+//   The kernel forms E FACTORED: the row loop accumulates S = sum_i v~_i and X = sum_i v~_i |x~_i| (one packed fma per
+// pair of rows; A and Bc are not needed before the loop has ended, so the DPP sum, the square root and the products
+// behind them leave the step's set-up), and E = fma(A, S, Bc X) is formed once per wavefront from the totals.  Its own
+// roundings: S and X are sums of non-negative terms, each through one chain of ceil(B / 2) fused additions per half, the
+// sum of the halves and six scan steps, so the computed totals are at least (1 - (ceil(B / 2) + 7) u) of the exact ones;
+// the product Bc X and the fma add 2 u.  With B <= 128 the computed E falls short of the exact one by at most
+// (64 + 9) u = 4.4e-6 of itself -- 1/2300 of the 1 % allowance in A and Bc, 1/11000 of the margin's 5 % -- and the
+// per-term form it replaces (E += v~ (A + Bc |x~|), the same chain) fell short by the same (ceil(B / 2) + 9) u.  kx, vc and
+// the summation term of A are unchanged: the exponent, the value and the order of the sums over pairs are formed as before.
+// (Rounds 5a-5o ran with the cruder kx = 32, vc = 24, B + 16 for the
 // sums: 0.75 % of config 3's and 1.9 % of config 4's draws repeated; profiles/r05_experiments.md section 11.)  A decision is certified when the boundaries on both sides of the target are
 // more than 2.1 E away (2 E would do).  Terms that fp32 flushes to zero or holds as denormals are below 2^-126 times a
 // front that the range checks bound by 2^28 each: with total >= 2^-40 required, their sum is below 2^-40 of the margin.
@@ -83,7 +93,20 @@ struct ScreenEval {
   float cen[D];  // centre'_d
   float b[D];    // UNI: -c0 / c_d (the level's shared variance + leave-one-out variance); else: the leave-one-out variance
   float scale;   // UNI: rsqrt(prod_d c_d)
-  float A, Bc;
+  float a2;      // lanes = dimensions: (g_d / sigma_d)^2 of the bound's na without its factor u^2, 0 in the other lanes
+  int nsum;      // ceil(B / 2): the additions behind each half of a lane's sums
+  // The bound's coefficients A and Bc (header comment).  Nothing in the row loop reads them, so they are formed behind it,
+  // between the stages of the lanes' scans.
+  __device__ __forceinline__ void bound(float &A, float &Bc) const {
+    float s = a2;
+    s += dpp_fetch<0x111, 0xF>(s);  // row_shr:1, 2, 4: lane 7 holds the sum over the (at most 8) dimension lanes
+    s += dpp_fetch<0x112, 0xF>(s);
+    s += dpp_fetch<0x114, 0xF>(s);
+    const float na = __builtin_sqrtf(lane_read(s, 7)) * (kScreenU * kScreenSqrtC0 * 1.01f);
+    using SC = ScreenConst<D>;
+    Bc = (kScreenLn2 * 1.01f) * (na + (UNI ? SC::kx_uni : SC::kx_node) * kScreenU);
+    A = (kScreenLn2 * 1.01f) * na + (static_cast<float>(nsum + 9) + (UNI ? SC::vc_uni : SC::vc_node)) * kScreenU;
+  }
   static constexpr bool kUni = UNI;
   using TA = TileAddr<float>;
   template <typename V, typename LD>
@@ -116,7 +139,8 @@ struct ScreenEval {
     return front * Num<V>::exp_fast(x, nullptr);
   }
   // one PAIR of rows; e = (row 2p, field 0, this lane).  The fields are requested first (one ds_read_b64 per field and
-  // lane: load_pair), the arithmetic follows a trip later: value sums S and error-bound sums E (both halves)
+  // lane: load_pair), the arithmetic follows later: value sums S and the sums X of v |x| (both halves), from which the
+  // error-bound sum is A S + Bc X (screen_decide)
   static constexpr int kFields = UNI ? D + 1 : 2 * D + 1;
   struct Pair { kdehip_f2 f[kFields]; };
   static __device__ __forceinline__ Pair load(LdsPtr<float> e) {
@@ -125,12 +149,11 @@ struct ScreenEval {
     for (int f = 0; f < kFields; ++f) r.f[f] = load_pair(e + f * TA::kField);
     return r;
   }
-  __device__ __forceinline__ kdehip_f2 pair(const Pair &r, kdehip_f2 &S, kdehip_f2 &E) const {
+  __device__ __forceinline__ kdehip_f2 pair(const Pair &r, kdehip_f2 &S, kdehip_f2 &X) const {
     kdehip_f2 x;
     const kdehip_f2 v = value<kdehip_f2>([&](int f) { return r.f[f]; }, x);
     S += v;
-    const kdehip_f2 g = Num<kdehip_f2>::fma(-x, kdehip_f2(Bc), kdehip_f2(A));
-    E = Num<kdehip_f2>::fma(v, g, E);
+    X = Num<kdehip_f2>::fma(v, -x, X);
     return v;
   }
   // one entry (second pass); e = (its row, field 0, its lane)
@@ -141,32 +164,56 @@ struct ScreenEval {
   }
 };
 
-// First pass over `npairs` row pairs from `e` (= pair 0, field 0, this lane; LDS): value sums S and error-bound sums E.
-// Two pairs per trip, the next pair's fields requested before the current pair is evaluated (ping-pong registers).
-// The sums of a lane: the even rows' and the odd rows' halves of one packed accumulator each (values, error bounds): a
-// chain of ceil(B / 2) additions each over all chunks, which is what the bound's summation term counts.  (Two accumulators
-// each -- even and odd PAIRS, ceil(B / 4) + 1 additions, the term 15 u smaller at 64 rows -- measured: config 4 -0.7 %,
-// config 3 +0.3 %; not kept.)
+// First pass over `npairs` row pairs from `e` (= pair 0, field 0, this lane; LDS): value sums S and the sums X of v |x|.
+// Shared-bandwidth tiles of more than 4 dimensions: a ring of THREE register sets, the fields of two pairs in flight ahead
+// of the pair being evaluated (2 (D + 1) <= 14 outstanding ds_read_b64, inside the 4-bit counter), three pairs per trip;
+// a request past the last pair reads the last pair again, never past the tile.  Measured (profiles/screen_rows_after.md):
+// config 3 (D = 6, 8 pairs per step) -1.4 %, config 4 (D = 3: 4 loads and a dozen instructions per pair, the ring's
+// address arithmetic and its two re-read pairs per call weigh more) +1.5 % -- so the smaller tiles and the per-node tiles
+// (2 D + 1 = 13 loads per pair: two pairs ahead do not fit the counter) keep two pairs per trip with one pair ahead.
+// The sums of a lane: the even rows' and the odd rows' halves of one packed accumulator each (values, v |x|): a chain of
+// ceil(B / 2) additions each over all chunks, in the order of the pairs, which is what the bound's summation term counts.
+// (Two accumulators each -- even and odd PAIRS, ceil(B / 4) + 1 additions, the term 15 u smaller at 64 rows -- measured:
+// config 4 -0.7 %, config 3 +0.3 %; not kept.)
 struct ScreenSums {
-  kdehip_f2 S = {0.0f, 0.0f}, E = {0.0f, 0.0f};
+  kdehip_f2 S = {0.0f, 0.0f}, X = {0.0f, 0.0f};
   __device__ __forceinline__ float values() const { return S.x + S.y; }
-  __device__ __forceinline__ float errors() const { return E.x + E.y; }
+  __device__ __forceinline__ float moments() const { return X.x + X.y; }
 };
 template <int D, bool UNI>
 __device__ __forceinline__ void screen_rows(LdsPtr<float> e, int npairs, int RS, const ScreenEval<D, UNI> &ev, ScreenSums &q) {
   using Ev = ScreenEval<D, UNI>;
   typename Ev::Pair ra = Ev::load(e);
   int p = 0;
-  for (; p + 2 <= npairs; p += 2) {
-    const typename Ev::Pair rb = Ev::load(e + RS);  // pair p + 1
-    __builtin_amdgcn_sched_barrier(0);
-    ev.pair(ra, q.S, q.E);
-    e += (p + 2 < npairs) ? 2 * RS : RS;  // pair p + 2, or pair p + 1 again (never past the tile)
-    ra = Ev::load(e);
-    __builtin_amdgcn_sched_barrier(0);
-    ev.pair(rb, q.S, q.E);
+  if constexpr (UNI && D > 4) {
+    const int last = npairs - 1;
+    auto at = [&](int k) { return e + (k < last ? k : last) * RS; };  // pair k, or the last pair again (never past the tile)
+    typename Ev::Pair rb = Ev::load(at(1));
+    for (; p + 3 <= npairs; p += 3) {
+      const typename Ev::Pair rc = Ev::load(at(p + 2));
+      __builtin_amdgcn_sched_barrier(0);
+      ev.pair(ra, q.S, q.X);
+      ra = Ev::load(at(p + 3));
+      __builtin_amdgcn_sched_barrier(0);
+      ev.pair(rb, q.S, q.X);
+      rb = Ev::load(at(p + 4));
+      __builtin_amdgcn_sched_barrier(0);
+      ev.pair(rc, q.S, q.X);
+    }
+    if (p < npairs) ev.pair(ra, q.S, q.X);
+    if (p + 1 < npairs) ev.pair(rb, q.S, q.X);
+  } else {
+    for (; p + 2 <= npairs; p += 2) {
+      const typename Ev::Pair rb = Ev::load(e + RS);  // pair p + 1
+      __builtin_amdgcn_sched_barrier(0);
+      ev.pair(ra, q.S, q.X);
+      e += (p + 2 < npairs) ? 2 * RS : RS;  // pair p + 2, or pair p + 1 again (never past the tile)
+      ra = Ev::load(e);
+      __builtin_amdgcn_sched_barrier(0);
+      ev.pair(rb, q.S, q.X);
+    }
+    if (p < npairs) ev.pair(ra, q.S, q.X);
   }
-  if (p < npairs) ev.pair(ra, q.S, q.E);
 }
 
 // The decision from the lanes' sums: the tile position of the entry u selects, or -1 when the fp32 decision cannot be
@@ -174,12 +221,14 @@ __device__ __forceinline__ void screen_rows(LdsPtr<float> e, int npairs, int RS,
 // at most 64 rows per lane, one second-pass round) or in global memory (TWO: at most 128 rows, two rounds).
 template <int D, bool UNI, bool TWO, typename P>
 __device__ __forceinline__ int screen_decide(P rows, int n, int B, int RS, int lane, const ScreenEval<D, UNI> &ev, double u,
-                                             float s1, float e1 SSTAMP_PARAMS) {
+                                             float s1, float x1 SSTAMP_PARAMS) {
   using TA = TileAddr<float>;
   SSTAMP(tq1);
   const float incl = wave_inclusive_scan(s1);
-  const float einc = wave_inclusive_scan(e1);
-  const float total = lane_read(incl, 63), etot = lane_read(einc, 63);
+  const float xinc = wave_inclusive_scan(x1);
+  float A, Bc;
+  ev.bound(A, Bc);
+  const float total = lane_read(incl, 63), etot = fmaf(A, total, Bc * lane_read(xinc, 63));
   if (!(total >= 0x1p-40f && total < 0x1p100f)) return -1;  // (also a NaN)
   const double td = u * static_cast<double>(total), md = kScreenMargin * static_cast<double>(etot);
   // first lane that certainly reaches the target = first lane that possibly does
@@ -233,13 +282,13 @@ __device__ __forceinline__ int screen_draw(LdsPtr<float> rows, int n, int B, int
   KDEHIP_PRIO_ROWS();
   screen_rows<D, UNI>(rows + lane * TA::kLane, (B + 1) >> 1, RS, ev, q);  // (the missing second row of the last pair is padding: weight 0)
   KDEHIP_PRIO_CHAIN();
-  const float s1 = q.values(), e1 = q.errors();
+  const float s1 = q.values(), x1 = q.moments();
 #ifdef KDEHIP_SCREEN_STAMPS
-  asm volatile("" ::"v"(s1), "v"(e1));
+  asm volatile("" ::"v"(s1), "v"(x1));
 #endif
   SSTAMP(tq1);
   SSTAMP_ADD(4, tq0, tq1);
-  return screen_decide<D, UNI, false>(rows, n, B, RS, lane, ev, u, s1, e1 SSTAMP_ARGS);
+  return screen_decide<D, UNI, false>(rows, n, B, RS, lane, ev, u, s1, x1 SSTAMP_ARGS);
 }
 
 }  // namespace kdehip
