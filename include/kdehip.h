@@ -1157,7 +1157,7 @@ int kdehip_density_condition_device(kdehip_device_density **out, const kdehip_de
 
 /* ---- (5j) non-finite positions from the caller ----------------------------------------------------------------------------
  * For the entries that take an array of positions -- kdehip_evaluate[_manifold] and kdehip_evaluate_log with pos,
- * kdehip_evaluate_grad, kdehip_meanshift with start, kdehip_conditional, kdehip_condition_weights,
+ * kdehip_evaluate_grad, kdehip_evaluate_hess (5k), kdehip_meanshift with start, kdehip_conditional, kdehip_condition_weights,
  * kdehip_density_condition_device, and the resident and batched forms of each:
  *   a NaN in any coordinate of a query (for the conditionals: in any given value) makes every floating-point output of THAT
  *   query NaN -- p, log p, every gradient component, logz, mean, var, the whole row of w_out, the drawn point -- with ind = 0;
@@ -1166,6 +1166,68 @@ int kdehip_density_condition_device(kdehip_device_density **out, const kdehip_de
  *   +-Inf in a coordinate is infinitely far from every leaf: p = 0, log p = logz = -Inf, and everything else as for "S empty"
  *   in 5h / 5i (gradient 0, the start returned with iters = 0, mean / var / the point NaN, ind = 0, the row of w_out all 0).
  * NaN or Inf INSIDE a density (points, weights, bandwidths) is outside this contract. */
+
+/* ---- (5k) the curvature of the density: the Hessian of log p and a covariance for every mode -------------------------------
+ * How wide is a mode?  getKDEfit (5c) is ONE moment-matched Gaussian for the whole density -- for a multimodal belief the
+ * wrong width in the way getKDEMax is the wrong mode.  The entries below give the Hessian of log p at a query and, where it is
+ * negative definite, the covariance of the Gaussian with that curvature (the Laplace approximation of the mode)
+ * (csrc/modes.hip; this library's own, the reference has no counterpart).  With d_ik, a_i, S, m, S_0 and S_k exactly as in 5h
+ * and t_i = w_i exp(a_i - m):
+ *   S_kl  = sum_{i in S} t_i d_ik d_il                                 (k <= l: D (D + 1) / 2 sums)
+ *   g_k   = -S_k / (S_0 v_k)                                           (the gradient of log p, as 5h)
+ *   H_kl  = S_kl / (S_0 v_k v_l) - delta_kl / v_k - g_k g_l            (the Hessian of log p at x)
+ * Equivalently -H = V^-1 - V^-1 C V^-1 with V = diag(v) and C the covariance of the differences d_i under the
+ * responsibilities t_i / S_0: C is positive semidefinite, so wherever -H is definite (-H)^-1 - V is positive semidefinite --
+ * a mode is never narrower than the kernel.
+ * Covariance: cov = (-H)^-1 from a Cholesky factorisation of -H.  If every pivot is finite and > 0, definite = 1; otherwise
+ * definite = 0 and all D x D entries of cov are NaN -- the query sits at a saddle, a minimum or in a flat direction, not at a
+ * maximum.
+ * Layout: hess and cov are [Nq][D][D], the full matrix; both triangles are stored from the one computed value, so the matrices
+ * are symmetric bit for bit.  logp is [Nq], grad [Nq][D], definite [Nq] int32.
+ * S empty: logp = -Inf, grad = 0, hess = 0, definite = 0, cov = NaN.  A query with a NaN coordinate (5j): NaN in every
+ * floating-point output of that query and definite = 0.  In a circular dimension d_ik is wrapped and H is the Hessian of that
+ * expression (as the gradient of 5h is its gradient): exact wherever no difference that carries weight sits on the cut.
+ * The sum is split as in 5h: consecutive 128-leaf chunks in groups that depend on (npts, Nq) alone; a group carries
+ * (m, s_0, s_k, s_kl), rescaled by exp(m_old - m_new) once per chunk; within a chunk t_i, d_ik t_i and (d_ik t_i) d_il are
+ * summed from 0 in leaf order (one fma each for s_k and s_kl) and the chunk's sums are then added to the carried ones; the
+ * groups are combined in group order with M = max m_g, sum_g s_jg exp(m_g - M).  No atomics.  Then, per query,
+ *   g_k = -S_k / (S_0 v_k);  H_kl = fma(-g_k, g_l, S_kl / ((S_0 v_k) v_l) [- 1 / v_k when k == l])            (k <= l)
+ *   -H = L L^T column by column: pivot_j = -H_jj - sum_{i<j} L_ji^2 (i ascending, one fma each), L_jj = sqrt(pivot_j),
+ *   L_rj = (-H_rj - sum_{i<j} L_ri L_ji) / L_jj;  R = L^-1 by forward substitution;  cov_kl = sum_{r >= l} R_rk R_rl (k <= l).
+ * So the host entry, a resident call and any batch return the same bits, run after run.  Bit equality of logp and grad with
+ * kdehip_evaluate_grad is NOT promised: it is another kernel.
+ * Cancellation: at a mode of data spread sigma under a bandwidth h << sigma, H_kk is the difference of two terms of size
+ * 1 / h^2 whose result is about 1 / (sigma^2 + h^2): roughly log10(sigma^2 / h^2) digits are lost.  Harmless in fp64 for any
+ * bandwidth the LOOCV search returns; it is why there is no fp32 variant.
+ * Only the Hessian of log p crosses the ABI (that of p is p (H + g g^T)).  fp64 only.
+ * Errors, all checked before any device is touched: null arguments (every output NULL included), Nq < 0, a manifold byte
+ * above 1 or a mask bit at or above D, densities on different devices within one batch -- KDEHIP_ERR_ARG; D outside
+ * 1..KDEHIP_MAX_DIMS or per-point bandwidths -- KDEHIP_ERR_UNSUPPORTED.  Nq == 0 and n == 0 are KDEHIP_OK.
+ * Not here: leave-one-out curvature, per-point bandwidths, kernels other than the Gaussian, fp32. */
+/* Host density, blocking: pos as kdehip_evaluate takes it.  Any output may be NULL, but not all of them. */
+int kdehip_evaluate_hess(const kdehip_density *bd, const double *pos, int64_t Nq, double *logp, double *grad, double *hess,
+                         double *cov, int32_t *definite, int device, const uint8_t *manifold);
+/* Resident density, device arrays, enqueue only on `stream`. */
+int kdehip_evaluate_hess_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, double *d_logp, double *d_grad,
+                                double *d_hess, double *d_cov, int32_t *d_definite, const uint8_t *manifold, void *stream);
+typedef struct kdehip_hess_item {
+  const kdehip_device_density *bd;
+  const double *d_pos;      /* device, [Nq][D] */
+  int64_t Nq;
+  double *d_logp;           /* device, [Nq], or NULL */
+  double *d_grad;           /* device, [Nq][D], or NULL */
+  double *d_hess;           /* device, [Nq][D][D], or NULL */
+  double *d_cov;            /* device, [Nq][D][D], or NULL */
+  int32_t *d_definite;      /* device, [Nq], or NULL (not all five NULL) */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+  uint32_t reserved_;
+} kdehip_hess_item;
+/* Resident densities (mixed D, N and Nq), all on one device.  Enqueue only on `stream`: one partial launch per distinct
+ * (D, circular) and ONE finish launch for all items together, and no read-back -- so the call can be captured in a HIP graph,
+ * under the rules of kdehip_meanshift_device_batch (5h): the blocks of a captured call ((2 + D + D (D + 1) / 2) * groups * Nq
+ * doubles of scratch per item) are kept until kdehip_clear_cache, which INVALIDATES every graph captured from this entry.
+ * Every item's results are bit for bit those of kdehip_evaluate_hess_device. */
+int kdehip_evaluate_hess_device_batch(int n, const kdehip_hess_item *items, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@ This package is the Python host mirror of the reference's interface for that pat
 (`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`,
 `sample/rand/resample`, `evalAvgLogL/entropy/kld/minkld`, `evaluate_log`, `marginal`, `getKDERange/getKDEMax/getKDEMean/getKDEfit`,
 `intersIntgAppxIS`, and the library's own exact overlap measures `intersIntg/ise/mmd` and joint modes
-`evaluate_grad/meanshift/modes/getKDEMode` and conditionals
+`evaluate_grad/meanshift/modes/getKDEMode`, their curvature `evaluate_hess/laplace/fit_modes/getKDEModeFit` and conditionals
 `condition/conditional_weights/conditional_moments/sample_conditional`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
@@ -20,6 +20,7 @@ from .sample import rand, resample, sample, sample_device_batch  # noqa: F401
 from .loglik import entropy, eval_avg_logl_device_batch, evalAvgLogL, kld, kld_batch, minkld  # noqa: F401
 from .overlap import intersIntg, ise, ise_batch, kernel_sum, kernel_sum_device_batch, mmd, mmd_batch  # noqa: F401
 from .modes import evaluate_grad, getKDEMode, meanshift, meanshift_device_batch, modes  # noqa: F401
+from .curvature import evaluate_hess, evaluate_hess_device_batch, fit_modes, getKDEModeFit, laplace  # noqa: F401
 from .conditional import (condition, conditional_device_batch, conditional_moments, conditional_weights,  # noqa: F401
                           sample_conditional)
 from .summary import (getKDEfit, getKDEMax, getKDEMean, getKDERange, getKDERangeLinspace, intersIntgAppxIS,  # noqa: F401

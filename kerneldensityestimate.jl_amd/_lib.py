@@ -77,6 +77,13 @@ class CMeanshiftItem(C.Structure):
                 ("d_iters", C.c_void_p), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class CHessItem(C.Structure):
+    """struct kdehip_hess_item"""
+    _fields_ = [("bd", C.c_void_p), ("d_pos", C.c_void_p), ("Nq", C.c_int64), ("d_logp", C.c_void_p), ("d_grad", C.c_void_p),
+                ("d_hess", C.c_void_p), ("d_cov", C.c_void_p), ("d_definite", C.c_void_p), ("circular_mask", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
 class CConditionalItem(C.Structure):
     """struct kdehip_conditional_item"""
     _fields_ = [("bd", C.c_void_p), ("d_given", C.c_void_p), ("Nq", C.c_int64), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
@@ -190,6 +197,10 @@ SIGNATURES = {
     "kdehip_meanshift": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, C.c_int, u8p]),
     "kdehip_meanshift_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, u8p]),
     "kdehip_meanshift_device_batch": (C.c_int, [C.c_int, C.POINTER(CMeanshiftItem), f64p, C.c_int, C.c_void_p]),
+    "kdehip_evaluate_hess": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, f64p, f64p, f64p, f64p, i32p, C.c_int, u8p]),
+    "kdehip_evaluate_hess_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, u8p, C.c_void_p]),
+    "kdehip_evaluate_hess_device_batch": (C.c_int, [C.c_int, C.POINTER(CHessItem), C.c_void_p]),
     "kdehip_conditional": (C.c_int, [C.POINTER(CDensity), C.c_uint32, f64p, C.c_int64, C.c_uint64, C.c_int64, f64p, f64p, f64p,
                                      f64p, i64p, C.c_int, u8p]),
     "kdehip_conditional_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,

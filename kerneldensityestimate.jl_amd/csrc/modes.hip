@@ -19,6 +19,8 @@
 // No atomics; the in-place update is ordered by the stream.  The group split (split_chunks(N, Nq, 1)) depends on the item's
 // sizes alone and a frozen query is never written again, so a query's trajectory depends on the density, its start and tol
 // alone: the host entry, a resident call and any batch give the same bits, however the sweeps are grouped into rounds.
+// The curvature (section 5k: the Hessian of log p and the covariance of a mode) is the same sweep with the second moments
+// carried too, on a run of its own (CurvItem, CurvRun): see "curvature" below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -232,6 +234,220 @@ __global__ void moments_live_kernel(const MomentItem *__restrict__ items, int n)
   *it.nlive = s;
 }
 
+// ---- curvature (include/kdehip.h section 5k) ------------------------------------------------------------------------------
+// The second moments S_kl = sum_{i in S} t_i d_ik d_il (k <= l) beside (m, S_0, S_k), the Hessian of log p and, where -H is
+// positive definite, its inverse: the covariance of the Gaussian that has the density's curvature at x.
+//   curvature_partial_kernel<D>  the sweep and the two passes of moments_partial_kernel, carrying 2 + D + D(D+1)/2 values
+//                                per lane: per pair D multiplies (u = d_k t) and D(D+1)/2 fmas (fma(u, d_l, c_kl)) beside
+//                                the moments' work; scratch [2 + D + D(D+1)/2][ngroups][Nq];
+//   curvature_finish_kernel      ONE launch for all items, one thread per query: the groups combined in group order, then g,
+//                                H, the Cholesky factor of -H and the inverse, instantiated per D (compile-time indices).
+constexpr int tri_count(int D) { return D * (D + 1) / 2; }
+constexpr int tri_index(int D, int k, int l) { return k * D - k * (k - 1) / 2 + (l - k); }  // k <= l, row-major upper triangle
+
+struct CurvItem : PairHead {
+  const double *bw;   // [D] the density's first leaf's variances
+  double *logp;       // [Nq], or null
+  double *grad;       // [Nq][D], or null
+  double *hess;       // [Nq][D][D], or null
+  double *cov;        // [Nq][D][D], or null
+  int32_t *definite;  // [Nq], or null
+  double *partial;    // [2 + D + D(D+1)/2][ngroups][Nq]: m, s_0, s_1..s_D, s_kl (k <= l, row by row)
+  double norm0;
+  int32_t ngroups, nfb, D, pad_;
+};
+
+// partial[0][g][q] = m, [1] = s_0, [2 + k] = s_{k+1}, [2 + D + tri_index(k, l)] = s_kl over the source chunks of group g in
+// chunk order, exactly as moments_partial_kernel words it: per staged chunk the chunk's maximum over S, the carried sums
+// rescaled ONCE by exp_nonpos(m_old - m_new), then the chunk's own sums (from 0, in source order) added to the carried ones.
+template <int D, bool CIRC>
+__global__ __launch_bounds__(kEvalThreads) void curvature_partial_kernel(const CurvItem *__restrict__ items,
+                                                                         const int32_t *__restrict__ first, int n,
+                                                                         const uint32_t *__restrict__ masks) {
+  constexpr int T = tri_count(D), W = 1 + D + T;
+  __shared__ double sSrc[2][kEvalChunk * (D + 1)];
+  __shared__ double sExpTab[32];
+  if (threadIdx.x < 32) sExpTab[threadIdx.x] = kExp2Tab[threadIdx.x];
+  const ItemBlock ib = item_block(first, n);
+  const CurvItem pb = items[ib.item];
+  const unsigned circ = circ_mask<CIRC>(masks, ib.item);
+  const PairPlace at = pair_place(pb, ib.k);
+  if (at.c_begin >= at.c_end) return;  // block-uniform, before any barrier
+  double nhib[D];  // -1/(2 bw_k)
+#pragma unroll
+  for (int k = 0; k < D; ++k) nhib[k] = -0.5 / pb.bw[k];
+  double m = -INFINITY, s[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) s[j] = 0.0;
+  pair_sweep<D, CIRC>(pb, at, circ, nhib, sSrc, [&](auto &&each) {
+    double cm = -INFINITY;
+    each([&](int64_t, double w, double a) { cm = (w > 0.0) ? fmax(cm, a) : cm; });
+    if (cm > m) {  // (m == -Inf: the sums are still 0)
+      const double r = exp_nonpos(m - cm, sExpTab);
+#pragma unroll
+      for (int j = 0; j < W; ++j) s[j] *= r;
+      m = cm;
+    }
+    double c[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) c[j] = 0.0;
+    each([&](int64_t, double w, double a, const double (&d)[D]) {
+      const double t = (w > 0.0) ? w * exp_nonpos(a - m, sExpTab) : 0.0;  // in S: a <= m
+      c[0] += t;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        c[k + 1] = fma(d[k], t, c[k + 1]);
+        const double u = d[k] * t;
+#pragma unroll
+        for (int l = k; l < D; ++l) c[1 + D + tri_index(D, k, l)] = fma(u, d[l], c[1 + D + tri_index(D, k, l)]);
+      }
+    });
+#pragma unroll
+    for (int j = 0; j < W; ++j) s[j] += c[j];
+  });
+  if (at.q < pb.Nq) {
+    const int64_t row = static_cast<int64_t>(pb.ngroups) * pb.Nq, o = at.grp * pb.Nq + at.q;
+    pb.partial[o] = m;
+#pragma unroll
+    for (int j = 0; j < W; ++j) pb.partial[(j + 1) * row + o] = s[j];
+  }
+}
+
+// One query of an item of dimension D.  The groups in group order: M = max m_g, S_j = sum_g s_jg exp(m_g - M); then
+//   log p = M + log S_0 - log norm,  g_k = -S_k / (S_0 v_k),
+//   H_kl  = fma(-g_k, g_l, S_kl / ((S_0 v_k) v_l) [- 1 / v_k if k == l])     (k <= l; both triangles store that one value)
+//   -H = L L^T by Cholesky, column by column (pivot_j = -H_jj - sum_{i<j} L_ji^2 in ascending i); definite = every pivot
+//   finite and > 0; then cov = L^-T L^-1 (k <= l, the products summed in ascending row), else all of cov NaN.
+// No source in S: -Inf, 0, 0, definite 0, cov NaN.  A query with a NaN coordinate: NaN everywhere, definite 0.
+template <int D>
+__device__ __forceinline__ void curvature_finish_query(const CurvItem &it, int64_t q) {
+  constexpr int T = tri_count(D), W = 1 + D + T;
+  const int64_t row = static_cast<int64_t>(it.ngroups) * it.Nq;
+  const double *pm = it.partial + q;
+  double M = -INFINITY;
+  for (int g = 0; g < it.ngroups; ++g) M = fmax(M, pm[static_cast<int64_t>(g) * it.Nq]);
+  double S[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) S[j] = 0.0;
+  const bool some = M > -INFINITY;
+  if (some) {
+    for (int g = 0; g < it.ngroups; ++g) {
+      const double mg = pm[static_cast<int64_t>(g) * it.Nq];
+      if (mg > -INFINITY) {
+        const double e = exp(mg - M);
+#pragma unroll
+        for (int j = 0; j < W; ++j) S[j] += pm[(j + 1) * row + static_cast<int64_t>(g) * it.Nq] * e;
+      }
+    }
+  }
+  const bool bad = query_has_nan(it.qry, q, D);  // (the sweep drops a NaN: pair_sweep.hpp)
+  const double nan = __builtin_nan("");
+  double v[D], g[D], H[D][D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    v[k] = it.bw[k];
+    g[k] = some ? -S[k + 1] / (S[0] * v[k]) : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+#pragma unroll
+    for (int l = k; l < D; ++l) {
+      double h = 0.0;
+      if (some) {
+        h = S[1 + D + tri_index(D, k, l)] / ((S[0] * v[k]) * v[l]);
+        if (k == l) h -= 1.0 / v[k];
+        h = fma(-g[k], g[l], h);
+      }
+      H[k][l] = h;
+      H[l][k] = h;
+    }
+  }
+  if (it.logp) {
+    double norm = it.norm0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) norm *= __dsqrt_rn(v[k]);  // gauss_norm
+    it.logp[q] = bad ? nan : some ? M + log(S[0]) - log(norm) : -INFINITY;
+  }
+  if (it.grad) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) it.grad[q * D + k] = bad ? nan : g[k];
+  }
+  if (it.hess) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+#pragma unroll
+      for (int l = 0; l < D; ++l) it.hess[(q * D + k) * D + l] = bad ? nan : H[k][l];
+    }
+  }
+  if (!it.cov && !it.definite) return;
+  // L in the lower triangle of A (A = -H), then its inverse in place of it
+  double L[D][D];
+  bool ok = some && !bad;
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    double p = -H[j][j];
+#pragma unroll
+    for (int i = 0; i < j; ++i) p = fma(-L[j][i], L[j][i], p);
+    ok = ok && (p > 0.0) && (p < INFINITY);  // (a NaN pivot fails the first comparison)
+    const double d = __dsqrt_rn(p);
+    L[j][j] = d;
+#pragma unroll
+    for (int r = j + 1; r < D; ++r) {
+      double a = -H[r][j];
+#pragma unroll
+      for (int i = 0; i < j; ++i) a = fma(-L[r][i], L[j][i], a);
+      L[r][j] = a / d;
+    }
+  }
+  if (it.definite) it.definite[q] = ok ? 1 : 0;
+  if (!it.cov) return;
+  double R[D][D];  // R = L^-1 (lower triangular), column by column: R_jj = 1 / L_jj, R_rj = -(sum_{i=j}^{r-1} L_ri R_ij) / L_rr
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    R[j][j] = 1.0 / L[j][j];
+#pragma unroll
+    for (int r = j + 1; r < D; ++r) {
+      double a = 0.0;
+#pragma unroll
+      for (int i = j; i < r; ++i) a = fma(L[r][i], R[i][j], a);
+      R[r][j] = -a / L[r][r];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+#pragma unroll
+    for (int l = k; l < D; ++l) {
+      double c = 0.0;
+#pragma unroll
+      for (int r = l; r < D; ++r) c = fma(R[r][k], R[r][l], c);  // (L^-T L^-1)_kl, rows r >= max(k, l) = l
+      c = ok ? c : nan;
+      it.cov[(q * D + k) * D + l] = c;
+      it.cov[(q * D + l) * D + k] = c;
+    }
+  }
+}
+
+// items [0, n), item i owns blocks [first[i], first[i+1]); the item's D is block-uniform
+__global__ __launch_bounds__(kFinishThreads) void curvature_finish_kernel(const CurvItem *__restrict__ items,
+                                                                        const int32_t *__restrict__ first, int n) {
+  const ItemBlock ib = item_block(first, n);
+  const CurvItem it = items[ib.item];
+  const int64_t q = static_cast<int64_t>(ib.k) * kFinishThreads + threadIdx.x;
+  if (q >= it.Nq) return;
+  static_assert(KDEHIP_MAX_DIMS == 8, "one case per dimension count");
+  switch (it.D) {
+    case 1: curvature_finish_query<1>(it, q); break;
+    case 2: curvature_finish_query<2>(it, q); break;
+    case 3: curvature_finish_query<3>(it, q); break;
+    case 4: curvature_finish_query<4>(it, q); break;
+    case 5: curvature_finish_query<5>(it, q); break;
+    case 6: curvature_finish_query<6>(it, q); break;
+    case 7: curvature_finish_query<7>(it, q); break;
+    case 8: curvature_finish_query<8>(it, q); break;
+    default: break;
+  }
+}
+
 // While the stream is being captured into a graph the calling thread's capture mode is relaxed (the call allocates and
 // copies), and the call's blocks must outlive the call: they are kept until kdehip_clear_cache (kdehip.h 5h: one pair of
 // blocks per capture, and clearing the cache invalidates the graph).  A call that fails after its upload leaves through
@@ -377,6 +593,62 @@ class MomentRun : public PairRun<MomentItem> {
   size_t nbase_ = 0, nsteps_ = 0, own_ = 0;
 };
 
+// The run of one curvature call: per item the scratch [2 + D + D(D+1)/2][ngroups][Nq].  Protocol: fill `items` (sizes, D)
+// and `circ` -> alloc(prefix bytes of caller data, result doubles of the caller) -> point the items at their data ->
+// start(stream) -> run() (one partial launch per distinct (D, circular), ONE finish launch) -> wait(), defer() or keep().
+class CurvRun : public PairRun<CurvItem> {
+ public:
+  int alloc(size_t prefix, size_t nresults) {
+    const size_t n = items.size();
+    int64_t pblocks = 0, fblocks = 0;
+    for (CurvItem &it : items) {
+      pblocks += split(it);
+      it.nfb = static_cast<int32_t>((it.Nq + kFinishThreads - 1) / kFinishThreads);
+      fblocks += it.nfb;
+    }
+    if (pblocks > INT32_MAX / 2 || fblocks > INT32_MAX / 2) return set_error(KDEHIP_ERR_UNSUPPORTED, "too many queries for one launch");
+    Carve c;
+    carve_head(c, prefix, 2, 0, nresults);  // first[] of the partial and of the finish kernel
+    std::vector<size_t> scratch(n);
+    for (size_t k = 0; k < n; ++k) scratch[k] = c.take(sizeof(double) * rows(items[k].D) * items[k].ngroups * items[k].Nq);
+    KDEHIP_CHECK(alloc_block(c));
+    for (size_t k = 0; k < n; ++k) items[k].partial = reinterpret_cast<double *>(dev() + scratch[k]);
+    return KDEHIP_OK;
+  }
+  int start(hipStream_t st) {
+    prepare([&](size_t k) { return 2 * items[k].D + (circ[k] ? 1 : 0); });  // by D; Euclidean items before circular ones
+    int32_t *ffirst = first(1);
+    ffirst[0] = 0;
+    for (size_t k = 0; k < items.size(); ++k) ffirst[k + 1] = ffirst[k] + items[k].nfb;
+    KDEHIP_CHECK(send(st));
+    return KDEHIP_OK;
+  }
+  int run() {
+    const hipStream_t st = stream();
+    KDEHIP_CHECK_RC(for_each_run([&](const CurvItem &it, const CurvItem *d_it, const int32_t *d_pfirst, int cnt, int blocks,
+                                     const uint32_t *d_masks) -> int {
+      KDEHIP_CHECK_RC(dispatch_dims(it.D, [&](auto dim) {
+        constexpr int kD = decltype(dim)::value;
+        launch_pair<CurvItem>(curvature_partial_kernel<kD, false>, curvature_partial_kernel<kD, true>, blocks, st, d_it, d_pfirst,
+                              cnt, d_masks);
+      }));
+      KDEHIP_CHECK(hipGetLastError());
+      return KDEHIP_OK;
+    }));
+    const int32_t *ffirst = first(1);
+    const size_t n = items.size();
+    if (ffirst[n] > 0) {
+      hipLaunchKernelGGL(curvature_finish_kernel, dim3(static_cast<unsigned>(ffirst[n])), dim3(kFinishThreads), 0, st, d_items(),
+                         d_first(1), static_cast<int>(n));
+      KDEHIP_CHECK(hipGetLastError());
+    }
+    return KDEHIP_OK;
+  }
+
+ private:
+  static size_t rows(int D) { return static_cast<size_t>(2 + D + tri_count(D)); }
+};
+
 // ---- arguments ------------------------------------------------------------------------------------------------------------
 
 int check_resident(const kdehip_device_density *bd) {
@@ -420,7 +692,8 @@ MomentItem resident_item(const kdehip_device_density *bd, int64_t Nq, int logdom
 
 // a host density's leaves, weights and bandwidth vector at offset 0 of the call's image: [means | weights | bw]
 size_t host_density_bytes(const kdehip_density *bd) { return sizeof(double) * (bd->npts * (bd->ndim + 1) + bd->ndim); }
-void pack_host_density(MomentRun &run, MomentItem &it, const kdehip_density *bd) {
+template <typename Run, typename Item>
+void pack_host_density(Run &run, Item &it, const kdehip_density *bd) {
   const int64_t N = bd->npts, D = bd->ndim;
   const LeafArrays src = pack_leaves(run, 0, bd);
   const size_t o_bw = sizeof(double) * N * (D + 1);
@@ -428,6 +701,16 @@ void pack_host_density(MomentRun &run, MomentItem &it, const kdehip_density *bd)
   it.src = src.means;
   it.w = src.weights;
   it.bw = reinterpret_cast<const double *>(run.dev() + o_bw);
+}
+
+CurvItem resident_curv_item(const kdehip_device_density *bd, int64_t Nq) {
+  CurvItem it{};
+  const int64_t N = bd->N;
+  const int D = bd->D;
+  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
+  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.N = N; it.Nq = Nq; it.D = D;
+  return it;
 }
 
 // The rounds of a blocking mean shift: kRound sweeps (fewer at the end), then one look at the number of live starts.
@@ -624,5 +907,110 @@ extern "C" int kdehip_meanshift_device_batch(int n, const kdehip_meanshift_item 
   KDEHIP_CHECK_RC(run.start(st));
   for (int s = 0; s < niter; ++s) KDEHIP_CHECK_RC(run.sweep());
   KDEHIP_CHECK_RC(run.close());
+  return scope.capturing() ? run.keep(device) : run.defer(device);
+}
+
+extern "C" int kdehip_evaluate_hess(const kdehip_density *bd, const double *pos, int64_t Nq, double *logp, double *grad, double *hess,
+                                    double *cov, int32_t *definite, int device, const uint8_t *manifold) {
+  // every check that needs no device comes first
+  if (!bd || (!logp && !grad && !hess && !cov && !definite)) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_host(bd));
+  const int D = static_cast<int>(bd->ndim);
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  if (Nq < 0 || (Nq > 0 && !pos)) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
+  KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
+  if (Nq == 0) return KDEHIP_OK;
+  DeviceGuard guard;
+  KDEHIP_CHECK_RC(guard.enter(device));
+  // caller data: [the density | queries]; results, those asked for only: [logp (Nq) | grad (Nq D) | hess (Nq D D) | cov (Nq D D) |
+  // definite (Nq int32)]
+  const size_t o_q = host_density_bytes(bd), prefix = o_q + sizeof(double) * Nq * D;
+  const size_t n = static_cast<size_t>(Nq);
+  size_t nres = 0;
+  auto take = [&](bool asked, size_t doubles) { const size_t at = nres; if (asked) nres += doubles; return at; };
+  const size_t r_logp = take(logp, n), r_grad = take(grad, n * D), r_hess = take(hess, n * D * D), r_cov = take(cov, n * D * D),
+               r_def = take(definite, (n + 1) / 2);
+  CurvRun run;
+  CurvItem it{};
+  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.N = bd->npts; it.Nq = Nq; it.D = D;
+  run.items.push_back(it);
+  run.circ.push_back(circ);
+  KDEHIP_CHECK_RC(run.alloc(prefix, nres));
+  CurvItem &ri = run.items[0];
+  pack_host_density(run, ri, bd);
+  std::memcpy(run.host() + o_q, pos, sizeof(double) * Nq * D);
+  ri.qry = reinterpret_cast<const double *>(run.dev() + o_q);
+  ri.logp = logp ? run.result(r_logp) : nullptr;
+  ri.grad = grad ? run.result(r_grad) : nullptr;
+  ri.hess = hess ? run.result(r_hess) : nullptr;
+  ri.cov = cov ? run.result(r_cov) : nullptr;
+  ri.definite = definite ? reinterpret_cast<int32_t *>(run.result(r_def)) : nullptr;
+  KDEHIP_CHECK_RC(run.start(hipStreamPerThread));
+  KDEHIP_CHECK_RC(run.run());
+  KDEHIP_CHECK_RC(run.wait());
+  if (logp) std::memcpy(logp, run.host_result(r_logp), sizeof(double) * n);
+  if (grad) std::memcpy(grad, run.host_result(r_grad), sizeof(double) * n * D);
+  if (hess) std::memcpy(hess, run.host_result(r_hess), sizeof(double) * n * D * D);
+  if (cov) std::memcpy(cov, run.host_result(r_cov), sizeof(double) * n * D * D);
+  if (definite) std::memcpy(definite, run.host_result(r_def), sizeof(int32_t) * n);
+  return KDEHIP_OK;
+}
+
+extern "C" int kdehip_evaluate_hess_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, double *d_logp,
+                                           double *d_grad, double *d_hess, double *d_cov, int32_t *d_definite,
+                                           const uint8_t *manifold, void *stream) {
+  if (!bd || (!d_logp && !d_grad && !d_hess && !d_cov && !d_definite)) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_resident(bd));
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
+  if (Nq == 0) return KDEHIP_OK;
+  DeviceGuard guard;
+  KDEHIP_CHECK_RC(guard.enter(bd->device));
+  CurvRun run;
+  run.items.push_back(resident_curv_item(bd, Nq));
+  run.circ.push_back(circ);
+  KDEHIP_CHECK_RC(run.alloc(0, 0));
+  CurvItem &ri = run.items[0];
+  ri.qry = d_pos;
+  ri.logp = d_logp; ri.grad = d_grad; ri.hess = d_hess; ri.cov = d_cov; ri.definite = d_definite;
+  KDEHIP_CHECK_RC(run.start(static_cast<hipStream_t>(stream)));
+  KDEHIP_CHECK_RC(run.run());
+  return run.defer(bd->device);
+}
+
+extern "C" int kdehip_evaluate_hess_device_batch(int n, const kdehip_hess_item *items, void *stream) {
+  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "curvature batch: bad item list");
+  if (n == 0) return KDEHIP_OK;
+  for (int i = 0; i < n; ++i) {
+    const kdehip_hess_item &h = items[i];
+    KDEHIP_CHECK_RC(check_resident(h.bd));
+    if (h.bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "curvature batch: densities on different devices");
+    if (h.circular_mask >> h.bd->D)
+      return set_error(KDEHIP_ERR_ARG, "curvature batch: circular_mask names a dimension the density does not have");
+    if (h.Nq < 0 || (h.Nq > 0 && !h.d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
+    if (!h.d_logp && !h.d_grad && !h.d_hess && !h.d_cov && !h.d_definite) return set_error(KDEHIP_ERR_ARG, "null argument");
+  }
+  const int device = items[0].bd->device;
+  DeviceGuard guard;
+  KDEHIP_CHECK_RC(guard.enter(device));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  CaptureScope scope(st);
+  CurvRun run;
+  for (int i = 0; i < n; ++i) {
+    const kdehip_hess_item &h = items[i];
+    if (h.Nq == 0) continue;
+    CurvItem it = resident_curv_item(h.bd, h.Nq);
+    it.qry = h.d_pos;
+    it.logp = h.d_logp; it.grad = h.d_grad; it.hess = h.d_hess; it.cov = h.d_cov; it.definite = h.d_definite;
+    run.items.push_back(it);
+    run.circ.push_back(h.circular_mask);
+  }
+  if (run.items.empty()) return KDEHIP_OK;
+  KDEHIP_CHECK_RC(run.alloc(0, 0));
+  KDEHIP_CHECK_RC(run.start(st));
+  KDEHIP_CHECK_RC(run.run());
   return scope.capturing() ? run.keep(device) : run.defer(device);
 }

@@ -876,6 +876,48 @@ from different modes.
 hip_getKDEMode(bd::BallTreeDensity; kwargs...) = hip_modes(bd; kwargs...)[1][:, 1]
 
 """
+    hip_evaluate_hess(bd, pos; manifold=nothing, device=0)
+
+`(logp, grad, hess, cov, definite)` at the columns of `pos` (`kdehip_evaluate_hess`, include/kdehip.h section 5k): `log p`,
+its gradient (`D x Nq`), its Hessian `H_kl = S_kl / (S_0 v_k v_l) - delta_kl / v_k - g_k g_l` (`D x D x Nq`, symmetric bit
+for bit), `cov = (-H)^-1` by Cholesky and `definite` (`Bool`, `Nq`): where a pivot fails -- a saddle, a minimum, a flat
+direction -- `definite` is false and that `cov[:, :, q]` is NaN.  The library's own: not installed by `enable!()`.
+"""
+function hip_evaluate_hess(bd::BallTreeDensity, pos::AbstractMatrix{Float64}; manifold=nothing, device::Int=0)
+  D = Ndim(bd)
+  D == size(pos, 1) || error("bd and pos must have the same dimension")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  Nq = size(pos, 2)
+  logp = zeros(Nq)
+  grad = zeros(D, Nq)
+  hess = zeros(D, D, Nq)
+  cov = zeros(D, D, Nq)
+  definite = zeros(Int32, Nq)
+  cd = Ref(CDensity(bd))
+  posd = Matrix{Float64}(pos)
+  GC.@preserve bd posd man begin
+    check(ccall((:kdehip_evaluate_hess, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Cint,
+                 Ptr{UInt8}),
+                cd, posd, Nq, logp, grad, hess, cov, definite, device, man))
+  end
+  return logp, grad, hess, cov, definite .!= 0
+end
+
+"""
+    hip_fit_modes(bd, starts=nothing; kwargs...)
+
+`(means, covs, mass, logp, definite)`: `hip_modes(bd, starts; kwargs...)`, then `hip_evaluate_hess` at the modes -- a Gaussian
+per mode, in descending `logp`.  `mass` is the basin mass of `hip_modes`, not a Laplace evidence.
+"""
+function hip_fit_modes(bd::BallTreeDensity, starts::Union{Nothing,AbstractMatrix{Float64}}=nothing; manifold=nothing,
+                       device::Int=0, kwargs...)
+  means, logp, mass, _ = hip_modes(bd, starts; manifold=manifold, device=device, kwargs...)
+  _, _, _, covs, definite = hip_evaluate_hess(bd, means; manifold=manifold, device=device)
+  return means, covs, mass, logp, definite
+end
+
+"""
     hip_getKDEMax(p; N=200, device=0)
 
 `getKDEMax(p; N)` (src/DualTree01.jl:558-570) on the GPU (`kdehip_kde_max`, include/kdehip.h section 5c): per dimension the

@@ -338,6 +338,22 @@ class DeviceDensity:
         from .modes import evaluate_grad
         return evaluate_grad(self, pos, log=log, manifold=manifold)
 
+    def evaluate_hess(self, pos, *, log=True, manifold=None):
+        """(log p, its gradient, its Hessian) at the columns of `pos` (kdehip_evaluate_hess_device, include/kdehip.h section
+        5k): `kdehip.evaluate_hess` of this density."""
+        from .curvature import evaluate_hess
+        return evaluate_hess(self, pos, log=log, manifold=manifold)
+
+    def laplace(self, pos, *, manifold=None):
+        """(cov, definite) at the columns of `pos`: `kdehip.laplace` of this density."""
+        from .curvature import laplace
+        return laplace(self, pos, manifold=manifold)
+
+    def fit_modes(self, starts=None, **kw):
+        """(means, covs, mass, logp, definite): `kdehip.fit_modes` of this density."""
+        from .curvature import fit_modes
+        return fit_modes(self, starts, **kw)
+
     def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None, manifold=None):
         """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):
         d_pts float64[D*Npts] (column-major D x Npts), d_ind int64[Npts] (1-based original indices), `ind` an optional
