@@ -1229,6 +1229,107 @@ typedef struct kdehip_hess_item {
  * Every item's results are bit for bit those of kdehip_evaluate_hess_device. */
 int kdehip_evaluate_hess_device_batch(int n, const kdehip_hess_item *items, void *stream);
 
+/* ---- (5l) the probability mass of a density: box mass, marginal cdf and quantiles ------------------------------------------
+ * How much of a belief lies somewhere?  getKDERange (5c) is a support box, not a probability.  For a Gaussian-kernel density
+ * with ONE bandwidth vector the mass of an axis-aligned box and the quantiles of a marginal have exact expressions; the entries
+ * below evaluate them (csrc/mass.hip; this library's own, the reference has no counterpart).  The density bd has dimension D,
+ * leaves i in LEAF ORDER, centres c_i, weights w_i and ONE bandwidth vector v (the rule of section 5: per-point bandwidths
+ * are KDEHIP_ERR_UNSUPPORTED, in evaluate's words).
+ *   dim_mask    (64 bits wide) bit d set = dimension d is bounded.  B = the bounded dimensions, ascending, nb = |B|.  Required:
+ *               1 <= nb <= D and no bit at or above D, otherwise KDEHIP_ERR_ARG.  An unbounded dimension contributes the
+ *               factor 1 and is never read.
+ *   a query     lo[q], hi[q]: nb values each, in the order of B.  -Inf and +Inf are bounds like any other.
+ * Box mass.  For k in B, s_k = 1.0 / sqrt(2 v_k), the root and the division correctly rounded, formed once and not per pair.
+ * For a pair (q, i) and k in B, with a = (lo_k - c_ik) * s_k and b = (hi_k - c_ik) * s_k (difference, then product):
+ *   f_ik = 0                                  if !(a < b)    (empty or degenerate; also what a NaN gives inside the sweep)
+ *        = (erfc(a) - erfc(b)) / 2            if a >= 0      (the box lies right of the centre)
+ *        = (erfc(-b) - erfc(-a)) / 2          if b <= 0      (left of it)
+ *        = 1 - (erfc(-a) + erfc(b)) / 2       otherwise      (it holds the centre)
+ *   mass[q] = sum_i w_i prod_{k in B, ascending} f_ik
+ * The three forms keep every difference in the tail where it is relatively accurate (the cdf form Phi(b) - Phi(a) loses all
+ * digits beyond 8 bandwidths on the right); they are part of the contract so that a model and the device share the formula.
+ * erfc is the device library's; its error, measured against the host libm's erfc over [0, 26], is in DESIGN.md section
+ * 24.  A leaf with w_i == 0 adds nothing.  A NaN in any bound of a query makes mass[q] NaN: the finish kernel asks this of the
+ * bounds themselves, as 5j words it for positions; no other query changes by a bit.  lo_k >= hi_k in any bounded dimension
+ * gives exactly 0.
+ * The sum is split as in 5b / 5f / 5h: consecutive 128-leaf chunks in groups that depend on (npts, Nq) alone; within a
+ * chunk w_i * (the product, k ascending from f_i,B_0) is summed from 0 in leaf order (a product, then a sum: no fma), the
+ * chunk's sum is added to the group's, and the groups are combined in group order.  No atomics.  Host, resident and batched
+ * calls return the same bits, run after run.
+ * Quantile.  For ONE dimension k (0-based `dim`) the marginal cdf and pdf are
+ *   F_k(x) = (sum_i w_i erfc(-t_i)) / 2,   f_k(x) = (sum_i w_i exp(-t_i^2)) * (s_k / sqrt(pi)),   t_i = (x - c_ik) * s_k
+ * (F_k is the box mass with B = {k}, lo = -Inf, hi = x), and for a level alpha[q] in (0, 1) x[q] solves F_k(x) = alpha[q] by
+ * a bracketed Newton iteration on the device:
+ *   bracket     [xl, xh] = [cmin - 39 sigma_k, cmax + 39 sigma_k], sigma_k = sqrt(v_k), cmin and cmax over the leaves with
+ *               w_i > 0: erfc(39 / sqrt 2) underflows, so F_k is exactly 0 at xl and exactly (sum_i w_i erfc(-t_i)) / 2 with
+ *               every erfc equal to 2 -- the total weight -- at xh.
+ *   iterate     the first x is 0.5 * (xl + xh).  After each evaluation r = F_k(x) - alpha: r < 0 moves xl to x, otherwise xh
+ *               moves to x.  The next x is the Newton point x - r / f_k(x) if f_k(x) > 0, the point lies strictly inside
+ *               (xl, xh) AND (the rtsafe rule) |2 r / f_k(x)| <= |the step before last|; otherwise it is xl + 0.5 * (xh - xl).
+ *               "The step before last" is the distance moved two iterates ago, a bisection counting as half its bracket; for
+ *               the first two decisions it is the width of the start bracket.  So a Newton step that no longer halves the
+ *               step before last forces a bisection.
+ *   stop        when |r| <= tol (converged = 1) or after max_iter evaluations (converged = 0).  tol (a HOST pointer to one
+ *               double, as kdehip_meanshift takes its tol; NULL means the default) is absolute in F: *tol must be finite and
+ *               >= 1e-14, and 0 means the default 1e-12; max_iter must be >= 1, and 0 means the default 100; anything else
+ *               is KDEHIP_ERR_ARG.
+ *   outputs     x [Nq]; optional (NULL to skip) resid [Nq] = F_k(x) - alpha at the returned x, iters [Nq] int32 = the number
+ *               of evaluations, converged [Nq] int32.
+ *   An alpha outside (0, 1) or NaN gives x = resid = NaN, iters = 0, converged = 0 for that level only; so does a density
+ *   none of whose leaves has w_i > 0.
+ * Order of the sums: lane t of the 256 adds its leaves i = t, t + 256, ... in that order (w_i * erfc(-t_i), w_i * exp(-t_i^2)),
+ * the 256 partial sums are combined in a fixed halving tree.  Host, resident and batched calls therefore return the same bits.
+ * `manifold` as in 5d.  A bounded dimension, or the quantile's dimension, that is circular is KDEHIP_ERR_UNSUPPORTED (the mass
+ * of an arc needs the wrapped kernel); circular dimensions that are not bounded are fine: they contribute the factor 1.
+ * The _device and _device_batch entries are enqueue-only: they do not synchronise the host, and a capture of ONE stream into a
+ * HIP graph can hold them, under the rules of kdehip_meanshift_device_batch (5h): the blocks of a captured call are kept until
+ * kdehip_clear_cache, which INVALIDATES every graph captured from these entries.
+ * Errors, all checked before any device is touched: null arguments, Nq < 0, a bad dim_mask or dim, a manifold byte above 1 or
+ * a circular_mask bit at or above D, a bad tol or max_iter, densities on different devices within one batch --
+ * KDEHIP_ERR_ARG; D outside 1..KDEHIP_MAX_DIMS, per-point bandwidths, a circular bounded dimension or a circular quantile
+ * dimension -- KDEHIP_ERR_UNSUPPORTED.  Nq == 0 and n == 0 are KDEHIP_OK.  fp64 only.
+ * Not here: circular bounded dimensions, rotated boxes, joint multi-dimensional quantile regions, per-point bandwidths. */
+/* Host density, host arrays, blocking.  lo, hi [Nq][nb]; mass [Nq]. */
+int kdehip_box_mass(const kdehip_density *bd, uint64_t dim_mask, const double *lo, const double *hi, int64_t Nq, double *mass,
+                    int device, const uint8_t *manifold);
+/* Resident density, device arrays, enqueue only on `stream` (hipStream_t, NULL = the null stream). */
+int kdehip_box_mass_device(const kdehip_device_density *bd, uint64_t dim_mask, const double *d_lo, const double *d_hi, int64_t Nq,
+                           double *d_mass, const uint8_t *manifold, void *stream);
+typedef struct kdehip_box_mass_item {
+  const kdehip_device_density *bd;
+  const double *d_lo;       /* device, [Nq][nb] */
+  const double *d_hi;       /* device, [Nq][nb] */
+  int64_t Nq;
+  double *d_mass;           /* device, [Nq] */
+  uint64_t dim_mask;        /* bit d = dimension d is bounded */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+  uint32_t reserved_;
+} kdehip_box_mass_item;
+/* Many resident items (mixed D, N, Nq and masks) on one device, enqueue only on `stream`: one sweep launch per distinct nb
+ * and ONE finish launch for all items together.  Every item's results are bit for bit those of kdehip_box_mass_device. */
+int kdehip_box_mass_device_batch(int n, const kdehip_box_mass_item *items, void *stream);
+/* Host density, host arrays, blocking.  alpha [Nq]; x [Nq]; resid, iters, converged [Nq] or NULL. */
+int kdehip_quantile(const kdehip_density *bd, int dim, const double *alpha, int64_t Nq, const double *tol, int max_iter, double *x,
+                    double *resid, int32_t *iters, int32_t *converged, int device, const uint8_t *manifold);
+/* Resident density, device arrays, enqueue only on `stream`. */
+int kdehip_quantile_device(const kdehip_device_density *bd, int dim, const double *d_alpha, int64_t Nq, const double *tol,
+                           int max_iter, double *d_x, double *d_resid, int32_t *d_iters, int32_t *d_converged, const uint8_t *manifold,
+                           void *stream);
+typedef struct kdehip_quantile_item {
+  const kdehip_device_density *bd;
+  const double *d_alpha;    /* device, [Nq] */
+  int64_t Nq;
+  double *d_x;              /* device, [Nq] */
+  double *d_resid;          /* device, [Nq], or NULL */
+  int32_t *d_iters;         /* device, [Nq], or NULL */
+  int32_t *d_converged;     /* device, [Nq], or NULL */
+  int32_t dim;              /* the marginal's dimension, 0-based */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+} kdehip_quantile_item;
+/* Many resident items (mixed D, N, Nq and dimensions) on one device, enqueue only on `stream`: ONE launch for all levels of
+ * all items.  Every item's results are bit for bit those of kdehip_quantile_device with the same tol and max_iter. */
+int kdehip_quantile_device_batch(int n, const kdehip_quantile_item *items, const double *tol, int max_iter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

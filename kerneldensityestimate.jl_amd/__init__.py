@@ -4,8 +4,9 @@ This package is the Python host mirror of the reference's interface for that pat
 (`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`,
 `sample/rand/resample`, `evalAvgLogL/entropy/kld/minkld`, `evaluate_log`, `marginal`, `getKDERange/getKDEMax/getKDEMean/getKDEfit`,
 `intersIntgAppxIS`, and the library's own exact overlap measures `intersIntg/ise/mmd` and joint modes
-`evaluate_grad/meanshift/modes/getKDEMode`, their curvature `evaluate_hess/laplace/fit_modes/getKDEModeFit` and conditionals
-`condition/conditional_weights/conditional_moments/sample_conditional`)
+`evaluate_grad/meanshift/modes/getKDEMode`, their curvature `evaluate_hess/laplace/fit_modes/getKDEModeFit`, conditionals
+`condition/conditional_weights/conditional_moments/sample_conditional` and probability masses
+`box_mass/cdf/quantile/median/interval/grid_mass`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
 """
@@ -23,6 +24,8 @@ from .modes import evaluate_grad, getKDEMode, meanshift, meanshift_device_batch,
 from .curvature import evaluate_hess, evaluate_hess_device_batch, fit_modes, getKDEModeFit, laplace  # noqa: F401
 from .conditional import (condition, conditional_device_batch, conditional_moments, conditional_weights,  # noqa: F401
                           sample_conditional)
+from .mass import (box_mass, box_mass_device_batch, cdf, grid_mass, interval, median, quantile,  # noqa: F401
+                   quantile_device_batch)
 from .summary import (getKDEfit, getKDEMax, getKDEMean, getKDERange, getKDERangeLinspace, intersIntgAppxIS,  # noqa: F401
                       marginal, summary_device_batch)
 

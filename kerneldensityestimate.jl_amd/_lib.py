@@ -84,6 +84,18 @@ class CHessItem(C.Structure):
                 ("reserved_", C.c_uint32)]
 
 
+class CBoxMassItem(C.Structure):
+    """struct kdehip_box_mass_item"""
+    _fields_ = [("bd", C.c_void_p), ("d_lo", C.c_void_p), ("d_hi", C.c_void_p), ("Nq", C.c_int64), ("d_mass", C.c_void_p),
+                ("dim_mask", C.c_uint64), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class CQuantileItem(C.Structure):
+    """struct kdehip_quantile_item"""
+    _fields_ = [("bd", C.c_void_p), ("d_alpha", C.c_void_p), ("Nq", C.c_int64), ("d_x", C.c_void_p), ("d_resid", C.c_void_p),
+                ("d_iters", C.c_void_p), ("d_converged", C.c_void_p), ("dim", C.c_int32), ("circular_mask", C.c_uint32)]
+
+
 class CConditionalItem(C.Structure):
     """struct kdehip_conditional_item"""
     _fields_ = [("bd", C.c_void_p), ("d_given", C.c_void_p), ("Nq", C.c_int64), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
@@ -201,6 +213,14 @@ SIGNATURES = {
     "kdehip_evaluate_hess_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, u8p, C.c_void_p]),
     "kdehip_evaluate_hess_device_batch": (C.c_int, [C.c_int, C.POINTER(CHessItem), C.c_void_p]),
+    "kdehip_box_mass": (C.c_int, [C.POINTER(CDensity), C.c_uint64, f64p, f64p, C.c_int64, f64p, C.c_int, u8p]),
+    "kdehip_box_mass_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, u8p, C.c_void_p]),
+    "kdehip_box_mass_device_batch": (C.c_int, [C.c_int, C.POINTER(CBoxMassItem), C.c_void_p]),
+    "kdehip_quantile": (C.c_int, [C.POINTER(CDensity), C.c_int, f64p, C.c_int64, f64p, C.c_int, f64p, f64p, i32p, i32p,
+                                  C.c_int, u8p]),
+    "kdehip_quantile_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, f64p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, u8p, C.c_void_p]),
+    "kdehip_quantile_device_batch": (C.c_int, [C.c_int, C.POINTER(CQuantileItem), f64p, C.c_int, C.c_void_p]),
     "kdehip_conditional": (C.c_int, [C.POINTER(CDensity), C.c_uint32, f64p, C.c_int64, C.c_uint64, C.c_int64, f64p, f64p, f64p,
                                      f64p, i64p, C.c_int, u8p]),
     "kdehip_conditional_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p,

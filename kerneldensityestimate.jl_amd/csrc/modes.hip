@@ -448,32 +448,7 @@ __global__ __launch_bounds__(kFinishThreads) void curvature_finish_kernel(const 
   }
 }
 
-// While the stream is being captured into a graph the calling thread's capture mode is relaxed (the call allocates and
-// copies), and the call's blocks must outlive the call: they are kept until kdehip_clear_cache (kdehip.h 5h: one pair of
-// blocks per capture, and clearing the cache invalidates the graph).  A call that fails after its upload leaves through
-// ~CallBlock, which synchronises the stream: on a capturing stream that is an error and ends the capture as invalid --
-// what a failed capture should be; the blocks go back to the cache, no node of a usable graph refers to them.
-class CaptureScope {
- public:
-  explicit CaptureScope(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
-      mode_ = hipStreamCaptureModeRelaxed;
-      on_ = hipThreadExchangeStreamCaptureMode(&mode_) == hipSuccess;
-      capturing_ = true;
-    }
-    (void)hipGetLastError();
-  }
-  ~CaptureScope() {
-    if (on_) (void)hipThreadExchangeStreamCaptureMode(&mode_);
-  }
-  bool capturing() const { return capturing_; }
-
- private:
-  hipStreamCaptureMode mode_ = hipStreamCaptureModeGlobal;
-  bool on_ = false, capturing_ = false;
-};
-
+// (CaptureScope, what a call does while its stream is being captured into a graph, is pair_sweep.hpp: mass.hip shares it)
 // The run of one call (pair_sweep.hpp PairRun) with the moments' scratch, per item [partial | frozen | live], and its
 // launches.  Protocol: fill `items` (evaluate items: sizes, D, logdom) and `circ` -> alloc(prefix bytes of caller data,
 // result doubles of the caller, steps?) -> the caller writes its data into host() and points the items at dev() ->

@@ -1,7 +1,8 @@
 // pair_sweep.hpp -- the all-pairs Gaussian sum behind evaluate.hip (eval_partial_kernel, eval_partial_log_kernel) and
 // ksum.hip (ksum_partial_kernel), written ONCE: the head both descriptors start with, a block's place in an item, the sweep
 // over the staged source chunks, the block reduction and the norm on the device; the skeleton of a call's run (EvalRun,
-// KsumRun) and two small readers of a host density on the host.  Included by those two files only.
+// KsumRun), the scope of a call on a capturing stream and two small readers of a host density on the host.  Included by the
+// files of entry points that run the sweep or its mapping (evaluate, ksum, modes, conditional, mass).
 //
 // The sweep: one lane per query point, a block owns kEvalThreads queries and ONE group of consecutive kEvalChunk-point source
 // chunks, which it stages through a two-buffer LDS ring ([point][D coordinates, weight], read back as broadcasts) and walks
@@ -257,6 +258,32 @@ class PairRun {
   CallBlock blk_;
   size_t o_items_ = 0, o_first_ = 0, o_masks_ = 0, o_res_ = 0, nres_ = 0;
   std::vector<int> keys_;
+};
+
+// While the stream is being captured into a graph the calling thread's capture mode is relaxed (the call allocates and
+// copies), and the call's blocks must outlive the call: they are kept until kdehip_clear_cache (kdehip.h 5h: one pair of
+// blocks per capture, and clearing the cache invalidates the graph).  A call that fails after its upload leaves through
+// ~CallBlock, which synchronises the stream: on a capturing stream that is an error and ends the capture as invalid --
+// what a failed capture should be; the blocks go back to the cache, no node of a usable graph refers to them.
+class CaptureScope {
+ public:
+  explicit CaptureScope(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+      mode_ = hipStreamCaptureModeRelaxed;
+      on_ = hipThreadExchangeStreamCaptureMode(&mode_) == hipSuccess;
+      capturing_ = true;
+    }
+    (void)hipGetLastError();
+  }
+  ~CaptureScope() {
+    if (on_) (void)hipThreadExchangeStreamCaptureMode(&mode_);
+  }
+  bool capturing() const { return capturing_; }
+
+ private:
+  hipStreamCaptureMode mode_ = hipStreamCaptureModeGlobal;
+  bool on_ = false, capturing_ = false;
 };
 
 // Every leaf of a host density has its first leaf's bandwidth -- the sums read ONE vector (bandwidthMin[1..D],

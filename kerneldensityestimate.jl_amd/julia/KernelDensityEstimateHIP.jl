@@ -918,6 +918,70 @@ function hip_fit_modes(bd::BallTreeDensity, starts::Union{Nothing,AbstractMatrix
 end
 
 """
+    hip_box_mass(bd, lo, hi; dims=nothing, manifold=nothing, device=0)
+
+The probability that `x[dims]` lies in the box `[lo[:, q], hi[:, q]]` under `bd`, one value per column
+(`kdehip_box_mass`, include/kdehip.h section 5l): `lo` and `hi` are `nb x Nq`, their rows in the order of `dims` (1-based,
+distinct; `nothing`: every dimension).  `-Inf` and `Inf` are bounds like any other, `lo >= hi` in a dimension gives exactly 0,
+a NaN bound gives NaN for that box only.  A circular dimension cannot be bounded.  The library's own: not installed by
+`enable!()`.
+"""
+function hip_box_mass(bd::BallTreeDensity, lo::AbstractMatrix{Float64}, hi::AbstractMatrix{Float64}; dims=nothing,
+                      manifold=nothing, device::Int=0)
+  D = Ndim(bd)
+  dl = dims === nothing ? collect(1:D) : collect(Int, dims)
+  (length(dl) >= 1 && allunique(dl) && all(d -> 1 <= d <= D, dl)) || error("dims must be distinct dimensions of bd, 1-based")
+  (size(lo) == size(hi) && size(lo, 1) == length(dl)) || error("lo and hi hold one row per bounded dimension")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  order = sortperm(dl)
+  mask = UInt64(0)
+  for d in dl
+    mask |= UInt64(1) << (d - 1)
+  end
+  Nq = size(lo, 2)
+  lod = Matrix{Float64}(lo[order, :])
+  hid = Matrix{Float64}(hi[order, :])
+  mass = zeros(Nq)
+  cd = Ref(CDensity(bd))
+  GC.@preserve bd lod hid man begin
+    check(ccall((:kdehip_box_mass, libkdehip), Cint,
+                (Ref{CDensity}, UInt64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Cint, Ptr{UInt8}),
+                cd, mask, lod, hid, Nq, mass, device, man))
+  end
+  return mass
+end
+
+"""
+    hip_quantile(bd, alpha, dim; tol=1e-12, max_iter=100, manifold=nothing, device=0)
+
+`(x, resid, iters, converged)`: the `alpha` quantiles of the marginal of dimension `dim` (1-based) of `bd`
+(`kdehip_quantile`, include/kdehip.h section 5l), by a bracketed Newton iteration on the device: `cdf(x) = alpha` to `tol`
+(absolute in the cdf); `resid = cdf(x) - alpha` at the returned `x`, `iters` the number of cdf evaluations, `converged`
+false where `max_iter` evaluations did not reach `tol`.  An `alpha` outside (0, 1) or NaN gives NaN for that level only.
+"""
+function hip_quantile(bd::BallTreeDensity, alpha::AbstractVector{Float64}, dim::Int; tol::Float64=1e-12, max_iter::Int=100,
+                      manifold=nothing, device::Int=0)
+  D = Ndim(bd)
+  1 <= dim <= D || error("dim must be a dimension of bd, 1-based")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  Nq = length(alpha)
+  av = Vector{Float64}(alpha)
+  tolv = [tol]
+  x = zeros(Nq)
+  resid = zeros(Nq)
+  iters = zeros(Int32, Nq)
+  converged = zeros(Int32, Nq)
+  cd = Ref(CDensity(bd))
+  GC.@preserve bd av tolv man begin
+    check(ccall((:kdehip_quantile, libkdehip), Cint,
+                (Ref{CDensity}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+                 Cint, Ptr{UInt8}),
+                cd, dim - 1, av, Nq, tolv, max_iter, x, resid, iters, converged, device, man))
+  end
+  return x, resid, iters, converged .!= 0
+end
+
+"""
     hip_getKDEMax(p; N=200, device=0)
 
 `getKDEMax(p; N)` (src/DualTree01.jl:558-570) on the GPU (`kdehip_kde_max`, include/kdehip.h section 5c): per dimension the

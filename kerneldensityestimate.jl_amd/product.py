@@ -354,6 +354,27 @@ class DeviceDensity:
         from .curvature import fit_modes
         return fit_modes(self, starts, **kw)
 
+    def box_mass(self, lo, hi, dims=None, *, manifold=None):
+        """the probability of the boxes [lo, hi] over `dims` (kdehip_box_mass_device, include/kdehip.h section 5l):
+        `kdehip.box_mass` of this density."""
+        from .mass import box_mass
+        return box_mass(self, lo, hi, dims, manifold=manifold)
+
+    def cdf(self, x, dim, *, manifold=None):
+        """the marginal cdf of dimension `dim` at `x`: `kdehip.cdf` of this density."""
+        from .mass import cdf
+        return cdf(self, x, dim, manifold=manifold)
+
+    def quantile(self, alpha, dim, **kw):
+        """the `alpha` quantiles of the marginal of dimension `dim` (kdehip_quantile_device): `kdehip.quantile` of this density."""
+        from .mass import quantile
+        return quantile(self, alpha, dim, **kw)
+
+    def interval(self, dim, level=0.95, **kw):
+        """(lo, hi), the central credible interval of dimension `dim`: `kdehip.interval` of this density."""
+        from .mass import interval
+        return interval(self, dim, level, **kw)
+
     def sample_device(self, d_pts, d_ind, Npts, *, seed, sample_offset=0, ind=None, stream=None, manifold=None):
         """`sample(p, Npts[, ind])` (reference src/KDE01.jl:164-189) into caller device arrays (torch tensors or addresses):
         d_pts float64[D*Npts] (column-major D x Npts), d_ind int64[Npts] (1-based original indices), `ind` an optional
