@@ -522,7 +522,9 @@ int kdehip_product_multi_timing(kdehip_product_multi *mp, double *kernel_ms, dou
  * preparation + every round of a search, per batch of rounds), kdehip_evaluate (which = 1: the partial and finish
  * kernels) and the GPU tree builder (which = 2: kdehip_make_densities_device's kernel) bracket their launches with a pair
  * of timing events; this returns the sum of those durations and the number of bracketed phases since the last read, and
- * resets both (process-wide sums).  bench.py --frow reports them as kernel time. */
+ * resets both (process-wide sums).  bench.py --frow reports them as kernel time.  kdehip_evaluate_tol (section 5m) adds, in
+ * the same way, its three passes one by one: which = 3 the chunk boxes, 4 the plan, 5 the sweep over the flagged chunks
+ * (which = 1 is then the whole call: the three passes and the finish kernel). */
 int kdehip_profile_phase_read(int which, double *total_ms, int64_t *count);
 /* The fp32 screen of the deep levels (csrc/screen_device.hpp) certifies its decisions with an error bound whose premise is
  * that the hardware's v_rcp_f32, v_rsq_f32 and v_exp_f32 are within 1 ulp (a relative error of at most 2 u, u = 2^-24).
@@ -1329,6 +1331,64 @@ typedef struct kdehip_quantile_item {
 /* Many resident items (mixed D, N, Nq and dimensions) on one device, enqueue only on `stream`: ONE launch for all levels of
  * all items.  Every item's results are bit for bit those of kdehip_quantile_device with the same tol and max_iter. */
 int kdehip_quantile_device_batch(int n, const kdehip_quantile_item *items, const double *tol, int max_iter, void *stream);
+
+/* ---- (5m) evaluation within a tolerance: the all-pairs sum pruned on the ball tree ------------------------------------------
+ * The reference's other evaluation mode, setForceEvalDirect!(false): a pair of balls is left alone once their boxes show it
+ * can no longer move the result by errTol (src/DualTree01.jl:248-299).  Here the balls are the sweep's own: the leaves are in
+ * LEAF ORDER, so every chunk of 128 consecutive leaves is a compact ball of the tree, and a query block is 256 consecutive
+ * queries in the order the entry processes them.  With p what kdehip_evaluate (section 5) defines, every query q gets
+ *   p(q) * (1 - rel_tol) - abs_tol  <=  p_hat(q)  <=  p(q)                                     (up to rounding, below)
+ * -- a truncation: only non-negative terms are left out, p_hat is never above p; it is not the reference's midpoint of two
+ * bounds.  The density has dimension D, N leaves i with centres c_i and weights w_i, ONE bandwidth vector v, and
+ * nh_k = -0.5 / v_k (one correctly rounded division), as in section 5.  The rule (csrc/evaltol.hip):
+ *  1. Chunk boxes.  For chunk c (the leaves 128 c .. min(128 c + 127, N - 1)): lo_c[k], hi_c[k] = the least and the largest
+ *     c_ik over its leaves, W_c = the sum of its weights from 0 in leaf order.
+ *  2. Bounds of a pair (q, c), by the sweep's own chain -- acc = fma(d * d, nh_k, acc), from 0, k ascending:
+ *       a_min(q, c) with d = dmin_k = max(0, lo_c[k] - x_qk, x_qk - hi_c[k]),
+ *       a_max(q, c) with d = dmax_k = max(|lo_c[k] - x_qk|, |x_qk - hi_c[k]|);
+ *     in a circular dimension the box is not used: dmin_k = 0 and dmax_k = pi (1 + 2^-20) (pi as fp64 rounds it; the factor
+ *     covers the rounding of the wrap).  Every leaf i of c has a_max <= a_i <= a_min, for the COMPUTED values: each
+ *     operation of the chain is monotone in |d| and correctly rounded, so no margin is needed on a_min.
+ *  3. A lower bound L_q of the unnormalised sum, the larger of
+ *       sum over c, ascending, of W_c * exp(a_max(q, c)), and
+ *       the exact partial sum of the chunk with the largest a_min(q, c) (ties: the lowest c), as the sweep forms it:
+ *       sum over its leaves in leaf order of w_i exp(a_i).
+ *     For leave-one-out the query is leaf q of the density: the first bound then leaves out the whole chunk q / 128 (the
+ *     weight W_c - w_q of its other leaves cannot be formed without cancellation), the second the term i == q alone.
+ *  4. tau_q = max(rel_tol * L_q, abs_tol * norm), norm the Gaussian constant of section 5.  Chunk c is NEEDED by q iff
+ *     tau_q == 0 or a_min(q, c) > log(tau_q) - 2^-20.  The 2^-20 is the rounding margin: it lowers tau_q by one part in a
+ *     million, a thousand times more than the errors it has to cover (the exponential's and the logarithm's few ulp, the
+ *     N / 128 + 128 additions behind L_q, and sum_i w_i = 1 only to N ulp).  A tile (query block, chunk) is VISITED iff some
+ *     live query of the block needs the chunk; live = q < Nq and no NaN coordinate.
+ *  5. The result: the direct sweep of section 5 restricted to the visited tiles -- the same groups of consecutive chunks
+ *     (a function of (N, Nq) alone), the same chunk order within a group, the same arithmetic per pair; a group with no
+ *     visited chunk contributes 0 -- and then the same finish: the groups in group order, / norm, / (1 - w_q) for
+ *     leave-one-out, NaN for a query with a NaN coordinate, output through the permutation.
+ * Why it holds: a skipped term has a_i <= a_min <= log tau_q - 2^-20, so what q loses is at most tau_q sum_c W_c <= tau_q,
+ * and rel_tol * L_q <= rel_tol * (the unnormalised p).  "Up to rounding": p_hat and p are two fp64 sums of the kept terms in
+ * the same order, so they differ from the exact bound by what any two such sums may differ, some N ulp.
+ * Consequences: rel_tol == abs_tol == 0 visits every tile and returns kdehip_evaluate's bits; the result depends on the
+ * density, the queries IN THEIR PROCESSING ORDER (which queries share a block) and the two tolerances alone, so it is the
+ * same run after run and between the two entries.  No atomics.
+ *   rel_tol, abs_tol   HOST pointers to one double each, as kdehip_quantile takes its tol.  NULL rel_tol = 1e-3 (the
+ *                      reference's default errTol), NULL abs_tol = 0.  Required: 0 <= rel_tol < 1, 0 <= abs_tol < Inf;
+ *                      anything else, NaN included, is KDEHIP_ERR_ARG.
+ *   stats              int64[2] or NULL: the tiles visited, and the tiles in all = ceil(Nq / 256) * ceil(N / 128).
+ * Errors, all checked before any device is touched: the tolerances and those of kdehip_evaluate / kdehip_evaluate_device_at
+ * with their codes (per-point bandwidths and D above KDEHIP_MAX_DIMS are KDEHIP_ERR_UNSUPPORTED).  fp64 only.
+ * Not here: batches of many small items (two chunks leave nothing to prune), tolerance forms of the log-domain entries, of
+ * the log-likelihoods, the gradients and the kernel sums, per-point bandwidths. */
+/* Host density, host arrays, blocking.  The queries are processed in the given order; leave_one_out processes the density's
+ * leaves in leaf order and returns the values in original point order, as kdehip_evaluate does. */
+int kdehip_evaluate_tol(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, const double *rel_tol,
+                        const double *abs_tol, double *p_out, int64_t *stats, int device, const uint8_t *manifold);
+/* Resident densities: at's leaves in leaf order are the queries, d_out [at's npts] in at's original point order; at == bd is
+ * leave-one-out.  d_stats: DEVICE int64[2] or NULL.  Enqueue only on `stream`: no read-back between the passes, so a capture
+ * of ONE stream into a HIP graph can hold the call, under the rules of kdehip_meanshift_device_batch (5h): the blocks of a
+ * captured call are kept until kdehip_clear_cache, which INVALIDATES every graph captured from this entry.  Bit for bit
+ * kdehip_evaluate_tol of the same densities' host arrays. */
+int kdehip_evaluate_device_at_tol(const kdehip_device_density *bd, const kdehip_device_density *at, const double *rel_tol,
+                                  const double *abs_tol, double *d_out, int64_t *d_stats, void *stream, const uint8_t *manifold);
 
 #ifdef __cplusplus
 }

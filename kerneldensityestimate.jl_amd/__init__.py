@@ -2,7 +2,7 @@
 
 This package is the Python host mirror of the reference's interface for that path
 (`kde!`, `BallTreeDensity`, `getPoints/getBW/getWeights`, `Npts/Ndim`, `prodAppxMSGibbsS`, `gibbs1`,
-`sample/rand/resample`, `evalAvgLogL/entropy/kld/minkld`, `evaluate_log`, `marginal`, `getKDERange/getKDEMax/getKDEMean/getKDEfit`,
+`sample/rand/resample`, `evalAvgLogL/entropy/kld/minkld`, `evaluate_log`, `evaluate_tol/setForceEvalDirect`, `marginal`, `getKDERange/getKDEMax/getKDEMean/getKDEfit`,
 `intersIntgAppxIS`, and the library's own exact overlap measures `intersIntg/ise/mmd` and joint modes
 `evaluate_grad/meanshift/modes/getKDEMode`, their curvature `evaluate_hess/laplace/fit_modes/getKDEModeFit`, conditionals
 `condition/conditional_weights/conditional_moments/sample_conditional` and probability masses
@@ -26,6 +26,7 @@ from .conditional import (condition, conditional_device_batch, conditional_momen
                           sample_conditional)
 from .mass import (box_mass, box_mass_device_batch, cdf, grid_mass, interval, median, quantile,  # noqa: F401
                    quantile_device_batch)
+from .evaltol import evaluate_tol, getForceEvalDirect, setForceEvalDirect  # noqa: F401
 from .summary import (getKDEfit, getKDEMax, getKDEMean, getKDERange, getKDERangeLinspace, intersIntgAppxIS,  # noqa: F401
                       marginal, summary_device_batch)
 

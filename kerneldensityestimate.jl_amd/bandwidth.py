@@ -82,7 +82,12 @@ def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, d
     """`evaluateDualTree(bd, pos, lvFlag)` (src/DualTree01.jl:370-421) with FORCE_EVAL_DIRECT = true
     (errTol is then unused, as in the reference).  pos: (D, Nq) matrix, a vector of 1-D positions, or a
     BallTreeDensity whose points are used; lvFlag=True (or pos is bd) evaluates leave-one-out at bd's
-    own points and returns the values in the original point order."""
+    own points and returns the values in the original point order.
+    After `setForceEvalDirect(False)` the call is `evaluate_tol(bd, pos, rel_tol=errTol, lvFlag=lvFlag)`: the sum pruned on
+    the ball tree, within the relative tolerance errTol from below (include/kdehip.h section 5m)."""
+    from . import evaltol
+    if not evaltol.getForceEvalDirect():
+        return evaltol.evaluate_tol(bd, pos, rel_tol=errTol, lvFlag=lvFlag, device=device, manifold=manifold)
     return _evaluate(_lib.lib.kdehip_evaluate_manifold, bd, pos, lvFlag, device, manifold)
 
 

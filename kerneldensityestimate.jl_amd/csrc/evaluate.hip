@@ -19,6 +19,8 @@
 //                           (or -Inf if a flag is up) into one double.
 // Log-domain items (kdehip.h section 5f: log p by log-sum-exp, finite where p underflows) run eval_partial_log_kernel<D> and
 // eval_finish_log_kernel in launches of their own, with the same sweep, split and reduction.
+// Evaluation within a tolerance (kdehip.h section 5m: kdehip_evaluate_tol, kdehip_evaluate_device_at_tol) is the same run
+// with the three passes of evaltol.hip in the place of eval_partial_kernel; the finish kernel does not know the difference.
 // The group split (split_chunks(N, Nq, 1)) depends on the item's (N, Nq) alone, so nothing depends on the launch or the
 // batch: the host entry, a single device call and any batch give the same bits.
 #include <hip/hip_runtime.h>
@@ -31,6 +33,7 @@
 
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
+#include "evaltol.hpp"
 #include "manifold_arg.hpp"
 #include "fastexp.hpp"
 #include "kdehip_internal.hpp"
@@ -252,7 +255,8 @@ __global__ void logl_reduce_kernel(const EvalItem *__restrict__ items, int n) {
 // log-likelihood), or as many as a blocking caller asks alloc for (the host evaluation's Nq values).
 class EvalRun : public PairRun<EvalItem> {
  public:
-  int alloc(size_t prefix, size_t nresults = 0) {  // nresults == 0: one per item
+  // (`extra`: bytes of further scratch behind the items', for the passes of a tolerance-bounded evaluation)
+  int alloc(size_t prefix, size_t nresults = 0, size_t extra = 0) {  // nresults == 0: one per item
     const size_t n = items.size();
     int64_t pblocks = 0, fblocks = 0;
     for (EvalItem &it : items) {
@@ -268,9 +272,11 @@ class EvalRun : public PairRun<EvalItem> {
       const EvalItem &it = items[k];
       scratch_[k] = c.take(sizeof(double) * ((it.logdom ? 2 : 1) * it.ngroups * it.Nq + it.nfb) + sizeof(int32_t) * it.nfb);
     }
+    o_extra_ = c.take(extra);
     KDEHIP_CHECK(alloc_block(c));
     return KDEHIP_OK;
   }
+  unsigned char *extra() const { return dev() + o_extra_; }
   int enqueue(hipStream_t st) {
     KDEHIP_CHECK_RC(upload(st));
     return launch();
@@ -295,8 +301,11 @@ class EvalRun : public PairRun<EvalItem> {
   // the launches behind the upload: two kernels (and their log-domain twins for the log-domain items), and the per-item
   // reduce when an item asks for a log-likelihood
   int launch() {
+    KDEHIP_CHECK_RC(launch_sweep());
+    return launch_finish();
+  }
+  int launch_sweep() {
     const hipStream_t st = stream();
-    const size_t n = items.size();
     // one launch per distinct D, and one more for its circular and for its log-domain items
     KDEHIP_CHECK_RC(for_each_run([&](const EvalItem &it, const EvalItem *d_it, const int32_t *d_pfirst, int cnt, int blocks,
                                      const uint32_t *d_masks) -> int {
@@ -312,6 +321,11 @@ class EvalRun : public PairRun<EvalItem> {
       KDEHIP_CHECK(hipGetLastError());
       return KDEHIP_OK;
     }));
+    return KDEHIP_OK;
+  }
+  int launch_finish() {
+    const hipStream_t st = stream();
+    const size_t n = items.size();
     const int32_t *ffirst = first(1);
     size_t nd = 0;  // the direct items are the first nd
     while (nd < n && !items[nd].logdom) ++nd;
@@ -330,6 +344,7 @@ class EvalRun : public PairRun<EvalItem> {
 
  private:
   std::vector<size_t> scratch_;
+  size_t o_extra_ = 0;
 };
 
 }  // namespace
@@ -378,10 +393,83 @@ extern "C" int kdehip_evaluate(const kdehip_density *bd, const double *pos, int6
   return kdehip_evaluate_manifold(bd, pos, Nq, leave_one_out, p_out, device, nullptr);
 }
 
+namespace {
+
+// The tolerances of an evaluation within a tolerance (section 5m), and where its tile counts go: a host int64[2] for the
+// blocking entry, a device one for the resident entry, or null.
+struct TolArgs {
+  double rel_tol, abs_tol;
+  int64_t *stats;
+};
+
+// NULL rel_tol: the reference's default errTol, 1e-3; NULL abs_tol: 0
+int read_tolerances(const double *rel_tol, const double *abs_tol, TolArgs *out) {
+  out->rel_tol = rel_tol ? *rel_tol : 1e-3;
+  out->abs_tol = abs_tol ? *abs_tol : 0.0;
+  if (!(out->rel_tol >= 0.0 && out->rel_tol < 1.0))
+    return set_error(KDEHIP_ERR_ARG, "evaluate_tol: rel_tol must lie in [0, 1)");
+  if (!(out->abs_tol >= 0.0 && out->abs_tol < INFINITY))
+    return set_error(KDEHIP_ERR_ARG, "evaluate_tol: abs_tol must be finite and >= 0");
+  return KDEHIP_OK;
+}
+
+// four events around the three passes while kdehip_profile_sampler is on (kdehip_profile_phase_read 3..5); otherwise none
+class TolMarks {
+ public:
+  explicit TolMarks(bool wanted) {
+    if (!wanted || !profile_phases_on()) return;
+    for (hipEvent_t &e : ev_)
+      if (hipEventCreate(&e) != hipSuccess) { e = nullptr; drop(); return; }
+    on_ = true;
+  }
+  TolMarks(const TolMarks &) = delete;
+  TolMarks &operator=(const TolMarks &) = delete;
+  ~TolMarks() { drop(); }
+  hipEvent_t *events() { return on_ ? ev_ : nullptr; }
+  // once the stream has been synchronised by the caller
+  void collect() {
+    for (int k = 0; on_ && k < 3; ++k) {
+      float ms = 0.0f;
+      if (hipEventElapsedTime(&ms, ev_[k], ev_[k + 1]) == hipSuccess) profile_phase_add(kPhaseTolBox + k, ms);
+    }
+    drop();
+  }
+
+ private:
+  void drop() {
+    for (hipEvent_t &e : ev_) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    on_ = false;
+  }
+  hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool on_ = false;
+};
+
+// the passes that take the direct sweep's place for item 0 of a run that has been uploaded, with tol_scratch_bytes of `extra`
+int enqueue_tol(const EvalRun &run, uint32_t circ, const TolArgs &tol, int64_t *d_stats, hipStream_t st,
+                hipEvent_t *marks = nullptr) {
+  const EvalItem &it = run.items[0];
+  TolPass t{};
+  t.src = it.src; t.w = it.w; t.qry = it.qry; t.bw = it.bw;
+  t.N = it.N; t.Nq = it.Nq; t.chunks_per_group = it.chunks_per_group;
+  t.ngroups = it.ngroups; t.D = it.D; t.loo = it.loo;
+  t.circ = circ;
+  t.norm0 = it.norm0; t.rel_tol = tol.rel_tol; t.abs_tol = tol.abs_tol;
+  t.partial = it.partial;
+  t.scratch = run.extra();
+  t.stats = d_stats;
+  return enqueue_tol_passes(t, st, marks);
+}
+
+}  // namespace
+
 // The bodies of the entries: `logdom` selects the log-domain kernels (section 5f); everything else -- checks, layout of the
 // call's block, streams -- is shared, so a log-domain entry refuses what its direct twin refuses, with the same words.
+// `tol` (direct items only): the passes of section 5m in place of the sweep, the tile counts behind the Nq results.
 static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out, int device,
-                         const uint8_t *manifold, bool logdom) {
+                         const uint8_t *manifold, bool logdom, const TolArgs *tol = nullptr) {
   if (!bd || !p_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
@@ -392,7 +480,10 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
     return set_error(KDEHIP_ERR_ARG, "malformed density");
   if (leave_one_out) Nq = N;
   else if (!pos || Nq < 0) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
-  if (Nq == 0) return KDEHIP_OK;
+  if (Nq == 0) {
+    if (tol && tol->stats) tol->stats[0] = tol->stats[1] = 0;
+    return KDEHIP_OK;
+  }
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));  // (the reference's evalDirect reads bandwidthMin[1..D])
   DeviceGuard guard;
   int rc = guard.enter(device);
@@ -411,7 +502,8 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   it.N = N; it.Nq = Nq; it.D = D; it.loo = leave_one_out ? 1 : 0; it.logdom = logdom ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);
-  KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq)));
+  static_assert(sizeof(int64_t) == sizeof(double), "the tile counts take two result slots");
+  KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq) + (tol ? 2 : 0), tol ? tol_scratch_bytes(N, Nq, D) : 0));
   unsigned char *h = run.host(), *d = run.dev();
   const LeafArrays src = pack_leaves(run, 0, bd);
   std::memcpy(h + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
@@ -426,11 +518,20 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   ri.out = run.result(0);
   KDEHIP_CHECK_RC(run.upload(st));
   PhaseTimer timer(kPhaseEvaluate, st);  // kdehip_profile_phase_read: the two launches, not the copies
-  KDEHIP_CHECK_RC(run.launch());
+  TolMarks marks(tol != nullptr);
+  if (tol) {
+    KDEHIP_CHECK_RC(enqueue_tol(run, circ, *tol, reinterpret_cast<int64_t *>(run.result(static_cast<size_t>(Nq))), st,
+                                marks.events()));
+    KDEHIP_CHECK_RC(run.launch_finish());
+  } else {
+    KDEHIP_CHECK_RC(run.launch());
+  }
   timer.stop();
   KDEHIP_CHECK_RC(run.wait());
   timer.collect();
+  marks.collect();
   std::memcpy(p_out, run.host_result(0), sizeof(double) * Nq);
+  if (tol && tol->stats) std::memcpy(tol->stats, run.host_result(static_cast<size_t>(Nq)), sizeof(int64_t) * 2);
   return KDEHIP_OK;
 }
 
@@ -602,6 +703,41 @@ static int evaluate_resident_at(const kdehip_device_density *bd, const kdehip_de
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
   return run.defer(bd->device);
+}
+
+// ---- evaluation within a tolerance (kdehip.h section 5m): the bodies above with the passes of evaltol.hip in the sweep's place
+extern "C" int kdehip_evaluate_tol(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,
+                                   const double *rel_tol, const double *abs_tol, double *p_out, int64_t *stats, int device,
+                                   const uint8_t *manifold) {
+  TolArgs tol{};
+  KDEHIP_CHECK_RC(read_tolerances(rel_tol, abs_tol, &tol));
+  tol.stats = stats;
+  return evaluate_host(bd, pos, Nq, leave_one_out, p_out, device, manifold, false, &tol);
+}
+
+extern "C" int kdehip_evaluate_device_at_tol(const kdehip_device_density *bd, const kdehip_device_density *at,
+                                             const double *rel_tol, const double *abs_tol, double *d_out, int64_t *d_stats,
+                                             void *stream, const uint8_t *manifold) {
+  TolArgs tol{};
+  KDEHIP_CHECK_RC(read_tolerances(rel_tol, abs_tol, &tol));
+  if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_pair(bd, at, at == bd));
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  DeviceGuard guard;
+  KDEHIP_CHECK_RC(guard.enter(bd->device));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  CaptureScope scope(st);  // (a captured call's blocks are kept until kdehip_clear_cache: section 5h)
+  EvalRun run;
+  EvalItem it = pair_item(bd, at, at == bd, false, false);
+  it.out = d_out;
+  run.items.push_back(it);
+  run.circ.push_back(circ);
+  KDEHIP_CHECK_RC(run.alloc(0, 0, tol_scratch_bytes(it.N, it.Nq, it.D)));
+  KDEHIP_CHECK_RC(run.upload(st));
+  KDEHIP_CHECK_RC(enqueue_tol(run, circ, tol, d_stats, st));
+  KDEHIP_CHECK_RC(run.launch_finish());
+  return scope.capturing() ? run.keep(bd->device) : run.defer(bd->device);
 }
 
 extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,

@@ -8,7 +8,9 @@
 
 namespace kdehip {
 
-enum ProfilePhase : int { kPhaseLoocv = 0, kPhaseEvaluate = 1, kPhaseTreeBuild = 2, kPhaseCount = 3 };
+// (3..5: the three passes of kdehip_evaluate_tol, each between two events of its own -- evaltol.hip)
+enum ProfilePhase : int { kPhaseLoocv = 0, kPhaseEvaluate = 1, kPhaseTreeBuild = 2, kPhaseTolBox = 3, kPhaseTolPlan = 4,
+                          kPhaseTolSweep = 5, kPhaseCount = 6 };
 bool profile_phases_on();                        // devmem.cpp (set by kdehip_profile_sampler)
 void profile_phases_set(bool on);
 void profile_phase_add(int which, double ms);

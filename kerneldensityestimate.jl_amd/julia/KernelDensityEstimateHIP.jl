@@ -611,6 +611,34 @@ function hip_evaluate_log(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, lvF
 end
 
 """
+    hip_evaluate_tol(bd, pos, lvFlag=false; rel_tol=1e-3, abs_tol=0.0, manifold=nothing, device=0)
+
+`evaluateDualTree(bd, pos, lvFlag)` within a tolerance (`kdehip_evaluate_tol`, include/kdehip.h section 5m): the all-pairs
+sum pruned on the 128-leaf chunks of `bd`, `p (1 - rel_tol) - abs_tol <= result <= p` -- the library's form of
+`setForceEvalDirect!(false)`.  The columns of `pos` are processed in the given order, 256 to a block: pass them in the leaf
+order of a tree over them for the most pruning.  Returns `(values, (tiles visited, tiles in all))`.  Not installed by
+`enable!()`: the override keeps summing every pair.
+"""
+function hip_evaluate_tol(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, lvFlag::Bool=false; rel_tol::Float64=1e-3,
+                          abs_tol::Float64=0.0, manifold=nothing, device::Int=0)
+  Ndim(bd) == size(pos, 1) || error("bd and pos must have the same dimension")
+  man = manifold === nothing ? zeros(UInt8, Ndim(bd)) : manifold_bytes(manifold, Ndim(bd))
+  Nq = lvFlag ? Npts(bd) : size(pos, 2)
+  out = zeros(Nq)
+  stats = zeros(Int64, 2)
+  rt = [rel_tol]
+  at = [abs_tol]
+  cd = Ref(CDensity(bd))
+  posd = Matrix{Float64}(pos)
+  GC.@preserve bd posd man rt at stats begin
+    check(ccall((:kdehip_evaluate_tol, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Cint, Ptr{UInt8}),
+                cd, posd, size(pos, 2), lvFlag ? 1 : 0, rt, at, out, stats, device, man))
+  end
+  return out, (stats[1], stats[2])
+end
+
+"""
     hip_evalAvgLogL_log(bd1, bd2; manifold=nothing, device=0)
 
 Log-domain `evalAvgLogL` (`kdehip_eval_avg_logl_log`, section 5f): the sum over `W != 0` of `W log p` with `log p` by

@@ -332,6 +332,33 @@ class DeviceDensity:
     def __call__(self, pos=None, lvFlag=False, manifold=None):
         return self.evaluate(pos, lvFlag, manifold=manifold)
 
+    def evaluate_tol(self, at=None, rel_tol=1e-3, abs_tol=0.0, manifold=None, return_stats=False):
+        """`.evaluate(at)` within a tolerance (kdehip_evaluate_device_at_tol, include/kdehip.h section 5m): this density at
+        the points of the DeviceDensity `at`, processed in ITS leaf order, values in its original order as a numpy array;
+        `at` None or self: leave-one-out at the density's own points.  p (1 - rel_tol) - abs_tol <= value <= p, bit for bit
+        `kdehip.evaluate_tol` of the host arrays.  return_stats=True: also (tiles visited, tiles in all)."""
+        import torch
+        at = self if at is None else at
+        if not isinstance(at, DeviceDensity):
+            raise TypeError("evaluate_tol: a DeviceDensity is evaluated within a tolerance at a DeviceDensity")
+        if at.dims != self.dims:
+            raise ValueError("bd and pos must have the same dimension")
+        dev = torch.device("cuda", self.device)
+        man = _mf.parse(manifold, self.dims)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            out = torch.empty(max(1, at.num_points), dtype=torch.float64, device=dev)
+            stats = torch.zeros(2, dtype=torch.int64, device=dev)
+            _lib.check(_lib.lib.kdehip_evaluate_device_at_tol(
+                self._h, at._h, C.byref(C.c_double(float(rel_tol))), C.byref(C.c_double(float(abs_tol))), addr(out),
+                addr(stats), addr(st.cuda_stream), _mf.pointer(man)))
+            st.synchronize()
+            vals = out.cpu().numpy()[:at.num_points].copy()
+            if return_stats:
+                s = stats.cpu().numpy()
+                return vals, (int(s[0]), int(s[1]))
+            return vals
+
     def evaluate_grad(self, pos, *, log=True, manifold=None):
         """(log p, its gradient) -- or (p, its gradient) with log=False -- at the columns of `pos` (kdehip_evaluate_grad_device,
         include/kdehip.h section 5h): `kdehip.evaluate_grad` of this density."""
