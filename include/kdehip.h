@@ -524,7 +524,8 @@ int kdehip_product_multi_timing(kdehip_product_multi *mp, double *kernel_ms, dou
  * of timing events; this returns the sum of those durations and the number of bracketed phases since the last read, and
  * resets both (process-wide sums).  bench.py --frow reports them as kernel time.  kdehip_evaluate_tol (section 5m) adds, in
  * the same way, its three passes one by one: which = 3 the chunk boxes, 4 the plan, 5 the sweep over the flagged chunks
- * (which = 1 is then the whole call: the three passes and the finish kernel). */
+ * (which = 1 is then the whole call: the three passes and the finish kernel).  kdehip_knn (section 5n) likewise: which = 6 the
+ * chunk boxes, 7 the plan, 8 the sweep. */
 int kdehip_profile_phase_read(int which, double *total_ms, int64_t *count);
 /* The fp32 screen of the deep levels (csrc/screen_device.hpp) certifies its decisions with an error bound whose premise is
  * that the hardware's v_rcp_f32, v_rsq_f32 and v_exp_f32 are within 1 ulp (a relative error of at most 2 u, u = 2^-24).
@@ -1389,6 +1390,54 @@ int kdehip_evaluate_tol(const kdehip_density *bd, const double *pos, int64_t Nq,
  * kdehip_evaluate_tol of the same densities' host arrays. */
 int kdehip_evaluate_device_at_tol(const kdehip_device_density *bd, const kdehip_device_density *at, const double *rel_tol,
                                   const double *abs_tol, double *d_out, int64_t *d_stats, void *stream, const uint8_t *manifold);
+
+/* ---- (5n) nearest neighbours on the ball tree: the k leaves nearest to a query ----------------------------------------------
+ * The ball tree's own question, which the reference no longer asks (the toolbox it rewrites had knn; only neighborMinMax,
+ * src/CrossValidation.jl:100-108, is left of it).  The skeleton is 5m's: the leaves are in LEAF ORDER, every chunk of 128
+ * consecutive leaves is a compact box, a query block is 256 consecutive queries in the order the entry processes them.  Unlike
+ * 5m the answer is EXACT: what brute force over all N leaves returns, bit for bit.
+ * Distance.  d2(q, i) = acc after acc = fma(d_k * d_k, s_k, acc), from 0, k ascending, with d_k = x_qk - c_ik, wrapped to
+ *   [-pi, pi) in a circular dimension as in 5d.  s_k > 0 is a per-dimension scale; scale == NULL is s_k = 1, the squared
+ *   Euclidean distance.  The chain is monotone in |d_k| and correctly rounded, so the nearest-corner value of a chunk box,
+ *       dmin2(q, c): the same chain on dmin_k = max(0, lo_c[k] - x_qk, x_qk - hi_c[k]), dmin_k = 0 in a circular dimension,
+ *   is <= the COMPUTED d2(q, i) of every leaf i of c: no rounding margin.
+ * Result for a query q: the k leaves with the smallest key (d2, original point index), in ascending order of that key -- ties
+ *   in d2 go to the lower original index, so the answer depends neither on the tree nor on the processing order.
+ *   d2_out [Nq][k] doubles and idx_out [Nq][k] int64 (k fastest: a (k, Nq) column-major matrix), idx 1-BASED original indices,
+ *   the convention of kdehip_sample's labels.  A query with a non-finite coordinate gets NaN distances and index 0.
+ * Leave-one-out: the queries are the density's own leaves, and leaf q is excluded BY INDEX, not by distance -- a duplicate of
+ *   the point stays a neighbour at distance 0.
+ * Limits: 1 <= k <= KDEHIP_KNN_MAX_K; k <= N (N - 1 for leave-one-out); D <= KDEHIP_MAX_DIMS; N < 2^31 - 1; fp64 only.  The
+ *   bandwidths are not read: per-point bandwidths are fine (as kdehip_kernel_sum with explicit variances).
+ * The plan (csrc/knn.hip), part of the contract so that `stats` is reproducible:
+ *  1. Chunk boxes lo_c, hi_c as in 5m step 1.
+ *  2. Per query, c* = the chunk with the smallest dmin2(q, c), ties to the lowest c.  For a leave-one-out query whose own chunk
+ *     holds no other leaf, that chunk does not count.
+ *  3. r_q = the k-th smallest d2 among the eligible leaves of c* (all of them; without leaf q for leave-one-out), computed
+ *     exactly; +Inf if c* has fewer than k eligible leaves.
+ *  4. Chunk c is NEEDED by q iff dmin2(q, c) <= r_q (non-strict: a tie may win on index).
+ *  5. A tile (query block, chunk) is VISITED iff some live query of the block needs the chunk; live = q < Nq and every
+ *     coordinate finite.
+ *  6. stats: int64[2] or NULL -- the tiles visited, and the tiles in all = ceil(Nq / 256) * ceil(N / 128), as in 5m.
+ * The sweep visits the flagged tiles only; a lane may also leave a staged chunk alone that its own current k-th candidate
+ * already excludes.  Whatever is skipped holds no leaf that could enter the list (d2 >= dmin2 > the k-th key's d2), so the
+ * result is the exact one.  No atomics.
+ * Errors, all checked before any device is touched: KDEHIP_ERR_ARG for NULL outputs, Nq < 0, k out of range, a scale that is
+ * not finite and > 0, a manifold byte above 1; KDEHIP_ERR_UNSUPPORTED for D above KDEHIP_MAX_DIMS; KDEHIP_ERR_DIM_MISMATCH for
+ * `at` of another dimension.  Nq == 0 is KDEHIP_OK.
+ * Not here: batches of many small items, radius queries, k > KDEHIP_KNN_MAX_K, fp32. */
+#define KDEHIP_KNN_MAX_K 32
+/* Host density, host arrays, blocking.  The queries are processed in the given order; leave_one_out (pos, Nq unread) processes
+ * the density's leaves in leaf order and returns the columns in original point order, as kdehip_evaluate does.  scale: NULL or
+ * D doubles. */
+int kdehip_knn(const kdehip_density *bd, const double *pos, int64_t Nq, int k, int leave_one_out, const double *scale,
+               double *d2_out, int64_t *idx_out, int64_t *stats, int device, const uint8_t *manifold);
+/* Resident densities: at's leaves in leaf order are the queries, the columns of d_d2_out / d_idx_out (DEVICE, [at's npts][k])
+ * in at's original point order; at == bd is leave-one-out.  scale: HOST pointer or NULL.  d_stats: DEVICE int64[2] or NULL.
+ * Enqueue only on `stream` and capturable under the rules of kdehip_evaluate_device_at_tol.  Bit for bit kdehip_knn of the
+ * same densities' host arrays. */
+int kdehip_knn_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, int k, const double *scale,
+                         double *d_d2_out, int64_t *d_idx_out, int64_t *d_stats, void *stream, const uint8_t *manifold);
 
 #ifdef __cplusplus
 }

@@ -203,6 +203,8 @@ SIGNATURES = {
     "kdehip_eval_avg_logl_log_device_batch": (C.c_int, [C.c_int, C.POINTER(CLoglManifoldItem), C.c_void_p, C.c_void_p]),
     "kdehip_evaluate_tol": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, f64p, f64p, f64p, i64p, C.c_int, u8p]),
     "kdehip_evaluate_device_at_tol": (C.c_int, [C.c_void_p, C.c_void_p, f64p, f64p, C.c_void_p, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_knn": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, C.c_int, f64p, f64p, i64p, i64p, C.c_int, u8p]),
+    "kdehip_knn_device_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u8p]),
     "kdehip_kernel_sum": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), f64p, C.c_int, f64p, C.c_int, u8p]),
     "kdehip_kernel_sum_device": (C.c_int, [C.c_void_p, C.c_void_p, f64p, C.c_int, f64p, u8p]),
     "kdehip_kernel_sum_device_batch": (C.c_int, [C.c_int, C.POINTER(CKsumItem), C.c_void_p, C.c_void_p]),

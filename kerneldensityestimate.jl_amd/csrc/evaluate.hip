@@ -413,40 +413,6 @@ int read_tolerances(const double *rel_tol, const double *abs_tol, TolArgs *out) 
   return KDEHIP_OK;
 }
 
-// four events around the three passes while kdehip_profile_sampler is on (kdehip_profile_phase_read 3..5); otherwise none
-class TolMarks {
- public:
-  explicit TolMarks(bool wanted) {
-    if (!wanted || !profile_phases_on()) return;
-    for (hipEvent_t &e : ev_)
-      if (hipEventCreate(&e) != hipSuccess) { e = nullptr; drop(); return; }
-    on_ = true;
-  }
-  TolMarks(const TolMarks &) = delete;
-  TolMarks &operator=(const TolMarks &) = delete;
-  ~TolMarks() { drop(); }
-  hipEvent_t *events() { return on_ ? ev_ : nullptr; }
-  // once the stream has been synchronised by the caller
-  void collect() {
-    for (int k = 0; on_ && k < 3; ++k) {
-      float ms = 0.0f;
-      if (hipEventElapsedTime(&ms, ev_[k], ev_[k + 1]) == hipSuccess) profile_phase_add(kPhaseTolBox + k, ms);
-    }
-    drop();
-  }
-
- private:
-  void drop() {
-    for (hipEvent_t &e : ev_) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    on_ = false;
-  }
-  hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on_ = false;
-};
-
 // the passes that take the direct sweep's place for item 0 of a run that has been uploaded, with tol_scratch_bytes of `extra`
 int enqueue_tol(const EvalRun &run, uint32_t circ, const TolArgs &tol, int64_t *d_stats, hipStream_t st,
                 hipEvent_t *marks = nullptr) {
@@ -518,7 +484,7 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   ri.out = run.result(0);
   KDEHIP_CHECK_RC(run.upload(st));
   PhaseTimer timer(kPhaseEvaluate, st);  // kdehip_profile_phase_read: the two launches, not the copies
-  TolMarks marks(tol != nullptr);
+  PassMarks marks(kPhaseTolBox, tol != nullptr);  // kdehip_profile_phase_read 3..5
   if (tol) {
     KDEHIP_CHECK_RC(enqueue_tol(run, circ, *tol, reinterpret_cast<int64_t *>(run.result(static_cast<size_t>(Nq))), st,
                                 marks.events()));

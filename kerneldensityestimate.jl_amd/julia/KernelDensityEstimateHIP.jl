@@ -639,6 +639,37 @@ function hip_evaluate_tol(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, lvF
 end
 
 """
+    hip_knn(bd, pos, k=1, lvFlag=false; scale=nothing, manifold=nothing, device=0)
+
+The `k` points of `bd` nearest to every column of `pos` (`kdehip_knn`, include/kdehip.h section 5n): exact, ties in distance
+to the lower point index.  Returns `(d2, idx, (tiles visited, tiles in all))`, `d2` the `k x Nq` SQUARED distances and `idx`
+the 1-based columns of `getPoints(bd)`.  `lvFlag=true`: the neighbours of `bd`'s own points, each left out by index (`pos`
+unread).  `scale`: `nothing` (Euclidean) or one factor `> 0` per dimension, `d2 = sum_k scale[k] d_k^2`.  The columns of
+`pos` are processed in the given order, 256 to a block: pass them in the leaf order of a tree over them for the most
+pruning.  The reference has no counterpart, so `enable!()` installs nothing.
+"""
+function hip_knn(bd::BallTreeDensity, pos::AbstractMatrix{Float64}, k::Int=1, lvFlag::Bool=false; scale=nothing,
+                 manifold=nothing, device::Int=0)
+  Ndim(bd) == size(pos, 1) || error("bd and pos must have the same dimension")
+  man = manifold === nothing ? zeros(UInt8, Ndim(bd)) : manifold_bytes(manifold, Ndim(bd))
+  sc = scale === nothing ? ones(Ndim(bd)) : Vector{Float64}(scale)
+  length(sc) == Ndim(bd) || error("scale needs one entry per dimension")
+  Nq = lvFlag ? Npts(bd) : size(pos, 2)
+  d2 = zeros(max(k, 1), Nq)
+  idx = zeros(Int64, max(k, 1), Nq)
+  stats = zeros(Int64, 2)
+  cd = Ref(CDensity(bd))
+  posd = Matrix{Float64}(pos)
+  GC.@preserve bd posd man sc d2 idx stats begin
+    check(ccall((:kdehip_knn, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Int64, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Cint,
+                 Ptr{UInt8}),
+                cd, posd, size(pos, 2), k, lvFlag ? 1 : 0, sc, d2, idx, stats, device, man))
+  end
+  return d2, idx, (stats[1], stats[2])
+end
+
+"""
     hip_evalAvgLogL_log(bd1, bd2; manifold=nothing, device=0)
 
 Log-domain `evalAvgLogL` (`kdehip_eval_avg_logl_log`, section 5f): the sum over `W != 0` of `W log p` with `log p` by

@@ -359,6 +359,36 @@ class DeviceDensity:
                 return vals, (int(s[0]), int(s[1]))
             return vals
 
+    def knn(self, at=None, k=1, metric="euclid", manifold=None, squared=False, return_stats=False):
+        """The k points of this density nearest to every point of the DeviceDensity `at` (kdehip_knn_device_at, include/kdehip.h
+        section 5n): `(dist, idx)`, numpy arrays of shape (k, at's npts) in ITS original point order, `idx` 1-based among this
+        density's points; `at` None or self: every point's neighbours among the others, itself left out by index.  Bit for
+        bit `kdehip.knn` of the host arrays.  return_stats=True: also (tiles visited, tiles in all)."""
+        import torch
+        from .knn import _finish, _scale
+        at = self if at is None else at
+        if not isinstance(at, DeviceDensity):
+            raise TypeError("knn: a DeviceDensity is searched from the points of a DeviceDensity")
+        if at.dims != self.dims:
+            raise ValueError("bd and pos must have the same dimension")
+        k = int(k)
+        dev = torch.device("cuda", self.device)
+        man = _mf.parse(manifold, self.dims)
+        sc = _scale(self, metric, self.dims)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            n = max(1, at.num_points * max(k, 1))
+            d2 = torch.empty(n, dtype=torch.float64, device=dev)
+            idx = torch.empty(n, dtype=torch.int64, device=dev)
+            stats = torch.zeros(2, dtype=torch.int64, device=dev)
+            _lib.check(_lib.lib.kdehip_knn_device_at(self._h, at._h, k, _lib.optr(sc, f64p), addr(d2), addr(idx), addr(stats),
+                                                     addr(st.cuda_stream), _mf.pointer(man)))
+            st.synchronize()
+            shape = (at.num_points, k)
+            return _finish(np.ascontiguousarray(d2.cpu().numpy()[:shape[0] * k].reshape(shape).T),
+                           np.ascontiguousarray(idx.cpu().numpy()[:shape[0] * k].reshape(shape).T), stats.cpu().numpy(),
+                           squared, return_stats)
+
     def evaluate_grad(self, pos, *, log=True, manifold=None):
         """(log p, its gradient) -- or (p, its gradient) with log=False -- at the columns of `pos` (kdehip_evaluate_grad_device,
         include/kdehip.h section 5h): `kdehip.evaluate_grad` of this density."""
