@@ -613,6 +613,25 @@ int kdehip_make_density_tree(int64_t D, int64_t N, const double *points, const d
                              double *bandwidth, double *bandwidthMin, double *bandwidthMax,
                              const uint8_t *tree_manifold /* D bytes or NULL */);
 
+/* A density whose points each have a bandwidth of their own (multibandwidth = 1; the `else` branch of makeBallTreeDensity,
+ * src/BallTreeDensity01.jl:216-225, which kde! never takes).  ks: D*N standard deviations, column-major (ks[i*D + k] is
+ * point i's in dimension k), in the ORIGINAL point order of `points`; squared inside.  There is no nks.
+ *   - The tree, the boxes, the weights and the means are exactly kdehip_make_density_tree's: they do not depend on ks.
+ *   - bandwidthMin / bandwidthMax are D*2N here, rows by node like `bandwidth`.  The leaf rows of all three are ks^2 through
+ *     the permutation; an internal row of `bandwidth` is the moment match of calcStatsDensity! (:180-185), of Min / Max the
+ *     smaller / larger of its children's rows by the reference's strict comparisons (:164-177).
+ *   - A ks entry that is not finite and > 0 is KDEHIP_ERR_ARG, checked before any array is written.
+ *   - With all N columns of ks equal, `bandwidth` is bit for bit kdehip_make_density_tree's with that column.
+ * What reads such a density: section 5o (evaluation, log-likelihoods), the sampler (non-uniform tiles), kdehip_sample (the
+ * drawn leaf's own variance), kdehip_kernel_sum with explicit variances, kdehip_knn, kdehip_density_upload.  Every other
+ * entry keeps refusing it with KDEHIP_ERR_UNSUPPORTED. */
+int kdehip_make_density_varbw(int64_t D, int64_t N, const double *points, const double *ks /* D*N */,
+                              const double *weights_in, double *centers, double *ranges, double *weights,
+                              int64_t *left_child, int64_t *right_child, int64_t *lowest_leaf,
+                              int64_t *highest_leaf, int64_t *permutation, double *means,
+                              double *bandwidth, double *bandwidthMin /* D*2N */, double *bandwidthMax /* D*2N */,
+                              const uint8_t *tree_manifold /* D bytes or NULL */);
+
 /* The bandwidth-dependent half of the construction on an existing tree: topology, bounding boxes, weights and means
  * do not depend on ks, only `bandwidth` (leaves ks^2, internal nodes by moment matching,
  * src/BallTreeDensity01.jl:141-187) and bandwidthMin/Max do.  Lets kde!(points) build its tree while the GPU searches
@@ -1438,6 +1457,54 @@ int kdehip_knn(const kdehip_density *bd, const double *pos, int64_t Nq, int k, i
  * same densities' host arrays. */
 int kdehip_knn_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, int k, const double *scale,
                          double *d_d2_out, int64_t *d_idx_out, int64_t *d_stats, void *stream, const uint8_t *manifold);
+
+/* ---- (5o) densities with per-point bandwidths: evaluation and log-likelihoods ------------------------------------------------
+ * The sample-point adaptive estimator: every source i has variances v_ik of its own (kdehip_make_density_varbw, section 4),
+ *     p(x) = (2 pi)^(-D/2) sum_i w_i / prod_k sqrt(v_ik) exp(a_i),   a_i = sum_k diff_k(x_k, c_ik)^2 nh_ik,  nh_ik = -0.5 / v_ik
+ * (k ascending, one fma per dimension; diff_k the plain difference, through wrap() in a circular dimension, 5d).  The entries
+ * of 5, 5b and 5f read ONE bandwidth vector and keep refusing such densities; these read a variance per source and accept
+ * ANY density, one with a single vector included -- its values agree with 5 / 5f to rounding, not bit for bit, because the
+ * normaliser is folded into every term here and applied once after the sum there.
+ * The plan (csrc/varbw.hip, csrc/pair_sweep.hpp pair_sweep_var):
+ *  1. A prepass over the N leaves, in leaf order, into the call's block: nh_ik; c_i = w_i / prod_k sqrt(v_ik) (k ascending,
+ *     correctly rounded roots); for log_domain != 0 instead lc_i = log w_i - 1/2 sum_k log v_ik, -Inf for w_i == 0.
+ *  2. The sweep keeps the mapping of 5: one lane per query, 256 queries per block, groups of 128-leaf chunks through a
+ *     two-buffer LDS ring, the split a function of (N, Nq) alone.  It stages 2D + 1 values per source: [c_i. | nh_i. | c_i].
+ *     Direct step: sum c_i exp(a_i), the self term dropped for leave-one-out.  Log step: t_i = a_i + lc_i, m = max t_i over
+ *     S = { w_i > 0, i != q if leave-one-out }, s = sum exp(t_i - m), rescaled once per chunk (5f).  The maximum is over
+ *     t_i, not a_i: the normalisers differ per source.
+ *  3. The finish sums the group partials in group order (no atomics): p = sum / (2 pi)^(D/2) [/ (1 - w_q)], or
+ *     log p = M + log S - (D/2) log 2pi [- log(1 - w_q)], -Inf for S empty.  A query with a NaN coordinate gets NaN (5j).
+ *     A log-likelihood is sum_q W_q log p_q under the rules of 5b (direct) or 5f (log_domain): src/DualTree01.jl:456-466.
+ * The host entry, a resident call and a second run give the same bits.
+ * Errors, all checked before any device is touched: KDEHIP_ERR_ARG for NULL arguments, leave_one_out with at != bd, a manifold
+ * byte above 1; KDEHIP_ERR_UNSUPPORTED for D outside 1..KDEHIP_MAX_DIMS; KDEHIP_ERR_DIM_MISMATCH for `at` of another
+ * dimension.  The variances themselves are not examined: a non-positive one gives what the arithmetic gives.
+ * Not here: evaluation within a tolerance (5m), gradients, Hessians and modes (5h, 5k), conditionals (5i), box masses and
+ * quantiles (5l), kdehip_kernel_sum with var == NULL, the bandwidth metric of kdehip_knn, resident marginal / condition of
+ * such densities, a batched entry, a D + 2 staging for variances that are one vector times a per-point scale, fp32. */
+/* Host density, host arrays, blocking; one pinned upload, as kdehip_evaluate.  leave_one_out: pos and Nq are unread, the values
+ * come back in original point order. */
+int kdehip_evaluate_varbw(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, int log_domain,
+                          double *p_out, int device, const uint8_t *manifold);
+/* evalAvgLogL (5b; log_domain: 5f) of bd at at's points; at == NULL with leave_one_out means bd.  Blocking. */
+int kdehip_eval_avg_logl_varbw(const kdehip_density *bd, const kdehip_density *at, int leave_one_out, int log_domain,
+                               double *out, int device, const uint8_t *manifold);
+/* Resident densities, enqueue only on `stream`: d_out (DEVICE) gets at's npts values in at's original point order.
+ * leave_one_out needs at == bd; at == bd without it keeps the self terms.  A capture of ONE stream into a HIP graph can hold
+ * these three calls under the rules of kdehip_evaluate_device_at_tol (5m): the blocks of a captured call are kept until
+ * kdehip_clear_cache. */
+int kdehip_evaluate_varbw_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                    int log_domain, double *d_out, void *stream, const uint8_t *manifold);
+/* ... at Nq positions in HBM (d_pos: [Nq][D]), values in query order */
+int kdehip_evaluate_varbw_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int log_domain,
+                                 double *d_out, void *stream, const uint8_t *manifold);
+/* ... the log-likelihood into ONE double in HBM */
+int kdehip_eval_avg_logl_varbw_device(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
+                                      int log_domain, double *d_out, void *stream, const uint8_t *manifold);
+/* 1 if every leaf of the resident density has its first leaf's variances (what the entries of 5 / 5b / 5f ask), else 0;
+ * 0 with KDEHIP_ERR_ARG in kdehip_last_error for NULL. */
+int kdehip_density_uniform_bandwidth(const kdehip_device_density *density);
 
 #ifdef __cplusplus
 }

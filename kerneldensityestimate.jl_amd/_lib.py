@@ -304,6 +304,15 @@ SIGNATURES = {
                                                       u8p]),
     "kdehip_inters_intg_appx_is_device_manifold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, f64p, u8p]),
     "kdehip_density_marginal_device_tree": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, i32p, u8p]),
+    # per-point bandwidths (include/kdehip.h sections 4 and 5o): the builder, and evaluation / log-likelihoods of ANY density
+    "kdehip_make_density_varbw": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, f64p, f64p, f64p, f64p,
+                                            i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p, f64p, u8p]),
+    "kdehip_evaluate_varbw": (C.c_int, [C.POINTER(CDensity), f64p, C.c_int64, C.c_int, C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_eval_avg_logl_varbw": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int, C.c_int, f64p, C.c_int, u8p]),
+    "kdehip_evaluate_varbw_device_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_evaluate_varbw_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_eval_avg_logl_varbw_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_density_uniform_bandwidth": (C.c_int, [C.c_void_p]),
     "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
                                          u8p]),
     "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,

@@ -75,7 +75,7 @@ def evaluate_log(bd, pos=None, lvFlag=False, manifold=None, device=0):
     if not isinstance(bd, BallTreeDensity) or isinstance(pos, DeviceDensity):
         raise TypeError("evaluate_log: a BallTreeDensity at host points or a BallTreeDensity (a DeviceDensity has "
                         ".evaluate_log)")
-    return _evaluate(_lib.lib.kdehip_evaluate_log, bd, pos, lvFlag, device, manifold)
+    return _evaluate(_lib.lib.kdehip_evaluate_log, bd, pos, lvFlag, device, manifold, log=True)
 
 
 def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, device=0, manifold=None):
@@ -84,14 +84,19 @@ def evaluateDualTree(bd: BallTreeDensity, pos=None, lvFlag=False, errTol=1e-3, d
     BallTreeDensity whose points are used; lvFlag=True (or pos is bd) evaluates leave-one-out at bd's
     own points and returns the values in the original point order.
     After `setForceEvalDirect(False)` the call is `evaluate_tol(bd, pos, rel_tol=errTol, lvFlag=lvFlag)`: the sum pruned on
-    the ball tree, within the relative tolerance errTol from below (include/kdehip.h section 5m)."""
+    the ball tree, within the relative tolerance errTol from below (include/kdehip.h section 5m).
+    A density with per-point bandwidths (`kde_varbw`, multibandwidth == 1) goes to kdehip_evaluate_varbw (section 5o), here
+    and in `evaluate_log`; `evaluate_tol` keeps refusing it."""
     from . import evaltol
     if not evaltol.getForceEvalDirect():
         return evaltol.evaluate_tol(bd, pos, rel_tol=errTol, lvFlag=lvFlag, device=device, manifold=manifold)
     return _evaluate(_lib.lib.kdehip_evaluate_manifold, bd, pos, lvFlag, device, manifold)
 
 
-def _evaluate(entry, bd, pos, lvFlag, device, manifold):
+def _evaluate(entry, bd, pos, lvFlag, device, manifold, log=False):
+    if bd.multibandwidth == 1:  # per-point bandwidths: the entry of section 5o, which takes the domain as an argument
+        def entry(cd, pos, Nq, loo, out, device, mp, _log=int(log)):
+            return _lib.lib.kdehip_evaluate_varbw(cd, pos, Nq, loo, _log, out, device, mp)
     cd = bd._cstruct()
     man, mp = _man_ptr(manifold, bd.bt.dims)  # (manifold: circular differences in those dimensions, kdehip.h section 5d)
     if lvFlag or pos is bd:

@@ -64,6 +64,21 @@ class DensityBuilder {
   void build(const double *wnorm, const double *var) {
     wnorm_ = wnorm;
     leaf_var_ = var;
+    run();
+  }
+
+  // Per-point bandwidths (kdehip_make_density_varbw): var [N][D], the variances of every input point in input order;
+  // bwmin / bwmax [2N][D], rows by node like bw.  The tree does not depend on them.
+  void build_varbw(const double *wnorm, const double *var, double *bwmin, double *bwmax) {
+    wnorm_ = wnorm;
+    point_var_ = var;
+    bwmin_ = bwmin;
+    bwmax_ = bwmax;
+    run();
+  }
+
+ private:
+  void run() {
     Scratch s(D_);
     int depth = 0;
     if (N_ >= kSplitLeaves) {  // (small densities never start the workers)
@@ -74,7 +89,6 @@ class DensityBuilder {
     if (N_ == 1) right_[0] = -1;  // single-point density, :358-360
   }
 
- private:
   static constexpr int64_t kSplitLeaves = 512;  // a node with fewer leaves is built by the thread that reached it
 
   struct Scratch {  // per host thread
@@ -93,8 +107,11 @@ class DensityBuilder {
         const double x = pts_[src * D_ + k];
         centers_[(id - 1) * D_ + k] = x;
         means_[(id - 1) * D_ + k] = x;
-        bw_[(id - 1) * D_ + k] = leaf_var_[k];
+        bw_[(id - 1) * D_ + k] = point_var_ ? point_var_[src * D_ + k] : leaf_var_[k];
       }
+      if (point_var_)
+        for (int64_t k = 0; k < D_; ++k)
+          bwmin_[(id - 1) * D_ + k] = bwmax_[(id - 1) * D_ + k] = point_var_[src * D_ + k];
     }
   }
 
@@ -262,6 +279,14 @@ class DensityBuilder {
       mu(id)[k] = m;
       var(id)[k] = wa * (var(a)[k] + ma * ma) + wb * (var(b)[k] + mb * mb) - m * m;
     }
+    if (point_var_) {  // the !bwUniform branch, BallTreeDensity01.jl:164-177
+      const double *maxA = bwmax_ + (a - 1) * D_, *maxB = bwmax_ + (b - 1) * D_;
+      const double *minA = bwmin_ + (a - 1) * D_, *minB = bwmin_ + (b - 1) * D_;
+      for (int64_t k = 0; k < D_; ++k) {
+        bwmax_[(id - 1) * D_ + k] = (maxA[k] > maxB[k]) ? maxA[k] : maxB[k];
+        bwmin_[(id - 1) * D_ + k] = (minA[k] < minB[k]) ? minA[k] : minB[k];
+      }
+    }
   }
 
   // buildBall!, BallTree01.jl:342-411.  Child ids are handed out (left, then right) before either
@@ -295,6 +320,8 @@ class DensityBuilder {
   int64_t *left_, *right_, *lo_, *hi_, *perm_;
   double *means_, *bw_;
   const double *wnorm_ = nullptr, *leaf_var_ = nullptr;
+  const double *point_var_ = nullptr;            // build_varbw: [N][D], input order
+  double *bwmin_ = nullptr, *bwmax_ = nullptr;   // build_varbw: [2N][D]
   std::vector<int64_t> slot_;
   std::vector<int64_t> circ_;       // the circular dimensions, ascending (empty: the Euclidean builder)
   std::vector<uint8_t> circ_flag_;  // [D]
@@ -364,6 +391,54 @@ extern "C" int kdehip_make_density_tree(int64_t D, int64_t N, const double *poin
         .build(wnorm.data(), var.data());
   } catch (const std::exception &e) {  // (scratch allocation on this or a worker thread: nothing may cross the C boundary)
     return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_make_density: ") + e.what());
+  }
+  return KDEHIP_OK;
+}
+
+// Per-point bandwidths (include/kdehip.h section 4): the same tree, and the reference's multibandwidth = 1 arrays
+// (makeBallTreeDensity, src/BallTreeDensity01.jl:216-225; calcStatsDensity!, :164-185)
+extern "C" int kdehip_make_density_varbw(int64_t D, int64_t N, const double *points, const double *ks,
+                                         const double *weights_in, double *centers, double *ranges, double *weights,
+                                         int64_t *left_child, int64_t *right_child, int64_t *lowest_leaf,
+                                         int64_t *highest_leaf, int64_t *permutation, double *means, double *bandwidth,
+                                         double *bandwidthMin, double *bandwidthMax, const uint8_t *tree_manifold) {
+  using namespace kdehip;
+  if (D < 1 || N < 1) return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_varbw: need D >= 1 and N >= 1");
+  if (!points || !ks || !centers || !ranges || !weights || !left_child || !right_child ||
+      !lowest_leaf || !highest_leaf || !permutation || !means || !bandwidth || !bandwidthMin ||
+      !bandwidthMax)
+    return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_varbw: null pointer");
+  if (manifold_arg(tree_manifold, D, nullptr, kHostTreeManifold) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  for (int64_t i = 0; i < N * D; ++i)
+    if (!(ks[i] > 0.0 && ks[i] < INFINITY))
+      return set_error(KDEHIP_ERR_ARG, "kdehip_make_density_varbw: every bandwidth must be finite and > 0");
+
+  const size_t nd = static_cast<size_t>(2 * N * D);
+  std::memset(centers, 0, nd * sizeof(double));
+  std::memset(ranges, 0, nd * sizeof(double));
+  std::memset(means, 0, nd * sizeof(double));
+  std::memset(bandwidth, 0, nd * sizeof(double));
+  std::memset(bandwidthMin, 0, nd * sizeof(double));
+  std::memset(bandwidthMax, 0, nd * sizeof(double));
+  for (int64_t i = 0; i < N; ++i) {  // internal slots, then leaf slots, as kdehip_make_density_tree
+    weights[i] = 0.0;
+    left_child[i] = right_child[i] = lowest_leaf[i] = highest_leaf[i] = 1;
+    permutation[i] = 0;
+    const int64_t id = N + 1 + i;
+    left_child[id - 1] = lowest_leaf[id - 1] = highest_leaf[id - 1] = id;
+    right_child[id - 1] = -1;
+  }
+  try {
+    double total = 0.0;
+    for (int64_t i = 0; i < N; ++i) total += weights_in ? weights_in[i] : 1.0;
+    std::vector<double> wnorm(static_cast<size_t>(N)), var(static_cast<size_t>(N * D));
+    for (int64_t i = 0; i < N; ++i) wnorm[static_cast<size_t>(i)] = (weights_in ? weights_in[i] : 1.0) / total;  // KDE01.jl:46
+    for (int64_t i = 0; i < N * D; ++i) var[static_cast<size_t>(i)] = ks[i] * ks[i];  // ks.^2, KDE01.jl:45
+    DensityBuilder(D, N, points, centers, ranges, weights, left_child, right_child, lowest_leaf, highest_leaf,
+                   permutation, means, bandwidth, tree_manifold)
+        .build_varbw(wnorm.data(), var.data(), bandwidthMin, bandwidthMax);
+  } catch (const std::exception &e) {
+    return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_make_density_varbw: ") + e.what());
   }
   return KDEHIP_OK;
 }

@@ -2,7 +2,8 @@
 // ksum.hip (ksum_partial_kernel), written ONCE: the head both descriptors start with, a block's place in an item, the sweep
 // over the staged source chunks, the block reduction and the norm on the device; the skeleton of a call's run (EvalRun,
 // KsumRun), the scope of a call on a capturing stream and two small readers of a host density on the host.  Included by the
-// files of entry points that run the sweep or its mapping (evaluate, ksum, modes, conditional, mass).
+// files of entry points that run the sweep or its mapping (evaluate, ksum, modes, conditional, mass), and by varbw.hip, whose
+// sweep over sources with variances of their own (pair_sweep_var) stands beside it.
 //
 // The sweep: one lane per query point, a block owns kEvalThreads queries and ONE group of consecutive kEvalChunk-point source
 // chunks, which it stages through a two-buffer LDS ring ([point][D coordinates, weight], read back as broadcasts) and walks
@@ -109,6 +110,55 @@ __device__ __forceinline__ void pair_sweep(const PairHead &h, const PairPlace &a
         }
         if constexpr (kDiffs) f(i0 + i, s[D], acc, diff);
         else f(i0 + i, s[D], acc);  // acc <= 0
+      }
+    });
+  }
+}
+
+// The same walk for sources that each have variances of their own (varbw.hip; kdehip.h section 5o): a second function, so
+// that pair_sweep above stays what it was.  Per source the ring holds [D coordinates | D values nh_ik = -1/(2 v_ik) | c_i]
+// (2D + 1 doubles, read back as broadcasts), c_i being whatever the kernel's step wants next to the exponent -- the folded
+// normaliser w_i / prod_k sqrt(v_ik) or its logarithm.  Same mapping, same chunks, same barriers; the exponent is
+//   a_i = sum_k diff_k(x_qk, c_ik)^2 nh_ik     (k ascending, one fma per dimension)
+// and each(f) calls f(i, c_i, a_i).
+template <int D, bool CIRC, typename Step>
+__device__ __forceinline__ void pair_sweep_var(const PairHead &h, const double *__restrict__ nh /* [N][D] */,
+                                               const double *__restrict__ cc /* [N] */, const PairPlace &at, unsigned circ,
+                                               double (&sSrc)[2][kEvalChunk * (2 * D + 1)], Step &&step) {
+  constexpr int kRow = 2 * D + 1;
+  const double *const src = h.src;
+  const int64_t N = h.N;
+  double x[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = (at.q < h.Nq) ? h.qry[at.q * D + k] : 0.0;
+  auto stage = [&](int64_t c, int buf) {
+    const int64_t i0 = c * kEvalChunk;
+    const int cnt = static_cast<int>((N - i0 < kEvalChunk) ? (N - i0) : kEvalChunk);
+    for (int t = threadIdx.x; t < cnt * kRow; t += kEvalThreads) {
+      const int i = t / kRow, f = t % kRow;
+      sSrc[buf][t] = (f < D) ? src[(i0 + i) * D + f] : (f < 2 * D) ? nh[(i0 + i) * D + (f - D)] : cc[i0 + i];
+    }
+  };
+  if (at.c_begin < at.c_end) stage(at.c_begin, 0);
+  for (int64_t c = at.c_begin; c < at.c_end; ++c) {
+    const int buf = static_cast<int>((c - at.c_begin) & 1);
+    __syncthreads();  // chunk c is staged; the other buffer is free again
+    if (c + 1 < at.c_end) stage(c + 1, buf ^ 1);
+    const int64_t i0 = c * kEvalChunk;
+    const int cnt = static_cast<int>((N - i0 < kEvalChunk) ? (N - i0) : kEvalChunk);
+    step([&](auto &&f) {
+      for (int i = 0; i < cnt; ++i) {
+        const double *s = sSrc[buf] + i * kRow;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          double d = x[k] - s[k];
+          if constexpr (CIRC) {
+            if ((circ >> k) & 1u) d = circ_wrap(d);
+          }
+          acc = fma(d * d, s[D + k], acc);
+        }
+        f(i0 + i, s[2 * D], acc);  // acc <= 0
       }
     });
   }

@@ -74,12 +74,13 @@ def _prepare(points, ks, weights):
     return D, N, flat, ks, w
 
 
-def _empty_density(D, N) -> BallTreeDensity:
-    """The reference's twelve arrays as views of ONE block: a fresh allocation of this size is an mmap of its own, and a
+def _empty_density(D, N, multibw=False) -> BallTreeDensity:
+    """The reference's twelve arrays as views of ONE block (multibw: bandwidthMin / Max hold a row per NODE, D*2N, and
+    multibandwidth is 1 -- makeBallTreeDensity's `else` branch, src/BallTreeDensity01.jl:216-225): a fresh allocation of this size is an mmap of its own, and a
     dozen mmap/munmap pairs per density (with the TLB shoot-downs a munmap costs a process that runs worker threads) were
     a third of `kde()`'s time."""
     f8 = [("centers", 2 * N * D), ("ranges", 2 * N * D), ("means", 2 * N * D), ("bandwidth", 2 * N * D),
-          ("bandwidthMin", N * D), ("bandwidthMax", N * D), ("weights", 2 * N)]
+          ("bandwidthMin", (2 if multibw else 1) * N * D), ("bandwidthMax", (2 if multibw else 1) * N * D), ("weights", 2 * N)]
     i8 = ["left_child", "right_child", "lowest_leaf", "highest_leaf", "permutation"]
     words = sum(n for _, n in f8) + len(i8) * 2 * N
     block = np.empty(words, dtype=np.float64)
@@ -96,7 +97,7 @@ def _empty_density(D, N) -> BallTreeDensity:
         setattr(bt, name, views[name])
     bd = BallTreeDensity()
     bd.bt = bt
-    bd.multibandwidth = 0
+    bd.multibandwidth = 1 if multibw else 0
     bd.tree_manifold = None
     for name in ("means", "bandwidth", "bandwidthMin", "bandwidthMax"):
         setattr(bd, name, views[name])

@@ -40,7 +40,9 @@ def _mask(man):
 def evalAvgLogL(bd1, bd2, *, device=0, manifold=None, log_domain=False) -> float:
     """`evalAvgLogL(bd1, bd2)` (src/DualTree01.jl:450-470): sum over bd2's points of W log L, L = bd1 at those points
     (leave-one-out when `bd1 is bd2`), W = bd2's weights; -inf when an L == 0 carries weight.  `log_domain=True`: the sum
-    over W != 0 of W log p with log p by log-sum-exp (section 5f), finite wherever bd1 has a weighted point."""
+    over W != 0 of W log p with log p by log-sum-exp (section 5f), finite wherever bd1 has a weighted point.
+    A bd1 with per-point bandwidths (multibandwidth == 1; a DeviceDensity whose leaves do not share one vector) is
+    evaluated by the entries of section 5o; bd2 contributes points and weights only."""
     kind = _kind(bd1, bd2)
     if _dims(bd1) != _dims(bd2):
         raise ValueError("evaluate -- dimensions of two BallTreeDensities must match")
@@ -51,8 +53,22 @@ def evalAvgLogL(bd1, bd2, *, device=0, manifold=None, log_domain=False) -> float
     if kind == "host":
         c1 = bd1._cstruct()
         c2 = c1 if loo else bd2._cstruct()
+        if bd1.multibandwidth == 1:  # per-point bandwidths (section 5o)
+            _lib.check(_lib.lib.kdehip_eval_avg_logl_varbw(C.byref(c1), C.byref(c2), loo, int(bool(log_domain)), C.byref(out),
+                                                           int(device), mp))
+            return float(out.value)
         fn = _lib.lib.kdehip_eval_avg_logl_log if log_domain else _lib.lib.kdehip_eval_avg_logl_manifold
         _lib.check(fn(C.byref(c1), C.byref(c2), loo, C.byref(out), int(device), mp))
+    elif bd1._h and not _lib.lib.kdehip_density_uniform_bandwidth(bd1._h):
+        import torch
+        dev = torch.device("cuda", bd1.device)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            d_out = torch.empty(1, dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib.kdehip_eval_avg_logl_varbw_device(bd1._h, bd2._h, loo, int(bool(log_domain)), _lib.addr(d_out),
+                                                                  _lib.addr(st.cuda_stream), mp))
+            st.synchronize()
+            return float(d_out.cpu()[0])
     else:
         fn = _lib.lib.kdehip_eval_avg_logl_log_device if log_domain else _lib.lib.kdehip_eval_avg_logl_device_manifold
         _lib.check(fn(bd1._h, bd2._h, loo, C.byref(out), mp))

@@ -285,7 +285,8 @@ class DeviceDensity:
         torch tensor on the density's device -- a device tensor, enqueued on the current torch stream --, or a DeviceDensity
         -- values at its points in ITS original order (getPoints order), as a numpy array.  `pos is self` or lvFlag=True:
         leave-one-out at the density's own points, original order.  `manifold`: circular differences in those dimensions
-        (include/kdehip.h section 5d)."""
+        (include/kdehip.h section 5d).  A density whose leaves do not share one bandwidth vector
+        (kdehip_density_uniform_bandwidth) goes to the entries of section 5o."""
         import torch
         dev = torch.device("cuda", self.device)
         man = _mf.parse(manifold, self.dims)
@@ -294,14 +295,19 @@ class DeviceDensity:
             pos = self
         if pos is None:
             raise TypeError("evaluate: pos is required unless lvFlag=True")
+        varbw = bool(self._h) and not _lib.lib.kdehip_density_uniform_bandwidth(self._h)  # per-point bandwidths: section 5o
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev)
             if isinstance(pos, DeviceDensity):
                 if pos.dims != self.dims:
                     raise ValueError("bd and pos must have the same dimension")
                 out = torch.empty(max(1, pos.num_points), dtype=torch.float64, device=dev)
-                at_entry = _lib.lib.kdehip_evaluate_log_device_at if _log else _lib.lib.kdehip_evaluate_device_at_manifold
-                _lib.check(at_entry(self._h, pos._h, addr(out), addr(st.cuda_stream), mp))
+                if varbw:
+                    _lib.check(_lib.lib.kdehip_evaluate_varbw_device_at(self._h, pos._h, 1 if pos is self else 0, int(_log),
+                                                                        addr(out), addr(st.cuda_stream), mp))
+                else:
+                    at_entry = _lib.lib.kdehip_evaluate_log_device_at if _log else _lib.lib.kdehip_evaluate_device_at_manifold
+                    _lib.check(at_entry(self._h, pos._h, addr(out), addr(st.cuda_stream), mp))
                 st.synchronize()
                 return out.cpu().numpy()[:pos.num_points].copy()
             tensor = hasattr(pos, "data_ptr")
@@ -314,8 +320,12 @@ class DeviceDensity:
             # column-major D x Nq = the (Nq, D) row-major array
             flat = P.t().contiguous().to(dev, torch.float64) if tensor else torch.from_numpy(np.ascontiguousarray(P.T)).to(dev)
             out = torch.empty(max(1, Nq), dtype=torch.float64, device=dev)
-            entry = _lib.lib.kdehip_evaluate_log_device if _log else _lib.lib.kdehip_evaluate_device_manifold
-            _lib.check(entry(self._h, addr(flat), Nq, 0, addr(out), addr(st.cuda_stream), mp))
+            if varbw:
+                _lib.check(_lib.lib.kdehip_evaluate_varbw_device(self._h, addr(flat), Nq, int(_log), addr(out),
+                                                                 addr(st.cuda_stream), mp))
+            else:
+                entry = _lib.lib.kdehip_evaluate_log_device if _log else _lib.lib.kdehip_evaluate_device_manifold
+                _lib.check(entry(self._h, addr(flat), Nq, 0, addr(out), addr(st.cuda_stream), mp))
             if tensor:
                 return out[:Nq]
             st.synchronize()

@@ -142,6 +142,9 @@ def marginal(p, dims, *, manifold=None, tree_manifold=None):
     dl = _dims_list(dims, p.bt.dims)
     tman = _mf.select(_manifold(p, tree_manifold, attr="tree_manifold"), dl)
     _manifold(p, manifold)   # (validated; a BallTreeDensity has no manifold record)
+    if p.multibandwidth == 1:  # per-point bandwidths: every point keeps its own, the selected rows
+        from .varbw import kde_varbw
+        return kde_varbw(_leaf_points(p)[dl, :], getBW(p)[dl, :], getWeights(p), tree_manifold=tman)
     return kde(_leaf_points(p)[dl, :], getBW(p)[dl, 0], getWeights(p), tree_manifold=tman)
 
 
