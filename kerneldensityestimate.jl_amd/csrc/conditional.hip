@@ -29,6 +29,7 @@
 #include <cstring>
 #include <vector>
 
+#include "density_args.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "manifold_arg.hpp"
@@ -41,7 +42,6 @@ using namespace kdehip;
 
 namespace {
 
-const char kOneBandwidth[] = "per-point bandwidths are not supported (the reference's kde! never builds them)";
 
 constexpr int kFinishThreads = kEvalThreads;  // a finish block is a query block: its chosen flags are that block's
 
@@ -465,50 +465,31 @@ int check_outputs(const void *logz, const void *mean, const void *var, const voi
   return KDEHIP_OK;
 }
 
-int check_resident(const kdehip_device_density *bd) {
-  if (!bd) return set_error(KDEHIP_ERR_ARG, "null density");
-  if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  return KDEHIP_OK;
-}
-
-int check_host(const kdehip_density *bd) {
-  if (!bd) return set_error(KDEHIP_ERR_ARG, "null argument");
-  if (bd->ndim < 1 || bd->ndim > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (bd->npts < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
-    return set_error(KDEHIP_ERR_ARG, "malformed density");
-  return KDEHIP_OK;
-}
+const char kGiven[] = "given must hold Nq >= 0 queries", kDeviceGiven[] = "d_given must hold Nq >= 0 queries";
 
 CondItem base_item(int64_t N, int D, int64_t Nq, uint32_t gmask, bool moments, uint64_t seed, int64_t offset) {
   CondItem it{};
   it.N = N; it.Nq = Nq; it.D = D; it.gmask = gmask; it.ng = popcount32(gmask);
-  it.norm0 = std::pow(2.0 * M_PI, it.ng / 2.0);
+  it.norm0 = gauss_norm0(it.ng);
   it.mom = moments ? 1 : 0; it.seed = seed; it.offset = offset;
   return it;
 }
 
 void point_resident(CondItem &it, const kdehip_device_density *bd) {
-  const int64_t N = bd->N;
-  const int D = bd->D;
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
-  it.perm = bd->perm + N;
-  it.ref = bd->means;  // node 1, the root
+  const LeafRows leaf = leaf_rows(bd);
+  it.src = leaf.src; it.w = leaf.w; it.bw = leaf.bw; it.perm = leaf.perm; it.ref = leaf.ref;
 }
 
-// a host density at offset 0 of the call's image: [means | weights | bw | r | permutation]
-size_t host_density_bytes(const kdehip_density *bd) {
-  return sizeof(double) * (bd->npts * (bd->ndim + 1) + 2 * bd->ndim) + sizeof(int64_t) * bd->npts;
+// a host density at offset 0 of the call's image: the plain form (density_args.hpp), then [r | permutation]
+size_t cond_density_bytes(const kdehip_density *bd) {
+  return host_density_bytes(bd) + sizeof(double) * bd->ndim + sizeof(int64_t) * bd->npts;
 }
-void pack_host_density(CondRun &run, CondItem &it, const kdehip_density *bd) {
+void pack_cond_density(CondRun &run, CondItem &it, const kdehip_density *bd) {
   const int64_t N = bd->npts, D = bd->ndim;
-  const LeafArrays src = pack_leaves(run, 0, bd);
-  const size_t o_bw = sizeof(double) * N * (D + 1), o_ref = o_bw + sizeof(double) * D, o_perm = o_ref + sizeof(double) * D;
-  std::memcpy(run.host() + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
+  const size_t o_ref = host_density_bytes(bd), o_perm = o_ref + sizeof(double) * D;
+  it.bw = pack_host_density(run, it, bd);
   std::memcpy(run.host() + o_ref, bd->means, sizeof(double) * D);
   std::memcpy(run.host() + o_perm, bd->permutation + N, sizeof(int64_t) * N);
-  it.src = src.means;
-  it.w = src.weights;
-  it.bw = reinterpret_cast<const double *>(run.dev() + o_bw);
   it.ref = reinterpret_cast<const double *>(run.dev() + o_ref);
   it.perm = reinterpret_cast<const int64_t *>(run.dev() + o_perm);
 }
@@ -521,12 +502,12 @@ extern "C" int kdehip_conditional(const kdehip_density *bd, uint32_t given_mask,
   // every check that needs no device comes first
   if (!bd) return set_error(KDEHIP_ERR_ARG, "null argument");
   KDEHIP_CHECK_RC(check_outputs(logz, mean, var, pts, ind));
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   KDEHIP_CHECK_RC(check_mask(given_mask, D));
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !given)) return set_error(KDEHIP_ERR_ARG, "given must hold Nq >= 0 queries");
+  KDEHIP_CHECK_RC(check_query_count(given, Nq, kGiven));
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
   KDEHIP_CHECK_RC(check_free_moments(mean || var, circ, given_mask));
   if (Nq == 0) return KDEHIP_OK;
@@ -537,12 +518,12 @@ extern "C" int kdehip_conditional(const kdehip_density *bd, uint32_t given_mask,
   run.circ.push_back(circ);
   const int ng = run.items[0].ng, nf = D - ng;
   // caller data: [the density | queries]; results: [logz (Nq) | mean (Nq nf) | var (Nq nf) | pts (Nq nf) | ind (Nq int64)]
-  const size_t o_q = host_density_bytes(bd), prefix = o_q + sizeof(double) * Nq * ng;
+  const size_t o_q = cond_density_bytes(bd), prefix = o_q + sizeof(double) * Nq * ng;
   const size_t r_mean = static_cast<size_t>(Nq), r_var = r_mean + static_cast<size_t>(Nq) * nf,
                r_pts = r_var + static_cast<size_t>(Nq) * nf, r_ind = r_pts + static_cast<size_t>(Nq) * nf;
   KDEHIP_CHECK_RC(run.alloc(prefix, r_ind + static_cast<size_t>(Nq)));
   CondItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  pack_cond_density(run, ri, bd);
   std::memcpy(run.host() + o_q, given, sizeof(double) * Nq * ng);
   ri.given = reinterpret_cast<const double *>(run.dev() + o_q);
   ri.logz = logz ? run.result(0) : nullptr;
@@ -561,17 +542,16 @@ extern "C" int kdehip_conditional(const kdehip_density *bd, uint32_t given_mask,
 }
 
 extern "C" int kdehip_conditional_device_batch(int n, const kdehip_conditional_item *items, void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "conditional batch: bad item list");
+  KDEHIP_CHECK_RC(check_batch_list(n, items, "conditional batch: "));
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
     const kdehip_conditional_item &c = items[i];
-    KDEHIP_CHECK_RC(check_resident(c.bd));
+    KDEHIP_CHECK_RC(check_resident_density(c.bd, false));
     KDEHIP_CHECK_RC(check_outputs(c.d_logz, c.d_mean, c.d_var, c.d_pts, c.d_ind));
-    if (c.bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "conditional batch: densities on different devices");
+    KDEHIP_CHECK_RC(check_same_device(c.bd, items[0].bd, "conditional batch: "));
     KDEHIP_CHECK_RC(check_mask(c.given_mask, c.bd->D));
-    if (c.circular_mask >> c.bd->D)
-      return set_error(KDEHIP_ERR_ARG, "conditional batch: circular_mask names a dimension the density does not have");
-    if (c.Nq < 0 || (c.Nq > 0 && !c.d_given)) return set_error(KDEHIP_ERR_ARG, "d_given must hold Nq >= 0 queries");
+    KDEHIP_CHECK_RC(check_circular_mask(c.circular_mask, c.bd->D, "conditional batch: "));
+    KDEHIP_CHECK_RC(check_query_count(c.d_given, c.Nq, kDeviceGiven));
     if (!leaves_share_bandwidth(c.bd)) return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
     KDEHIP_CHECK_RC(check_free_moments(c.d_mean || c.d_var, c.circular_mask, c.given_mask));
   }
@@ -597,7 +577,7 @@ extern "C" int kdehip_conditional_device_batch(int n, const kdehip_conditional_i
     ri.logz = c.d_logz; ri.mean = c.d_mean; ri.var = c.d_var; ri.pts = c.d_pts; ri.ind = c.d_ind;
   }
   KDEHIP_CHECK_RC(run.run(static_cast<hipStream_t>(stream)));
-  return run.defer(device);
+  return finish_enqueue(run, nullptr, device);
 }
 
 extern "C" int kdehip_conditional_device(const kdehip_device_density *bd, uint32_t given_mask, const double *d_given, int64_t Nq,
@@ -605,7 +585,7 @@ extern "C" int kdehip_conditional_device(const kdehip_device_density *bd, uint32
                                          double *d_pts, int64_t *d_ind, const uint8_t *manifold, void *stream) {
   if (!bd) return set_error(KDEHIP_ERR_ARG, "null density");
   uint32_t circ = 0;
-  KDEHIP_CHECK_RC(check_resident(bd));
+  KDEHIP_CHECK_RC(check_resident_density(bd, false));
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   kdehip_conditional_item c{};
   c.bd = bd; c.d_given = d_given; c.Nq = Nq; c.seed = seed; c.sample_offset = sample_offset;
@@ -617,13 +597,13 @@ extern "C" int kdehip_conditional_device(const kdehip_device_density *bd, uint32
 extern "C" int kdehip_condition_weights(const kdehip_density *bd, uint32_t given_mask, const double *given, int64_t Nq,
                                         double *w_out, double *logz, int device, const uint8_t *manifold) {
   if (!bd || !w_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
   KDEHIP_CHECK_RC(check_mask(given_mask, D));
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !given)) return set_error(KDEHIP_ERR_ARG, "given must hold Nq >= 0 queries");
+  KDEHIP_CHECK_RC(check_query_count(given, Nq, kGiven));
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
@@ -633,11 +613,11 @@ extern "C" int kdehip_condition_weights(const kdehip_density *bd, uint32_t given
   run.circ.push_back(circ);
   const int ng = run.items[0].ng;
   // caller data: [the density | queries]; results: [w_out (Nq N) | logz (Nq)]
-  const size_t o_q = host_density_bytes(bd), prefix = o_q + sizeof(double) * Nq * ng;
+  const size_t o_q = cond_density_bytes(bd), prefix = o_q + sizeof(double) * Nq * ng;
   const size_t r_logz = static_cast<size_t>(Nq) * N;
   KDEHIP_CHECK_RC(run.alloc(prefix, r_logz + static_cast<size_t>(Nq)));
   CondItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  pack_cond_density(run, ri, bd);
   std::memcpy(run.host() + o_q, given, sizeof(double) * Nq * ng);
   ri.given = reinterpret_cast<const double *>(run.dev() + o_q);
   ri.wout = run.result(0);
@@ -654,11 +634,11 @@ extern "C" int kdehip_condition_weights_device(const kdehip_device_density *bd, 
                                                int64_t Nq, double *d_w_out, double *d_logz, const uint8_t *manifold,
                                                void *stream) {
   if (!bd || !d_w_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_resident(bd));
+  KDEHIP_CHECK_RC(check_resident_density(bd, false));
   KDEHIP_CHECK_RC(check_mask(given_mask, bd->D));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !d_given)) return set_error(KDEHIP_ERR_ARG, "d_given must hold Nq >= 0 queries");
+  KDEHIP_CHECK_RC(check_query_count(d_given, Nq, kDeviceGiven));
   if (!leaves_share_bandwidth(bd)) return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
@@ -674,5 +654,5 @@ extern "C" int kdehip_condition_weights_device(const kdehip_device_density *bd, 
   ri.logz = d_logz;
   KDEHIP_CHECK_RC(run.run(static_cast<hipStream_t>(stream)));
   KDEHIP_CHECK_RC(run.weights());
-  return run.defer(bd->device);
+  return finish_enqueue(run, nullptr, bd->device);
 }

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "density_args.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "evaltol.hpp"
@@ -359,30 +360,16 @@ bool kdehip::leaves_share_bandwidth(const kdehip_device_density *h) {
 
 namespace {
 
-const char kOneBandwidth[] = "per-point bandwidths are not supported (the reference's kde! never builds them)";
-
-// the checks every resident entry makes; `at` may be bd
-int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at, int loo) {
-  if (!bd || !at) return set_error(KDEHIP_ERR_ARG, "null density");
-  if (loo && at != bd) return set_error(KDEHIP_ERR_ARG, "leave_one_out needs at == bd");
-  if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (at->D != bd->D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "evaluate -- dimensions of two BallTreeDensities must match");
-  if (at->device != bd->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
-  if (!leaves_share_bandwidth(bd)) return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
-  return KDEHIP_OK;
-}
-
 // bd at at's leaf points (tree order; out, if any, through at's permutation), W = at's leaf weights
 EvalItem pair_item(const kdehip_device_density *bd, const kdehip_device_density *at, int loo, bool logl, bool logdom) {
+  const LeafRows src = leaf_rows(bd), qry = leaf_rows(at);
   EvalItem it{};
-  const int64_t N = bd->N, Nq = at->N;
-  const int D = bd->D;
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
-  it.qry = at->means + Nq * D;
-  it.qw = logl ? at->weights + Nq : nullptr;
-  it.perm = at->perm + Nq;
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = Nq; it.D = D; it.loo = loo ? 1 : 0; it.logdom = logdom ? 1 : 0;
+  it.src = src.src; it.w = src.w; it.bw = src.bw;
+  it.qry = qry.src;
+  it.qw = logl ? qry.w : nullptr;
+  it.perm = qry.perm;
+  it.norm0 = gauss_norm0(bd->D);
+  it.N = bd->N; it.Nq = at->N; it.D = bd->D; it.loo = loo ? 1 : 0; it.logdom = logdom ? 1 : 0;
   return it;
 }
 
@@ -437,13 +424,11 @@ int enqueue_tol(const EvalRun &run, uint32_t circ, const TolArgs &tol, int64_t *
 static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out, double *p_out, int device,
                          const uint8_t *manifold, bool logdom, const TolArgs *tol = nullptr) {
   if (!bd || !p_out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
-  if (D < 1 || D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (N < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
-    return set_error(KDEHIP_ERR_ARG, "malformed density");
   if (leave_one_out) Nq = N;
   else if (!pos || Nq < 0) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
   if (Nq == 0) {
@@ -452,33 +437,28 @@ static int evaluate_host(const kdehip_density *bd, const double *pos, int64_t Nq
   }
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));  // (the reference's evalDirect reads bandwidthMin[1..D])
   DeviceGuard guard;
-  int rc = guard.enter(device);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(guard.enter(device));
   hipStream_t st = hipStreamPerThread;  // the calling thread's own stream, like every blocking entry point (kdehip.h)
-  // caller data: [leaf means (leaf centres == the points, tree order) | leaf weights | leaf bandwidth | queries, or
+  // caller data: [the density (leaf means | leaf weights | leaf bandwidth: density_args.hpp) | queries, or
   // (leave-one-out) the leaf row of the permutation: p[getIndexOf(locations, j)] (:335), results in the caller's original
   // order].  ONE pinned image goes up in one DMA and the Nq results come back in one; everything is enqueued on the
   // calling thread's stream and the host waits once (pageable hipMemcpy calls, one per array, cost more than the kernel
   // for anything below ~10^8 kernel evaluations).
-  const size_t o_bw = sizeof(double) * N * (D + 1), o_q = o_bw + sizeof(double) * D;
+  const size_t o_q = host_density_bytes(bd);
   const size_t prefix = o_q + (leave_one_out ? sizeof(int64_t) * N : sizeof(double) * Nq * D);
   EvalRun run;
   EvalItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(D);
   it.N = N; it.Nq = Nq; it.D = D; it.loo = leave_one_out ? 1 : 0; it.logdom = logdom ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);
   static_assert(sizeof(int64_t) == sizeof(double), "the tile counts take two result slots");
   KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq) + (tol ? 2 : 0), tol ? tol_scratch_bytes(N, Nq, D) : 0));
   unsigned char *h = run.host(), *d = run.dev();
-  const LeafArrays src = pack_leaves(run, 0, bd);
-  std::memcpy(h + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
+  EvalItem &ri = run.items[0];
+  ri.bw = pack_host_density(run, ri, bd);
   if (leave_one_out) std::memcpy(h + o_q, bd->permutation + N, sizeof(int64_t) * N);
   else std::memcpy(h + o_q, pos, sizeof(double) * Nq * D);
-  EvalItem &ri = run.items[0];
-  ri.src = src.means;
-  ri.w = src.weights;
-  ri.bw = reinterpret_cast<const double *>(d + o_bw);
   ri.qry = leave_one_out ? ri.src : reinterpret_cast<const double *>(d + o_q);
   ri.perm = leave_one_out ? reinterpret_cast<const int64_t *>(d + o_q) : nullptr;
   ri.out = run.result(0);
@@ -523,26 +503,21 @@ static int eval_avg_logl_host(const kdehip_density *bd, const kdehip_density *at
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
-  int rc = guard.enter(device);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(guard.enter(device));
   hipStream_t st = hipStreamPerThread;
   const bool self = at == bd;
   // caller data: [bd leaf means | bd leaf weights | bd leaf bandwidth | at leaf means | at leaf weights] (at == bd: none)
-  const size_t o_bw = sizeof(double) * N * (D + 1), o_q = o_bw + sizeof(double) * D;
-  const size_t prefix = o_q + (self ? 0 : sizeof(double) * Nq * (D + 1));
+  const size_t o_q = host_density_bytes(bd), prefix = o_q + (self ? 0 : sizeof(double) * Nq * (D + 1));
   EvalRun run;
   EvalItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(static_cast<int>(D));
   it.N = N; it.Nq = Nq; it.D = static_cast<int32_t>(D); it.loo = leave_one_out ? 1 : 0; it.logdom = logdom ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix));
-  const LeafArrays src = pack_leaves(run, 0, bd), qry = self ? src : pack_leaves(run, o_q, at);
-  std::memcpy(run.host() + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
   EvalItem &ri = run.items[0];
-  ri.src = src.means;
-  ri.w = src.weights;
-  ri.bw = reinterpret_cast<const double *>(run.dev() + o_bw);
+  ri.bw = pack_host_density(run, ri, bd);
+  const LeafArrays qry = self ? LeafArrays{ri.src, ri.w} : pack_leaves(run, o_q, at);
   ri.qry = qry.means;
   ri.qw = qry.weights;
   ri.logl = run.result(0);
@@ -568,16 +543,14 @@ static int eval_avg_logl_batch(int n, const kdehip_logl_manifold_item *items, do
   if (n < 0 || (n > 0 && (!items || !d_out))) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: bad item list");
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
-    const int rc = check_pair(items[i].bd, items[i].at, items[i].leave_one_out);
-    if (rc != KDEHIP_OK) return rc;
-    if (items[i].bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: densities on different devices");
+    KDEHIP_CHECK_RC(check_pair(items[i].bd, items[i].at, items[i].leave_one_out, true));
+    KDEHIP_CHECK_RC(check_same_device(items[i].bd, items[0].bd, "evalAvgLogL batch: "));
     if (items[i].circular_mask >> items[i].bd->D)
       return set_error(KDEHIP_ERR_ARG, "evalAvgLogL batch: circular_mask names a dimension the densities do not have");
   }
   const int device = items[0].bd->device;
   DeviceGuard guard;
-  int rc = guard.enter(device);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(guard.enter(device));
   EvalRun run;
   for (int i = 0; i < n; ++i) {
     run.items.push_back(pair_item(items[i].bd, items[i].at, items[i].leave_one_out, true, logdom));
@@ -586,7 +559,7 @@ static int eval_avg_logl_batch(int n, const kdehip_logl_manifold_item *items, do
   }
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
-  return run.defer(device);
+  return finish_enqueue(run, nullptr, device);
 }
 
 extern "C" int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
@@ -597,13 +570,11 @@ extern "C" int kdehip_eval_avg_logl_device(const kdehip_device_density *bd, cons
 static int eval_avg_logl_resident(const kdehip_device_density *bd, const kdehip_device_density *at, int leave_one_out,
                                   double *out, const uint8_t *manifold, bool logdom) {
   if (!out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  int rc = check_pair(bd, at, leave_one_out);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(check_pair(bd, at, leave_one_out, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
-  rc = guard.enter(bd->device);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(guard.enter(bd->device));
   EvalRun run;
   run.items.push_back(pair_item(bd, at, leave_one_out, true, logdom));
   run.circ.push_back(circ);
@@ -627,15 +598,13 @@ static int evaluate_resident(const kdehip_device_density *bd, const double *d_po
                              void *stream, const uint8_t *manifold, bool logdom) {
   if (!bd || !d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
   if (leave_one_out) return evaluate_resident_at(bd, bd, d_out, stream, manifold, logdom);
-  if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
-  int rc = check_pair(bd, bd, 0);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(check_query_count(d_pos, Nq, "d_pos must hold Nq >= 0 points"));
+  KDEHIP_CHECK_RC(check_pair(bd, bd, 0, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
-  rc = guard.enter(bd->device);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(guard.enter(bd->device));
   EvalRun run;
   EvalItem it = pair_item(bd, bd, 0, false, logdom);
   it.qry = d_pos; it.perm = nullptr; it.Nq = Nq; it.out = d_out;
@@ -643,7 +612,7 @@ static int evaluate_resident(const kdehip_device_density *bd, const double *d_po
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
-  return run.defer(bd->device);
+  return finish_enqueue(run, nullptr, bd->device);
 }
 
 extern "C" int kdehip_evaluate_device_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out,
@@ -654,13 +623,11 @@ extern "C" int kdehip_evaluate_device_at(const kdehip_device_density *bd, const 
 static int evaluate_resident_at(const kdehip_device_density *bd, const kdehip_device_density *at, double *d_out, void *stream,
                                 const uint8_t *manifold, bool logdom) {
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  int rc = check_pair(bd, at, at == bd);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(check_pair(bd, at, at == bd, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
-  rc = guard.enter(bd->device);
-  if (rc != KDEHIP_OK) return rc;
+  KDEHIP_CHECK_RC(guard.enter(bd->device));
   EvalRun run;
   EvalItem it = pair_item(bd, at, at == bd, false, logdom);
   it.out = d_out;
@@ -668,7 +635,7 @@ static int evaluate_resident_at(const kdehip_device_density *bd, const kdehip_de
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
-  return run.defer(bd->device);
+  return finish_enqueue(run, nullptr, bd->device);
 }
 
 // ---- evaluation within a tolerance (kdehip.h section 5m): the bodies above with the passes of evaltol.hip in the sweep's place
@@ -687,7 +654,7 @@ extern "C" int kdehip_evaluate_device_at_tol(const kdehip_device_density *bd, co
   TolArgs tol{};
   KDEHIP_CHECK_RC(read_tolerances(rel_tol, abs_tol, &tol));
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_pair(bd, at, at == bd));
+  KDEHIP_CHECK_RC(check_pair(bd, at, at == bd, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   DeviceGuard guard;
@@ -703,7 +670,7 @@ extern "C" int kdehip_evaluate_device_at_tol(const kdehip_device_density *bd, co
   KDEHIP_CHECK_RC(run.upload(st));
   KDEHIP_CHECK_RC(enqueue_tol(run, circ, tol, d_stats, st));
   KDEHIP_CHECK_RC(run.launch_finish());
-  return scope.capturing() ? run.keep(bd->device) : run.defer(bd->device);
+  return finish_enqueue(run, &scope, bd->device);
 }
 
 extern "C" int kdehip_evaluate_manifold(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,

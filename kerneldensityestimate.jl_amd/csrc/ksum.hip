@@ -24,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "density_args.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "manifold_arg.hpp"
@@ -35,7 +36,8 @@ using namespace kdehip;
 
 namespace {
 
-const char kOneBandwidth[] = "per-point bandwidths need explicit variances (the sum of the leaf variances is one vector)";
+// (this unit's own words: not density_args.hpp's kOneBandwidth)
+const char kNeedVariances[] = "per-point bandwidths need explicit variances (the sum of the leaf variances is one vector)";
 
 // One sum: the N leaves of A (the head's sources) against the M = Nq leaves of B (its queries).
 struct KsumItem : PairHead {
@@ -169,27 +171,26 @@ int check_resident(const kdehip_device_density *a, const kdehip_device_density *
   if (a->D != b->D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "kernel sum -- dimensions of two BallTreeDensities must match");
   if (a->device != b->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
   if (!var && !(leaves_share_bandwidth(a) && leaves_share_bandwidth(b)))
-    return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
+    return set_error(KDEHIP_ERR_UNSUPPORTED, kNeedVariances);
   KDEHIP_CHECK_RC(check_var(var, a->D));
   if (mask >> a->D) return set_error(KDEHIP_ERR_ARG, "kernel sum: circular_mask names a dimension the densities do not have");
   return KDEHIP_OK;
 }
 
 KsumItem resident_item(const kdehip_device_density *a, const kdehip_device_density *b, int normalize) {
+  const LeafRows la = leaf_rows(a), lb = leaf_rows(b);
   KsumItem it{};
-  const int64_t N = a->N, M = b->N;
-  const int D = a->D;
-  it.src = a->means + N * D; it.w = a->weights + N; it.va = a->bandwidth + N * D;
-  it.qry = b->means + M * D; it.qw = b->weights + M; it.vb = b->bandwidth + M * D;
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = M; it.D = D; it.normalize = normalize ? 1 : 0;
+  it.src = la.src; it.w = la.w; it.va = la.bw;
+  it.qry = lb.src; it.qw = lb.w; it.vb = lb.bw;
+  it.norm0 = gauss_norm0(a->D);
+  it.N = a->N; it.Nq = b->N; it.D = a->D; it.normalize = normalize ? 1 : 0;
   return it;
 }
 
 // a host density as the sum reads it: leaves, weights and (without explicit variances) ONE bandwidth vector
 int check_host(const kdehip_density *p, bool need_bw) {
   if (p->npts < 1 || !p->means || !p->weights || (need_bw && !p->bandwidth)) return set_error(KDEHIP_ERR_ARG, "malformed density");
-  return need_bw ? check_one_bandwidth(p, kOneBandwidth) : KDEHIP_OK;
+  return need_bw ? check_one_bandwidth(p, kNeedVariances) : KDEHIP_OK;
 }
 
 }  // namespace
@@ -213,7 +214,7 @@ extern "C" int kdehip_kernel_sum_device_batch(int n, const kdehip_ksum_item *ite
   }
   KDEHIP_CHECK_RC(run.alloc(0));
   KDEHIP_CHECK_RC(run.enqueue(static_cast<hipStream_t>(stream)));
-  return run.defer(device);
+  return finish_enqueue(run, nullptr, device);
 }
 
 extern "C" int kdehip_kernel_sum_device(const kdehip_device_density *a, const kdehip_device_density *b, const double *var,
@@ -258,7 +259,7 @@ extern "C" int kdehip_kernel_sum(const kdehip_density *a, const kdehip_density *
   const size_t o_vb = o_va + (var ? 0 : sizeof(double) * D), prefix = o_vb + (var ? 0 : sizeof(double) * D);
   KsumRun run;
   KsumItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(static_cast<int>(D));
   it.N = N; it.Nq = M; it.D = static_cast<int32_t>(D); it.normalize = normalize ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);

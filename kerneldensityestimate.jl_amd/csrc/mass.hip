@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "density_args.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "manifold_arg.hpp"
@@ -32,7 +33,6 @@ using namespace kdehip;
 
 namespace {
 
-const char kOneBandwidth[] = "per-point bandwidths are not supported (the reference's kde! never builds them)";
 constexpr int kFinishThreads = 256;    // queries per finish block
 constexpr int kQuantileThreads = 256;  // lanes of the workgroup that solves one level
 
@@ -327,32 +327,15 @@ class QuantRun : public PairRun<QuantItem> {
   }
 };
 
-// ---- arguments (none of these touches a device) --------------------------------------------------------------------------
+// ---- arguments (none of these touches a device; the density's own checks are density_args.hpp) ---------------------------
 
-int check_resident(const kdehip_device_density *bd) {
-  if (!bd) return set_error(KDEHIP_ERR_ARG, "null density");
-  if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (!leaves_share_bandwidth(bd)) return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
-  return KDEHIP_OK;
-}
-
-int check_host(const kdehip_density *bd) {
-  if (!bd) return set_error(KDEHIP_ERR_ARG, "null argument");
-  if (bd->ndim < 1 || bd->ndim > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (bd->npts < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
-    return set_error(KDEHIP_ERR_ARG, "malformed density");
-  return KDEHIP_OK;
-}
+const char kBoxes[] = "lo and hi must hold Nq >= 0 boxes", kDeviceBoxes[] = "d_lo and d_hi must hold Nq >= 0 boxes";
+const char kLevels[] = "alpha must hold Nq >= 0 levels", kDeviceLevels[] = "d_alpha must hold Nq >= 0 levels";
 
 // the bounded dimensions of a box: between 1 and D of them, none at or above D, none circular
 int check_box(uint64_t dim_mask, uint32_t circ, int D) {
   if (dim_mask == 0u || (dim_mask >> D)) return set_error(KDEHIP_ERR_ARG, "box mass: dim_mask names between 1 and ndims dimensions of the density");
   if (dim_mask & circ) return set_error(KDEHIP_ERR_UNSUPPORTED, "box mass: a circular dimension cannot be bounded");
-  return KDEHIP_OK;
-}
-
-int check_circular_mask(uint32_t circ, int D) {
-  if (circ >> D) return set_error(KDEHIP_ERR_ARG, "circular_mask names a dimension the density does not have");
   return KDEHIP_OK;
 }
 
@@ -378,49 +361,17 @@ void set_dims(MassItem &it, uint64_t dim_mask) {
     if ((dim_mask >> d) & 1u) it.dims[it.nb++] = static_cast<uint8_t>(d);
 }
 
-MassItem resident_mass_item(const kdehip_device_density *bd, uint64_t dim_mask, int64_t Nq) {
-  MassItem it{};
-  const int64_t N = bd->N;
-  const int D = bd->D;
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
-  it.N = N; it.Nq = Nq; it.D = D;
-  set_dims(it, dim_mask);
-  return it;
-}
-
-QuantItem resident_quant_item(const kdehip_device_density *bd, int dim, int64_t Nq, double tol, int max_iter) {
-  QuantItem it{};
-  const int64_t N = bd->N;
-  const int D = bd->D;
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
-  it.N = N; it.Nq = Nq; it.D = D; it.dim = dim; it.tol = tol; it.max_iter = max_iter;
-  return it;
-}
-
-// a host density's leaves, weights and bandwidth vector at offset 0 of the call's image: [means | weights | bw]
-size_t host_density_bytes(const kdehip_density *bd) { return sizeof(double) * (bd->npts * (bd->ndim + 1) + bd->ndim); }
-template <typename Run, typename Item>
-void pack_host_density(Run &run, Item &it, const kdehip_density *bd) {
-  const int64_t N = bd->npts, D = bd->ndim;
-  const LeafArrays src = pack_leaves(run, 0, bd);
-  const size_t o_bw = sizeof(double) * N * (D + 1);
-  std::memcpy(run.host() + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
-  it.src = src.means;
-  it.w = src.weights;
-  it.bw = reinterpret_cast<const double *>(run.dev() + o_bw);
-}
-
 }  // namespace
 
 extern "C" int kdehip_box_mass(const kdehip_density *bd, uint64_t dim_mask, const double *lo, const double *hi, int64_t Nq,
                                double *mass, int device, const uint8_t *manifold) {
   // every check that needs no device comes first
   if (!bd || !mass) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && (!lo || !hi))) return set_error(KDEHIP_ERR_ARG, "lo and hi must hold Nq >= 0 boxes");
+  KDEHIP_CHECK_RC(check_query_count(lo && hi ? lo : nullptr, Nq, kBoxes));
   KDEHIP_CHECK_RC(check_box(dim_mask, circ, D));
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
   if (Nq == 0) return KDEHIP_OK;
@@ -436,7 +387,7 @@ extern "C" int kdehip_box_mass(const kdehip_density *bd, uint64_t dim_mask, cons
   run.items.push_back(it);
   KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq)));
   MassItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  ri.bw = pack_host_density(run, ri, bd);
   std::memcpy(run.host() + o_lo, lo, bounds);
   std::memcpy(run.host() + o_hi, hi, bounds);
   ri.qry = reinterpret_cast<const double *>(run.dev() + o_lo);
@@ -449,38 +400,15 @@ extern "C" int kdehip_box_mass(const kdehip_density *bd, uint64_t dim_mask, cons
   return KDEHIP_OK;
 }
 
-extern "C" int kdehip_box_mass_device(const kdehip_device_density *bd, uint64_t dim_mask, const double *d_lo, const double *d_hi,
-                                      int64_t Nq, double *d_mass, const uint8_t *manifold, void *stream) {
-  if (!bd || !d_mass) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_resident(bd));
-  uint32_t circ = 0;
-  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && (!d_lo || !d_hi))) return set_error(KDEHIP_ERR_ARG, "d_lo and d_hi must hold Nq >= 0 boxes");
-  KDEHIP_CHECK_RC(check_box(dim_mask, circ, bd->D));
-  if (Nq == 0) return KDEHIP_OK;
-  DeviceGuard guard;
-  KDEHIP_CHECK_RC(guard.enter(bd->device));
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  CaptureScope scope(st);
-  MassRun run;
-  run.items.push_back(resident_mass_item(bd, dim_mask, Nq));
-  KDEHIP_CHECK_RC(run.alloc(0, 0));
-  MassItem &ri = run.items[0];
-  ri.qry = d_lo; ri.hi = d_hi; ri.out = d_mass;
-  KDEHIP_CHECK_RC(run.start(st));
-  KDEHIP_CHECK_RC(run.run());
-  return scope.capturing() ? run.keep(bd->device) : run.defer(bd->device);
-}
-
 extern "C" int kdehip_box_mass_device_batch(int n, const kdehip_box_mass_item *items, void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "box mass batch: bad item list");
+  KDEHIP_CHECK_RC(check_batch_list(n, items, "box mass batch: "));
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
     const kdehip_box_mass_item &b = items[i];
-    KDEHIP_CHECK_RC(check_resident(b.bd));
-    if (b.bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "box mass batch: densities on different devices");
-    KDEHIP_CHECK_RC(check_circular_mask(b.circular_mask, b.bd->D));
-    if (b.Nq < 0 || (b.Nq > 0 && (!b.d_lo || !b.d_hi))) return set_error(KDEHIP_ERR_ARG, "d_lo and d_hi must hold Nq >= 0 boxes");
+    KDEHIP_CHECK_RC(check_resident_density(b.bd, true));
+    KDEHIP_CHECK_RC(check_same_device(b.bd, items[0].bd, "box mass batch: "));
+    KDEHIP_CHECK_RC(check_circular_mask(b.circular_mask, b.bd->D, ""));
+    KDEHIP_CHECK_RC(check_query_count(b.d_lo && b.d_hi ? b.d_lo : nullptr, b.Nq, kDeviceBoxes));
     if (!b.d_mass) return set_error(KDEHIP_ERR_ARG, "null argument");
     KDEHIP_CHECK_RC(check_box(b.dim_mask, b.circular_mask, b.bd->D));
   }
@@ -493,7 +421,11 @@ extern "C" int kdehip_box_mass_device_batch(int n, const kdehip_box_mass_item *i
   for (int i = 0; i < n; ++i) {
     const kdehip_box_mass_item &b = items[i];
     if (b.Nq == 0) continue;
-    MassItem it = resident_mass_item(b.bd, b.dim_mask, b.Nq);
+    const LeafRows leaf = leaf_rows(b.bd);
+    MassItem it{};
+    it.src = leaf.src; it.w = leaf.w; it.bw = leaf.bw;
+    it.N = b.bd->N; it.Nq = b.Nq; it.D = b.bd->D;
+    set_dims(it, b.dim_mask);
     it.qry = b.d_lo; it.hi = b.d_hi; it.out = b.d_mass;
     run.items.push_back(it);
   }
@@ -501,7 +433,21 @@ extern "C" int kdehip_box_mass_device_batch(int n, const kdehip_box_mass_item *i
   KDEHIP_CHECK_RC(run.alloc(0, 0));
   KDEHIP_CHECK_RC(run.start(st));
   KDEHIP_CHECK_RC(run.run());
-  return scope.capturing() ? run.keep(device) : run.defer(device);
+  return finish_enqueue(run, &scope, device);
+}
+
+// One item of the batch: the entry's own checks are those the batch does not make, or makes later than this entry always
+// has; the boxes and the bounded dimensions are checked there, in this entry's order and words.
+extern "C" int kdehip_box_mass_device(const kdehip_device_density *bd, uint64_t dim_mask, const double *d_lo, const double *d_hi,
+                                      int64_t Nq, double *d_mass, const uint8_t *manifold, void *stream) {
+  if (!bd || !d_mass) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_resident_density(bd, true));
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  kdehip_box_mass_item b{};
+  b.bd = bd; b.d_lo = d_lo; b.d_hi = d_hi; b.Nq = Nq; b.d_mass = d_mass;
+  b.dim_mask = dim_mask; b.circular_mask = circ;
+  return kdehip_box_mass_device_batch(1, &b, stream);
 }
 
 extern "C" int kdehip_quantile(const kdehip_density *bd, int dim, const double *alpha, int64_t Nq, const double *tol_arg, int max_iter,
@@ -509,11 +455,11 @@ extern "C" int kdehip_quantile(const kdehip_density *bd, int dim, const double *
                                const uint8_t *manifold) {
   // every check that needs no device comes first
   if (!bd || !x) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !alpha)) return set_error(KDEHIP_ERR_ARG, "alpha must hold Nq >= 0 levels");
+  KDEHIP_CHECK_RC(check_query_count(alpha, Nq, kLevels));
   double tol = 0.0;
   KDEHIP_CHECK_RC(check_iteration(tol_arg, &tol, &max_iter));
   KDEHIP_CHECK_RC(check_quantile_dim(dim, circ, D));
@@ -534,7 +480,7 @@ extern "C" int kdehip_quantile(const kdehip_density *bd, int dim, const double *
   run.items.push_back(it);
   KDEHIP_CHECK_RC(run.alloc(prefix, nres));
   QuantItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  ri.bw = pack_host_density(run, ri, bd);
   std::memcpy(run.host() + o_alpha, alpha, sizeof(double) * n);
   ri.qry = reinterpret_cast<const double *>(run.dev() + o_alpha);
   ri.x = run.result(r_x);
@@ -551,45 +497,18 @@ extern "C" int kdehip_quantile(const kdehip_density *bd, int dim, const double *
   return KDEHIP_OK;
 }
 
-extern "C" int kdehip_quantile_device(const kdehip_device_density *bd, int dim, const double *d_alpha, int64_t Nq,
-                                      const double *tol_arg, int max_iter, double *d_x, double *d_resid, int32_t *d_iters, int32_t *d_converged,
-                                      const uint8_t *manifold, void *stream) {
-  if (!bd || !d_x) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_resident(bd));
-  uint32_t circ = 0;
-  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !d_alpha)) return set_error(KDEHIP_ERR_ARG, "d_alpha must hold Nq >= 0 levels");
-  double tol = 0.0;
-  KDEHIP_CHECK_RC(check_iteration(tol_arg, &tol, &max_iter));
-  KDEHIP_CHECK_RC(check_quantile_dim(dim, circ, bd->D));
-  if (Nq == 0) return KDEHIP_OK;
-  DeviceGuard guard;
-  KDEHIP_CHECK_RC(guard.enter(bd->device));
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  CaptureScope scope(st);
-  QuantRun run;
-  run.items.push_back(resident_quant_item(bd, dim, Nq, tol, max_iter));
-  KDEHIP_CHECK_RC(run.alloc(0, 0));
-  QuantItem &ri = run.items[0];
-  ri.qry = d_alpha;
-  ri.x = d_x; ri.resid = d_resid; ri.iters = d_iters; ri.converged = d_converged;
-  KDEHIP_CHECK_RC(run.start(st));
-  KDEHIP_CHECK_RC(run.run());
-  return scope.capturing() ? run.keep(bd->device) : run.defer(bd->device);
-}
-
 extern "C" int kdehip_quantile_device_batch(int n, const kdehip_quantile_item *items, const double *tol_arg, int max_iter,
                                             void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "quantile batch: bad item list");
+  KDEHIP_CHECK_RC(check_batch_list(n, items, "quantile batch: "));
   double tol = 0.0;
   KDEHIP_CHECK_RC(check_iteration(tol_arg, &tol, &max_iter));
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
     const kdehip_quantile_item &b = items[i];
-    KDEHIP_CHECK_RC(check_resident(b.bd));
-    if (b.bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "quantile batch: densities on different devices");
-    KDEHIP_CHECK_RC(check_circular_mask(b.circular_mask, b.bd->D));
-    if (b.Nq < 0 || (b.Nq > 0 && !b.d_alpha)) return set_error(KDEHIP_ERR_ARG, "d_alpha must hold Nq >= 0 levels");
+    KDEHIP_CHECK_RC(check_resident_density(b.bd, true));
+    KDEHIP_CHECK_RC(check_same_device(b.bd, items[0].bd, "quantile batch: "));
+    KDEHIP_CHECK_RC(check_circular_mask(b.circular_mask, b.bd->D, ""));
+    KDEHIP_CHECK_RC(check_query_count(b.d_alpha, b.Nq, kDeviceLevels));
     if (!b.d_x) return set_error(KDEHIP_ERR_ARG, "null argument");
     KDEHIP_CHECK_RC(check_quantile_dim(b.dim, b.circular_mask, b.bd->D));
   }
@@ -602,7 +521,10 @@ extern "C" int kdehip_quantile_device_batch(int n, const kdehip_quantile_item *i
   for (int i = 0; i < n; ++i) {
     const kdehip_quantile_item &b = items[i];
     if (b.Nq == 0) continue;
-    QuantItem it = resident_quant_item(b.bd, b.dim, b.Nq, tol, max_iter);
+    const LeafRows leaf = leaf_rows(b.bd);
+    QuantItem it{};
+    it.src = leaf.src; it.w = leaf.w; it.bw = leaf.bw;
+    it.N = b.bd->N; it.Nq = b.Nq; it.D = b.bd->D; it.dim = b.dim; it.tol = tol; it.max_iter = max_iter;
     it.qry = b.d_alpha;
     it.x = b.d_x; it.resid = b.d_resid; it.iters = b.d_iters; it.converged = b.d_converged;
     run.items.push_back(it);
@@ -611,5 +533,20 @@ extern "C" int kdehip_quantile_device_batch(int n, const kdehip_quantile_item *i
   KDEHIP_CHECK_RC(run.alloc(0, 0));
   KDEHIP_CHECK_RC(run.start(st));
   KDEHIP_CHECK_RC(run.run());
-  return scope.capturing() ? run.keep(device) : run.defer(device);
+  return finish_enqueue(run, &scope, device);
+}
+
+// one item of the batch, likewise
+extern "C" int kdehip_quantile_device(const kdehip_device_density *bd, int dim, const double *d_alpha, int64_t Nq,
+                                      const double *tol_arg, int max_iter, double *d_x, double *d_resid, int32_t *d_iters, int32_t *d_converged,
+                                      const uint8_t *manifold, void *stream) {
+  if (!bd || !d_x) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_resident_density(bd, true));
+  uint32_t circ = 0;
+  if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  KDEHIP_CHECK_RC(check_query_count(d_alpha, Nq, kDeviceLevels));
+  kdehip_quantile_item b{};
+  b.bd = bd; b.d_alpha = d_alpha; b.Nq = Nq; b.d_x = d_x; b.d_resid = d_resid; b.d_iters = d_iters; b.d_converged = d_converged;
+  b.dim = dim; b.circular_mask = circ;
+  return kdehip_quantile_device_batch(1, &b, tol_arg, max_iter, stream);
 }

@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "density_args.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "manifold_arg.hpp"
@@ -39,8 +40,6 @@
 using namespace kdehip;
 
 namespace {
-
-const char kOneBandwidth[] = "per-point bandwidths are not supported (the reference's kde! never builds them)";
 
 constexpr int kFinishThreads = kEvalThreads;  // a finish block is a query block: its live count is that block's
 constexpr int kRound = 8;                     // step sweeps between two reads of the live count (blocking calls)
@@ -626,20 +625,7 @@ class CurvRun : public PairRun<CurvItem> {
 
 // ---- arguments ------------------------------------------------------------------------------------------------------------
 
-int check_resident(const kdehip_device_density *bd) {
-  if (!bd) return set_error(KDEHIP_ERR_ARG, "null density");
-  if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (!leaves_share_bandwidth(bd)) return set_error(KDEHIP_ERR_UNSUPPORTED, kOneBandwidth);
-  return KDEHIP_OK;
-}
-
-int check_host(const kdehip_density *bd) {
-  if (!bd) return set_error(KDEHIP_ERR_ARG, "null argument");
-  if (bd->ndim < 1 || bd->ndim > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (bd->npts < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
-    return set_error(KDEHIP_ERR_ARG, "malformed density");
-  return KDEHIP_OK;
-}
+const char kPositions[] = "pos must hold Nq >= 0 points", kDevicePositions[] = "d_pos must hold Nq >= 0 points";
 
 int check_iteration(const double *tol, int maxiter) {
   if (!tol) return set_error(KDEHIP_ERR_ARG, "null argument");
@@ -655,36 +641,20 @@ int check_starts(const void *start, int64_t nstart, int64_t npts) {
 }
 
 MomentItem resident_item(const kdehip_device_density *bd, int64_t Nq, int logdom) {
+  const LeafRows leaf = leaf_rows(bd);
   MomentItem it{};
-  const int64_t N = bd->N;
-  const int D = bd->D;
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
-  it.perm = bd->perm + N;
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = Nq; it.D = D; it.logdom = logdom ? 1 : 0;
+  it.src = leaf.src; it.w = leaf.w; it.bw = leaf.bw; it.perm = leaf.perm;
+  it.norm0 = gauss_norm0(bd->D);
+  it.N = bd->N; it.Nq = Nq; it.D = bd->D; it.logdom = logdom ? 1 : 0;
   return it;
 }
 
-// a host density's leaves, weights and bandwidth vector at offset 0 of the call's image: [means | weights | bw]
-size_t host_density_bytes(const kdehip_density *bd) { return sizeof(double) * (bd->npts * (bd->ndim + 1) + bd->ndim); }
-template <typename Run, typename Item>
-void pack_host_density(Run &run, Item &it, const kdehip_density *bd) {
-  const int64_t N = bd->npts, D = bd->ndim;
-  const LeafArrays src = pack_leaves(run, 0, bd);
-  const size_t o_bw = sizeof(double) * N * (D + 1);
-  std::memcpy(run.host() + o_bw, bd->bandwidth + N * D, sizeof(double) * D);
-  it.src = src.means;
-  it.w = src.weights;
-  it.bw = reinterpret_cast<const double *>(run.dev() + o_bw);
-}
-
 CurvItem resident_curv_item(const kdehip_device_density *bd, int64_t Nq) {
+  const LeafRows leaf = leaf_rows(bd);
   CurvItem it{};
-  const int64_t N = bd->N;
-  const int D = bd->D;
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.bw = bd->bandwidth + N * D;
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
-  it.N = N; it.Nq = Nq; it.D = D;
+  it.src = leaf.src; it.w = leaf.w; it.bw = leaf.bw;
+  it.norm0 = gauss_norm0(bd->D);
+  it.N = bd->N; it.Nq = Nq; it.D = bd->D;
   return it;
 }
 
@@ -722,11 +692,11 @@ extern "C" int kdehip_evaluate_grad(const kdehip_density *bd, const double *pos,
                                     double *grad, int device, const uint8_t *manifold) {
   // every check that needs no device comes first
   if (!bd || (!val && !grad)) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !pos)) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
+  KDEHIP_CHECK_RC(check_query_count(pos, Nq, kPositions));
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
@@ -735,13 +705,13 @@ extern "C" int kdehip_evaluate_grad(const kdehip_density *bd, const double *pos,
   const size_t o_q = host_density_bytes(bd), prefix = o_q + sizeof(double) * Nq * D;
   MomentRun run;
   MomentItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(D);
   it.N = bd->npts; it.Nq = Nq; it.D = D; it.logdom = log_domain ? 1 : 0;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq) * (D + 1), false));
   MomentItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  ri.bw = pack_host_density(run, ri, bd);
   std::memcpy(run.host() + o_q, pos, sizeof(double) * Nq * D);
   ri.qry = reinterpret_cast<const double *>(run.dev() + o_q);
   ri.val = val ? run.result(0) : nullptr;
@@ -757,10 +727,10 @@ extern "C" int kdehip_evaluate_grad(const kdehip_density *bd, const double *pos,
 extern "C" int kdehip_evaluate_grad_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int log_domain,
                                            double *d_val, double *d_grad, const uint8_t *manifold, void *stream) {
   if (!bd || (!d_val && !d_grad)) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_resident(bd));
+  KDEHIP_CHECK_RC(check_resident_density(bd, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
+  KDEHIP_CHECK_RC(check_query_count(d_pos, Nq, kDevicePositions));
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
   KDEHIP_CHECK_RC(guard.enter(bd->device));
@@ -774,13 +744,13 @@ extern "C" int kdehip_evaluate_grad_device(const kdehip_device_density *bd, cons
   ri.grad = d_grad;
   KDEHIP_CHECK_RC(run.start(static_cast<hipStream_t>(stream)));
   KDEHIP_CHECK_RC(run.close());
-  return run.defer(bd->device);
+  return finish_enqueue(run, nullptr, bd->device);
 }
 
 extern "C" int kdehip_meanshift(const kdehip_density *bd, const double *start, int64_t nstart, const double *tol, int maxiter, double *x,
                                 double *logp, int32_t *iters, int device, const uint8_t *manifold) {
   if (!bd || !x || !logp || !iters) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
   uint32_t circ = 0;
@@ -795,13 +765,13 @@ extern "C" int kdehip_meanshift(const kdehip_density *bd, const double *start, i
   const size_t o_s = host_density_bytes(bd), prefix = o_s + (start ? sizeof(double) * nstart * D : sizeof(int64_t) * N);
   MomentRun run;
   MomentItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(D);
   it.N = N; it.Nq = nstart; it.D = D; it.logdom = 1; it.tol = *tol;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, shift_results(nstart, D), true));
   MomentItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  ri.bw = pack_host_density(run, ri, bd);
   if (start) {
     std::memcpy(run.host() + o_s, start, sizeof(double) * nstart * D);
     ri.start = reinterpret_cast<const double *>(run.dev() + o_s);
@@ -820,7 +790,7 @@ extern "C" int kdehip_meanshift(const kdehip_density *bd, const double *start, i
 extern "C" int kdehip_meanshift_device(const kdehip_device_density *bd, const double *d_start, int64_t nstart, const double *tol,
                                        int maxiter, double *x, double *logp, int32_t *iters, const uint8_t *manifold) {
   if (!bd || !x || !logp || !iters) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_resident(bd));
+  KDEHIP_CHECK_RC(check_resident_density(bd, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   KDEHIP_CHECK_RC(check_starts(d_start, nstart, bd->N));
@@ -844,15 +814,14 @@ extern "C" int kdehip_meanshift_device(const kdehip_device_density *bd, const do
 }
 
 extern "C" int kdehip_meanshift_device_batch(int n, const kdehip_meanshift_item *items, const double *tol, int niter, void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "mean shift batch: bad item list");
+  KDEHIP_CHECK_RC(check_batch_list(n, items, "mean shift batch: "));
   KDEHIP_CHECK_RC(check_iteration(tol, niter));
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
     const kdehip_meanshift_item &m = items[i];
-    KDEHIP_CHECK_RC(check_resident(m.bd));
-    if (m.bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "mean shift batch: densities on different devices");
-    if (m.circular_mask >> m.bd->D)
-      return set_error(KDEHIP_ERR_ARG, "mean shift batch: circular_mask names a dimension the density does not have");
+    KDEHIP_CHECK_RC(check_resident_density(m.bd, true));
+    KDEHIP_CHECK_RC(check_same_device(m.bd, items[0].bd, "mean shift batch: "));
+    KDEHIP_CHECK_RC(check_circular_mask(m.circular_mask, m.bd->D, "mean shift batch: "));
     KDEHIP_CHECK_RC(check_starts(m.d_start, m.nstart, m.bd->N));
     if (m.nstart > 0 && (!m.d_x || !m.d_logp || !m.d_iters)) return set_error(KDEHIP_ERR_ARG, "null argument");
   }
@@ -882,18 +851,18 @@ extern "C" int kdehip_meanshift_device_batch(int n, const kdehip_meanshift_item 
   KDEHIP_CHECK_RC(run.start(st));
   for (int s = 0; s < niter; ++s) KDEHIP_CHECK_RC(run.sweep());
   KDEHIP_CHECK_RC(run.close());
-  return scope.capturing() ? run.keep(device) : run.defer(device);
+  return finish_enqueue(run, &scope, device);
 }
 
 extern "C" int kdehip_evaluate_hess(const kdehip_density *bd, const double *pos, int64_t Nq, double *logp, double *grad, double *hess,
                                     double *cov, int32_t *definite, int device, const uint8_t *manifold) {
   // every check that needs no device comes first
   if (!bd || (!logp && !grad && !hess && !cov && !definite)) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_host(bd));
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !pos)) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
+  KDEHIP_CHECK_RC(check_query_count(pos, Nq, kPositions));
   KDEHIP_CHECK_RC(check_one_bandwidth(bd, kOneBandwidth));
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
@@ -908,13 +877,13 @@ extern "C" int kdehip_evaluate_hess(const kdehip_density *bd, const double *pos,
                r_def = take(definite, (n + 1) / 2);
   CurvRun run;
   CurvItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(D);
   it.N = bd->npts; it.Nq = Nq; it.D = D;
   run.items.push_back(it);
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, nres));
   CurvItem &ri = run.items[0];
-  pack_host_density(run, ri, bd);
+  ri.bw = pack_host_density(run, ri, bd);
   std::memcpy(run.host() + o_q, pos, sizeof(double) * Nq * D);
   ri.qry = reinterpret_cast<const double *>(run.dev() + o_q);
   ri.logp = logp ? run.result(r_logp) : nullptr;
@@ -937,10 +906,10 @@ extern "C" int kdehip_evaluate_hess_device(const kdehip_device_density *bd, cons
                                            double *d_grad, double *d_hess, double *d_cov, int32_t *d_definite,
                                            const uint8_t *manifold, void *stream) {
   if (!bd || (!d_logp && !d_grad && !d_hess && !d_cov && !d_definite)) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_resident(bd));
+  KDEHIP_CHECK_RC(check_resident_density(bd, true));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
+  KDEHIP_CHECK_RC(check_query_count(d_pos, Nq, kDevicePositions));
   if (Nq == 0) return KDEHIP_OK;
   DeviceGuard guard;
   KDEHIP_CHECK_RC(guard.enter(bd->device));
@@ -953,19 +922,18 @@ extern "C" int kdehip_evaluate_hess_device(const kdehip_device_density *bd, cons
   ri.logp = d_logp; ri.grad = d_grad; ri.hess = d_hess; ri.cov = d_cov; ri.definite = d_definite;
   KDEHIP_CHECK_RC(run.start(static_cast<hipStream_t>(stream)));
   KDEHIP_CHECK_RC(run.run());
-  return run.defer(bd->device);
+  return finish_enqueue(run, nullptr, bd->device);
 }
 
 extern "C" int kdehip_evaluate_hess_device_batch(int n, const kdehip_hess_item *items, void *stream) {
-  if (n < 0 || (n > 0 && !items)) return set_error(KDEHIP_ERR_ARG, "curvature batch: bad item list");
+  KDEHIP_CHECK_RC(check_batch_list(n, items, "curvature batch: "));
   if (n == 0) return KDEHIP_OK;
   for (int i = 0; i < n; ++i) {
     const kdehip_hess_item &h = items[i];
-    KDEHIP_CHECK_RC(check_resident(h.bd));
-    if (h.bd->device != items[0].bd->device) return set_error(KDEHIP_ERR_ARG, "curvature batch: densities on different devices");
-    if (h.circular_mask >> h.bd->D)
-      return set_error(KDEHIP_ERR_ARG, "curvature batch: circular_mask names a dimension the density does not have");
-    if (h.Nq < 0 || (h.Nq > 0 && !h.d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
+    KDEHIP_CHECK_RC(check_resident_density(h.bd, true));
+    KDEHIP_CHECK_RC(check_same_device(h.bd, items[0].bd, "curvature batch: "));
+    KDEHIP_CHECK_RC(check_circular_mask(h.circular_mask, h.bd->D, "curvature batch: "));
+    KDEHIP_CHECK_RC(check_query_count(h.d_pos, h.Nq, kDevicePositions));
     if (!h.d_logp && !h.d_grad && !h.d_hess && !h.d_cov && !h.d_definite) return set_error(KDEHIP_ERR_ARG, "null argument");
   }
   const int device = items[0].bd->device;
@@ -987,5 +955,5 @@ extern "C" int kdehip_evaluate_hess_device_batch(int n, const kdehip_hess_item *
   KDEHIP_CHECK_RC(run.alloc(0, 0));
   KDEHIP_CHECK_RC(run.start(st));
   KDEHIP_CHECK_RC(run.run());
-  return scope.capturing() ? run.keep(device) : run.defer(device);
+  return finish_enqueue(run, &scope, device);
 }

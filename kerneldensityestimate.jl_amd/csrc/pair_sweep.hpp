@@ -1,9 +1,10 @@
 // pair_sweep.hpp -- the all-pairs Gaussian sum behind evaluate.hip (eval_partial_kernel, eval_partial_log_kernel) and
 // ksum.hip (ksum_partial_kernel), written ONCE: the head both descriptors start with, a block's place in an item, the sweep
 // over the staged source chunks, the block reduction and the norm on the device; the skeleton of a call's run (EvalRun,
-// KsumRun), the scope of a call on a capturing stream and two small readers of a host density on the host.  Included by the
-// files of entry points that run the sweep or its mapping (evaluate, ksum, modes, conditional, mass), and by varbw.hip, whose
-// sweep over sources with variances of their own (pair_sweep_var) stands beside it.
+// KsumRun) and the scope of a call on a capturing stream on the host.  Included by the files of entry points that run the
+// sweep or its mapping (evaluate, evaltol, knn, ksum, modes, conditional, mass), and by varbw.hip, whose sweep over sources
+// with variances of their own (pair_sweep_var) stands beside it.  What those entries do with a density ARGUMENT -- its
+// checks, its leaf rows, its image in the call's block, the keep-or-defer ending -- is density_args.hpp, on top of this file.
 //
 // The sweep: one lane per query point, a block owns kEvalThreads queries and ONE group of consecutive kEvalChunk-point source
 // chunks, which it stages through a two-buffer LDS ring ([point][D coordinates, weight], read back as broadcasts) and walks
@@ -335,28 +336,5 @@ class CaptureScope {
   hipStreamCaptureMode mode_ = hipStreamCaptureModeGlobal;
   bool on_ = false, capturing_ = false;
 };
-
-// Every leaf of a host density has its first leaf's bandwidth -- the sums read ONE vector (bandwidthMin[1..D],
-// BallTreeDensity01.jl:98); otherwise KDEHIP_ERR_UNSUPPORTED in the caller's words.
-static inline int check_one_bandwidth(const kdehip_density *p, const char *words) {
-  const int64_t N = p->npts, D = p->ndim;
-  const double *bw = p->bandwidth + N * D;
-  for (int64_t i = 0; i < N; ++i)
-    for (int64_t k = 0; k < D; ++k)
-      if (p->bandwidth[(N + i) * D + k] != bw[k]) return set_error(KDEHIP_ERR_UNSUPPORTED, words);
-  return KDEHIP_OK;
-}
-
-// A host density's leaf means (leaf centres == the points, tree order) and, right behind them, its leaf weights copied to
-// offset `at` of the call's pinned image: the device pointers to both.
-struct LeafArrays { const double *means, *weights; };
-template <typename Run>
-static LeafArrays pack_leaves(const Run &run, size_t at, const kdehip_density *p) {
-  const int64_t N = p->npts, D = p->ndim;
-  const size_t o_w = at + sizeof(double) * N * D;
-  std::memcpy(run.host() + at, p->means + N * D, sizeof(double) * N * D);
-  std::memcpy(run.host() + o_w, p->weights + N, sizeof(double) * N);
-  return {reinterpret_cast<const double *>(run.dev() + at), reinterpret_cast<const double *>(run.dev() + o_w)};
-}
 
 }  // namespace kdehip

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "density_args.hpp"
 #include "device_density.hpp"
 #include "entry_helpers.hpp"
 #include "fastexp.hpp"
@@ -288,31 +289,21 @@ class VarRun : public PairRun<VarItem> {
 
 VarItem blank_item(int64_t N, int64_t Nq, int D, int loo, int logdom) {
   VarItem it{};
-  it.norm0 = std::pow(2.0 * M_PI, D / 2.0);
+  it.norm0 = gauss_norm0(D);
   it.lognorm0 = 0.5 * D * std::log(2.0 * M_PI);
   it.N = N; it.Nq = Nq; it.D = D; it.loo = loo ? 1 : 0; it.logdom = logdom ? 1 : 0;
   return it;
 }
 
-// the checks every resident entry makes; `at` may be bd.  (No test of the bandwidths: these entries take any density.)
-int check_pair(const kdehip_device_density *bd, const kdehip_device_density *at, int loo) {
-  if (!bd || !at) return set_error(KDEHIP_ERR_ARG, "null density");
-  if (loo && at != bd) return set_error(KDEHIP_ERR_ARG, "leave_one_out needs at == bd");
-  if (bd->D < 1 || bd->D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
-  if (at->D != bd->D) return set_error(KDEHIP_ERR_DIM_MISMATCH, "evaluate -- dimensions of two BallTreeDensities must match");
-  if (at->device != bd->device) return set_error(KDEHIP_ERR_ARG, "densities on different devices");
-  return KDEHIP_OK;
-}
-
-// bd at at's leaf points (leaf order; out, if any, through at's permutation), W = at's leaf weights
+// bd at at's leaf points (leaf order; out, if any, through at's permutation), W = at's leaf weights.  (The entries check the
+// pair without the test of the bandwidths: they take any density.)
 VarItem pair_item(const kdehip_device_density *bd, const kdehip_device_density *at, int loo, bool logl, int logdom) {
-  const int64_t N = bd->N, Nq = at->N;
-  const int D = bd->D;
-  VarItem it = blank_item(N, Nq, D, loo, logdom);
-  it.src = bd->means + N * D; it.w = bd->weights + N; it.var = bd->bandwidth + N * D;
-  it.qry = at->means + Nq * D;
-  it.qw = logl ? at->weights + Nq : nullptr;
-  it.perm = at->perm + Nq;
+  const LeafRows src = leaf_rows(bd), qry = leaf_rows(at);
+  VarItem it = blank_item(bd->N, at->N, bd->D, loo, logdom);
+  it.src = src.src; it.w = src.w; it.var = src.bw;
+  it.qry = qry.src;
+  it.qw = logl ? qry.w : nullptr;
+  it.perm = qry.perm;
   return it;
 }
 
@@ -327,7 +318,7 @@ int enqueue_resident(const VarItem &it, uint32_t circ, int device, void *stream)
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(0, 1));
   KDEHIP_CHECK_RC(run.enqueue(st));
-  return scope.capturing() ? run.keep(device) : run.defer(device);
+  return finish_enqueue(run, &scope, device);
 }
 
 }  // namespace
@@ -343,13 +334,11 @@ extern "C" int kdehip_density_uniform_bandwidth(const kdehip_device_density *h) 
 extern "C" int kdehip_evaluate_varbw(const kdehip_density *bd, const double *pos, int64_t Nq, int leave_one_out,
                                      int log_domain, double *p_out, int device, const uint8_t *manifold) {
   if (!bd || !p_out) return set_error(KDEHIP_ERR_ARG, "null argument");
+  KDEHIP_CHECK_RC(check_host_density(bd));
   const int D = static_cast<int>(bd->ndim);
   const int64_t N = bd->npts;
-  if (bd->ndim < 1 || bd->ndim > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "ndims outside 1..KDEHIP_MAX_DIMS");
   uint32_t circ = 0;
   if (manifold_arg(manifold, D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
-  if (N < 1 || !bd->means || !bd->bandwidth || !bd->weights || !bd->permutation)
-    return set_error(KDEHIP_ERR_ARG, "malformed density");
   if (leave_one_out) Nq = N;
   else if (!pos || Nq < 0) return set_error(KDEHIP_ERR_ARG, "pos must hold Nq >= 0 points");
   if (Nq == 0) return KDEHIP_OK;
@@ -358,21 +347,17 @@ extern "C" int kdehip_evaluate_varbw(const kdehip_density *bd, const double *pos
   hipStream_t st = hipStreamPerThread;  // the calling thread's own stream, like every blocking entry point
   // caller data: [leaf means | leaf weights | leaf variances | queries, or (leave-one-out) the leaf row of the permutation]:
   // one pinned image up, the Nq results back, as kdehip_evaluate
-  const size_t o_var = sizeof(double) * N * (D + 1), o_q = o_var + sizeof(double) * N * D;
+  const size_t o_q = host_density_bytes(bd, true);
   const size_t prefix = o_q + (leave_one_out ? sizeof(int64_t) * N : sizeof(double) * Nq * D);
   VarRun run;
   run.items.push_back(blank_item(N, Nq, D, leave_one_out, log_domain));
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, static_cast<size_t>(Nq)));
   unsigned char *h = run.host(), *d = run.dev();
-  const LeafArrays src = pack_leaves(run, 0, bd);
-  std::memcpy(h + o_var, bd->bandwidth + N * D, sizeof(double) * N * D);
+  VarItem &ri = run.items[0];
+  ri.var = pack_host_density(run, ri, bd, true);
   if (leave_one_out) std::memcpy(h + o_q, bd->permutation + N, sizeof(int64_t) * N);
   else std::memcpy(h + o_q, pos, sizeof(double) * Nq * D);
-  VarItem &ri = run.items[0];
-  ri.src = src.means;
-  ri.w = src.weights;
-  ri.var = reinterpret_cast<const double *>(d + o_var);
   ri.qry = leave_one_out ? ri.src : reinterpret_cast<const double *>(d + o_q);
   ri.perm = leave_one_out ? reinterpret_cast<const int64_t *>(d + o_q) : nullptr;
   ri.out = run.result(0);
@@ -406,18 +391,14 @@ extern "C" int kdehip_eval_avg_logl_varbw(const kdehip_density *bd, const kdehip
   hipStream_t st = hipStreamPerThread;
   const bool self = at == bd;
   // caller data: [bd leaf means | bd leaf weights | bd leaf variances | at leaf means | at leaf weights] (at == bd: none)
-  const size_t o_var = sizeof(double) * N * (D + 1), o_q = o_var + sizeof(double) * N * D;
-  const size_t prefix = o_q + (self ? 0 : sizeof(double) * Nq * (D + 1));
+  const size_t o_q = host_density_bytes(bd, true), prefix = o_q + (self ? 0 : sizeof(double) * Nq * (D + 1));
   VarRun run;
   run.items.push_back(blank_item(N, Nq, static_cast<int>(D), leave_one_out, log_domain));
   run.circ.push_back(circ);
   KDEHIP_CHECK_RC(run.alloc(prefix, 1));
-  const LeafArrays src = pack_leaves(run, 0, bd), qry = self ? src : pack_leaves(run, o_q, at);
-  std::memcpy(run.host() + o_var, bd->bandwidth + N * D, sizeof(double) * N * D);
   VarItem &ri = run.items[0];
-  ri.src = src.means;
-  ri.w = src.weights;
-  ri.var = reinterpret_cast<const double *>(run.dev() + o_var);
+  ri.var = pack_host_density(run, ri, bd, true);
+  const LeafArrays qry = self ? LeafArrays{ri.src, ri.w} : pack_leaves(run, o_q, at);
   ri.qry = qry.means;
   ri.qw = qry.weights;
   ri.logl = run.result(0);
@@ -431,7 +412,7 @@ extern "C" int kdehip_evaluate_varbw_device_at(const kdehip_device_density *bd, 
                                                int leave_one_out, int log_domain, double *d_out, void *stream,
                                                const uint8_t *manifold) {
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_pair(bd, at, leave_one_out));
+  KDEHIP_CHECK_RC(check_pair(bd, at, leave_one_out, false));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (at->N == 0) return KDEHIP_OK;
@@ -443,8 +424,8 @@ extern "C" int kdehip_evaluate_varbw_device_at(const kdehip_device_density *bd, 
 extern "C" int kdehip_evaluate_varbw_device(const kdehip_device_density *bd, const double *d_pos, int64_t Nq, int log_domain,
                                             double *d_out, void *stream, const uint8_t *manifold) {
   if (!bd || !d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  if (Nq < 0 || (Nq > 0 && !d_pos)) return set_error(KDEHIP_ERR_ARG, "d_pos must hold Nq >= 0 points");
-  KDEHIP_CHECK_RC(check_pair(bd, bd, 0));
+  KDEHIP_CHECK_RC(check_query_count(d_pos, Nq, "d_pos must hold Nq >= 0 points"));
+  KDEHIP_CHECK_RC(check_pair(bd, bd, 0, false));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   if (Nq == 0) return KDEHIP_OK;
@@ -457,7 +438,7 @@ extern "C" int kdehip_eval_avg_logl_varbw_device(const kdehip_device_density *bd
                                                  int leave_one_out, int log_domain, double *d_out, void *stream,
                                                  const uint8_t *manifold) {
   if (!d_out) return set_error(KDEHIP_ERR_ARG, "null argument");
-  KDEHIP_CHECK_RC(check_pair(bd, at, leave_one_out));
+  KDEHIP_CHECK_RC(check_pair(bd, at, leave_one_out, false));
   uint32_t circ = 0;
   if (manifold_arg(manifold, bd->D, &circ) != KDEHIP_OK) return KDEHIP_ERR_ARG;
   VarItem it = pair_item(bd, at, leave_one_out, true, log_domain);
