@@ -1506,6 +1506,76 @@ int kdehip_eval_avg_logl_varbw_device(const kdehip_device_density *bd, const kde
  * 0 with KDEHIP_ERR_ARG in kdehip_last_error for NULL. */
 int kdehip_density_uniform_bandwidth(const kdehip_device_density *density);
 
+/* ---- (5p) the exact product of two densities: labels, draws and log Z -------------------------------------------------------
+ * The samplers of sections 1-3 approximate a product after Niter sweeps.  For TWO densities the product has a closed form
+ * (csrc/prodexact.hip; this library's own: the reference has no counterpart, the toolbox it descends from had productExact).
+ * For p of dimension D with leaves i in LEAF ORDER, centres a_i, weights alpha_i and ONE bandwidth vector u (variances, the
+ * rule of section 5), and q with b_j, beta_j and v, of the same D in 1..KDEHIP_MAX_DIMS: p q is a mixture of N1 N2 Gaussians
+ * that share the variance u_k v_k / s_k, s_k = u_k + v_k; component (i, j) has the mean a_ik + (b_jk - a_ik) u_k / s_k and a
+ * weight proportional to alpha_i beta_j N(a_i - b_j; 0, s).  Euclidean, fp64 only.  With S_p = { i : alpha_i > 0 } and
+ * S_q = { j : beta_j > 0 }:
+ *   e_ij  = sum_k (a_ik - b_jk)^2 * (-0.5 / s_k), k ascending, one fma per dimension: the direct kernel's expression (5)
+ *   m_i   = max_{j in S_q} e_ij,  T_i = sum_{j in S_q} beta_j exp(e_ij - m_i),  L_i = log alpha_i + m_i + log T_i   (the log
+ *           domain of 5f; L_i = -Inf outside S_p)
+ *   M     = max_{i in S_p} L_i,  R_i = exp(L_i - M),  R = sum_{i in S_p} R_i
+ *   logz  = M + log R - log((2 pi)^(D/2) prod_k sqrt(s_k))
+ *           (= log int p q; finite where the integral itself, 5g, underflows to 0)
+ * The draw: draw t of Np has the global index g = sample_offset + t and the random numbers
+ *   u = kdehip_philox_fill_uniform(seed, g, 1, K = 2),  n = kdehip_philox_fill_normal(seed, g, 1, R = D).
+ * i is the first leaf of S_p whose cumulative sum of R (leaf order) exceeds u[0] * R; j is the first leaf of S_q whose
+ * cumulative sum of beta_j exp(e_ij - m_i) exceeds u[1] * T_i; in either search, if rounding leaves none, the last leaf of the set.
+ *   ind[t]    = (the 1-based ORIGINAL index of i in p, the 1-based ORIGINAL index of j in q)          (int64 [Np][2])
+ *   pts[t][k] = fma(b_jk - a_ik, u_k / s_k, a_ik) + sqrt(u_k v_k / s_k) * n[k]                       (double [Np][D])
+ * -- the divide, the product u_k v_k, its divide by s_k and the root each correctly rounded, the last multiply and add rounded
+ * separately as in 2f.
+ * Numerics and determinism: the cumulative sums are defined in exact arithmetic.  The implementation forms the sums over j in
+ * the group split of 5b / 5i (128-leaf chunks of q in groups that depend on (N2, N1) alone, combined in group order) and the
+ * scan of R_i in 256 contiguous segments of ceil(N1 / 256) leaves (each summed left to right, the segment totals summed left to
+ * right), so a threshold within a relative 1e-9 of a boundary may resolve to the neighbouring leaf of the set.  Everything
+ * else about a label is exact -- a leaf outside S_p or S_q is never drawn --, and the host entry, a resident call and an item
+ * of any batch return the same bits run after run.  No atomics.
+ * S_p or S_q empty: logz = -Inf, ind = (0, 0) and the point is NaN.  No entry reads out of bounds.
+ * Cost: one exp per (i, j) pair for the rows; at most one exp per (draw, j) pair for the labels -- only the group of q's
+ * chunks a draw's second threshold fell into is swept again, and a (256-draw block, group) pair that no draw chose is not
+ * swept at all.
+ * Errors, all checked before any device is touched: null arguments (all outputs NULL included; pts and ind are given together
+ * or not at all), Np < 0, densities on different devices -- KDEHIP_ERR_ARG; D differs between p and q --
+ * KDEHIP_ERR_DIM_MISMATCH; D outside 1..KDEHIP_MAX_DIMS or per-point bandwidths -- KDEHIP_ERR_UNSUPPORTED.  Np == 0 and
+ * n == 0 are KDEHIP_OK (with Np == 0 a logz that was asked for is still written).
+ * Not here: circular dimensions, partialDimMask, more than two densities in one sweep (fold: product_components, then a
+ * density of the mixture), fp32. */
+/* Host densities, host arrays, blocking.  pts [Np][D] with ind [Np][2], logz [1]: pts and ind together; not all NULL. */
+int kdehip_prod_exact(const kdehip_density *p, const kdehip_density *q, int64_t Np, uint64_t seed, int64_t sample_offset,
+                      double *pts, int64_t *ind, double *logz, int device);
+/* Resident densities, device arrays, enqueue only on `stream` (hipStream_t, NULL = the null stream), no read-back.  A capture
+ * of ONE stream into a HIP graph can hold the call under the rules of kdehip_evaluate_device_at_tol (5m): the blocks of a
+ * captured call are kept until kdehip_clear_cache. */
+int kdehip_prod_exact_device(const kdehip_device_density *p, const kdehip_device_density *q, int64_t Np, uint64_t seed,
+                             int64_t sample_offset, double *d_pts, int64_t *d_ind, double *d_logz, void *stream);
+typedef struct kdehip_prod_exact_item {
+  const kdehip_device_density *p;
+  const kdehip_device_density *q;
+  int64_t Np;
+  uint64_t seed;
+  int64_t sample_offset;
+  double *d_pts;            /* device, [Np][D], or NULL (then d_ind is NULL too) */
+  int64_t *d_ind;           /* device, [Np][2] */
+  double *d_logz;           /* device, [1], or NULL */
+} kdehip_prod_exact_item;
+/* Many resident items (mixed D, N1, N2 and Np) on one device, enqueue only on `stream`.  Launches per pass are one per
+ * distinct D for all items together.  Every item's results are bit for bit those of kdehip_prod_exact_device. */
+int kdehip_prod_exact_device_batch(int n, const kdehip_prod_exact_item *items, void *stream);
+/* The mixture itself, in ORIGINAL point order and row-major: component c = i N2 + j (i, j 0-based original indices) has
+ * means[c][k] = the mean above (without the noise) and weights[c] = exp((log alpha_i + log beta_j + e_ij) - (M + log R)), 0
+ * outside S_p x S_q (and everywhere when either set is empty); var[k] = u_k v_k / s_k.  means [N1 N2][D], weights [N1 N2],
+ * var [D]: none may be NULL.  N1 N2 > 2^20 is KDEHIP_ERR_UNSUPPORTED; the other refusals are those above.  Host densities,
+ * blocking. */
+int kdehip_product_components(const kdehip_density *p, const kdehip_density *q, double *means, double *weights, double *var,
+                              int device);
+/* Resident densities, device arrays, enqueue only on `stream`. */
+int kdehip_product_components_device(const kdehip_device_density *p, const kdehip_device_density *q, double *d_means,
+                                     double *d_weights, double *d_var, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

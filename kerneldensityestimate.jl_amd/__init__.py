@@ -6,7 +6,7 @@ This package is the Python host mirror of the reference's interface for that pat
 `intersIntgAppxIS`, and the library's own exact overlap measures `intersIntg/ise/mmd` and joint modes
 `evaluate_grad/meanshift/modes/getKDEMode`, their curvature `evaluate_hess/laplace/fit_modes/getKDEModeFit`, conditionals
 `condition/conditional_weights/conditional_moments/sample_conditional` and probability masses
-`box_mass/cdf/quantile/median/interval/grid_mass`, nearest neighbours `knn/entropy_knn/kld_knn`, and per-point bandwidths `kde_varbw/adaptive_scales/kde_adaptive`)
+`box_mass/cdf/quantile/median/interval/grid_mass`, the exact product of two densities `prod_exact/product_components/log_intersIntg/mul_exact`, nearest neighbours `knn/entropy_knn/kld_knn`, and per-point bandwidths `kde_varbw/adaptive_scales/kde_adaptive`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
 """
@@ -24,6 +24,7 @@ from .modes import evaluate_grad, getKDEMode, meanshift, meanshift_device_batch,
 from .curvature import evaluate_hess, evaluate_hess_device_batch, fit_modes, getKDEModeFit, laplace  # noqa: F401
 from .conditional import (condition, conditional_device_batch, conditional_moments, conditional_weights,  # noqa: F401
                           sample_conditional)
+from .prodexact import log_intersIntg, mul_exact, prod_exact, prod_exact_device_batch, product_components  # noqa: F401
 from .mass import (box_mass, box_mass_device_batch, cdf, grid_mass, interval, median, quantile,  # noqa: F401
                    quantile_device_batch)
 from .evaltol import evaluate_tol, getForceEvalDirect, setForceEvalDirect  # noqa: F401

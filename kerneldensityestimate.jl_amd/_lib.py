@@ -103,6 +103,12 @@ class CConditionalItem(C.Structure):
                 ("given_mask", C.c_uint32), ("circular_mask", C.c_uint32)]
 
 
+class CProdExactItem(C.Structure):
+    """struct kdehip_prod_exact_item"""
+    _fields_ = [("p", C.c_void_p), ("q", C.c_void_p), ("Np", C.c_int64), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
+                ("d_pts", C.c_void_p), ("d_ind", C.c_void_p), ("d_logz", C.c_void_p)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -313,6 +319,14 @@ SIGNATURES = {
     "kdehip_evaluate_varbw_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, u8p]),
     "kdehip_eval_avg_logl_varbw_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, u8p]),
     "kdehip_density_uniform_bandwidth": (C.c_int, [C.c_void_p]),
+    # the exact product of two densities (include/kdehip.h section 5p)
+    "kdehip_prod_exact": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, f64p, i64p, f64p,
+                                    C.c_int]),
+    "kdehip_prod_exact_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "kdehip_prod_exact_device_batch": (C.c_int, [C.c_int, C.POINTER(CProdExactItem), C.c_void_p]),
+    "kdehip_product_components": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), f64p, f64p, f64p, C.c_int]),
+    "kdehip_product_components_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
                                          u8p]),
     "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,

@@ -832,6 +832,44 @@ function hip_mmd(p::BallTreeDensity, q::BallTreeDensity, bw::AbstractVector{Floa
 end
 
 """
+    hip_prod_exact(p, q, Np=Npts(p); seed=rand(UInt64), sample_offset=0, device=0)
+
+`(pts, ind, logz)`: `Np` EXACT draws of the product of two densities (`kdehip_prod_exact`, include/kdehip.h section 5p) --
+`pts` is `D x Np`, `ind` is `2 x Np` (the 1-based original indices of the drawn kernels of `p` and `q`), `logz` is
+`log(integral of p q)`.  One all-pairs pass and two inverse-CDF walks per draw: no sweeps, no `Niter`.  Both densities
+need ONE bandwidth vector.  The library's own: not installed by `enable!()`.
+"""
+function hip_prod_exact(p::BallTreeDensity, q::BallTreeDensity, Np::Int=Npts(p); seed::UInt64=rand(UInt64),
+                        sample_offset::Int=0, device::Int=0)
+  Ndim(p) == Ndim(q) || error("prod_exact -- dimensions of two BallTreeDensities must match")
+  pts = zeros(Ndim(p), max(Np, 0))
+  ind = zeros(Int64, 2, max(Np, 0))
+  logz = Ref{Float64}(0.0)
+  cp = Ref(CDensity(p))
+  cq = p === q ? cp : Ref(CDensity(q))
+  GC.@preserve p q pts ind begin
+    check(ccall((:kdehip_prod_exact, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Int64, UInt64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Cint),
+                cp, cq, Np, seed, sample_offset, pts, ind, logz, device))
+  end
+  return pts, ind, logz[]
+end
+
+"`log(hip_intersIntg(p, q))` by log-sum-exp (`kdehip_prod_exact` with no draws): finite where the integral underflows to 0."
+function hip_log_intersIntg(p::BallTreeDensity, q::BallTreeDensity; device::Int=0)
+  Ndim(p) == Ndim(q) || error("prod_exact -- dimensions of two BallTreeDensities must match")
+  logz = Ref{Float64}(0.0)
+  cp = Ref(CDensity(p))
+  cq = p === q ? cp : Ref(CDensity(q))
+  GC.@preserve p q begin
+    check(ccall((:kdehip_prod_exact, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Int64, UInt64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Cint),
+                cp, cq, 0, UInt64(0), 0, Ptr{Float64}(C_NULL), Ptr{Int64}(C_NULL), logz, device))
+  end
+  return logz[]
+end
+
+"""
     hip_evaluate_grad(bd, pos; log=true, manifold=nothing, device=0)
 
 `(val, grad)` at the columns of `pos` (`kdehip_evaluate_grad`, include/kdehip.h section 5h): `log p` and its gradient

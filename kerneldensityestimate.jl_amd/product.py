@@ -452,6 +452,16 @@ class DeviceDensity:
         _lib.check(_lib.lib.kdehip_sample_device_manifold(self._h, int(Npts), u64(seed), int(sample_offset), addr(ind),
                                                           addr(d_pts), addr(d_ind), addr(stream), _mf.pointer(man)))
 
+    def prod_exact(self, other, d_pts, d_ind, *, Np, seed, sample_offset=0, d_logz=None, stream=None):
+        """Np exact draws of the product self * other (include/kdehip.h section 5p) into caller device arrays (torch tensors
+        or addresses): d_pts float64[Np][D] (= column-major D x Np), d_ind int64[Np][2] (1-based original indices in self
+        and other), d_logz an optional float64[1] for log int p q; d_pts and d_ind may both be None when d_logz is given.
+        Enqueue only on `stream`, no read-back (kdehip_prod_exact_device)."""
+        if not isinstance(other, DeviceDensity):
+            raise TypeError("both densities must be BallTreeDensity, or both DeviceDensity")
+        _lib.check(_lib.lib.kdehip_prod_exact_device(self._h, other._h, int(Np), u64(seed), int(sample_offset), addr(d_pts),
+                                                     addr(d_ind), addr(d_logz), addr(stream)))
+
     def resample(self, Np=None, *, seed=None, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`resample(p, Np, :lcv)` (reference src/BallTreeDensity01.jl:312-334) without leaving the device: Np samples
         (None = Npts(p)), then `kde!(points)` on the device matrix (kdehip_resample_device).  The default is Euclidean, also
