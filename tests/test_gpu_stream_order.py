@@ -10,7 +10,12 @@ np.array_equal, NaNs equal.
 Every scenario asserts that the hold was still running when its last enqueue returned (`gate.query()` is False): the hold then
 covered every call, and no call waited for its stream -- the header's "does not synchronise the host".  A 50 ms hold is
 calibrated once per module from the measured rate of the sleep kernel's clock.  Assertions are made after the streams have been
-synchronised, so that a failing test leaves nothing pending."""
+synchronised, so that a failing test leaves nothing pending.
+
+The blocking entries that take "the hipStream_t that produced" their device matrix and wait for it
+(`cases.BLOCKING_WAITS`) have a test of their own at the end: there the hold must be running immediately before the call and
+over after it.  Every stream used here is one of the module's two (`_streams()`): a further pool stream would keep a hardware
+queue and change which queue the library's preparation stream shares (tests/test_gpu_prodexact.py)."""
 import numpy as np
 import pytest
 
@@ -227,7 +232,10 @@ def test_nine_products_on_a_held_stream():
 
 
 # ---- 5. teardown with work in flight ------------------------------------------------------------------------------------------
-TEARDOWN_ROWS = ["kdehip_evaluate_device", "kdehip_knn_device_at", "kdehip_sample_device"]
+# (the last row's densities are one resident plan: closing the row is kdehip_product_destroy, which "waits for the device
+# first if runs were enqueued")
+TEARDOWN_ROWS = ["kdehip_evaluate_device", "kdehip_knn_device_at", "kdehip_sample_device", "kdehip_prod_exact_device",
+                 "kdehip_evaluate_varbw_device_at", "kdehip_product_sample_philox"]
 
 
 def _teardown(name, end):
@@ -261,6 +269,57 @@ def test_closing_a_density_under_a_pending_call(name):
 def test_clearing_the_cache_under_a_pending_call(name):
     """kdehip_clear_cache drains the deferred-release queue before it hands the blocks back to the driver"""
     _teardown(name, lambda row: kdehip._clib.kdehip_clear_cache())
+
+
+# ---- 6. blocking entries that wait for the stream that produces their input ---------------------------------------------------
+_BT_ARRAYS = ("centers", "ranges", "weights", "left_child", "right_child", "lowest_leaf", "highest_leaf", "permutation")
+_BD_ARRAYS = ("means", "bandwidth", "bandwidthMin", "bandwidthMax")
+
+
+def _density_arrays(d):
+    """every array of a density the library built, and its bandwidth search"""
+    host = d.download()
+    out = {k: np.asarray(getattr(host.bt, k)) for k in _BT_ARRAYS}
+    out.update({k: np.asarray(getattr(host, k)) for k in _BD_ARRAYS})
+    out["bw"], out["nevals"] = np.asarray(d.bw), np.asarray([d.nevals])
+    return out
+
+
+@pytest.mark.parametrize("name", cases.BLOCKING_WAITS)
+def test_a_blocking_entry_waits_for_the_stream_that_produces_its_matrix(name):
+    """kdehip_density_from_device_points[_manifold|_tree]: "`stream` = the hipStream_t that produced it, waited for".  The
+    matrix holds a decoy when the call is made; the copy of the true points is pending behind the hold on `a`.  The call
+    blocks, so the hold is looked at immediately BEFORE it; the density that comes back is, array for array, the one the
+    same entry builds from the true matrix with the device idle."""
+    import torch
+    a, _ = _streams()
+    true, decoy = cases.blocking_case(name)
+    d_true, d_decoy = cases._dev(true.T), cases._dev(decoy.T)
+    work = d_decoy.clone()
+    made = []
+    try:
+        torch.cuda.synchronize()
+        made.append(cases.blocking_build(name, d_true, None))
+        made.append(cases.blocking_build(name, d_decoy, None))
+        want, other = _density_arrays(made[0]), _density_arrays(made[1])
+        # the premise: the decoy's density is another one (its points, its search)
+        assert not np.array_equal(want["bw"], other["bw"]) and not np.array_equal(want["means"], other["means"])
+        torch.cuda.synchronize()
+        gate = hold(a)
+        with torch.cuda.stream(a):
+            work.copy_(d_true, non_blocking=True)
+        held = not gate.query()
+        made.append(cases.blocking_build(name, work, a.cuda_stream))
+        passed = gate.query()
+        a.synchronize()
+        assert held, ENDED
+        assert passed, "the call returned while the stream it was given was still held"
+        bad = _diff(_density_arrays(made[2]), want, "built behind the hold")
+        assert not bad, bad
+    finally:
+        torch.cuda.synchronize()
+        for d in made:
+            d.close()
 
 
 def test_nothing_is_left_pending():
