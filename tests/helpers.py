@@ -70,3 +70,69 @@ def weyl_normal(n, a1, a2):
 def kat_streams(nU, nN):
     """randU / randN of the KAT fixtures (reference allocation sizes, src/MSGibbs01.jl:661-662)."""
     return weyl(nU, (np.sqrt(5.0) - 1.0) / 2.0, 0.0123), weyl_normal(nN, np.sqrt(7.0) % 1.0, np.sqrt(11.0) % 1.0)
+
+
+# ---- the split of the all-pairs sums, restated from the comments of csrc/entry_helpers.hpp and csrc/summary.hip -------------
+def _ceil_div(a, b):
+    return -(-int(a) // int(b))
+
+
+def device_cus():
+    """compute units of cuda:0 as torch reports them (256 on an MI355X in SPX mode)"""
+    import torch
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+def chunks_per_group(N, Nq, cus=None, chunk=128, threads=256, max_groups=64, nprob=1):
+    """split_chunks: the ceil(N / 128) source chunks go to `want` groups of consecutive chunks, want = ceil(8 CUs / qblocks)
+    clamped to [1, 64] and to the chunk count, qblocks = ceil(Nq / 256) query blocks (times the problems of a batch)"""
+    cus = device_cus() if cus is None else cus
+    nchunks = _ceil_div(N, chunk)
+    qblocks = _ceil_div(Nq, threads) * max(1, nprob)
+    want = max(1, min(_ceil_div(8 * cus, qblocks), max_groups, nchunks))
+    return _ceil_div(nchunks, want)
+
+
+def grid_chunks_per_group(N, Ngrid, cus=None):
+    """the grid kernel's own split (csrc/summary.hip): 256-leaf chunks, 256 grid points per block, at most 256 groups"""
+    return chunks_per_group(N, Ngrid, cus, chunk=256, threads=256, max_groups=256)
+
+
+def assert_chunks_per_group(N, Nq, want, grid=False):
+    """the premise of a large-N case: on this device a group of the sweep walks `want` chunks"""
+    cus = device_cus()
+    got = grid_chunks_per_group(N, Nq, cus) if grid else chunks_per_group(N, Nq, cus)
+    assert got == want, (f"with {cus} compute units the {'grid ' if grid else ''}split gives N = {N}, Nq = {Nq} groups of {got} "
+                         f"chunk(s), not the {want} this case is here for: it would cover nothing")
+
+
+def rescale_premise(pts, w, var, X, cpg, man=None, chunk=128):
+    """Per query (column of X): does some group of `cpg` consecutive `chunk`-leaf chunks have BOTH a later
+    chunk that raises the group's running maximum of a_i over S = {w_i > 0} by at least log 2 over a non-empty earlier chunk
+    (the carried sums are rescaled by at most 1/2) AND a maximum within 30 of the query's overall maximum (the group counts in
+    the result).  pts (D, N), w (N,) in LEAF order; var (D,); man: None or one 0 / 1 per dimension."""
+    import math
+    D, N = pts.shape
+    nch = _ceil_div(N, chunk)
+    hit = np.zeros(X.shape[1], dtype=bool)
+    for q in range(X.shape[1]):
+        d = X[:, q:q + 1] - pts
+        if man is not None:
+            c = np.asarray(man, dtype=bool)
+            d[c] = d[c] - 2.0 * math.pi * np.floor((d[c] + math.pi) / (2.0 * math.pi))
+        a = np.where(w > 0.0, -0.5 * np.sum(d * d / np.asarray(var)[:, None], axis=0), -np.inf)
+        cmax = np.array([a[c * chunk:(c + 1) * chunk].max() for c in range(nch)])
+        M = cmax.max()
+        ok = False
+        for g0 in range(0, nch, cpg):
+            run = -np.inf
+            fired = False
+            for cm in cmax[g0:g0 + cpg]:
+                if run > -np.inf and cm >= run + math.log(2.0):
+                    fired = True
+                run = max(run, cm)
+            if fired and run >= M - 30.0:
+                ok = True
+                break
+        hit[q] = ok
+    return hit

@@ -44,12 +44,47 @@ def fma_fraction(a, b, c):
 _fma = np.frompyfunc(fma, 3, 1)
 
 
+def _two_sum(a, b):
+    """a + b = s + e exactly (Knuth)"""
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def fma_array(t, s, acc):
+    """`fma` element by element on arrays, t, s, acc >= 0 and far from overflow and underflow, without a Python call per
+    element: t * s = p + e exactly (Dekker's product on Veltkamp's split), p + acc = s1 + e1 and e1 + e = y + ey exactly, and
+    fl(s1 + y) is the rounding of the exact sum unless s1 + y lies within |ey| of a point halfway between two doubles -- those
+    elements (none, as a rule) are redone by `fma`"""
+    t, acc = np.asarray(t, dtype=np.float64), np.asarray(acc, dtype=np.float64)
+    s = np.float64(s)
+    p = t * s
+    c = 134217729.0  # 2^27 + 1
+    th = c * t
+    th = th - (th - t)
+    tl = t - th
+    sh = c * s
+    sh = sh - (sh - s)
+    sl = s - sh
+    e = ((th * sh - p) + th * sl + tl * sh) + tl * sl
+    s1, e1 = _two_sum(p, acc)
+    y, ey = _two_sum(e1, e)
+    r, err = _two_sum(s1, y)
+    h = np.spacing(r)
+    near = (ey != 0.0) & ((np.abs(np.abs(err) - 0.5 * h) <= 4.0 * np.abs(ey)) | (np.abs(np.abs(err) - 0.25 * h) <= 4.0 * np.abs(ey)))
+    if near.any():
+        r = np.array(r)
+        for i in zip(*np.nonzero(near)):
+            r[i] = fma(float(t[i]), float(s), float(acc[i]))
+    return r
+
+
 def _chain(diffs, scale):
     """acc = fma(d_k * d_k, s_k, acc) from 0, k ascending; diffs: a list of D equal-shaped arrays"""
     acc = np.zeros_like(diffs[0])
     for k, d in enumerate(diffs):
         t = d * d
-        acc = acc + t if scale is None else _fma(t, float(scale[k]), acc).astype(np.float64)
+        acc = acc + t if scale is None else fma_array(t, float(scale[k]), acc)
     return acc
 
 
@@ -81,8 +116,11 @@ def dmin2(lo, hi, qry, scale=None, circ=()):
 
 def _topk(d2row, orig, k, skip=None):
     """the k smallest (d2, original index) of one query: (d2 (k,), idx (k,)); `skip`: a leaf position left out"""
-    keys = [(float(d2row[i]), int(orig[i])) for i in range(len(orig)) if i != skip]
-    keys.sort()
+    d = np.array(d2row, dtype=np.float64)
+    if skip is not None:
+        d[skip] = np.inf
+    kth = np.partition(d, k - 1)[k - 1]  # only the leaves up to the k-th smallest distance, ties included, can be among the k
+    keys = sorted((float(d[i]), int(orig[i])) for i in np.nonzero(d <= kth)[0] if i != skip)
     return np.array([a for a, _ in keys[:k]]), np.array([b for _, b in keys[:k]], dtype=np.int64)
 
 
@@ -92,20 +130,25 @@ def all_dist2(pts, qry, scale=None, circ=()):
     return dist2(pts, np.where(live[:, None], qry, 0.0), scale, circ)
 
 
-def knn(pts, orig, qry, k, loo=False, scale=None, circ=(), d2=None):
-    """brute force: (d2 (Nq, k), idx (Nq, k)) in processing order; a non-finite query gets NaN and 0"""
+def knn(pts, orig, qry, k, loo=False, scale=None, circ=(), d2=None, rows=None):
+    """brute force: (d2 (Nq, k), idx (Nq, k)) in processing order; a non-finite query gets NaN and 0.  `rows` (leave-one-out
+    of a large density, block by block): a slice of the leaves; qry is pts[rows] and query q is leaf rows.start + q"""
     Nq = qry.shape[0]
+    r0 = 0 if rows is None else rows.start
     d2o, ido = np.full((Nq, k), np.nan), np.zeros((Nq, k), dtype=np.int64)
     live = np.isfinite(qry).all(axis=1)
     if d2 is None:
         d2 = all_dist2(pts, qry, scale, circ)
     for q in np.nonzero(live)[0]:
-        d2o[q], ido[q] = _topk(d2[q], orig, k, q if loo else None)
+        d2o[q], ido[q] = _topk(d2[q], orig, k, r0 + q if loo else None)
     return d2o, ido
 
 
-def plan(pts, orig, qry, k, loo=False, scale=None, circ=(), d2=None):
-    """steps 1-6: dict with cstar (Nq,), r (Nq,), need (Nq, nc) bool, visited (qblocks, nc) bool and stats"""
+def plan(pts, orig, qry, k, loo=False, scale=None, circ=(), d2=None, rows=None):
+    """steps 1-6: dict with cstar (Nq,), r (Nq,), need (Nq, nc) bool, visited (qblocks, nc) bool and stats.  `rows` as in `knn`,
+    starting at a multiple of BLOCK: the query blocks of that slice (the stats of the slices add up)"""
+    r0 = 0 if rows is None else rows.start
+    assert r0 % BLOCK == 0
     if d2 is None:
         d2 = all_dist2(pts, qry, scale, circ)
     N, Nq = pts.shape[0], qry.shape[0]
@@ -118,14 +161,14 @@ def plan(pts, orig, qry, k, loo=False, scale=None, circ=(), d2=None):
     need = np.zeros((Nq, nc), dtype=bool)
     for q in np.nonzero(live)[0]:
         row = dm[q].copy()
-        own = q // CHUNK
+        own = (r0 + q) // CHUNK
         if loo and min(CHUNK, N - own * CHUNK) == 1:
             row[own] = np.inf  # the own chunk holds no other leaf: it does not count
         c = int(np.argmin(row))  # (the first of equal minima: the lowest c)
         cstar[q] = c
         sl = slice(c * CHUNK, min(N, (c + 1) * CHUNK))
         near = d2[q, sl]
-        keep = [i for i in range(near.shape[0]) if not (loo and sl.start + i == q)]
+        keep = [i for i in range(near.shape[0]) if not (loo and sl.start + i == r0 + q)]
         if len(keep) >= k:
             r[q] = np.sort(near[keep])[k - 1]
         need[q] = dm[q] <= r[q]

@@ -8,7 +8,8 @@ against its absolute sum, A_k = sum t_i |d_ik|, A_kl = sum t_i |d_ik d_il|):
   grad_k    1e-12 * A_k / (S_0 v_k)
   hess_kl   1e-12 * ( A_kl / (S_0 v_k v_l) + delta_kl / v_k + (A_k / (S_0 v_k)) (A_l / (S_0 v_l)) )
   cov       against numpy.linalg.inv(-hess) of the Hessian the call returned: max|diff| <= 64 * 2^-53 * kappa_2(H) * max|cov|,
-            the c D u kappa form of the Cholesky bound with c D = 64 at D <= 8; kappa_2 <= 1e6 is asserted first."""
+            the c D u kappa form of the Cholesky bound with c D = 64 at D <= 8; kappa_2 <= 1e6 is asserted first.
+Section 11 repeats the comparisons where a group of the sweep walks two and three chunks (N = 128 * 64 + 1, 128 * 128 + 1)."""
 import importlib.util
 import math
 import os
@@ -20,6 +21,7 @@ import kdehip
 from kdehip import _lib
 from tests import curvature_model as cm
 from tests import modes_model as mm
+from tests.helpers import assert_chunks_per_group, rescale_premise
 from tests.test_gpu_ksum import SHAPES, _arrays, _density
 
 pytestmark = pytest.mark.gpu
@@ -443,3 +445,88 @@ def test_resident_arguments_are_refused_before_the_device_is_used():
             kdehip.laplace(dq, np.zeros((2, 3)))
         assert e.value.code == _lib.ERR_UNSUPPORTED
         torch.cuda.synchronize()
+
+
+# ---- 11. groups of several chunks ------------------------------------------------------------------------------------------
+# Every size above gives a group of the sweep ONE chunk, so the rescale of curvature_partial_kernel's 1 + D + D(D+1)/2 carried
+# sums (45 at D = 8) by exp_nonpos(m - cm) never met a non-zero sum.  N = 128 * 64 + 1 gives a group two chunks (the last
+# group one chunk of one leaf), N = 128 * 128 + 1 three.  The premises are those of tests/test_gpu_modes.py section 7, asserted
+# before the library is called: the split restated in tests/helpers.py, and from the model's leaf-order arrays alone that for
+# a quarter of the queries a group both rescales its carried sums by 1/2 or less and lies within 30 of the overall maximum.
+# Nq is small where D is large: the model sums 2 (1 + D + D(D+1)/2) series per query by math.fsum.
+BIG_HESS = [(8, 128 * 64 + 1, 7, None), (3, 128 * 128 + 1, 257, None), (5, 128 * 64 + 1, 7, None),
+            (3, 128 * 64 + 1, 7, (0, 0, 1))]
+
+
+def _leaf_order(p):
+    """(points (D, N), weights (N,)) of a host density in LEAF order: the order the sweep's chunks are cut from"""
+    N, D = p.bt.num_points, p.bt.dims
+    return np.ascontiguousarray(p.bt.centers[N * D:].reshape(N, D).T), p.bt.weights[N:].copy()
+
+
+@pytest.mark.parametrize("D,N,Nq,man", BIG_HESS)
+def test_evaluate_hess_with_groups_of_several_chunks(D, N, Nq, man):
+    import torch
+    man = None if man is None else list(man)
+    rng = np.random.default_rng(1000 * D + 10 * N + Nq)
+    p = _density(rng, D, N)
+    A = _arrays(p)
+    X = A[0][:, rng.integers(0, N, size=Nq)] + np.sqrt(A[2])[:, None] * rng.standard_normal((D, Nq))  # among the points
+    per_group = 2 if N < 128 * 128 else 3
+    assert_chunks_per_group(N, Nq, per_group)
+    pts, w = _leaf_order(p)
+    hit = rescale_premise(pts, w, A[2], X, per_group, man)
+    print("queries with a rescale by <= 1/2 in a group within 30 of the maximum:", int(hit.sum()), "of", hit.size)
+    assert hit.mean() >= 0.25, (int(hit.sum()), hit.size)
+    want, wgrad, gscale, whess, hscale = cm.evaluate_hess(A, X, man)
+    host = _all_outputs(p, X, manifold=man)
+    val, grad, hess, cov, definite = host
+    assert val.shape == (Nq,) and grad.shape == (D, Nq) and hess.shape == (D, D, Nq) and cov.shape == (D, D, Nq)
+    _close_logp(val, want)
+    _close_scaled(grad, wgrad, gscale)
+    _close_scaled(hess, whess, hscale)
+    assert np.array_equal(hess, hess.transpose(1, 0, 2)) and np.array_equal(cov, cov.transpose(1, 0, 2), equal_nan=True)
+    assert np.all(np.isnan(cov[:, :, ~definite])) and np.all(np.isfinite(cov[:, :, definite]))
+    for q in range(Nq):  # definite where the model's -H is safely so (its smallest eigenvalue above the Hessian's own bound)
+        ev = np.linalg.eigvalsh(-whess[:, :, q])
+        margin = D * 1e-12 * float(np.max(hscale[:, :, q]))
+        if ev.min() > margin:
+            assert definite[q]
+            _check_cov(hess[:, :, q], cov[:, :, q], None if man is not None else A[2])
+        elif ev.min() < -margin:
+            assert not definite[q]
+    # host == resident == its place in a batch whose first item is small: the large item's launch starts at a block offset
+    small = _case(3, 127, 128)
+    with kdehip.DeviceDensity(p) as d, kdehip.DeviceDensity(small["p"]) as ds:
+        assert _same(_all_outputs(d, X, manifold=man), host)
+        items = _batch_items([ds, d], [small, dict(X=X)])
+        items[1]["manifold"] = man
+        kdehip.evaluate_hess_device_batch(items)
+        torch.cuda.synchronize()
+        assert _same(_batch_results(items[0]), small["host"]) and _same(_batch_results(items[1]), host)
+
+
+def test_a_mode_covariance_with_groups_of_two_chunks():
+    """section 8 on mm.three_clusters(2, 128 * 64 + 1): the modes from eight starts, the curvature at them"""
+    N = 128 * 64 + 1
+    pts, sd, w = mm.three_clusters(2, N)
+    p = kdehip.kde(pts, sd, w)
+    A = _arrays(p)
+    starts = np.array([[0.0, 3.0, 0.0, 1.2, 1.9, -0.6, 0.3, 3.5], [0.0, 0.0, -3.0, 0.2, -0.3, -1.2, -1.9, 0.6]])
+    assert_chunks_per_group(N, starts.shape[1], 2)
+    assert_chunks_per_group(N, 3, 2)
+    modes = kdehip.modes(p, starts, maxiter=200)[0]
+    assert modes.shape == (2, 3)
+    lpts, lw = _leaf_order(p)
+    hit = rescale_premise(lpts, lw, A[2], modes, 2)
+    assert hit.any(), hit
+    val, grad, hess, cov, definite = _all_outputs(p, modes)
+    want, wgrad, gscale, whess, hscale = cm.evaluate_hess(A, modes)
+    _close_logp(val, want)
+    _close_scaled(grad, wgrad, gscale)
+    _close_scaled(hess, whess, hscale)
+    assert definite.all()
+    for q in range(3):
+        _check_cov(hess[:, :, q], cov[:, :, q], sd * sd)
+    means, covs, fmass, flogp, fdef = kdehip.fit_modes(p, starts, maxiter=200)
+    assert np.array_equal(means, modes) and np.array_equal(covs, cov) and fdef.all()

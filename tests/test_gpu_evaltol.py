@@ -15,6 +15,8 @@ import pytest
 
 import kdehip
 from kdehip import _lib
+from tests import evaltol_model as em
+from tests.helpers import assert_chunks_per_group
 from tests.test_evaltol_host import SHAPES, leaf_arrays, queries
 from tests.test_gpu_mass import _density
 
@@ -56,11 +58,21 @@ def _bounded(got, direct, rel, ab):
 
 
 CASES = [(D, N, Nq, circular) for D, N, Nq in SHAPES for circular in (False, True)]
+# N = 128 * 129 + 1: 130 chunks, so tol_plan_kernel stages a second tile of boxes (128 to a tile) and a row of flags has three
+# words; a group of the sweep walks three chunks (asserted where the case is used, from the split restated in tests/helpers.py)
+BIG = (2, 128 * 129 + 1, 300, False)
+
+
+def _premise(D, N, Nq):
+    if N == BIG[1]:
+        assert_chunks_per_group(N, Nq, 3)
+        assert_chunks_per_group(N, N, 5)  # leave-one-out: 65 query blocks, 32 groups
 
 
 # ---- 1. no tolerance: the direct evaluation's bits ---------------------------------------------------------------------------
-@pytest.mark.parametrize("D,N,Nq,circular", CASES)
+@pytest.mark.parametrize("D,N,Nq,circular", CASES + [BIG])
 def test_no_tolerance_is_the_direct_evaluation_bit_for_bit(D, N, Nq, circular):
+    _premise(D, N, Nq)
     c = _case(D, N, Nq, circular)
     p, man = c["p"], c["man"]
     total = ((Nq + 255) // 256) * ((N + 127) // 128)
@@ -80,8 +92,9 @@ def test_no_tolerance_is_the_direct_evaluation_bit_for_bit(D, N, Nq, circular):
 
 
 # ---- 2. the bound ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,N,Nq,circular", CASES)
+@pytest.mark.parametrize("D,N,Nq,circular", CASES + [BIG])
 def test_every_value_lies_within_the_tolerance_below_the_direct_one(D, N, Nq, circular):
+    _premise(D, N, Nq)
     c = _case(D, N, Nq, circular)
     assert np.all(c["direct"] > 0.0) and np.all(c["direct_loo"] >= 0.0)
     for rel, ab in TOLS:
@@ -106,9 +119,12 @@ def test_a_nan_query_gets_nan_and_the_others_keep_the_bound(D, N, Nq, circular):
         _bounded(np.delete(got, 1), np.delete(c["direct"], 1), 1e-2, 0.0)
 
 
-@pytest.mark.parametrize("D,N,Nq,circular", [(1, 5, 3, False), (2, 129, 257, False), (6, 257, 5, False), (2, 8200, 300, False)])
+@pytest.mark.parametrize("D,N,Nq,circular", [(1, 5, 3, False), (2, 129, 257, False), (6, 257, 5, False), (2, 8200, 300, False),
+                                              BIG])
 def test_queries_far_outside_the_data_get_the_direct_values(D, N, Nq, circular):
     """50 bandwidths beyond the data in every dimension: L_q underflows to 0, tau_q is 0, every chunk is needed"""
+    if N == BIG[1]:
+        assert_chunks_per_group(N, 5, 3)
     c = _case(D, N, Nq, circular)
     pts, _, v, _ = leaf_arrays(c["p"])
     far = (pts.max(axis=0) + 50.0 * np.sqrt(v))[:, None] + np.arange(3.0)[None, :]
@@ -140,6 +156,40 @@ def test_separated_clusters_visit_at_most_a_quarter_of_the_tiles():
     print("tiles visited / total:", stats)
     assert stats[1] == 32 and stats[0] > 0
     assert stats[0] * 4 <= stats[1]
+    _bounded(got, direct, 1e-3, 0.0)
+    with kdehip.DeviceDensity(p) as d:
+        got_d, stats_d = d.evaluate_tol(None, 1e-3, return_stats=True)
+    assert stats_d == stats and np.array_equal(got_d, got)
+
+
+def test_separated_clusters_in_a_second_tile_of_boxes():
+    """N = Nq = 128 * 129 + 1 in tree order, built like the test above: four clusters of 4128 points (one of 4129) 40 apart,
+    bandwidth 0.3.  The tree splits at the median of the widest dimension, so the clusters are runs of leaves; the last run
+    covers chunks 128 and 129, which the first tile of 128 boxes does not reach: the plan's second tile decides those flags.  The tiles visited are the model's (tests/evaltol_model.py) to the count."""
+    N = 128 * 129 + 1
+    assert_chunks_per_group(N, N, 5)  # (65 query blocks: 32 groups)
+    rng = np.random.default_rng(2025)
+    centres = np.array([[-20.0, -20.0], [-20.0, 20.0], [20.0, -20.0], [20.0, 20.0]])
+    sizes = [N // 4 + (1 if j < N % 4 else 0) for j in range(4)]
+    pts = np.concatenate([c[:, None] + rng.standard_normal((2, n)) for c, n in zip(centres, sizes)], axis=1)
+    pts = pts[:, rng.permutation(N)]
+    p = kdehip.kde(pts, [0.3])
+    leaves, w, v, _ = leaf_arrays(p)
+    # the premises, on the leaves and the model alone: some cluster lies wholly in chunks 128 and beyond, none of the chunks
+    # below 120 holds a leaf of it, and pruning happens
+    which = (leaves[:, 0] > 0).astype(int) * 2 + (leaves[:, 1] > 0).astype(int)
+    assert np.all(np.abs(np.abs(leaves) - 20.0) < 8.0)
+    tail = which[128 * 128:]
+    assert np.all(tail == tail[0]) and not np.any(which[:128 * 96] == tail[0])
+    pl = em.plan(leaves, w, v, leaves, 1e-3, 0.0, loo=True)
+    want = (int(pl["visited"].sum()), int(pl["visited"].size))
+    print("the model's tiles visited / total:", want)
+    assert want[1] == ((N + 255) // 256) * 130 and 0 < want[0] * 3 <= want[1]
+    assert pl["visited"][:, 128:].any() and not pl["visited"][:, 128:].all()
+    direct = kdehip.evaluateDualTree(p, lvFlag=True)
+    got, stats = kdehip.evaluate_tol(p, None, 1e-3, lvFlag=True, return_stats=True)
+    print("tiles visited / total:", stats)
+    assert stats == want
     _bounded(got, direct, 1e-3, 0.0)
     with kdehip.DeviceDensity(p) as d:
         got_d, stats_d = d.evaluate_tol(None, 1e-3, return_stats=True)

@@ -4,7 +4,8 @@
 Nothing here has a tolerance but the estimators: the search is exact, so indices are compared with `==`, squared distances
 with np.array_equal (the contract's distance is a chain of correctly rounded operations, which the model restates to the bit),
 and the tile counts with the model's plan.  The estimators are sums of N logarithms: 1e-12, the project's tolerance for sums
-(tests/test_gpu_ksum.py)."""
+(tests/test_gpu_ksum.py).  Section 8 has the sizes at which a row of flags has more than one word and the boxes more than one tile
+(N = 128 * 64 + 1, 128 * 129 + 1); the model runs its leave-one-out there in row blocks."""
 import ctypes as C
 import math
 
@@ -14,6 +15,7 @@ import pytest
 import kdehip
 from kdehip import _lib
 from tests import knn_model as km
+from tests.helpers import assert_chunks_per_group
 from tests.test_gpu_evaltol import leaf_arrays
 
 pytestmark = pytest.mark.gpu
@@ -266,3 +268,134 @@ def test_the_estimators_are_the_models_formulas_of_the_models_distances():
             kdehip.kld_knn(p, dq, k)
     dup = kdehip.kde(np.concatenate([P[:, :50]] * 5, axis=1), [0.4])  # every point has k = 4 duplicates: -inf
     assert kdehip.entropy_knn(dup, k) == -np.inf
+
+
+# ---- 8. more than one flag word, more than one box tile ----------------------------------------------------------------------
+# A row of the plan's flags has one 64-bit word per 64 chunks and the boxes are staged in tiles of 128 chunks, so with the
+# sizes above (at most 8 chunks) the second word, `next()` crossing a word, the second tile (`c0 > 0`) and a group of the sweep
+# that walks more than one chunk never ran.
+#   N = 128 * 64 + 1   65 chunks: two flag words, the second holding one chunk of one leaf; a group of the sweep walks 2 chunks
+#   N = 128 * 129 + 1  130 chunks: a second box tile of two boxes, three flag words, a last chunk of one leaf; 3 chunks a group
+# (N - 1) % 128 == 0 in both: in leave-one-out the last leaf is alone in its chunk, at 16513 in the second tile.
+# The points are the module's clustered columns with the first 256 and the last 128 moved 40 away along dimension 0, so that
+# tree order separates them.  Queries 0 .. 127 lie beside the first 128 leaves and queries 128 .. 255 beside some of the last 120 but
+# the lone last one:
+# the first query block needs chunks at both ends of the row and nothing in between, and `next()` jumps over the words
+# between them; the other 44 queries are clustered columns again.
+BIG_SHAPES = {8193: (2, 300, ("euclid", "circular"), (1, 8, 32)), 16513: (3, 300, ("euclid", "scale"), (1, 8))}
+_BIG = {}
+
+
+def _big_case(N, variant):
+    if (N, variant) not in _BIG:
+        D, Nq, _, _ = BIG_SHAPES[N]
+        rng = np.random.default_rng(5000 * D + 10 * N + Nq)
+        circular = variant == "circular"
+        pts = np.stack([_column(rng, N, circular and j == D - 1) for j in range(D)])
+        pts[0, :256] -= 40.0   # the tree splits at the median of the widest dimension, the lower values to the left: these
+        pts[0, -128:] += 40.0  # become the first 256 leaves or so (chunks 0, 1) and the last 128 (what the plan makes of it is
+        #                        asserted on the model where it is used)
+        p = kdehip.kde(pts, [0.5])
+        leaves, _, _, where = leaf_arrays(p)
+        pos = np.stack([_column(rng, Nq, circular and j == D - 1) for j in range(D)])
+        pos[:, :128] = leaves[:128].T + 0.01 * rng.standard_normal((D, 128))
+        pos[:, 128:256] = leaves[rng.integers(N - 120, N - 1, size=128)].T + 0.01 * rng.standard_normal((D, 128))
+        pos[:, 256] = leaves[-1] + 0.001 * rng.standard_normal(D)  # beside the lone last leaf: the second block needs its chunk
+        scale = rng.uniform(0.3, 3.0, size=D) if variant == "scale" else None
+        circ = (D - 1,) if circular else ()
+        qry = np.ascontiguousarray(pos.T)
+        _BIG[(N, variant)] = dict(p=p, pos=pos, qry=qry, leaves=leaves, where=where, orig=where + 1, scale=scale, circ=circ,
+                                  man=([0] * (D - 1) + [1]) if circular else None,
+                                  metric="euclid" if scale is None else scale, d2=km.all_dist2(leaves, qry, scale, circ))
+    return _BIG[(N, variant)]
+
+
+def _gap(row):
+    """the longest unvisited stretch between two visited chunks of one query block that lie in different flag words"""
+    at = np.nonzero(row)[0]
+    return max([b - a - 1 for a, b in zip(at[:-1], at[1:]) if a // 64 != b // 64], default=0)
+
+
+@pytest.mark.parametrize("N,variant", [(N, v) for N, (_, _, vs, _) in BIG_SHAPES.items() for v in vs])
+def test_the_search_with_several_flag_words_and_box_tiles(N, variant):
+    D, Nq, _, ks = BIG_SHAPES[N]
+    assert_chunks_per_group(N, Nq, 2 if N == 8193 else 3)
+    c = _big_case(N, variant)
+    kw = dict(scale=c["scale"], circ=c["circ"], d2=c["d2"])
+    nc = (N + 127) // 128
+    for k in ks:
+        pl = km.plan(c["leaves"], c["orig"], c["qry"], k, **kw)
+        # the premises, on the model alone
+        assert pl["stats"][0] < pl["stats"][1] == 2 * nc  # pruning happens: a flag in the wrong word changes what is scanned
+        assert (pl["cstar"] < 64).any() and (pl["cstar"] >= (128 if N == 16513 else 63)).any(), np.unique(pl["cstar"])
+        if N == 16513:  # a block visits chunks of two flag words and none of the 64 or more between them
+            assert max(_gap(row) for row in pl["visited"]) >= 64, [_gap(row) for row in pl["visited"]]
+        else:  # (65 chunks: the second word is chunk 64 alone) a block visits it, and a block leaves most of the first word out
+            assert pl["visited"][:, 64].any() and any(0 < row[:64].sum() < 32 for row in pl["visited"])
+        d2, idx = km.knn(c["leaves"], c["orig"], c["qry"], k, **kw)
+        got = kdehip.knn(c["p"], c["pos"], k=k, order="given", metric=c["metric"], manifold=c["man"], squared=True,
+                         return_stats=True)
+        print("N", N, variant, "k", k, "tiles visited / total:", got[2], "model:", pl["stats"])
+        _same(got, (d2.T, idx.T, pl["stats"]))
+    with kdehip.DeviceDensity(c["p"]) as d, kdehip.DeviceDensity(kdehip.kde(c["pos"], [1.0])) as a:  # resident == host
+        kw = dict(k=8, metric=c["metric"], manifold=c["man"], squared=True, return_stats=True)
+        host = kdehip.knn(c["p"], kdehip.kde(c["pos"], [1.0]), **kw)
+        got = d.knn(a, **kw)
+        assert np.array_equal(got[0], host[0]) and np.array_equal(got[1], host[1]) and got[2] == host[2]
+
+
+_BIG_LOO = {}
+
+
+def _big_loo(N, variant, k=8):
+    """the model's leave-one-out search of a large density in row blocks of 1024 leaves (never an N x N array): (d2 (k, N),
+    idx (k, N)) in the caller's order, the summed stats and every leaf's nearest chunk"""
+    if (N, variant) not in _BIG_LOO:
+        c = _big_case(N, variant)
+        d2s, idxs, cstar, visited, total = [], [], [], 0, 0
+        for r in range(0, N, 1024):
+            rows = slice(r, min(N, r + 1024))
+            qry = c["leaves"][rows]
+            kw = dict(loo=True, scale=c["scale"], circ=c["circ"], d2=km.all_dist2(c["leaves"], qry, c["scale"], c["circ"]),
+                      rows=rows)
+            d2, idx = km.knn(c["leaves"], c["orig"], qry, k, **kw)
+            pl = km.plan(c["leaves"], c["orig"], qry, k, **kw)
+            d2s.append(d2)
+            idxs.append(idx)
+            cstar.append(pl["cstar"])
+            visited, total = visited + pl["stats"][0], total + pl["stats"][1]
+        back = np.argsort(c["where"])  # leaf q is original point where[q]
+        _BIG_LOO[(N, variant)] = dict(d2=np.concatenate(d2s)[back].T, idx=np.concatenate(idxs)[back].T,
+                                      stats=(visited, total), cstar=np.concatenate(cstar))
+    return _BIG_LOO[(N, variant)]
+
+
+@pytest.mark.parametrize("N,variant", [(8193, "euclid"), (8193, "circular"), (16513, "euclid")])
+def test_leave_one_out_with_the_last_leaf_alone_in_its_chunk(N, variant):
+    assert (N - 1) % 128 == 0
+    assert_chunks_per_group(N, N, 2 if N == 8193 else 5)  # (N = Nq = 16513: 65 query blocks, 32 groups)
+    c = _big_case(N, variant)
+    m = _big_loo(N, variant)
+    nc = (N + 127) // 128
+    # the premises, on the model alone: the lone leaf's own chunk does not count for it, pruning happens, both ends occur
+    assert m["cstar"][N - 1] != nc - 1 and m["cstar"][N - 2] < nc - 1
+    assert m["stats"][0] < m["stats"][1] == ((N + 255) // 256) * nc
+    assert (m["cstar"] < 64).any() and (m["cstar"] >= (128 if N == 16513 else 63)).any()
+    got = kdehip.knn(c["p"], k=8, lvFlag=True, metric=c["metric"], manifold=c["man"], squared=True, return_stats=True)
+    print("N", N, variant, "tiles visited / total:", got[2], "model:", m["stats"])
+    _same(got, (m["d2"], m["idx"], m["stats"]))
+    with kdehip.DeviceDensity(c["p"]) as d:
+        again = d.knn(None, k=8, metric=c["metric"], manifold=c["man"], squared=True, return_stats=True)
+        assert np.array_equal(again[0], got[0]) and np.array_equal(again[1], got[1]) and again[2] == got[2]
+
+
+def test_entropy_knn_with_two_flag_words():
+    N, k = 8193, 4
+    c = _big_case(N, "euclid")
+    eps = np.sqrt(_big_loo(N, "euclid")["d2"][k - 1])  # the model's 4th leave-one-out neighbour of every point
+    want = km.entropy_kl(eps, 2, k)
+    got = kdehip.entropy_knn(c["p"], k)
+    print("entropy_knn:", got, "model:", want, "difference:", abs(got - want))
+    assert abs(got - want) <= 1e-12
+    with kdehip.DeviceDensity(c["p"]) as d:
+        assert abs(kdehip.entropy_knn(d, k) - want) <= 1e-12

@@ -19,13 +19,15 @@ import pytest
 import kdehip
 from kdehip import _lib
 from tests import mass_model as mm
+from tests.helpers import assert_chunks_per_group
 from tests.test_gpu_ksum import _arrays
 
 pytestmark = pytest.mark.gpu
 
 # (D, dims, N, Nq): the smallest case; two chunks and groups with Nq across a block; gathered dimensions; 6-D; 8-D; 65 chunks
-# (two chunks per group: the ring's second buffer)
-SHAPES = [(1, [0], 5, 3), (2, [0, 1], 129, 257), (3, [0, 2], 300, 7), (6, None, 257, 5), (8, None, 130, 3), (2, [1], 8200, 3)]
+# (two chunks per group: the ring's second buffer); 129 chunks (three per group: a buffer staged a second time)
+SHAPES = [(1, [0], 5, 3), (2, [0, 1], 129, 257), (3, [0, 2], 300, 7), (6, None, 257, 5), (8, None, 130, 3), (2, [1], 8200, 3),
+          (2, [1], 16500, 3)]
 LEVELS = np.array([1e-9, 0.025, 0.5, 0.975, 1.0 - 1e-9])
 
 
@@ -81,6 +83,8 @@ def _close(got, want):
 # ---- 1. the model ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("D,dims,N,Nq", SHAPES)
 def test_box_mass_equals_the_model(D, dims, N, Nq):
+    if N > 8192:  # a large shape is here for the chunks a group walks: asserted from the split restated in tests/helpers.py
+        assert_chunks_per_group(N, Nq, 2 if N == 8200 else 3)
     c = _case(D, dims, N, Nq)
     assert np.all(c["model"] > 0.0) and int(np.sum(c["A"][1] == 0.0)) == (1 if N > 1 else 0)
     assert np.isinf(c["lo"]).any() and np.isinf(c["hi"]).any()

@@ -9,7 +9,9 @@ Tolerances, none of them taken from the code under test:
 Where every exponent is huge (the query far from all data) the model forms a_i with the header's one fma per dimension
 (modes_model.moments(fma=True), exactly rounded), so the same bounds hold there.
 The one-step check reads the stored point, not the step: the roundings of storing it ride on the step's bound, each counted
-where it occurs (see the test)."""
+where it occurs (see the test).
+Section 7 repeats the comparisons at N = 128 * 64 + 1 and 128 * 128 + 1, where a group of the sweep walks two and three chunks
+and the carried sums are rescaled: what the smaller sizes never run."""
 import math
 
 import numpy as np
@@ -18,6 +20,7 @@ import pytest
 import kdehip
 from kdehip import _lib
 from tests import modes_model as mm
+from tests.helpers import assert_chunks_per_group, rescale_premise
 from tests.test_gpu_ksum import SHAPES, _arrays, _density, _weights
 
 pytestmark = pytest.mark.gpu
@@ -430,3 +433,174 @@ def test_circular_data_that_never_wraps_gives_the_euclidean_bits():
     with kdehip.DeviceDensity(p) as d:
         d.manifold = np.array([0, 1], dtype=np.uint8)
         assert _same(kdehip.meanshift(d, tol=TOL, maxiter=60, manifold="inherit"), kdehip.meanshift(p, tol=TOL, maxiter=60))
+
+
+# ---- 7. groups of several chunks -------------------------------------------------------------------------------------------
+# The sizes above give every group of the sweep ONE chunk (split_chunks of csrc/entry_helpers.hpp wants all 64 groups on the
+# 256 CUs of an MI355X), so `if (cm > m)` of moments_partial_kernel never met carried sums.  Here a group walks two chunks
+# (N = 128 * 64 + 1: 65 chunks, the last group one chunk of one leaf) or three (N = 128 * 128 + 1), with 257 queries: a second
+# query block with one live lane.  Two premises are asserted before the library is called, the first from the split restated
+# in tests/helpers.py, the second from the model's leaf-order arrays alone (helpers.rescale_premise): for a quarter of the
+# queries some group has a later chunk that raises the running maximum by log 2 or more over a non-empty earlier one -- the
+# carried s[0..D] are scaled by 1/2 or less -- and a maximum within 30 of the query's overall one, so the group counts.
+BIG_NQ = 257
+BIG_GRAD = [(1, 128 * 64 + 1, None), (6, 128 * 64 + 1, None), (8, 128 * 128 + 1, None), (3, 128 * 64 + 1, (0, 0, 1))]
+_BIG = {}
+
+
+def _leaf_order(p):
+    """(points (D, N), weights (N,)) of a host density in LEAF order: the order the sweep's chunks are cut from"""
+    N, D = p.bt.num_points, p.bt.dims
+    return np.ascontiguousarray(p.bt.centers[N * D:].reshape(N, D).T), p.bt.weights[N:].copy()
+
+
+def _big(D, N):
+    """a density of one large shape and BIG_NQ queries among its points, a bandwidth or so off them: built once, shared, never
+    changed"""
+    if (D, N) not in _BIG:
+        rng = np.random.default_rng(1000 * D + 10 * N + BIG_NQ)
+        p = _density(rng, D, N)
+        A = _arrays(p)
+        sd = np.sqrt(A[2])[:, None]
+        X = A[0][:, rng.integers(0, N, size=BIG_NQ)] + sd * rng.standard_normal((D, BIG_NQ))
+        _BIG[(D, N)] = dict(p=p, A=A, X=X, leaf=_leaf_order(p))
+    return _BIG[(D, N)]
+
+
+def _assert_the_rescale_fires_and_matters(c, Nq, per_group, man=None, X=None):
+    """the two premises of a large case, from the split restated in tests/helpers.py and from the model's arrays alone"""
+    N = c["A"][0].shape[1]
+    assert_chunks_per_group(N, Nq, per_group)
+    pts, w = c["leaf"]
+    hit = rescale_premise(pts, w, c["A"][2], c["X"] if X is None else X, per_group, man)
+    print("queries with a rescale by <= 1/2 in a group within 30 of the maximum:", int(hit.sum()), "of", hit.size)
+    assert hit.mean() >= 0.25, (int(hit.sum()), hit.size)
+
+
+@pytest.mark.parametrize("D,N,man", BIG_GRAD)
+def test_evaluate_grad_with_groups_of_several_chunks(D, N, man):
+    c = _big(D, N)
+    man = None if man is None else list(man)
+    _assert_the_rescale_fires_and_matters(c, BIG_NQ, 2 if N < 128 * 128 else 3, man)
+    want, wgrad, scale = mm.evaluate_grad(c["A"], c["X"], man)
+    val, grad = kdehip.evaluate_grad(c["p"], c["X"], manifold=man)
+    assert val.shape == (BIG_NQ,) and grad.shape == (D, BIG_NQ)
+    print("log p: max |delta| / max(1, |ref|)", float(np.max(np.abs(val - want) / np.maximum(1.0, np.abs(want)))),
+          "grad: max |delta| / scale", float(np.max(np.abs(grad - wgrad) / scale)))
+    _close_logp(val, want)
+    _close_scaled(grad, wgrad, scale)
+    pw = np.array([math.exp(v) for v in want])  # mm.evaluate_grad(..., log=False) without summing everything again
+    lwant, lgrad, lscale = pw, wgrad * pw, scale * pw
+    p, pgrad = kdehip.evaluate_grad(c["p"], c["X"], log=False, manifold=man)
+    assert np.all(lwant > 0.0)
+    _close_scaled(p, lwant, lwant)
+    _close_scaled(pgrad, lgrad, lscale)
+    with kdehip.DeviceDensity(c["p"]) as d:  # resident: the same bits as the host entry
+        for log, (hv, hg) in ((True, (val, grad)), (False, (p, pgrad))):
+            dv, dg = kdehip.evaluate_grad(d, c["X"], log=log, manifold=man)
+            assert np.array_equal(dv, hv) and np.array_equal(dg, hg)
+        if man is None:
+            dv, dg = d.evaluate_grad(c["X"])
+            assert np.array_equal(dv, val) and np.array_equal(dg, grad)
+
+
+@pytest.mark.parametrize("D,N,circular", [(2, 128 * 64 + 1, False), (2, 128 * 64 + 1, True), (6, 128 * 128 + 1, False)])
+def test_one_step_with_groups_of_several_chunks(D, N, circular):
+    """the one-step bound of section 2, where the step item's group walks two chunks (three at N = 128 * 128 + 1)"""
+    c = _big(D, N)
+    man = ([0] * (D - 1) + [1]) if circular else None
+    Nq = BIG_NQ if D == 2 else 40  # (the model sums 4 D + 2 series of N terms by math.fsum per query)
+    Xs = c["X"][:, :Nq]
+    _assert_the_rescale_fires_and_matters(c, Nq, 2 if N < 128 * 128 else 3, man, Xs)
+    x, logp, iters = kdehip.meanshift(c["p"], Xs, tol=0.0, maxiter=1, manifold=man)
+    assert x.shape == (D, Nq) and iters.tolist() == [-1] * Nq
+    circ = np.zeros(D, dtype=bool) if man is None else np.asarray(man, dtype=bool)
+    worst = 0.0
+    for q in range(Nq):
+        xn, dx, scale = mm.step(c["A"], Xs[:, q], man)
+        got = Xs[:, q] - x[:, q]
+        got = np.where(circ, mm.wrap(got), got)
+        X = np.abs(Xs[:, q])  # (the roundings of storing the point: see test_one_step_equals_the_models)
+        t = X + np.abs(dx)
+        store = U * (t + X + np.abs(xn))
+        store = store + np.where(circ, U * ((t + math.pi + np.abs(xn)) + (X + np.abs(xn) + math.pi + np.abs(dx))), 0.0)
+        worst = max(worst, float(np.max(np.abs(got - dx) / (1e-12 * scale + store))))
+        assert np.all(np.abs(got - dx) <= 1e-12 * scale + store), (q, got, dx, scale, store)
+        assert np.all(~circ | ((x[:, q] >= -math.pi) & (x[:, q] < math.pi)))
+        assert abs(logp[q] - mm.log_p(c["A"], x[:, q], man)) <= 1e-12 * max(1.0, abs(logp[q]))
+    print("largest |step - model| / bound:", worst)
+
+
+_BIG_CLUSTERS = {}
+
+
+def _big_clusters():
+    """mm.three_clusters(2, 128 * 64 + 1), eight starts between and beside the clusters, the model's run from them"""
+    if not _BIG_CLUSTERS:
+        pts, sd, w = mm.three_clusters(2, 128 * 64 + 1)
+        p = kdehip.kde(pts, sd, w)
+        A = _arrays(p)
+        rng = np.random.default_rng(8)
+        starts = np.array([[0.0, 3.0, 0.0, 1.2, 1.9, -0.6, 0.3, 3.5], [0.0, 0.0, -3.0, 0.2, -0.3, -1.2, -1.9, 0.6]])
+        starts = starts + 0.05 * rng.standard_normal(starts.shape)
+        _BIG_CLUSTERS.update(p=p, A=A, sd=sd, starts=starts, leaf=_leaf_order(p), X=starts,
+                             model=mm.meanshift(A, starts, TOL, 200))
+    return _BIG_CLUSTERS
+
+
+def _check_run(c, starts, x, logp, iters, model):
+    """the bounds of test_every_start_converges_to_one_of_three_modes for a run from given starts: the model's own step at
+    the returned point is within tol, the point lies within 1e-6 bandwidths of where the model's run ends, log p is the
+    model's there"""
+    A, sd = c["A"], c["sd"]
+    mx, mlogp, miters, _ = model
+    assert np.all(miters > 0) and np.all(iters > 0) and iters.max() <= 200
+    for q in range(x.shape[1]):
+        _, dx, scale = mm.step(A, x[:, q])
+        assert np.all(np.abs(dx) / sd <= TOL + 1e-12 * scale / sd), (q, dx)
+        assert abs(logp[q] - mm.log_p(A, x[:, q])) <= 1e-12 * max(1.0, abs(logp[q]))
+    far = np.max(np.abs(x - mx) / sd[:, None], axis=0)
+    print("largest distance from the model's end points, in bandwidths:", float(far.max()))
+    assert far.max() <= 1e-6, far
+    start_logp = np.array([mm.log_p(A, starts[:, q]) for q in range(starts.shape[1])])
+    assert np.all(logp >= start_logp - 1e-12 * np.maximum(1.0, np.abs(logp)))
+
+
+def test_the_iteration_with_groups_of_two_chunks_host_resident_and_batch():
+    import torch
+    c = _big_clusters()
+    starts = c["starts"]
+    _assert_the_rescale_fires_and_matters(c, starts.shape[1], 2)
+    run = kdehip.meanshift(c["p"], starts, tol=TOL, maxiter=200)
+    _check_run(c, starts, *run, c["model"])
+    assert len(set(np.round(run[0][0] / 3.0).astype(int).tolist())) >= 2  # the starts end in more than one mode
+    # the batch's first item is a small 1-D density from its own points: the large item's launch starts at a block offset
+    small = kdehip.kde(np.array([[0.1, 0.4, -0.3, 0.9, 0.5]]), [0.3])
+    small_run = kdehip.meanshift(small, tol=TOL, maxiter=200)
+    with kdehip.DeviceDensity(c["p"]) as d, kdehip.DeviceDensity(small) as ds:
+        assert _same(kdehip.meanshift(d, starts, tol=TOL, maxiter=200), run)
+        items = _batch([dict(density=ds, starts=None, manifold=None), dict(density=d, starts=starts, manifold=None)], TOL, 200)
+        kdehip.meanshift_device_batch(items, TOL, 200)
+        torch.cuda.synchronize()
+        got = _results(items)
+        assert _same(got[0], small_run) and _same(got[1], run)
+
+
+def test_a_dead_query_block_beside_a_walking_one_with_groups_of_two_chunks():
+    """257 starts: the 256 of the first query block sit on a mode and freeze after their first step, so that block's
+    `live[...] == 0` early return runs in every later sweep while the last lane's block walks its two chunks per group"""
+    c = _big_clusters()
+    assert_chunks_per_group(128 * 64 + 1, 257, 2)
+    mode = kdehip.meanshift(c["p"], c["model"][0][:, :1], tol=TOL, maxiter=200)[0]
+    lone = mode + np.array([[1.5], [0.0]])
+    starts = np.hstack([np.repeat(mode, 256, axis=1), lone])
+    model = mm.meanshift(c["A"], lone, TOL, 200)
+    assert model[2][0] > 1
+    x, logp, iters = kdehip.meanshift(c["p"], starts, tol=TOL, maxiter=200)
+    alone = kdehip.meanshift(c["p"], mode, tol=TOL, maxiter=200)
+    assert iters[:256].tolist() == [1] * 256 and alone[2].tolist() == [1]
+    assert np.array_equal(x[:, :256], np.repeat(alone[0], 256, axis=1)) and np.array_equal(logp[:256], np.repeat(alone[1], 256))
+    assert iters[256] > 1
+    _check_run(c, lone, x[:, 256:], logp[256:], iters[256:], model)
+    solo = kdehip.meanshift(c["p"], lone, tol=TOL, maxiter=200)
+    assert np.array_equal(solo[0], x[:, 256:]) and solo[2][0] == iters[256] and solo[1][0] == logp[256]

@@ -14,6 +14,7 @@ import pytest
 import kdehip
 from kdehip import _lib
 from kdehip.summary import grid
+from tests.helpers import assert_chunks_per_group
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,49 @@ def test_kde_max_matches_the_model_and_the_composition(D, N, weighted, Ngrid):
             assert abs(y[got] - y[k]) <= 1e-11 * y[k], (i, got, k)
     # the resident entry gives the same bits
     dm, dvals = kdehip.DeviceDensity(p).getKDEMax(Ngrid, values=True)
+    assert np.array_equal(dm, m) and np.array_equal(dvals, vals)
+
+
+# Groups of SEVERAL chunks in grid_partial_kernel (its own ring and split: 256-leaf chunks, at most 256 groups, which a grid of
+# up to a few thousand points all gets on the 256 CUs of an MI355X): a group holds more than one chunk only when N > 256 * 256.
+#   N = 256 * 256 + 1: 257 chunks, 2 per group, the last group ONE chunk of ONE leaf: the ring's second buffer, total += sum
+#   N = 512 * 256 + 1: 513 chunks, 3 per group: a buffer staged a second time
+# Small grids (2 points, and 257: a second grid block with one live lane) keep the np.longdouble model at a second or two;
+# the model is summed in blocks of grid points, never as an Ngrid x N array.
+def _marginal_model_blocked(p, i, x, rows=16):
+    """_marginal_model for a large density"""
+    m = kdehip.marginal(p, [i])
+    N = m.bt.num_points
+    mu = m.means[N:].astype(np.longdouble)
+    w = m.bt.weights[N:].astype(np.longdouble)
+    v = np.longdouble(m.bandwidth[N])
+    x = np.asarray(x, dtype=np.longdouble)
+    out = np.zeros(len(x), dtype=np.longdouble)
+    for r in range(0, len(x), rows):
+        d = x[r:r + rows, None] - mu[None, :]
+        out[r:r + rows] = (np.exp(-d * d / (2 * v)) * w[None, :]).sum(axis=1)
+    return out / np.sqrt(2 * np.longdouble(np.pi) * v)
+
+
+@pytest.mark.parametrize("D,N,weighted,Ngrid,per_group", [(1, 256 * 256 + 1, True, 2, 2), (1, 256 * 256 + 1, False, 257, 2),
+                                                          (1, 512 * 256 + 1, True, 257, 3), (3, 256 * 256 + 1, True, 2, 2)])
+def test_kde_max_with_groups_of_several_chunks(D, N, weighted, Ngrid, per_group):
+    assert_chunks_per_group(N, Ngrid, per_group, grid=True)
+    p = _density(D, N, seed=D * 1000 + N + Ngrid, weighted=weighted)
+    m, vals = kdehip.getKDEMax(p, Ngrid, values=True)
+    assert m.shape == (D,) and vals.shape == (D, Ngrid)
+    for i in range(D):
+        lo, hi = kdehip.getKDERange(kdehip.marginal(p, [i]), 0.1)[0]
+        x = grid(lo, hi, Ngrid)
+        model = _marginal_model_blocked(p, i, x)
+        err = np.abs(vals[i].astype(np.longdouble) - model)
+        print("dimension", i, "largest |value - model| / model:", float(np.max(err / model)))
+        assert np.all(model > 0) and np.all(err <= 1e-12 * model), float(np.max(err / model))
+        k = int(np.argmax(model))
+        got = int(np.flatnonzero(x == m[i])[0])
+        if got != k:  # only a near tie of the top two values may pick the other one
+            assert abs(model[got] - model[k]) <= 1e-11 * model[k], (i, got, k)
+    dm, dvals = kdehip.DeviceDensity(p).getKDEMax(Ngrid, values=True)  # the resident entry gives the same bits
     assert np.array_equal(dm, m) and np.array_equal(dvals, vals)
 
 
@@ -179,6 +223,19 @@ def test_inters_matches_the_fsum_model_host_and_resident(D, Np, Nq, N):
     assert abs(a - want) <= 1e-12 * abs(want)
     b = kdehip.intersIntgAppxIS(kdehip.DeviceDensity(p), kdehip.DeviceDensity(q), N)
     assert a == b
+
+
+def test_inters_with_a_density_of_several_chunks_per_group():
+    """p has 256 * 256 + 1 points and the grid 257: intersIntgAppxIS evaluates both densities on p's grid by the existing
+    evaluation, whose split (128-leaf chunks, at most 64 groups) gives a group nine chunks here"""
+    Np, N = 256 * 256 + 1, 257
+    assert_chunks_per_group(Np, N, 9)
+    p, q = _density(1, Np, seed=Np + 1), _density(1, 150, seed=157, weighted=True)
+    a = kdehip.intersIntgAppxIS(p, q, N)
+    want = _inters_model(p, q, N)
+    print("intersIntgAppxIS:", a, "model:", want, "relative difference:", abs(a - want) / abs(want))
+    assert abs(a - want) <= 1e-12 * abs(want)
+    assert a == kdehip.intersIntgAppxIS(kdehip.DeviceDensity(p), kdehip.DeviceDensity(q), N)
 
 
 def _offs(seed, offs, N, dim):

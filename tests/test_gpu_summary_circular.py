@@ -7,7 +7,8 @@ covariance; 1e-12 relative per grid value).  The argmax is the model's grid poin
 largest grid values are further apart than that tolerance, so that a tie cannot hide a wrong index.  Sizes: one point, two,
 around the wavefront (63, 64, 65), more than one staged chunk of 256 (257, 300); grids of 2, 3, 200 and 257 (two blocks).
 Data: angles straddling +-pi, the same plus 4 pi (any representative works), and angles over the whole circle (the 2 pi
-clamp of the range; its two-point grid is one angle twice, so that case checks the values only)."""
+clamp of the range; its two-point grid is one angle twice, so that case checks the values only).  One case has
+N = 256 * 256 + 1, where a group of the grid kernel holds two chunks."""
 import ctypes as C
 import functools
 import math
@@ -19,6 +20,7 @@ import kdehip
 from kdehip import _lib
 from kdehip._lib import f64p, ptr, u8p
 from tests import summary_circular_model as M
+from tests.helpers import assert_chunks_per_group
 
 pytestmark = pytest.mark.gpu
 
@@ -156,6 +158,23 @@ def test_grid_values_and_argmax(D, N, Ngrid):
             if kind == "wide" and N >= 3 and Ngrid == 200:   # the case does exercise the cut to one turn
                 circ = np.array(man, dtype=bool)
                 assert np.all(np.abs((xs[circ, -1] - xs[circ, 0]) - 2 * math.pi) < 1e-12)
+
+
+def test_grid_values_with_groups_of_two_chunks():
+    """grid_partial_kernel<true> where a group of its own split (256-leaf chunks, at most 256 groups) holds two chunks:
+    N = 256 * 256 + 1, 257 chunks, the ring's second buffer and `total += sum` over chunks; the last group is one leaf"""
+    D, N, kind, man, Ngrid = 1, 256 * 256 + 1, "straddle", (1,), 3
+    assert_chunks_per_group(N, Ngrid, 2, grid=True)
+    xs, vals, amax, checked = grid_model(D, N, kind, man, Ngrid)
+    p, _, _ = case(D, N, kind, man)
+    with kdehip.DeviceDensity(p) as dp:
+        m, got = kdehip.getKDEMax(dp, Ngrid, values=True, manifold=list(man))
+    err = np.abs(got.astype(np.longdouble) - vals)
+    print("largest |value - model| / model:", float(np.max(err / vals)))
+    assert np.all(err <= GRID_TOL * vals), float(np.max(err / vals))
+    assert np.array_equal(m[checked], amax[checked])
+    hm, hv = kdehip.getKDEMax(p, Ngrid, values=True, manifold=list(man))  # the host entry gives the same bits
+    assert np.array_equal(hm, m) and np.array_equal(hv, got)
 
 
 def _summary_all(dp, Ngrid, extend, manifold_bytes):

@@ -9,19 +9,29 @@ normalisers c_i, lc_i.  Routes (host entry, resident `at` form, resident positio
 Variances are drawn per point and per dimension as sd_k^2 u^2, u in [0.5, 2].  Sizes are those of
 tests/test_gpu_logdensity.py: N in {2, 127, 128, 129, 130, 300} (chunk tail, exact chunk, three one-chunk groups), Nq in
 {1, 3, 255, 256, 257} (lane tail, second query block), D in {1, 2, 3, 6, 8}; and N = 128 * 64 + 129 with Nq = 3, where a
-group walks two chunks and the carried (m, s) is rescaled (64 = kEvalMaxGroups, csrc/entry_helpers.hpp)."""
+group walks two chunks and the carried (m, s) is rescaled (64 = kEvalMaxGroups, csrc/entry_helpers.hpp), and
+N = 128 * 128 + 129, where it walks three and pair_sweep_var's ring stages a buffer a second time."""
 import numpy as np
 import pytest
 
 import kdehip
 from kdehip import _lib
 from tests import varbw_model as vm
+from tests.helpers import assert_chunks_per_group
 
 pytestmark = pytest.mark.gpu
 
 MAX_GROUPS = 64  # kEvalMaxGroups
 BIG = 128 * MAX_GROUPS + 129
-SHAPES = [(1, 2, 1), (2, 127, 255), (3, 128, 256), (6, 129, 257), (2, 300, 257), (6, 2, 255), (8, 130, 3), (3, BIG, 3)]
+BIG3 = 128 * 128 + 129  # three chunks per group
+SHAPES = [(1, 2, 1), (2, 127, 255), (3, 128, 256), (6, 129, 257), (2, 300, 257), (6, 2, 255), (8, 130, 3), (3, BIG, 3),
+          (3, BIG3, 3)]
+
+
+def _premise(N, Nq):
+    """a large shape is here for the chunks a group walks: asserted from the split restated in tests/helpers.py"""
+    if N in (BIG, BIG3):
+        assert_chunks_per_group(N, Nq, 2 if N == BIG else 3)
 
 
 def _pts(rng, D, N):
@@ -81,6 +91,7 @@ def _close_ll(got, want, what=""):
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("D,N,Nq", SHAPES)
 def test_values_equal_the_model(D, N, Nq, weighted):
+    _premise(N, Nq)
     pts, w, bw, pos = _case(100 * D + N + Nq + weighted, D, N, Nq, weighted)
     p = kdehip.kde_varbw(pts, bw, w)
     var = _var(p)
@@ -197,8 +208,9 @@ def test_edge_queries_and_weightless_sources():
     assert kdehip.evalAvgLogL(one, one, log_domain=True) == -np.inf
 
 
-@pytest.mark.parametrize("D,N,Nq", [(2, 300, 257), (6, 129, 255), (3, BIG, 3)])
+@pytest.mark.parametrize("D,N,Nq", [(2, 300, 257), (6, 129, 255), (3, BIG, 3), (3, BIG3, 3)])
 def test_host_entry_resident_calls_and_a_second_run_agree_bit_for_bit(D, N, Nq):
+    _premise(N, Nq)
     import torch
     pts, w, bw, pos = _case(9 * D + N, D, N, Nq, True)
     p = kdehip.kde_varbw(pts, bw, w)
