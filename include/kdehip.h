@@ -1576,6 +1576,70 @@ int kdehip_product_components(const kdehip_density *p, const kdehip_density *q, 
 int kdehip_product_components_device(const kdehip_device_density *p, const kdehip_device_density *q, double *d_means,
                                      double *d_weights, double *d_var, void *stream);
 
+/* ---- (5q) joint bandwidth selection: the leave-one-out likelihood over all dimensions ---------------------------------------
+ * kde!(points) (section 5, kdehip_auto_bandwidth) searches the leave-one-out likelihood of every 1-D marginal on its own; for
+ * D > 1 that undersmooths (the best 1-D bandwidth shrinks like N^(-1/5), the best joint one like N^(-1/(D+4))).  The entries
+ * below maximise the JOINT leave-one-out likelihood over the whole bandwidth vector by a fixed-point iteration
+ * (csrc/bwjoint.hip; this library's own, the reference has no counterpart).  For a density bd with leaves c_i in LEAF ORDER,
+ * weights w_i, a per-dimension `manifold` as in 5d (NULL = Euclidean) and a current variance vector v:
+ *   d_ijk = c_ik - c_jk, through wrap() first in a circular dimension
+ *   a_ij  = sum_k d_ijk^2 * (-0.5 / v_k): the expression and fma order of the direct kernel
+ *   S_i   = { j : w_j > 0, j != i } -- by INDEX: a duplicate of point i is in S_i; the rule of 5f otherwise
+ *   m_i   = max_{S_i} a_ij,  S0_i = sum_{S_i} w_j exp(a_ij - m_i),  T_ik = sum_{S_i} w_j exp(a_ij - m_i) d_ijk^2
+ *   Q     = { i : w_i > 0, S_i not empty },  W = sum_{i in Q} w_i
+ *   L(v)  = the leave-one-out average log-likelihood exactly as kdehip_eval_avg_logl_log(bd, bd, 1) defines it (5f):
+ *           sum over { i : w_i > 0 } of w_i (m_i + log S0_i - log norm(v) - log(1 - w_i)), -Inf if some such S_i is empty
+ *   v_new_k = ( sum_{i in Q} w_i T_ik / S0_i ) / W
+ * This is EM for a mixture with fixed centres and one shared diagonal covariance: T_ik / S0_i is the responsibility-weighted
+ * mean squared difference of point i (the 1 - w_i of leave-one-out cancels in it), so L(v_new) >= L(v) at every step.
+ * The iteration starts from v_0 = start_k^2 (start: D standard deviations; NULL = bd's own bandwidth, its first leaf's
+ * variances) and stops after the step with max_k |log(v_new_k / v_k)| / 2 <= tol -- a tolerance in log standard deviation --
+ * or after maxiter steps.  Results: bw_out = sqrt(v), D standard deviations; iters = the steps taken, negative when the last
+ * of them was still above tol (as kdehip_meanshift reports); logl = L at the returned bandwidth, from one closing sweep;
+ * trace (optional, maxiter + 1 doubles): trace[t] = L(v_t) for t = 0 .. |iters|, the rest is not written -- every sweep yields
+ * the L of the iterate it read, so the trace costs nothing extra.
+ * Degenerate data -- a v_new_k that is 0 or not finite: a dimension in which all points coincide, or fewer than two leaves of
+ * positive weight --: nothing is updated, the iteration freezes at the last valid iterate (iters keeps its value) and
+ * status = 1; with too few weighted leaves that iterate is the start itself, logl = -Inf and iters = 0.  status = 0 otherwise.
+ * Convergence is linear: two starts end within a few tol of each other, not at the same bits.  The contract is the trajectory
+ * from a given start, not "the optimum".
+ * Arithmetic and determinism: each step is one all-pairs sweep split as in 5b / 5f / 5h (128-leaf chunks in groups that depend
+ * on npts alone; a group carries (m, s_0, t_1..t_D), rescaled by exp(m_old - m_new) once per chunk; the groups combined in
+ * group order), the leaves' terms summed in the fixed 256-wide tree of 5b and the blocks in block order.  No atomics.  The
+ * sweeps of all items of a call share their launches (one per distinct (D, circular)), and a finished item is never written
+ * again: an item's result depends on the density, the start, tol and maxiter alone.  The host entry, the resident entry and
+ * any batch give the same bits, run after run, however the sweeps are grouped between the host's reads of the items' states.
+ * All three entries are BLOCKING and none takes a stream: the result is D doubles that the caller needs on the host to build
+ * the density, and the sweeps run in rounds with one read of the items' states between them.  tol is a HOST pointer to ONE
+ * value, as in 5h.
+ * Errors, all checked before any device is touched: a null bd, tol, bw_out, logl, iters or status, tol negative or not finite,
+ * maxiter < 0, npts < 2, a start entry not finite or <= 0, a manifold byte above 1 or a mask bit at or above D, batch items on
+ * different devices -- KDEHIP_ERR_ARG; D outside 1..KDEHIP_MAX_DIMS or per-point bandwidths (in kdehip_evaluate's words) --
+ * KDEHIP_ERR_UNSUPPORTED.  n == 0 is KDEHIP_OK; maxiter == 0 is KDEHIP_OK and returns the start with its logl.  fp64 only.
+ * Not here: per-point bandwidths, full covariance, applying the result to a resident density without leaving HBM, and an
+ * enqueue-only form on a caller's stream. */
+/* Host density, host results, blocking. */
+int kdehip_bandwidth_joint(const kdehip_density *bd, const double *start /* D sds, or NULL = bd's own bandwidth */,
+                           const double *tol, int maxiter, double *bw_out /* D sds */, double *logl, int32_t *iters,
+                           int32_t *status, double *trace /* [maxiter + 1] or NULL */, int device, const uint8_t *manifold);
+/* Resident density, HOST results (start is a host pointer too), blocking. */
+int kdehip_bandwidth_joint_device(const kdehip_device_density *bd, const double *start, const double *tol, int maxiter,
+                                  double *bw_out, double *logl, int32_t *iters, int32_t *status, double *trace,
+                                  const uint8_t *manifold);
+typedef struct kdehip_bwjoint_item {
+  const kdehip_device_density *bd;
+  const double *start;      /* HOST pointer, D standard deviations, or NULL = bd's own bandwidth */
+  double *bw_out;           /* host, [D] */
+  double *logl;             /* host, [1] */
+  int32_t *iters;           /* host, [1] */
+  int32_t *status;          /* host, [1] */
+  uint32_t circular_mask;   /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+  uint32_t reserved_;
+} kdehip_bwjoint_item;
+/* Many resident densities (mixed D and npts) on one device, host results, blocking: the serving shape.  The items share the
+ * three launches of a sweep, and every item's results are bit for bit those of kdehip_bandwidth_joint_device. */
+int kdehip_bandwidth_joint_device_batch(int n, const kdehip_bwjoint_item *items, const double *tol, int maxiter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ This package is the Python host mirror of the reference's interface for that pat
 `intersIntgAppxIS`, and the library's own exact overlap measures `intersIntg/ise/mmd` and joint modes
 `evaluate_grad/meanshift/modes/getKDEMode`, their curvature `evaluate_hess/laplace/fit_modes/getKDEModeFit`, conditionals
 `condition/conditional_weights/conditional_moments/sample_conditional` and probability masses
-`box_mass/cdf/quantile/median/interval/grid_mass`, the exact product of two densities `prod_exact/product_components/log_intersIntg/mul_exact`, nearest neighbours `knn/entropy_knn/kld_knn`, and per-point bandwidths `kde_varbw/adaptive_scales/kde_adaptive`)
+`box_mass/cdf/quantile/median/interval/grid_mass`, the exact product of two densities `prod_exact/product_components/log_intersIntg/mul_exact`, nearest neighbours `knn/entropy_knn/kld_knn`, per-point bandwidths `kde_varbw/adaptive_scales/kde_adaptive`, and the joint bandwidth `joint_bandwidth/kde_joint`)
 over the C ABI of libkdehip.so (include/kdehip.h).  The directory name contains a dot, so import it
 through the top-level `kdehip` module of this repository.
 """
@@ -30,6 +30,7 @@ from .mass import (box_mass, box_mass_device_batch, cdf, grid_mass, interval, me
 from .evaltol import evaluate_tol, getForceEvalDirect, setForceEvalDirect  # noqa: F401
 from .knn import entropy_knn, kld_knn, knn  # noqa: F401
 from .varbw import adaptive_scales, kde_adaptive, kde_varbw  # noqa: F401
+from .bwjoint import joint_bandwidth, joint_bandwidth_device_batch, kde_joint  # noqa: F401
 from .summary import (getKDEfit, getKDEMax, getKDEMean, getKDERange, getKDERangeLinspace, intersIntgAppxIS,  # noqa: F401
                       marginal, summary_device_batch)
 

@@ -109,6 +109,12 @@ class CProdExactItem(C.Structure):
                 ("d_pts", C.c_void_p), ("d_ind", C.c_void_p), ("d_logz", C.c_void_p)]
 
 
+class CBwJointItem(C.Structure):
+    """struct kdehip_bwjoint_item (`start` and the four results are HOST pointers)"""
+    _fields_ = [("bd", C.c_void_p), ("start", f64p), ("bw_out", f64p), ("logl", f64p), ("iters", i32p), ("status", i32p),
+                ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -327,6 +333,10 @@ SIGNATURES = {
     "kdehip_prod_exact_device_batch": (C.c_int, [C.c_int, C.POINTER(CProdExactItem), C.c_void_p]),
     "kdehip_product_components": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), f64p, f64p, f64p, C.c_int]),
     "kdehip_product_components_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # joint bandwidth selection (include/kdehip.h section 5q): blocking, host results
+    "kdehip_bandwidth_joint": (C.c_int, [C.POINTER(CDensity), f64p, f64p, C.c_int, f64p, f64p, i32p, i32p, f64p, C.c_int, u8p]),
+    "kdehip_bandwidth_joint_device": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, f64p, f64p, i32p, i32p, f64p, u8p]),
+    "kdehip_bandwidth_joint_device_batch": (C.c_int, [C.c_int, C.POINTER(CBwJointItem), f64p, C.c_int]),
     "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
                                          u8p]),
     "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,

@@ -1015,6 +1015,55 @@ function hip_fit_modes(bd::BallTreeDensity, starts::Union{Nothing,AbstractMatrix
 end
 
 """
+    hip_joint_bandwidth(bd, start=nothing; tol=1e-3, maxiter=200, manifold=nothing, device=0)
+
+`(bw, logl, iters, status, trace)` (`kdehip_bandwidth_joint`, include/kdehip.h section 5q): the `D` standard deviations the
+joint leave-one-out iteration `v_k <- sum_i w_i T_ik / S0_i / sum_i w_i` reaches from `start` (`D` standard deviations;
+`nothing`: the density's own bandwidth) once a step changes no log standard deviation by more than `tol`, or after `maxiter`
+steps.  `logl` = the leave-one-out average log-likelihood at `bw`; `iters` = the steps taken, negative where the last was still
+above `tol`; `status` = 1 when degenerate data froze the iteration; `trace` = the log-likelihood of every iterate, the start
+included.  `kde!(points)` searches every 1-D marginal on its own; this is the library's own: not installed by `enable!()`.
+"""
+function hip_joint_bandwidth(bd::BallTreeDensity, start::Union{Nothing,AbstractVector{Float64}}=nothing; tol::Float64=1e-3,
+                             maxiter::Int=200, manifold=nothing, device::Int=0)
+  D = Ndim(bd)
+  start === nothing || length(start) == D || error("start needs one standard deviation per dimension")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  bw = zeros(D)
+  logl = Float64[0.0]
+  iters = Int32[0]
+  status = Int32[0]
+  trace = fill(NaN, maxiter + 1)
+  cd = Ref(CDensity(bd))
+  sd = start === nothing ? zeros(0) : Vector{Float64}(start)
+  tolv = Float64[tol]
+  GC.@preserve bd sd tolv man begin
+    check(ccall((:kdehip_bandwidth_joint, libkdehip), Cint,
+                (Ref{CDensity}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64},
+                 Cint, Ptr{UInt8}),
+                cd, start === nothing ? Ptr{Float64}(C_NULL) : pointer(sd), tolv, maxiter, bw, logl, iters, status, trace, device,
+                man))
+  end
+  return bw, logl[1], Int(iters[1]), Int(status[1]), trace[1:abs(Int(iters[1])) + 1]
+end
+
+"""
+    hip_kde_joint(points[, weights]; start=nothing, tol=1e-3, maxiter=200, manifold=nothing, tree_manifold=nothing, device=0)
+
+`kde!(points, bw, weights)` with the joint bandwidth of `hip_joint_bandwidth`.  `start=nothing` starts the iteration from the
+bandwidth `kde!(points)` selects, so the result is never worse than `kde!(points)` in leave-one-out likelihood.
+"""
+function hip_kde_joint(points::AbstractMatrix{Float64}, weights::Union{Nothing,Vector{Float64}}=nothing;
+                       start::Union{Nothing,AbstractVector{Float64}}=nothing, tol::Float64=1e-3, maxiter::Int=200,
+                       manifold=nothing, tree_manifold=nothing, device::Int=0)
+  s = start !== nothing ? Vector{Float64}(start) :
+      manifold === nothing ? auto_bandwidth(points; device=device) : hip_auto_bandwidth(points, manifold; device=device)
+  p0 = kde!(points, s, weights; tree_manifold=tree_manifold)
+  bw, _, _, _, _ = hip_joint_bandwidth(p0; tol=tol, maxiter=maxiter, manifold=manifold, device=device)
+  return kde!(points, bw, weights; tree_manifold=tree_manifold)
+end
+
+"""
     hip_box_mass(bd, lo, hi; dims=nothing, manifold=nothing, device=0)
 
 The probability that `x[dims]` lies in the box `[lo[:, q], hi[:, q]]` under `bd`, one value per column

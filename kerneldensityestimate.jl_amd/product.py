@@ -405,6 +405,12 @@ class DeviceDensity:
         from .modes import evaluate_grad
         return evaluate_grad(self, pos, log=log, manifold=manifold)
 
+    def joint_bandwidth(self, start=None, tol=1e-3, maxiter=200, manifold=None, return_info=False):
+        """The (D,) standard deviations of the joint leave-one-out iteration from `start` (kdehip_bandwidth_joint_device,
+        include/kdehip.h section 5q): `kdehip.joint_bandwidth` of this density."""
+        from .bwjoint import joint_bandwidth
+        return joint_bandwidth(self, start, tol, maxiter, manifold, return_info)
+
     def evaluate_hess(self, pos, *, log=True, manifold=None):
         """(log p, its gradient, its Hessian) at the columns of `pos` (kdehip_evaluate_hess_device, include/kdehip.h section
         5k): `kdehip.evaluate_hess` of this density."""
