@@ -98,6 +98,25 @@ def grid_chunks_per_group(N, Ngrid, cus=None):
     return chunks_per_group(N, Ngrid, cus, chunk=256, threads=256, max_groups=256)
 
 
+def loocv_chunks_per_group(D, N, cus=None, nb=1, chunk=128, threads=256, max_groups=64):
+    """the bandwidth search's own split (csrc/loocv.hip LoocvSearch::begin, two-launch rounds): every one of the nm = nb * D
+    marginals walks ceil(N / 128) chunks for ceil(N / 256) query blocks; want = ceil(8 CUs / (qblocks * nm)) groups, clamped to
+    [1, 64] and to the chunk count"""
+    cus = device_cus() if cus is None else cus
+    nchunks = _ceil_div(N, chunk)
+    qblocks = _ceil_div(N, threads)
+    want = max(1, min(_ceil_div(8 * cus, qblocks * nb * D), max_groups, nchunks))
+    return _ceil_div(nchunks, want)
+
+
+def density_arrays(p):
+    """(points (D, N), weights (N,), leaf variances (D,)) of a host density with one bandwidth vector, in original point order:
+    the form the models of tests/*_model.py take a density in"""
+    import kdehip
+    N, D = p.bt.num_points, p.bt.dims
+    return kdehip.getPoints(p), kdehip.getWeights(p), p.bandwidth[N * D:(N + 1) * D].copy()
+
+
 def assert_chunks_per_group(N, Nq, want, grid=False):
     """the premise of a large-N case: on this device a group of the sweep walks `want` chunks"""
     cus = device_cus()

@@ -158,7 +158,7 @@ import json, sys, numpy as np, kdehip
 from tests.helpers import synth_mixture
 out = {}
 for D, N in [(1, 65), (1, 128), (2, 129), (1, 191), (3, 192), (1, 257), (2, 320), (6, 500), (1, 1000), (6, 1000), (2, 1999),
-             (6, 2048), (1, 2049), (3, 3000), (1, 4032), (2, 4096)]:
+             (6, 2048), (1, 2049), (3, 3000), (1, 4032), (2, 4096), (8, 4096), (8, 4000)]:
     rng = np.random.default_rng(1000 * D + N)
     bw, ne = kdehip.auto_bandwidth(synth_mixture(rng, D, N), return_evals=True)
     out[f"{D}x{N}"] = ([float(x) for x in bw], int(ne))
@@ -175,7 +175,16 @@ def test_fused_loocv_rounds_equal_the_two_launch_rounds():
     import os
     import subprocess
     import sys
+    from tests.helpers import device_cus, loocv_chunks_per_group
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # (8, 4096) and (8, 4000) are here for the two-launch form's own sweep (loo_round_partial_kernel): 32 chunks, 16 query
+    # blocks and 8 marginals leave 16 groups of TWO chunks, so a group stages its second buffer and adds a second `sum` to
+    # `total`; 4000 ends the second chunk of the last group 96 points short.  The fused rounds they are compared with are held
+    # to the oracle by test_loocv_bandwidth_parity_with_oracle.
+    for D, N in ((8, 4096), (8, 4000)):
+        got = loocv_chunks_per_group(D, N)
+        assert got == 2, (f"with {device_cus()} compute units the two-launch rounds of ({D}, {N}) walk {got} chunk(s) a group, "
+                          "not the 2 these shapes are here for: they would cover nothing")
     res = []
     # the library's choice (speculative rounds -- three evaluations per launch, csrc/loocv.hip loo_round_spec_kernel -- for
     # the smaller marginals, plain one-launch rounds for the larger), plain one-launch rounds everywhere, two-launch rounds
