@@ -525,7 +525,7 @@ int kdehip_product_multi_timing(kdehip_product_multi *mp, double *kernel_ms, dou
  * resets both (process-wide sums).  bench.py --frow reports them as kernel time.  kdehip_evaluate_tol (section 5m) adds, in
  * the same way, its three passes one by one: which = 3 the chunk boxes, 4 the plan, 5 the sweep over the flagged chunks
  * (which = 1 is then the whole call: the three passes and the finish kernel).  kdehip_knn (section 5n) likewise: which = 6 the
- * chunk boxes, 7 the plan, 8 the sweep. */
+ * chunk boxes, 7 the plan, 8 the sweep.  A refit (section 5r): which = 9, its passes from the copy to the examination. */
 int kdehip_profile_phase_read(int which, double *total_ms, int64_t *count);
 /* The fp32 screen of the deep levels (csrc/screen_device.hpp) certifies its decisions with an error bound whose premise is
  * that the hardware's v_rcp_f32, v_rsq_f32 and v_exp_f32 are within 1 ulp (a relative error of at most 2 u, u = 2^-24).
@@ -1639,6 +1639,99 @@ typedef struct kdehip_bwjoint_item {
 /* Many resident densities (mixed D and npts) on one device, host results, blocking: the serving shape.  The items share the
  * three launches of a sweep, and every item's results are bit for bit those of kdehip_bandwidth_joint_device. */
 int kdehip_bandwidth_joint_device_batch(int n, const kdehip_bwjoint_item *items, const double *tol, int maxiter);
+
+/* ---- (5r) reweighting and moving a density without re-forming its tree ------------------------------------------------------
+ * changeWeights!(bd, newWeights) and movePoints!(bd, delta) (reference src/BallTreeDensity01.jl:278-309): every leaf takes a
+ * new weight, or moves by an offset of its own, and the statistics of the internal nodes are recomputed from their children,
+ * bottom-up ("just fix up the statistics"); the tree itself -- child arrays, leaf ranges, permutation -- stays.  The topology
+ * of the reference's builder does not read the weights (most_spread_coord, src/BallTree01.jl:148), so a reweighted density IS
+ * the density kde!(getPoints(bd), bw, newWeights) would build for weights that kde! does not rescale; after a move the result
+ * is a VALID BUT LOOSER tree than a rebuild's, as in the reference: every node still bounds and summarises its leaves, so the
+ * sampler, evaluation within a tolerance (5m) and the neighbour search (5n) stay correct and prune less after large moves.
+ *
+ * The formula of one internal node from its children a and b -- calcStatsBall! (src/BallTree01.jl:282-336) and
+ * calcStatsDensity! (src/BallTreeDensity01.jl:141-187), as kdehip_make_density computes them, no fused multiply-add anywhere:
+ *   top = max(c_a + r_a, c_b + r_b), bottom = min(c_a - r_a, c_b - r_b), r = (top - bottom) / 2, c = bottom + r
+ *     (every + and - of this line through wrap() in a dimension tree_manifold marks circular)
+ *   w = w_a + w_b;  wt = w_a + w_b + eps;  u_a = w_a / wt, u_b = w_b / wt
+ *   m = u_a m_a + u_b m_b;  v = u_a (v_a + m_a^2) + u_b (v_b + m_b^2) - m^2
+ *   per-point bandwidths: bandwidthMax = max of the children's, bandwidthMin = min
+ *
+ * Host entry (CPU only, no device is touched).  The twelve input arrays are those kdehip_make_density (or _varbw) shapes, the
+ * twelve outputs have the same sizes and may not alias the inputs.
+ *   new_weights  npts doubles indexed by ORIGINAL point (leaf i takes new_weights[permutation - 1]), used AS GIVEN: the
+ *                reference does not normalise here.  NULL keeps the weights.
+ *   delta        ndims x npts column-major, indexed by ORIGINAL point, added to the leaf's centre and mean -- wrap(x + delta)
+ *                in a dimension tree_manifold marks circular (addop).  NULL moves nothing.
+ *   tree_manifold  ndims bytes or NULL (section 4).
+ *   varbw        0: one bandwidth vector; bandwidthMin / bandwidthMax (npts x ndims) are copied.  Nonzero: the arrays of
+ *                kdehip_make_density_varbw; bandwidthMin / bandwidthMax (2 npts x ndims) are recomputed for the internal nodes.
+ * Refusals, all before anything is written: a null array or both new_weights and delta NULL -- KDEHIP_ERR_ARG ("null"); a
+ * weight that is negative or not finite -- KDEHIP_ERR_ARG ("new_weights"); a delta that is not finite -- KDEHIP_ERR_ARG
+ * ("delta"); a tree_manifold byte above 1 -- KDEHIP_ERR_ARG; npts < 1 -- KDEHIP_ERR_ARG; ndims outside 1..KDEHIP_MAX_DIMS --
+ * KDEHIP_ERR_UNSUPPORTED ("ndims"); child arrays that are no tree -- KDEHIP_ERR_ARG. */
+int kdehip_density_refit(int64_t ndims, int64_t npts, const double *centers, const double *ranges, const double *weights,
+                         const int64_t *left_child, const int64_t *right_child, const int64_t *lowest_leaf,
+                         const int64_t *highest_leaf, const int64_t *permutation, const double *means, const double *bandwidth,
+                         const double *bandwidthMin, const double *bandwidthMax, int varbw, const double *new_weights,
+                         const double *delta, const uint8_t *tree_manifold, double *centers_out, double *ranges_out,
+                         double *weights_out, int64_t *left_child_out, int64_t *right_child_out, int64_t *lowest_leaf_out,
+                         int64_t *highest_leaf_out, int64_t *permutation_out, double *means_out, double *bandwidth_out,
+                         double *bandwidthMin_out, double *bandwidthMax_out);
+
+/* Resident entries (csrc/refit.hip).  The result is a NEW handle on p's device; p is not written and stays usable.  Both
+ * entries are BLOCKING, like every entry that makes a density, and take no stream: they run on the calling thread's own
+ * stream and wait for it, and the caller's device arrays must be complete when the call is made.
+ *   kind  KDEHIP_REFIT_KEEP     d_values is NULL; only d_delta is applied (d_delta NULL is then KDEHIP_ERR_ARG).
+ *         KDEHIP_REFIT_WEIGHTS  d_values = npts weights, used as given (a negative or non-finite one: KDEHIP_ERR_ARG).
+ *         KDEHIP_REFIT_LOGL     d_values = npts log-likelihoods l_i: the Bayes update of the weights,
+ *                                 m = max l_i over the leaves with w_i > 0,  S = sum_i w_i exp(l_i - m),
+ *                                 w_i' = (w_i exp(l_i - m)) / S   (a leaf with w_i = 0 keeps 0),
+ *                                 log_evidence = m + log S,  ess = 1 / sum_i w_i'^2.
+ *                               Both sums run over the 128-leaf chunks in LEAF order -- inside a chunk the fixed pairwise
+ *                               tree over its 128 terms (strides 64, 32, .., 1), then the chunks in chunk order -- with no
+ *                               atomics: a batch, a single call and every repeat give the same bits.  exp is the device
+ *                               library's.  S that is 0 or not finite, an l_i that is NaN or +Inf, or no leaf of positive
+ *                               weight: KDEHIP_ERR_ARG and *out = NULL, as kdehip_density_condition_device treats logz = -Inf.
+ *   leaf_order  0: d_values and d_delta are indexed by ORIGINAL point (the reference's convention, and the order in which
+ *               kdehip_evaluate_log_device_at(likelihood, p) returns its values); 1: by leaf position -- the order of
+ *               kdehip_evaluate_log_device when its queries are the density's own leaf rows.
+ *   d_delta     ndims x npts column-major device array or NULL; must be finite (else KDEHIP_ERR_ARG, *out = NULL).
+ *   tree_manifold  ndims bytes or NULL: the operators of the box formula and of the move.
+ *   log_evidence, ess  optional HOST doubles, written for KDEHIP_REFIT_LOGL only.
+ * The internal nodes are recomputed by the formula above, one node per lane, height by height (a height = one launch while it
+ * is wide, the top of the tree in one workgroup): bit for bit what kdehip_density_refit gives on the same arrays.  The child
+ * pairs and the height lists are derived from the child arrays once per handle and kept on it (an uploaded density keeps a
+ * copy of its child arrays for that).  What the sampler's packers know about a density's values -- one shared bandwidth per
+ * level, the range of the variances, finiteness -- is recomputed for the new values and equals what kdehip_density_upload of
+ * the same arrays finds.  If p was built by the library, the result keeps the twelve arrays for kdehip_density_download:
+ * centres, ranges, means, variances and weights are fetched AT THE REFIT, in the call's one readback; a result of an uploaded
+ * p has no such arrays, as p has none.  Per-point bandwidths are supported (bandwidthMin / bandwidthMax of a built source are
+ * its leaves' one vector and are copied).
+ * Refusals before any device work: null out or p, an unknown kind, d_values NULL (non-NULL) where kind needs (forbids) it,
+ * nothing to do, a tree_manifold byte above 1 -- KDEHIP_ERR_ARG; batch items on different devices -- KDEHIP_ERR_ARG.
+ * Not here: an enqueue-only (graph-capturable) refit, a refit in place, re-forming the tree after large moves. */
+#define KDEHIP_REFIT_KEEP 0
+#define KDEHIP_REFIT_WEIGHTS 1
+#define KDEHIP_REFIT_LOGL 2
+int kdehip_density_refit_device(kdehip_device_density **out, const kdehip_device_density *p, const double *d_values, int kind,
+                                int leaf_order, const double *d_delta, const uint8_t *tree_manifold, double *log_evidence,
+                                double *ess);
+typedef struct kdehip_refit_item {
+  const kdehip_device_density *p;
+  const double *d_values;       /* device, [npts], or NULL (KDEHIP_REFIT_KEEP) */
+  const double *d_delta;        /* device, [ndims x npts], or NULL */
+  double *log_evidence;         /* host, [1], or NULL */
+  double *ess;                  /* host, [1], or NULL */
+  int32_t kind;
+  int32_t leaf_order;
+  uint32_t circular_mask;       /* bit d = dimension d circular in the tree's operators; a bit at or above ndims is KDEHIP_ERR_ARG */
+  uint32_t reserved_;
+} kdehip_refit_item;
+/* Many densities (mixed in npts, ndims, kind and order) on one device: the items share their launches (the count does not
+ * depend on n while the heights are narrow) and ONE readback; every result is bit for bit the single call's.  One bad item
+ * fails the whole call: every out[i] is NULL and no handle is created. */
+int kdehip_density_refit_device_batch(int n, const kdehip_refit_item *items, kdehip_device_density **out);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,12 @@ class CBwJointItem(C.Structure):
                 ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class CRefitItem(C.Structure):
+    """struct kdehip_refit_item (`log_evidence` and `ess` are HOST pointers)"""
+    _fields_ = [("p", C.c_void_p), ("d_values", C.c_void_p), ("d_delta", C.c_void_p), ("log_evidence", f64p), ("ess", f64p),
+                ("kind", C.c_int32), ("leaf_order", C.c_int32), ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class CSummaryItem(C.Structure):
     """struct kdehip_summary_item"""
     _fields_ = [("density", C.c_void_p), ("extend", C.c_double), ("Ngrid", C.c_int64), ("d_range", C.c_void_p),
@@ -337,6 +343,13 @@ SIGNATURES = {
     "kdehip_bandwidth_joint": (C.c_int, [C.POINTER(CDensity), f64p, f64p, C.c_int, f64p, f64p, i32p, i32p, f64p, C.c_int, u8p]),
     "kdehip_bandwidth_joint_device": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, f64p, f64p, i32p, i32p, f64p, u8p]),
     "kdehip_bandwidth_joint_device_batch": (C.c_int, [C.c_int, C.POINTER(CBwJointItem), f64p, C.c_int]),
+    # reweighting and moving a density without re-forming its tree (include/kdehip.h section 5r): blocking, no stream
+    "kdehip_density_refit": (C.c_int, [C.c_int64, C.c_int64, f64p, f64p, f64p, i64p, i64p, i64p, i64p, i64p, f64p, f64p, f64p,
+                                       f64p, C.c_int, f64p, f64p, u8p, f64p, f64p, f64p, i64p, i64p, i64p, i64p, i64p, f64p,
+                                       f64p, f64p, f64p]),
+    "kdehip_density_refit_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, u8p,
+                                              f64p, f64p]),
+    "kdehip_density_refit_device_batch": (C.c_int, [C.c_int, C.POINTER(CRefitItem), C.POINTER(C.c_void_p)]),
     "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
                                          u8p]),
     "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,

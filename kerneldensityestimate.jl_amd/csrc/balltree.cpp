@@ -77,6 +77,17 @@ class DensityBuilder {
     run();
   }
 
+  // kdehip_density_refit: the arrays hold a finished density whose leaves have new values; every internal node of `order`
+  // again, read back to front (children first).  bwmin / bwmax [2N][D]: per-point bandwidths (the !bwUniform branch), or null.
+  void refit(const std::vector<int64_t> &order, double *bwmin, double *bwmax) {
+    if (bwmin && bwmax) {
+      point_var_ = bw_;  // (summarize reads it as the branch's flag only)
+      bwmin_ = bwmin;
+      bwmax_ = bwmax;
+    }
+    for (size_t t = order.size(); t-- > 0;) summarize(order[t]);
+  }
+
  private:
   void run() {
     Scratch s(D_);
@@ -454,6 +465,77 @@ extern "C" int kdehip_density_set_bandwidth(int64_t D, int64_t N, const double *
                                             double *bandwidth, double *bandwidthMin, double *bandwidthMax) {
   return kdehip::set_bandwidth_examined(D, N, ks, nks, weights, left_child, right_child, means, bandwidth, bandwidthMin,
                                         bandwidthMax, nullptr, nullptr);
+}
+
+// changeWeights! / movePoints! (src/BallTreeDensity01.jl:278-309; include/kdehip.h section 5r): new leaf values through the
+// permutation, then calcStatsBall! / calcStatsDensity! of every internal node, children first -- the tree is not re-formed.
+extern "C" int kdehip_density_refit(int64_t D, int64_t N, const double *centers, const double *ranges, const double *weights,
+                                    const int64_t *left_child, const int64_t *right_child, const int64_t *lowest_leaf,
+                                    const int64_t *highest_leaf, const int64_t *permutation, const double *means,
+                                    const double *bandwidth, const double *bandwidthMin, const double *bandwidthMax, int varbw,
+                                    const double *new_weights, const double *delta, const uint8_t *tree_manifold,
+                                    double *centers_out, double *ranges_out, double *weights_out, int64_t *left_child_out,
+                                    int64_t *right_child_out, int64_t *lowest_leaf_out, int64_t *highest_leaf_out,
+                                    int64_t *permutation_out, double *means_out, double *bandwidth_out,
+                                    double *bandwidthMin_out, double *bandwidthMax_out) {
+  using namespace kdehip;
+  if (!centers || !ranges || !weights || !left_child || !right_child || !lowest_leaf || !highest_leaf || !permutation || !means ||
+      !bandwidth || !bandwidthMin || !bandwidthMax || !centers_out || !ranges_out || !weights_out || !left_child_out ||
+      !right_child_out || !lowest_leaf_out || !highest_leaf_out || !permutation_out || !means_out || !bandwidth_out ||
+      !bandwidthMin_out || !bandwidthMax_out)
+    return set_error(KDEHIP_ERR_ARG, "kdehip_density_refit: null array");
+  if (!new_weights && !delta)
+    return set_error(KDEHIP_ERR_ARG, "kdehip_density_refit: new_weights and delta are both null: nothing to do");
+  if (D < 1 || D > KDEHIP_MAX_DIMS) return set_error(KDEHIP_ERR_UNSUPPORTED, "kdehip_density_refit: ndims outside 1..KDEHIP_MAX_DIMS");
+  if (N < 1) return set_error(KDEHIP_ERR_ARG, "kdehip_density_refit: need npts >= 1");
+  uint32_t circ = 0;
+  if (manifold_arg(tree_manifold, D, &circ, kHostTreeManifold) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+  for (int64_t i = 0; new_weights && i < N; ++i)
+    if (!(new_weights[i] >= 0.0 && new_weights[i] < INFINITY))
+      return set_error(KDEHIP_ERR_ARG, "kdehip_density_refit: new_weights must be finite and not negative");
+  for (int64_t i = 0; delta && i < N * D; ++i)
+    if (!(std::fabs(delta[i]) < INFINITY)) return set_error(KDEHIP_ERR_ARG, "kdehip_density_refit: delta must be finite");
+  for (int64_t i = N; i < 2 * N; ++i)
+    if (permutation[i] < 1 || permutation[i] > N)
+      return set_error(KDEHIP_ERR_ARG, "kdehip_density_refit: permutation outside 1..npts");
+  std::vector<int64_t> order;
+  try {
+    if (N == 1) order.push_back(1);
+    else if (children_first_order(N, left_child, right_child, order) != KDEHIP_OK) return KDEHIP_ERR_ARG;
+
+    const size_t nd = static_cast<size_t>(2 * N * D), n2 = static_cast<size_t>(2 * N), nb = varbw ? nd : nd / 2;
+    std::memcpy(centers_out, centers, nd * sizeof(double));
+    std::memcpy(ranges_out, ranges, nd * sizeof(double));
+    std::memcpy(means_out, means, nd * sizeof(double));
+    std::memcpy(bandwidth_out, bandwidth, nd * sizeof(double));
+    std::memcpy(bandwidthMin_out, bandwidthMin, nb * sizeof(double));
+    std::memcpy(bandwidthMax_out, bandwidthMax, nb * sizeof(double));
+    std::memcpy(weights_out, weights, n2 * sizeof(double));
+    std::memcpy(left_child_out, left_child, n2 * sizeof(int64_t));
+    std::memcpy(right_child_out, right_child, n2 * sizeof(int64_t));
+    std::memcpy(lowest_leaf_out, lowest_leaf, n2 * sizeof(int64_t));
+    std::memcpy(highest_leaf_out, highest_leaf, n2 * sizeof(int64_t));
+    std::memcpy(permutation_out, permutation, n2 * sizeof(int64_t));
+    for (int64_t id = N + 1; id <= 2 * N; ++id) {
+      const int64_t src = permutation[id - 1] - 1;
+      if (new_weights) weights_out[id - 1] = new_weights[src];
+      for (int64_t k = 0; delta && k < D; ++k) {
+        const double c = centers[(id - 1) * D + k] + delta[src * D + k], m = means[(id - 1) * D + k] + delta[src * D + k];
+        const bool wrap = (circ >> k) & 1u;  // addop
+        centers_out[(id - 1) * D + k] = wrap ? circ_wrap(c) : c;
+        means_out[(id - 1) * D + k] = wrap ? circ_wrap(m) : m;
+      }
+    }
+    // (a single-point density's root summarises its leaf with itself, and points at NO_CHILD afterwards: BallTree01.jl:351-362)
+    if (N == 1) right_child_out[0] = left_child_out[0];
+    DensityBuilder(D, N, nullptr, centers_out, ranges_out, weights_out, left_child_out, right_child_out, lowest_leaf_out,
+                   highest_leaf_out, permutation_out, means_out, bandwidth_out, tree_manifold)
+        .refit(order, varbw ? bandwidthMin_out : nullptr, varbw ? bandwidthMax_out : nullptr);
+    if (N == 1) right_child_out[0] = right_child[0];
+  } catch (const std::exception &e) {
+    return set_error(KDEHIP_ERR_ALLOC, std::string("kdehip_density_refit: ") + e.what());
+  }
+  return KDEHIP_OK;
 }
 
 // internal nodes 1 .. N-1 in pre-order from the root (read back to front: every node after its descendants)

@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -81,6 +82,19 @@ struct SharedBlock {
   void *mirror = nullptr;
   size_t mirror_bytes = 0;
 };
+
+// What a refit (include/kdehip.h section 5r, refit.hip) needs of a density's topology, made from the child arrays by the
+// first refit of a handle and shared by that density and every refit of it: ONE device block
+// [node ids | left child | right child] (int32 each) of the internal nodes, sorted by height -- a node of height h has
+// its children at heights below h, the leaves at height 0.
+struct RefitTable {
+  int device = 0;
+  void *d_tab = nullptr;
+  size_t bytes = 0;
+  int64_t nI = 0;             // internal nodes (N - 1; 1 for a single-point density)
+  std::vector<int64_t> hoff;  // height h = 1 .. H: the nodes [hoff[h - 1], hoff[h])
+  ~RefitTable();              // (refit.hip: the block goes back to the cache)
+};
 }  // namespace kdehip
 
 // A BallTreeDensity resident on one device (include/kdehip.h "densities in HBM").
@@ -119,6 +133,11 @@ struct kdehip_device_density {
   int cdf_rc = 0;         // KDEHIP_OK, or KDEHIP_ERR_ARG for weights / a permutation the table cannot be built from
   void *d_cdf = nullptr;
   size_t cdf_bytes = 0;
+  // Refits (section 5r): a density the caller uploaded keeps its child arrays (slots 1..N as int32: [left | right]) -- a
+  // built one has them in its mirror --, and the table made from them by the first refit.
+  std::vector<int32_t> kids;
+  mutable std::mutex refit_mu;
+  mutable std::shared_ptr<kdehip::RefitTable> refit;
 };
 
 namespace kdehip {

@@ -261,7 +261,7 @@ void profile_phase_add(int which, double ms) {
 
 extern "C" int kdehip_profile_phase_read(int which, double *total_ms, int64_t *count) {
   using namespace kdehip;
-  if (which < 0 || which >= kPhaseCount) return set_error(KDEHIP_ERR_ARG, "kdehip_profile_phase_read: which in 0..8");
+  if (which < 0 || which >= kPhaseCount) return set_error(KDEHIP_ERR_ARG, "kdehip_profile_phase_read: which in 0..9");
   std::lock_guard<std::mutex> lock(g_phase_mu);
   if (total_ms) *total_ms = g_phase_ms[which];
   if (count) *count = g_phase_n[which];

@@ -262,6 +262,18 @@ int upload_common(kdehip_device_density *h, const kdehip_density &host, hipStrea
     return set_error(KDEHIP_ERR_HIP, std::string("density upload: ") + hipGetErrorString(e != hipSuccess ? e : se));
   }
   bind_block(h, bl);
+  if (!h->built) {  // (a refit needs the child arrays, and the caller's go away: section 5r)
+    try {
+      h->kids.resize(static_cast<size_t>(2 * N));
+      for (int64_t i = 0; i < N; ++i) {
+        const int64_t a = host.left_child[i], b = host.right_child[i];
+        h->kids[static_cast<size_t>(i)] = (a >= 1 && a <= 2 * N) ? static_cast<int32_t>(a) : 0;
+        h->kids[static_cast<size_t>(N + i)] = (b >= 1 && b <= 2 * N) ? static_cast<int32_t>(b) : 0;
+      }
+    } catch (const std::exception &) {
+      std::vector<int32_t>().swap(h->kids);  // (no refit of this handle; everything else works)
+    }
+  }
   return KDEHIP_OK;
 }
 

@@ -9,9 +9,9 @@
 namespace kdehip {
 
 // (3..5: the three passes of kdehip_evaluate_tol, each between two events of its own -- evaltol.hip; 6..8: those of
-// kdehip_knn -- knn.hip)
+// kdehip_knn -- knn.hip; 9: the passes of a refit, copy to examination -- refit.hip)
 enum ProfilePhase : int { kPhaseLoocv = 0, kPhaseEvaluate = 1, kPhaseTreeBuild = 2, kPhaseTolBox = 3, kPhaseTolPlan = 4,
-                          kPhaseTolSweep = 5, kPhaseKnnBox = 6, kPhaseKnnPlan = 7, kPhaseKnnSweep = 8, kPhaseCount = 9 };
+                          kPhaseTolSweep = 5, kPhaseKnnBox = 6, kPhaseKnnPlan = 7, kPhaseKnnSweep = 8, kPhaseRefit = 9, kPhaseCount = 10 };
 bool profile_phases_on();                        // devmem.cpp (set by kdehip_profile_sampler)
 void profile_phases_set(bool on);
 void profile_phase_add(int which, double ms);

@@ -54,6 +54,24 @@ class BallTreeDensity:
         from .product import mul
         return mul([self, other])
 
+    # `changeWeights!` / `movePoints!` (reference src/BallTreeDensity01.jl:278-309) as NEW densities: the tree stays, the
+    # statistics of the internal nodes are recomputed (kdehip_density_refit, include/kdehip.h section 5r)
+    def changeWeights(self, w):
+        """new weights (N, original point order, used as given: not normalised), the same tree"""
+        from .refit import refit_host
+        return refit_host(self, new_weights=w)
+
+    def movePoints(self, delta, tree_manifold="inherit"):
+        """every point moved by its column of delta ((D, N), original order), the same -- now looser -- tree; a circular
+        dimension of tree_manifold (default: the operators the tree was built with) wraps the sum"""
+        from .refit import refit_host
+        return refit_host(self, delta=delta, tree_manifold="inherit" if tree_manifold is None else tree_manifold)
+
+    def bayes_update(self, logl):
+        """`w_i <- w_i exp(logl_i)`, normalised: (density, log_evidence, ess)"""
+        from .refit import host_bayes_update
+        return host_bayes_update(self, logl)
+
 
 def _prepare(points, ks, weights):
     pts = np.asarray(points, dtype=np.float64)

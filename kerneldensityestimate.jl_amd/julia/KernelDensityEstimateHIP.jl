@@ -1240,6 +1240,37 @@ function hip_resample(d::DeviceDensity, manifold::AbstractVector, Np::Int=-1; se
   return DeviceDensity(h[])
 end
 
+# changeWeights! / movePoints! and the Bayes update of a resident density as NEW handles (include/kdehip.h section 5r): the
+# tree stays, the node statistics are recomputed on the device.  d_values / d_delta are DEVICE pointers (npts doubles by
+# original point, or by leaf position with leaf_order=true; ndims x npts column-major); the calls block.
+function hip_refit(d::DeviceDensity, d_values::Ptr{Float64}, kind::Int, d_delta::Ptr{Float64}, leaf_order::Bool, tree_manifold)
+  tman = tree_manifold === nothing ? UInt8[] : manifold_bytes(tree_manifold, d.ndim)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  res = zeros(Float64, 2)  # log evidence, effective sample size
+  GC.@preserve tman res begin
+    check(ccall((:kdehip_density_refit_device, libkdehip), Cint,
+                (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}),
+                h, d.handle, d_values, kind, leaf_order ? 1 : 0, d_delta, isempty(tman) ? C_NULL : pointer(tman),
+                pointer(res), pointer(res) + 8))
+  end
+  return DeviceDensity(h[]), res[1], res[2]
+end
+
+"`changeWeights!(bd, newWeights)` (reference src/BallTreeDensity01.jl:298-309) of a resident density, as a new handle."
+function hip_changeWeights(d::DeviceDensity, d_weights::Ptr{Float64}; leaf_order::Bool=false, tree_manifold=nothing)
+  return hip_refit(d, d_weights, 1, Ptr{Float64}(C_NULL), leaf_order, tree_manifold)[1]
+end
+
+"`movePoints!(bd, delta)` (reference src/BallTreeDensity01.jl:281-296) of a resident density, as a new handle."
+function hip_movePoints(d::DeviceDensity, d_delta::Ptr{Float64}; leaf_order::Bool=false, tree_manifold=nothing)
+  return hip_refit(d, Ptr{Float64}(C_NULL), 0, d_delta, leaf_order, tree_manifold)[1]
+end
+
+"`w_i <- w_i exp(l_i)`, normalised, on a resident density: (new handle, log evidence, effective sample size)."
+function hip_bayes_update(d::DeviceDensity, d_logl::Ptr{Float64}; leaf_order::Bool=false, tree_manifold=nothing)
+  return hip_refit(d, d_logl, 2, Ptr{Float64}(C_NULL), leaf_order, tree_manifold)
+end
+
 "`marginal(p, dims)` of a resident density, its tree built with `tree_manifold[dims]` (`kdehip_density_marginal_device_tree`)."
 function hip_marginal(d::DeviceDensity, dims::Vector{Int}, tree_manifold::AbstractVector)
   tman = manifold_bytes(tree_manifold, d.ndim)[dims]

@@ -485,6 +485,32 @@ class DeviceDensity:
                                                             ptr(bw, f64p), C.byref(ne), _mf.pointer(man), _mf.pointer(tman)))
         return self._built(h, self.device, bw, int(ne.value), man, tman)
 
+    def changeWeights(self, w) -> "DeviceDensity":
+        """`changeWeights!` (reference src/BallTreeDensity01.jl:278-292) as a NEW resident density: weights w (N, original
+        point order, used as given; a tensor stays on the device), the same tree, the node statistics recomputed on the GPU
+        (kdehip_density_refit_device, include/kdehip.h section 5r)."""
+        from .refit import WEIGHTS, refit_device
+        return refit_device(self, w, WEIGHTS)[0]
+
+    def movePoints(self, delta) -> "DeviceDensity":
+        """`movePoints!` (reference src/BallTreeDensity01.jl:295-309) as a NEW resident density: every point moved by its
+        column of delta ((D, N), original order), the same -- now looser -- tree; the tree's recorded operators wrap the sum
+        in a circular dimension."""
+        from .refit import KEEP, refit_device
+        return refit_device(self, None, KEEP, delta)[0]
+
+    def bayes_update(self, logl, leaf_order=False):
+        """`w_i <- w_i L(x_i)` without leaving HBM: (DeviceDensity, log_evidence, ess).  logl: N log-likelihoods (by original
+        point, or by leaf position with leaf_order=True), or a DeviceDensity likelihood evaluated at this density's points."""
+        from .refit import device_bayes_update
+        return device_bayes_update(self, logl, leaf_order)
+
+    @classmethod
+    def refit_batch(cls, items):
+        """many refits in one call (kdehip_density_refit_device_batch): see `refit.refit_batch`"""
+        from .refit import refit_batch
+        return refit_batch(items)
+
     def marginal(self, dims, *, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`marginal(p, dims)` (reference src/KDE01.jl:143-153), dims 0-based, built on this density's device
         (kdehip_density_marginal_device): the same arrays as the host `marginal` of the same density.  `tree_manifold` (one
