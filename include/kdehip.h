@@ -1733,6 +1733,84 @@ typedef struct kdehip_refit_item {
  * fails the whole call: every out[i] is NULL and no handle is created. */
 int kdehip_density_refit_device_batch(int n, const kdehip_refit_item *items, kdehip_device_density **out);
 
+/* ---- (5s) entropic optimal transport between two densities: Sinkhorn's iteration and the barycentric map ---------------------
+ * kld, ise, mmd and intersIntg compare two densities point by point; none of them sees how FAR apart their mass lies, and none
+ * says how to move one onto the other.  The entries below solve the entropic optimal transport problem between the leaves of
+ * two densities (csrc/sinkhorn.hip; this library's own, the reference has no counterpart).
+ *   p has leaves x_i (i < N) and weights a_i, q has y_j (j < M) and b_j -- the weights as the densities hold them (kde's
+ *     sum to 1); the bandwidths play no part except in the default scale.
+ *   scale  a positive D-vector s; NULL = sqrt(v_p + v_q) per dimension, the combination of 5g, from the first leaves'
+ *          variances.  A density with per-point bandwidths must be given scale explicitly.
+ *   reg    eps > 0, in units of the scaled squared distance.
+ *   c_ij = 1/2 sum_k diff_k(x_i, y_j)^2 / s_k^2, diff_k the plain difference, through wrap() in a circular dimension (5d);
+ *   A_ij = -c_ij / eps = sum_k diff_k^2 * nhib_k, nhib_k = -1 / (2 eps s_k^2): the expression and fma order of the direct kernel.
+ * The potentials are kept divided by eps: phi_i, gamma_j.  With
+ *   T_x(gamma)_i = -LSE_{j : b_j > 0} (log b_j + gamma_j + A_ij),   T_y(phi)_j the same with the roles exchanged
+ * (log b_j + gamma_j is -Inf for a weightless leaf: it takes no part), a CROSS item (q is not p) starts from phi = gamma = 0,
+ * steps = 0 and repeats
+ *   1. tau = T_x(gamma), r_i = exp(phi_i - tau_i);
+ *   2. err = sum_{a_i > 0} a_i |r_i - 1|: the L1 row-marginal error of the plan at (phi, gamma);
+ *   3. mass = sum a_i r_i;
+ *   4. if (steps >= 1 and err <= tol) or steps == maxiter: finish with the current (phi, gamma);
+ *   5. otherwise phi = tau, gamma = T_y(phi), steps += 1.
+ * A SELF item (q is p: the same struct, the same handle) runs the same loop with tau = T_x(phi) over p's own leaves and step 5
+ * phi = (phi + tau) / 2, gamma = phi: the symmetric average, which on a symmetric problem converges in tens of steps where
+ * the alternating updates take thousands.
+ * Results of an item:
+ *   value = eps (sum a_i phi_i + sum b_j gamma_j - (mass - 1)): the dual objective, min <pi, c> + eps KL(pi | a x b) at
+ *           convergence; transport_cost = <pi, c> of the plan pi_ij = a_i b_j exp(phi_i + gamma_j + A_ij); err, mass;
+ *   iters = steps, negated if err > tol (the convention of 5q);
+ *   phi (N), gamma (M): in the order of getPoints / getWeights (by ORIGINAL point);
+ *   the barycentric map: m_i = sum_j e_ij diff(y_j, x_i) / sum_j e_ij, e_ij = exp(log b_j + gamma_j + A_ij - max_j), from one
+ *           more sweep at the finished potentials; it does not depend on phi_i or a_i, so weightless leaves of p move too.
+ *           delta = m; map = x + m, through wrap() in a circular dimension.
+ * The Sinkhorn divergence S(p, q) = value(p, q) - value(p, p) / 2 - value(q, q) / 2 is three items, one cross and two self,
+ * all three at ONE scale (the cross item's: kdehip_sinkhorn_item.scale_p / scale_q).
+ * Arithmetic and determinism: a half-step is one all-pairs sweep split as in 5b / 5f / 5q (128-leaf chunks in groups that
+ * depend on the two sizes alone; a group carries a running maximum and a sum rescaled once per chunk; the groups combined in
+ * group order), the queries' terms summed in the fixed 256-wide tree of 5b and the blocks in block order.  No atomics.  The
+ * half-steps of all items of a call share their launches (one per distinct (D, circular)), and a finished item is never
+ * written again: an item's result depends on the two densities, scale, reg, tol and maxiter alone.  The host entry, the
+ * resident entry and any batch give the same bits, however the iterations are grouped between the host's reads of the
+ * items' states.  Circular data in which no difference wraps give the Euclidean bits.
+ * All three entries are BLOCKING, take no stream and return host scalars.  reg and tol are HOST pointers to ONE value each, as
+ * tol is in 5h and 5q (an item of a batch holds the values themselves).
+ * Errors, KDEHIP_ERR_ARG, all checked before any device is touched: a null p, q, reg, tol or scalar result, ndims that differ or lie
+ * outside 1..KDEHIP_MAX_DIMS, reg or a scale entry not finite or <= 0, tol negative or NaN, maxiter < 0, a manifold byte above
+ * 1 or a mask bit at or above ndims, 2^31 points or more, densities on different devices, per-point bandwidths without a
+ * scale, and a host density without a leaf of positive weight.  A RESIDENT density without a leaf of positive weight is
+ * found by the first half-step (its weights live on the device): KDEHIP_ERR_ARG then too, the outputs are not meaningful.
+ * Not here: eps-annealing, unbalanced transport, barycentres, an enqueue-only form. */
+/* Host densities, host results, blocking.  phi [N], gamma [M], delta and map [ndims x N column-major, by original point]: each
+ * optional (NULL). */
+int kdehip_sinkhorn(const kdehip_density *p, const kdehip_density *q, const double *scale /* D, or NULL */, const double *reg,
+                    const double *tol, int maxiter, double *value, double *transport_cost, double *err, double *mass, int32_t *iters, double *phi,
+                    double *gamma, double *delta, double *map, int device, const uint8_t *manifold);
+/* Resident densities, HOST scalars (scale is a host pointer too), optional DEVICE vectors: d_phi [N], d_gamma [M], d_map
+ * [ndims x N column-major] by original point; d_delta [ndims x N column-major] in LEAF order -- ready for
+ * kdehip_density_refit_device(.., KDEHIP_REFIT_KEEP, leaf_order = 1, d_delta, ..).  Blocking: the vectors are complete on
+ * return, and the caller's own work on p and q must be complete when the call is made. */
+int kdehip_sinkhorn_device(const kdehip_device_density *p, const kdehip_device_density *q, const double *scale,
+                           const double *reg, const double *tol, int maxiter, double *value, double *transport_cost, double *err, double *mass,
+                           int32_t *iters, double *d_phi, double *d_gamma, double *d_delta, double *d_map,
+                           const uint8_t *manifold);
+typedef struct kdehip_sinkhorn_item {
+  const kdehip_device_density *p, *q;   /* q == p selects the self iteration */
+  const double *scale;                  /* HOST pointer, D entries, or NULL */
+  const kdehip_device_density *scale_p, *scale_q;   /* both NULL, or the two densities whose variances give the default scale
+                                                        in the place of p's and q's: the self items of a divergence take the
+                                                        cross item's scale.  Not read when scale is given. */
+  double reg, tol;
+  double *value, *transport_cost, *err, *mass;   /* host, [1] each */
+  int32_t *iters;                       /* host, [1] */
+  double *d_phi, *d_gamma, *d_delta, *d_map;     /* device or NULL, as kdehip_sinkhorn_device */
+  int32_t maxiter;
+  uint32_t circular_mask;               /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+} kdehip_sinkhorn_item;
+/* Many pairs (mixed D, sizes, cross and self) on one device: the items share the launches of every half-step, and every item's
+ * results are bit for bit those of kdehip_sinkhorn_device at the same scale.  One bad item fails the whole call. */
+int kdehip_sinkhorn_device_batch(int n, const kdehip_sinkhorn_item *items);
+
 #ifdef __cplusplus
 }
 #endif

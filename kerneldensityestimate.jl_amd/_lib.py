@@ -115,6 +115,14 @@ class CBwJointItem(C.Structure):
                 ("circular_mask", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class CSinkhornItem(C.Structure):
+    """struct kdehip_sinkhorn_item (`scale` and the five results are HOST pointers, the four vectors DEVICE addresses)"""
+    _fields_ = [("p", C.c_void_p), ("q", C.c_void_p), ("scale", f64p), ("scale_p", C.c_void_p), ("scale_q", C.c_void_p), ("reg", C.c_double), ("tol", C.c_double),
+                ("value", f64p), ("transport_cost", f64p), ("err", f64p), ("mass", f64p), ("iters", i32p),
+                ("d_phi", C.c_void_p), ("d_gamma", C.c_void_p), ("d_delta", C.c_void_p), ("d_map", C.c_void_p),
+                ("maxiter", C.c_int32), ("circular_mask", C.c_uint32)]
+
+
 class CRefitItem(C.Structure):
     """struct kdehip_refit_item (`log_evidence` and `ess` are HOST pointers)"""
     _fields_ = [("p", C.c_void_p), ("d_values", C.c_void_p), ("d_delta", C.c_void_p), ("log_evidence", f64p), ("ess", f64p),
@@ -350,6 +358,12 @@ SIGNATURES = {
     "kdehip_density_refit_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, u8p,
                                               f64p, f64p]),
     "kdehip_density_refit_device_batch": (C.c_int, [C.c_int, C.POINTER(CRefitItem), C.POINTER(C.c_void_p)]),
+    # entropic optimal transport (include/kdehip.h section 5s): blocking, host scalars, no stream
+    "kdehip_sinkhorn": (C.c_int, [C.POINTER(CDensity), C.POINTER(CDensity), f64p, f64p, f64p, C.c_int, f64p, f64p,
+                                  f64p, f64p, i32p, f64p, f64p, f64p, f64p, C.c_int, u8p]),
+    "kdehip_sinkhorn_device": (C.c_int, [C.c_void_p, C.c_void_p, f64p, f64p, f64p, C.c_int, f64p, f64p, f64p, f64p,
+                                         i32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u8p]),
+    "kdehip_sinkhorn_device_batch": (C.c_int, [C.c_int, C.POINTER(CSinkhornItem)]),
     "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
                                          u8p]),
     "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,

@@ -72,6 +72,32 @@ class BallTreeDensity:
         from .refit import host_bayes_update
         return host_bayes_update(self, logl)
 
+    # entropic optimal transport onto another density (include/kdehip.h section 5s): see transport.py
+    def sinkhorn(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False, device=0):
+        """the entropic transport value between this density and q (`q is self`: the symmetric iteration)"""
+        from .transport import sinkhorn
+        return sinkhorn(self, q, reg, scale, tol, maxiter, manifold, return_info, device)
+
+    def sinkhorn_divergence(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False, device=0):
+        """value(self, q) - value(self, self) / 2 - value(q, q) / 2; 0.0 when q is self"""
+        from .transport import sinkhorn_divergence
+        return sinkhorn_divergence(self, q, reg, scale, tol, maxiter, manifold, return_info, device)
+
+    def transport_map(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False, device=0):
+        """T (D, N): the barycentric image of every point under the plan onto q"""
+        from .transport import transport_map
+        return transport_map(self, q, reg, scale, tol, maxiter, manifold, return_info, device)
+
+    def transport_to(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False, device=0):
+        """`movePoints` by the barycentric displacement onto q: a new density, the same weights and tree"""
+        from .transport import transport_to
+        return transport_to(self, q, reg, scale, tol, maxiter, manifold, return_info, device)
+
+    def equalize(self, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False, device=0):
+        """the ensemble transform: the points moved so that equal weights represent this density"""
+        from .transport import equalize
+        return equalize(self, reg, scale, tol, maxiter, manifold, return_info, device)
+
 
 def _prepare(points, ks, weights):
     pts = np.asarray(points, dtype=np.float64)

@@ -1063,6 +1063,71 @@ function hip_kde_joint(points::AbstractMatrix{Float64}, weights::Union{Nothing,V
   return kde!(points, bw, weights; tree_manifold=tree_manifold)
 end
 
+# the first leaf's variances: the one bandwidth vector of a density that kde! built
+leaf_variances(bd::BallTreeDensity) = bd.bandwidth[bd.bt.num_points * bd.bt.dims .+ (1:bd.bt.dims)]
+
+"""
+    hip_sinkhorn(p, q; reg=1.0, scale=nothing, tol=1e-6, maxiter=1000, manifold=nothing, device=0)
+
+Entropic optimal transport between the points of `p` and of `q` (`kdehip_sinkhorn`, include/kdehip.h section 5s): the cost is
+`1/2 sum_k diff_k^2 / scale_k^2` (`scale=nothing`: `sqrt(v_p + v_q)`, the bandwidths combined), `reg` its entropic weight;
+`q === p` runs the symmetric iteration of `p` against itself.  Returns a named tuple: `value` (the dual objective),
+`transport_cost`, `err` (the L1 row-marginal error at the stop), `mass`, `iters` (negative where the last step was still above
+`tol`), the potentials `phi`, `gamma`, and `delta`, `map` (`D x N`): the barycentric displacement and image of every point
+of `p`, all in the order of `getPoints`.  The library's own: not installed by `enable!()`.
+"""
+function hip_sinkhorn(p::BallTreeDensity, q::BallTreeDensity; reg::Float64=1.0, scale::Union{Nothing,AbstractVector{Float64}}=nothing,
+                      tol::Float64=1e-6, maxiter::Int=1000, manifold=nothing, device::Int=0)
+  D = Ndim(p)
+  Ndim(q) == D || error("the two densities must have the same dimension")
+  scale === nothing || length(scale) == D || error("scale needs one entry per dimension")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  N, M = p.bt.num_points, q.bt.num_points
+  vals = zeros(4)
+  iters = Int32[0]
+  phi, gamma, delta, tmap = zeros(N), zeros(M), zeros(D, N), zeros(D, N)
+  cp = Ref(CDensity(p))
+  cq = q === p ? cp : Ref(CDensity(q))
+  sc = scale === nothing ? zeros(0) : Vector{Float64}(scale)
+  regv, tolv = Float64[reg], Float64[tol]
+  GC.@preserve p q sc regv tolv man vals begin
+    check(ccall((:kdehip_sinkhorn, libkdehip), Cint,
+                (Ref{CDensity}, Ref{CDensity}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{UInt8}),
+                cp, cq, scale === nothing ? Ptr{Float64}(C_NULL) : pointer(sc), regv, tolv, maxiter, pointer(vals, 1),
+                pointer(vals, 2), pointer(vals, 3), pointer(vals, 4), iters, phi, gamma, delta, tmap, device, man))
+  end
+  return (value=vals[1], transport_cost=vals[2], err=vals[3], mass=vals[4], iters=Int(iters[1]), phi=phi, gamma=gamma,
+          delta=delta, map=tmap)
+end
+
+"""
+    hip_sinkhorn_divergence(p, q; reg=1.0, scale=nothing, tol=1e-6, maxiter=1000, manifold=nothing, device=0)
+
+`S(p, q) = value(p, q) - value(p, p) / 2 - value(q, q) / 2`, all three at ONE scale (`scale=nothing`: the pair's
+`sqrt(v_p + v_q)`); `0.0` for `q === p`, by definition.
+"""
+function hip_sinkhorn_divergence(p::BallTreeDensity, q::BallTreeDensity; reg::Float64=1.0,
+                                 scale::Union{Nothing,AbstractVector{Float64}}=nothing, tol::Float64=1e-6, maxiter::Int=1000,
+                                 manifold=nothing, device::Int=0)
+  q === p && return 0.0
+  s = scale === nothing ? sqrt.(leaf_variances(p) .+ leaf_variances(q)) : Vector{Float64}(scale)
+  value(a, b) = hip_sinkhorn(a, b; reg=reg, scale=s, tol=tol, maxiter=maxiter, manifold=manifold, device=device).value
+  return value(p, q) - value(p, p) / 2 - value(q, q) / 2
+end
+
+"""
+    hip_transport_map(p, q; reg=1.0, scale=nothing, tol=1e-6, maxiter=1000, manifold=nothing, device=0)
+
+`T` (`D x N`): the barycentric image of every point of `p` under the entropic plan onto `q`, in the order of `getPoints`
+(wrapped to `[-pi, pi)` in a circular dimension).  `movePoints!(p, T - getPoints(p))` moves `p` there.
+"""
+function hip_transport_map(p::BallTreeDensity, q::BallTreeDensity; reg::Float64=1.0,
+                           scale::Union{Nothing,AbstractVector{Float64}}=nothing, tol::Float64=1e-6, maxiter::Int=1000,
+                           manifold=nothing, device::Int=0)
+  return hip_sinkhorn(p, q; reg=reg, scale=scale, tol=tol, maxiter=maxiter, manifold=manifold, device=device).map
+end
+
 """
     hip_box_mass(bd, lo, hi; dims=nothing, manifold=nothing, device=0)
 

@@ -511,6 +511,38 @@ class DeviceDensity:
         from .refit import refit_batch
         return refit_batch(items)
 
+    # entropic optimal transport onto another resident density (include/kdehip.h section 5s): see transport.py
+    def sinkhorn(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False):
+        """the entropic transport value between this density and q (`q is self`: the symmetric iteration)"""
+        from .transport import sinkhorn
+        return sinkhorn(self, q, reg, scale, tol, maxiter, manifold, return_info)
+
+    def sinkhorn_divergence(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False):
+        """value(self, q) - value(self, self) / 2 - value(q, q) / 2 in one batched run; 0.0 when q is self"""
+        from .transport import sinkhorn_divergence
+        return sinkhorn_divergence(self, q, reg, scale, tol, maxiter, manifold, return_info)
+
+    def transport_map(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False):
+        """T (D, N), a device tensor: the barycentric image of every point under the plan onto q"""
+        from .transport import transport_map
+        return transport_map(self, q, reg, scale, tol, maxiter, manifold, return_info)
+
+    def transport_to(self, q, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False) -> "DeviceDensity":
+        """`movePoints` by the barycentric displacement onto q: a new density; nothing leaves HBM"""
+        from .transport import transport_to
+        return transport_to(self, q, reg, scale, tol, maxiter, manifold, return_info)
+
+    def equalize(self, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, return_info=False) -> "DeviceDensity":
+        """the ensemble transform: the points moved so that equal weights represent this density"""
+        from .transport import equalize
+        return equalize(self, reg, scale, tol, maxiter, manifold, return_info)
+
+    @staticmethod
+    def sinkhorn_batch(pairs, reg=1.0, scale=None, tol=1e-6, maxiter=1000, manifold=None, vectors=False):
+        """many pairs in one call (kdehip_sinkhorn_device_batch): see `transport.sinkhorn_batch`"""
+        from .transport import sinkhorn_batch
+        return sinkhorn_batch(pairs, reg, scale, tol, maxiter, manifold, vectors)
+
     def marginal(self, dims, *, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`marginal(p, dims)` (reference src/KDE01.jl:143-153), dims 0-based, built on this density's device
         (kdehip_density_marginal_device): the same arrays as the host `marginal` of the same density.  `tree_manifold` (one
