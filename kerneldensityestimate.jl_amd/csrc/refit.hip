@@ -685,9 +685,10 @@ int refit_impl(int n, const kdehip_refit_item *items, kdehip_device_density **ou
   }
   KDEHIP_CHECK(blk.wait());
   device_time.collect();
-  // slot N is no node: no pass writes its box, the twelve arrays keep the source's
+  // slot N is no node: no pass writes its box, the twelve arrays keep the source's.  (A density of ONE point has no such
+  // slot: id 1 = N is its root, whose box the top kernel has just recomputed.)
   for (Plan &q : plans)
-    if (q.h->mirror) {
+    if (q.h->mirror && q.p->N > 1) {
       const size_t D = static_cast<size_t>(q.p->D), at = static_cast<size_t>(q.p->N - 1) * D;
       std::memcpy(q.h->m.centers + at, q.p->m.centers + at, sizeof(double) * D);
       std::memcpy(q.h->m.ranges + at, q.p->m.ranges + at, sizeof(double) * D);

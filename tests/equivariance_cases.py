@@ -4,7 +4,9 @@ exactly representable offset.  Imports without a GPU and without the library: a 
 argument and a case as a namespace, and is only ever run by the GPU module.
 
 "Every" is checked: tests/test_equivariance_table.py reads kerneldensityestimate.jl_amd/__init__.py as text and wants each
-public name in exactly one row's `entries` or in EXCLUDED (with the reason), both in this file.
+public name in exactly one row's `entries` or in EXCLUDED (with the reason), both in this file -- and likewise, under the
+name `module.name`, each public function and class of a module of the package that __init__.py imports nothing from (the
+families whose surface is methods of BallTreeDensity / DeviceDensity plus such a module: `refit`, `transport`).
 
 The laws, derived from the formulas of include/kdehip.h and not from the kernels.  With the points, the queries, the bounds
 and the bandwidths (standard deviations) multiplied by 2^k -- np.ldexp, so exactly -- every difference d, its square, the
@@ -406,6 +408,144 @@ def _mul_exact(kd, c):
     return got
 
 
+def _module(kd, name):
+    """a module of the package that its __init__ does not import"""
+    import importlib
+    return importlib.import_module(kd.__name__ + "." + name)
+
+
+def _all_dims(kd, dp):
+    """a BUILT twin of an uploaded density -- its marginal over all dimensions, made on the device without a bandwidth search
+    (tests/test_gpu_refit.py G8) --: the refit of a built density keeps the twelve arrays and can be downloaded"""
+    return dp.marginal(list(range(dp.dims)))
+
+
+def _refit_on_device(kd, dm, c):
+    """the four refits of the built resident density dm, downloaded, and whether a batch of the same four gives their bits"""
+    from tests import refit_model as rm
+    rf = _module(kd, "refit")
+    made = [dm.changeWeights(c.rw), dm.movePoints(c.rdelta), rf.refit_device(dm, c.rw, rf.WEIGHTS, c.rdelta)[0]]
+    upd, le, ess = dm.bayes_update(c.logl)
+    made.append(upd)
+    batch = kd.DeviceDensity.refit_batch([dict(density=dm, weights=c.rw), dict(density=dm, delta=c.rdelta),
+                                          dict(density=dm, weights=c.rw, delta=c.rdelta), dict(density=dm, logl=c.logl)])
+    host = [d.download() for d in made]
+    same = batch[3][1:] == (le, ess) and all(b[1] is None and b[2] is None for b in batch[:3])
+    for (b, _, _), h in zip(batch, host):
+        try:
+            rm.same_bits(b.download(), h, "a batch item")
+        except AssertionError:
+            same = False
+        b.close()
+    for d in made:
+        d.close()
+    return host, le, ess, same
+
+
+def _refit(kd, c):
+    p = c.p
+    rf = _module(kd, "refit")
+    made = [p.changeWeights(c.rw), p.movePoints(c.rdelta), rf.refit_host(p, new_weights=c.rw, delta=c.rdelta)]
+    upd, le, ess = p.bayes_update(c.logl)
+    out = dict(log_evidence=le, ess=ess)
+    for d, pre in zip(made + [upd], ("cw_", "mv_", "both_", "by_")):
+        out.update(fields(d, pre))
+    # the results as inputs of a consumer: what the resident route is compared by (the refit of an UPLOADED density has no
+    # arrays to download)
+    out.update(cw_p=kd.evaluateDualTree(made[0], c.X), mv_p=kd.evaluateDualTree(made[1], c.X), both_p=kd.evaluateDualTree(made[2], c.X))
+    # the device's refit has arithmetic of its own in the Bayes update (the host's is numpy's), so it gets laws of its own; on
+    # a built twin, whose arrays (dsrc_) are part of the output
+    with kd.DeviceDensity(p) as up, _all_dims(kd, up) as dm:
+        out.update(fields(dm.download(), "dsrc_"))
+        host, dle, dess, same = _refit_on_device(kd, dm, c)
+    for d, pre in zip(host, ("dcw_", "dmv_", "dboth_", "dby_")):
+        out.update(fields(d, pre))
+    out.update(dev_log_evidence=dle, dev_ess=dess, batch_is_singles=np.array([same]))
+    return out
+
+
+def _refit_resident(kd, c):
+    rf = _module(kd, "refit")
+    with c.dp.changeWeights(c.rw) as a, c.dp.movePoints(c.rdelta) as b, rf.refit_device(c.dp, c.rw, rf.WEIGHTS, c.rdelta)[0] as ab:
+        return dict(cw_p=a.evaluate(c.X), mv_p=b.evaluate(c.X), both_p=ab.evaluate(c.X))
+
+
+OT = dict(reg=1.0, tol=0.0, maxiter=8)   # a fixed number of steps, ending on a round boundary: no comparison with a tolerance
+_OT_SCALARS = ("value", "transport_cost", "err", "mass", "iters")
+_OT_VECTORS = ("phi", "gamma", "delta", "map")
+
+
+def _np(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _ot_item(info, prefix, leaf=None):
+    """the outputs of one item; a resident item's displacement comes in leaf order and goes back to the order of getPoints"""
+    out = {prefix + k: info[k] for k in _OT_SCALARS}
+    out.update({prefix + k: np.ascontiguousarray(_np(info[k])) for k in ("phi", "gamma", "map")})
+    if "delta" in info:
+        out[prefix + "delta"] = info["delta"]
+    else:
+        delta = np.empty_like(out[prefix + "map"])
+        delta[:, leaf] = _np(info["delta_leaf"])
+        out[prefix + "delta"] = delta
+    return out
+
+
+def _moved(kd, c, d, prefix):
+    """a moved density: its values at the queries -- on both routes -- and, of a host density, its arrays"""
+    if hasattr(d, "bt"):
+        return {prefix + "p": kd.evaluateDualTree(d, c.X), **fields(d, prefix)}
+    with d:
+        return {prefix + "p": d.evaluate(c.X)}
+
+
+def _transport(kd, c, p=None, q=None):
+    p, q = (c.p, c.q) if p is None else (p, q)
+    leaf = c.p.bt.permutation[c.N:] - 1
+    out = {}
+    T, info = p.transport_map(q, return_info=True, **OT)
+    out.update(_ot_item(info, "", leaf))
+    out.update(_ot_item(p.sinkhorn(q, scale=c.ot_scale, return_info=True, **OT)[1], "s_", leaf))
+    out.update(_ot_item(p.sinkhorn(p, return_info=True, **OT)[1], "self_", leaf))
+    S, dv = p.sinkhorn_divergence(q, return_info=True, **OT)
+    S2, dv2 = p.sinkhorn_divergence(q, scale=c.ot_scale, return_info=True, **OT)
+    out.update(S=S, S_cross=dv["cross"], S_self_p=dv["self_p"], S_self_q=dv["self_q"], S_iters=np.array(dv["iters"]),
+               s_S=S2, s_S_self_p=dv2["self_p"], s_S_self_q=dv2["self_q"])
+    out["map_is_info"] = np.array([np.array_equal(_np(T), out["map"]) and info["value"] == p.sinkhorn(q, **OT)])
+    out.update(_moved(kd, c, p.transport_to(q, **OT), "to_"))
+    out.update(_moved(kd, c, p.transport_to(q, scale=c.ot_scale, **OT), "s_to_"))
+    out.update(_moved(kd, c, p.equalize(**OT), "eq_"))
+    if p is c.p:  # the batch of the same pairs on resident twins: each item bit for bit the single call's
+        with kd.DeviceDensity(c.p) as dp, kd.DeviceDensity(c.q) as dq:
+            batch = kd.DeviceDensity.sinkhorn_batch([dict(p=dp, q=dq), dict(p=dp, q=dq, scale=c.ot_scale), dict(p=dp, q=dp)],
+                                                    vectors=True, **OT)
+            same = True
+            for item, prefix in zip(batch, ("", "s_", "self_")):
+                got = _ot_item(item, prefix, leaf)
+                same = same and all(np.float64(got[k]).tobytes() == np.float64(out[k]).tobytes()
+                                    for k in (prefix + n for n in _OT_SCALARS))
+                same = same and all(np.array_equal(got[k], out[k]) for k in (prefix + n for n in _OT_VECTORS))
+        out["batch_is_singles"] = np.array([same])
+    return out
+
+
+def _transport_resident(kd, c):
+    return _transport(kd, c, c.dp, c.dq)
+
+
+def _moved_laws(prefix):
+    """a density whose points are images under the map: under translation they are positions that round at 2^20, so of its
+    arrays the weights and the topology are claimed and the centres, ranges, means and variances are not"""
+    out = {prefix + name: bits(e, "same" if where == "bt" and e == 0 else None) for name, where, e in TREE_FIELDS}
+    out[prefix + "p"] = bits(mD, None)   # its values at the queries: what the resident route is compared by
+    return out
+
+
+def _ot_laws(prefix):
+    return {**{prefix + k: bits(0) for k in _OT_SCALARS + ("phi", "gamma")}, prefix + "delta": bits(1), prefix + "map": bits(1, "pos")}
+
+
 # the search's result: the base bandwidth times 2^k within the 1e-9 relative bound of test_loocv_bandwidth_parity_with_oracle
 _NO_CLAMP = ("the reference clamps the search's lower end, minm, to 1e-6 (src/CrossValidation.jl, golden_init in csrc/loocv.hip): an "
              "absolute length.  For k >= 0 the premise is that the smallest gap between sorted neighbours of every marginal of the "
@@ -484,6 +624,27 @@ ROWS = [
         "the bandwidth is held to the oracle's search on those draws",
         _mul_exact, {**field_laws("mx_", bandwidth=search(2), translated=False), **dict(bw=search(1, None), evals=bits(0, None))},
         scales=(30, 80), restriction=_NO_CLAMP + "; here the points are the draws, and the premise is asserted on them"),
+    # the two families whose surface is methods (BallTreeDensity / DeviceDensity) plus a module that __init__ does not re-export
+    Row("refit", ["refit.refit_host", "refit.bayes_weights", "refit.host_bayes_update", "refit.refit_device",
+                  "refit.device_bayes_update", "refit.refit_batch"],
+        "tests/refit_model.py (the arrays, bit for bit); the Bayes weights, evidence and ess against the formula in extended "
+        "precision (tests/test_refit_host.py bayes_reference)",
+        _refit, {**{n: law for pre in ("cw_", "mv_", "both_", "by_", "dsrc_", "dcw_", "dmv_", "dboth_", "dby_")
+                    for n, law in field_laws(pre).items()},
+                 **dict(cw_p=bits(mD), mv_p=bits(mD), both_p=bits(mD)),
+                 **dict(log_evidence=bits(0), ess=bits(0), dev_log_evidence=bits(0), dev_ess=bits(0), batch_is_singles=bits(0))},
+        _refit_resident),
+    Row("transport", ["transport.sinkhorn", "transport.sinkhorn_batch", "transport.sinkhorn_divergence", "transport.transport_map",
+                      "transport.transport_to", "transport.equalize"],
+        "tests/transport_model.py (iterate, divergence).  reg = 1, tol = 0 and eight steps, so that the step count is no "
+        "comparison with a tolerance; once at the default scale and once (s_) at a scale from the caller that is rescaled with "
+        "the data.  The moved densities (to_, s_to_, eq_): under translation their points are positions that round at 2^20, so "
+        "the statistics of their inner nodes differ and only the weights and the topology are claimed",
+        _transport, {**_ot_laws(""), **_ot_laws("s_"), **_ot_laws("self_"),
+                     **{k: bits(0) for k in ("S", "S_cross", "S_self_p", "S_self_q", "S_iters", "s_S", "s_S_self_p", "s_S_self_q",
+                                             "map_is_info", "batch_is_singles")},
+                     **_moved_laws("to_"), **_moved_laws("s_to_"), **_moved_laws("eq_")},
+        _transport_resident),
 ]
 
 EXCLUDED = {
@@ -512,6 +673,12 @@ EXCLUDED = {
     "LIB_PATH": "the path of the shared library: a string",
     "device_count": "asks the runtime for the number of devices",
     "version": "the version number of the library",
+    # modules that __init__ imports nothing from, by their qualified names
+    **{"manifold." + name: "parses and packs the manifold argument: it touches no data of a density"
+       for name in ("parse", "resolve", "select", "per_product", "per_item", "matrix", "mask", "pointer")},
+    **{"sharded." + name: "a wrapper over several processes whose numerics are prodAppxMSGibbsS's, excluded above: the Gibbs "
+                          "product's contract is not equivariant"
+       for name in ("shard_range", "ShardedProduct", "PendingProduct")},
 }
 
 

@@ -15,7 +15,10 @@ its docstring derives the laws; tests/test_equivariance_table.py keeps the table
    they follow: `laplace` against numpy's inverse of the entry's own Hessian (which `_check_hess` holds to the model at the
    queries, not at the starts), the summaries' grids against the package's `summary.grid`, `kde_adaptive` against
    `kde_varbw` of `adaptive_scales`' factors, the searched densities against `kde` of their own bandwidth.  Each says so.
-3. The resident route, at k = -80: the call on DeviceDensity arguments returns the host call's bits.
+3. The resident route, at k = -80: the call on DeviceDensity arguments returns the host call's bits.  The rows `refit` and
+   `transport` make densities; the refit of an UPLOADED density has no arrays to download, so on this route a made density is
+   compared by its values at the queries, and the device's own arithmetic (the Bayes update, the batches) runs inside the
+   host call on a built twin whose arrays are part of the output.
 4. Translation.  The same cases with every coordinate rounded to a multiple of 2^-20, |x| < 2^6, and per dimension an offset
    from +-2^20, +-3 2^19: x + t is exact.  Outputs the table marks "same" are bit for bit the untranslated ones; positions
    ("pos") are held to the family's model run on the translated inputs (the same `_check_*` functions), and to the
@@ -42,6 +45,7 @@ import numpy as np
 import pytest
 
 import kdehip
+from kdehip import refit as rf
 from tests import bwjoint_model as bm
 from tests import conditional_model as cm
 from tests import curvature_model as hm
@@ -54,8 +58,11 @@ from tests import mass_model as sm
 from tests import modes_model as mm
 from tests import prodexact_model as pm
 from tests import pymodel
+from tests import refit_model as rm
+from tests import transport_model as tm
 from tests import varbw_model as vm
 from tests.helpers import density_arrays
+from tests.test_refit_host import bayes_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +110,17 @@ def _inputs(ci, lattice=False):
                      X=X, starts=starts, lo=lo, hi=hi, edges=edges, v=sd3 * sd3, sd_mmd=rng.uniform(0.3, 0.9, size=D),
                      metric=rng.uniform(0.3, 3.0, size=D), bwpp=sd[:, None] * rng.uniform(0.5, 2.0, size=(D, N)),
                      labels=rng.integers(1, N + 1, size=ec.NDRAW), G=list(range(1, D, 2)), unit=1.0)
+    # (drawn after everything above, so that the older rows keep their numbers) the refit's new weights with exact zeros, its
+    # moves -- on the lattice too, so that x + t + delta is exact --, log-likelihoods that span a few hundred with one -Inf, and
+    # a transport scale from the caller
+    c.rw = rng.uniform(0.05, 2.0, size=N)
+    c.rw[::7] = 0.0
+    c.rdelta = rnd(0.3 * rng.standard_normal((D, N)))
+    c.logl = rng.uniform(-300.0, 0.0, size=N)
+    c.logl[1] = -math.inf
+    c.ot_scale = rng.uniform(0.5, 1.5, size=D)
     if lattice:
+        assert np.all(np.abs(c.rdelta) < 2.0 ** 6) and np.all(c.rdelta / LATTICE == np.round(c.rdelta / LATTICE))
         for a in (pts, pts2, X, starts, lo[np.isfinite(lo)], hi[np.isfinite(hi)], *edges):
             assert np.all(np.abs(a) < 2.0 ** 6) and np.all(a / LATTICE == np.round(a / LATTICE)), "an input left the lattice"
     return c
@@ -115,7 +132,7 @@ _POS = ("pts", "pts2", "X", "starts", "lo", "hi")
 def _scaled(c0, k):
     c = ec.namespace(**vars(c0))
     c.k = k
-    for name in _POS + ("sd", "sd2", "sd_mmd", "bwpp"):
+    for name in _POS + ("sd", "sd2", "sd_mmd", "bwpp", "rdelta", "ot_scale"):
         setattr(c, name, np.ldexp(getattr(c0, name), k))
     c.edges = [np.ldexp(e, k) for e in c0.edges]
     c.v, c.metric, c.unit = np.ldexp(c0.v, 2 * k), np.ldexp(c0.metric, -2 * k), math.ldexp(1.0, k)
@@ -752,6 +769,92 @@ def _check_mul_exact(c, o):
     assert o["evals"] > 0
 
 
+def _tree(o, prefix):
+    return {f: o[prefix + f] for f in rm.FIELDS}
+
+
+def _check_refit(c, o):
+    """at the terms of tests/test_gpu_refit.py: the arrays bit for bit tests/refit_model.py's (to which tests/test_refit_host.py
+    pins the host entry) -- the host's from the arrays of c.p, the device's from those of its built source (dsrc_) --; the
+    Bayes weights 1e-12 relative (+ 1e-300: subnormal weights), the evidence 1e-12 * max(1, |ref|) and the ess 1e-12 relative
+    against the formula in extended precision, and the updated arrays those of changeWeights of the weights the update made;
+    the values of the refitted densities at the queries 1e-12 relative to the direct sum (tests/evaltol_model.py)"""
+    D, N = c.D, c.N
+    dsrc = _tree(o, "dsrc_")
+    # the built twin: the points of c.p in its leaf order, and the weights within rounding of its renormalisation
+    _same("refit.dsrc_permutation", dsrc["permutation"], c.p.bt.permutation)
+    _same("refit.dsrc_ leaf means", dsrc["means"][N * D:], c.p.means[N * D:])
+    _hold("refit.dsrc_weights", dsrc["weights"], c.p.bt.weights, 1e-14)
+    perm = c.p.bt.permutation[N:] - 1
+    for src, pres in ((rm.arrays_of(c.p), ("cw_", "mv_", "both_", "by_")), (dsrc, ("dcw_", "dmv_", "dboth_", "dby_"))):
+        rm.same_bits(_tree(o, pres[0]), rm.refit(src, D, N, new_weights=c.rw), f"refit.{pres[0]} model")
+        rm.same_bits(_tree(o, pres[1]), rm.refit(src, D, N, delta=c.rdelta), f"refit.{pres[1]} model")
+        rm.same_bits(_tree(o, pres[2]), rm.refit(src, D, N, new_weights=c.rw, delta=c.rdelta), f"refit.{pres[2]} model")
+        pre = pres[3]
+        le, ess = (o["log_evidence"], o["ess"]) if pre == "by_" else (o["dev_log_evidence"], o["dev_ess"])
+        w0, got = np.empty(N), np.empty(N)
+        w0[perm], got[perm] = src["weights"][N:], o[pre + "weights"][N:]
+        wn, le_ref, ess_ref = bayes_reference(w0, c.logl)
+        _hold(f"refit.{pre}weights reference", got, wn, 1e-12 * np.abs(wn) + 1e-300)
+        assert got[1] == 0.0 and np.all(got[c.w == 0.0] == 0.0) and np.count_nonzero(got) > N // 2
+        _hold(f"refit.{pre}log_evidence reference", le, le_ref, 1e-12 * max(1.0, abs(le_ref)))
+        _hold(f"refit.{pre}ess reference", ess, ess_ref, 1e-12 * ess_ref)
+        rm.same_bits(_tree(o, pre), rm.refit(src, D, N, new_weights=got), f"refit.{pre} is changeWeights of its weights")
+    assert o["batch_is_singles"].all(), "an item of refit_batch differs from the single call"
+    X = _rows(c.X[:, c.sub])
+    for name, pts, w in (("cw_p", c.A[0], c.rw), ("mv_p", c.A[0] + c.rdelta, c.A[1]), ("both_p", c.A[0] + c.rdelta, c.rw)):
+        _rel12(f"refit.{name} model", o[name][c.sub], em.direct_fsum(_rows(pts), w, c.A[2], X))
+
+
+def _ot_against(key, o, prefix, want):
+    """tests/test_gpu_transport.py (`_check_item`, `_close`): the potentials 1e-9 * max(1, max |phi|, max |gamma|), the four
+    scalars and the map 1e-9 * max(1, |.|), the displacement 1e-9 * max(1, |map|)"""
+    big = max(1.0, float(np.abs(want["phi"]).max()), float(np.abs(want["gamma"]).max()))
+    assert o[prefix + "iters"] == want["iters"] == -ec.OT["maxiter"]
+    for name in ("phi", "gamma"):
+        assert np.all(np.isfinite(o[prefix + name]))
+        _hold(f"{key}.{prefix}{name} model", o[prefix + name], want[name], 1e-9 * big)
+    for name in ("value", "transport_cost", "err", "mass"):
+        _hold(f"{key}.{prefix}{name} model", o[prefix + name], want[name], 1e-9 * max(1.0, abs(want[name])))
+    size = np.maximum(1.0, np.abs(want["map"]))
+    assert np.all(np.isfinite(o[prefix + "map"])) and np.all(np.isfinite(o[prefix + "delta"]))
+    _hold(f"{key}.{prefix}map model", o[prefix + "map"], want["map"], 1e-9 * size)
+    _hold(f"{key}.{prefix}delta model", o[prefix + "delta"], want["delta"], 1e-9 * size)
+
+
+def _check_transport(c, o):
+    vp, vq = (c.A[0], c.A[1]), (c.B[0], c.B[1])
+    s, s_self = tm.default_scale(c.A[2], c.B[2]), tm.default_scale(c.A[2], c.A[2])
+    kw = (ec.OT["reg"], ec.OT["tol"], ec.OT["maxiter"])
+    _ot_against("transport", o, "", tm.iterate(vp, vq, s, *kw))
+    _ot_against("transport", o, "s_", tm.iterate(vp, vq, c.ot_scale, *kw))
+    _ot_against("transport", o, "self_", tm.iterate(vp, None, s_self, *kw))
+    _same("transport.self_gamma is self_phi", o["self_gamma"], o["self_phi"])
+    for pre, scale in (("", s), ("s_", c.ot_scale)):  # tests/test_gpu_transport.py G7: 1e-9 * max(1, |value(p, q)|)
+        want, (pq, pp, qq) = tm.divergence(vp, vq, scale, *kw)
+        _hold(f"transport.{pre}S model", o[pre + "S"], want, 1e-9 * max(1.0, abs(pq["value"])))
+        _hold(f"transport.{pre}S_self_p model", o[pre + "S_self_p"], pp["value"], 1e-9 * max(1.0, abs(pp["value"])))
+        _hold(f"transport.{pre}S_self_q model", o[pre + "S_self_q"], qq["value"], 1e-9 * max(1.0, abs(qq["value"])))
+    _same("transport.S_cross", np.float64(o["S_cross"]), np.float64(o["value"]))
+    assert list(o["S_iters"]) == [-ec.OT["maxiter"]] * 3
+    assert o["map_is_info"].all() and o["batch_is_singles"].all()
+    # the moved densities: movePoints by the displacement the call returns, and their points ARE the map (G5); their values at
+    # the queries 1e-12 relative to the direct sum over those points (tests/evaltol_model.py)
+    X = _rows(c.X[:, c.sub])
+    for pre in ("", "s_"):
+        moved = c.p.movePoints(o[pre + "delta"])
+        rm.same_bits(_tree(o, pre + "to_"), moved, f"transport.{pre}to_ is movePoints(delta)")
+        _same(f"transport.{pre}to_ points are the map", kdehip.getPoints(moved), o[pre + "map"])
+        _rel12(f"transport.{pre}to_p model", o[pre + "to_p"][c.sub], em.direct_fsum(_rows(o[pre + "map"]), c.A[1], c.A[2], X))
+    # equalize: equal weights transported onto p as it is, one refit with both
+    u = np.full(c.N, 1.0 / c.N)
+    out, info = c.p.equalize(return_info=True, **ec.OT)
+    _ot_against("transport", ec._ot_item(info, "eq_"), "eq_", tm.iterate((c.A[0], u), vp, s_self, *kw))
+    rm.same_bits(_tree(o, "eq_"), out, "transport.eq_ run after run")
+    rm.same_bits(out, rf.refit_host(c.p, new_weights=u, delta=info["delta"]), "transport.eq_ is one refit")
+    _rel12("transport.eq_p model", o["eq_p"][c.sub], em.direct_fsum(_rows(info["map"]), u, c.A[2], X))
+
+
 CHECKS = {name[len("_check_"):]: fn for name, fn in list(globals().items()) if name.startswith("_check_")}
 
 # ---- positions under translation: the untranslated output plus t, within a bound stated per output --------------------------
@@ -781,6 +884,9 @@ _POSITION = {
     ("summary", "mean"): (_ALL, 130.0, 0.0), ("summary", "fit_mean"): (_ALL, 130.0, 0.0),
     # lo - dr, hi + dr: one rounding (observed 0); the grid point lo + k h: k h, the sum and h itself, three (observed 0.8)
     ("summary", "range"): (_ALL, 1.0, 0.0), ("summary", "linspace"): (None, 3.0, 0.0),
+    # the image of a point is fl(x + m), m the displacement, which is formed from differences and keeps its bits: the sum's
+    # rounding at 2^20, half a spacing; the base's own rounding is far below it
+    ("transport", "map"): (_ALL, 1.0, 0.0), ("transport", "s_map"): (_ALL, 1.0, 0.0), ("transport", "self_map"): (_ALL, 1.0, 0.0),
 }
 
 

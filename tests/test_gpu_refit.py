@@ -2,8 +2,10 @@
 `DeviceDensity.changeWeights / movePoints / bayes_update / refit_batch` against the host entry kdehip_density_refit -- which
 tests/test_refit_host.py pins to a rebuild by `kde` and to the NumPy model -- BIT FOR BIT (G1), as an input of the sampler and
 of the other consumers (G2, G3: the test of the packers' recomputed facts), the Bayes update against the formula in extended
-precision with the bounds of the host test (G4), batches (G5), the two index conventions (G6), repeatability (G7) and the
-scaling law (G8).
+precision with the bounds of the host test (G4), batches (G5), the two index conventions (G6), repeatability (G7), the
+scaling law (G8), a density of one point (G9), a source with a bandwidth per point (G10), a tree built with circular
+operators, built and uploaded, alone and in a batch with a Euclidean item (G11), and more chunks than the fold's tile holds
+(G12).  The refit of an UPLOADED density has no arrays to download: it is compared as an input of the consumers.
 
 Shapes: two leaves is the smallest tree; 129 and 1025 cross a power of two (uneven heights); 5000 has heights wider than a
 workgroup, so it runs one launch per height as well as the one-workgroup top.  Every source is built once and never changed."""
@@ -310,3 +312,162 @@ def test_g8_exact_rescaling_of_points_bandwidths_and_delta(k):
             assert np.ldexp(base[f], k).tobytes() == scaled[f].tobytes(), f
         for f in ("bandwidth", "bandwidthMin", "bandwidthMax"):
             assert np.ldexp(base[f], 2 * k).tobytes() == scaled[f].tobytes(), f
+
+
+# ---- G9: one point -----------------------------------------------------------------------------------------------------------
+def _all_dims(dd):
+    """a BUILT twin of an uploaded density without a bandwidth search (as G8): its marginal over all dimensions"""
+    return dd.marginal(list(range(dd.dims)))
+
+
+def _same_consumers(res, host_refit, pos, manifold=None):
+    """G3's checks of a result whose arrays cannot be downloaded (the source was uploaded): as an input of evaluate,
+    evaluate_log and sample it gives the bits of the uploaded host refit"""
+    with kdehip.DeviceDensity(host_refit) as up:
+        kw = {} if manifold is None else dict(manifold=manifold)
+        assert res.evaluate(pos, **kw).tobytes() == up.evaluate(pos, **kw).tobytes()
+        assert res.evaluate_log(pos, **kw).tobytes() == up.evaluate_log(pos, **kw).tobytes()
+        if res.num_points > 1:
+            assert res.evaluate_log(lvFlag=True, **kw).tobytes() == up.evaluate_log(lvFlag=True, **kw).tobytes()
+        (x1, l1), (x2, l2) = kdehip.sample(res, 300, seed=9), kdehip.sample(up, 300, seed=9)
+        assert l1.tobytes() == l2.tobytes() and x1.tobytes() == x2.tobytes()
+
+
+@pytest.mark.parametrize("source", ["built", "uploaded"])
+@pytest.mark.parametrize("D", [1, 6])
+def test_g9_a_density_of_one_point(D, source):
+    """N = 1: the tree is its root with the one leaf as both children (the `left[0] != 2` case of ensure_table), no internal
+    node of two children.  Id 1 is the root AND "slot N": the arrays of a moved built density once kept the source's box there
+    (the copy that preserves the unused slot N of larger trees), which the comparison of `centers` after a move holds now."""
+    rng = np.random.default_rng(900 + D)
+    hp = kdehip.kde(_points(rng, D, 1), rng.uniform(0.2, 0.6, size=D))
+    assert hp.bt.left_child[0] == 2
+    w, delta, logl = np.array([0.75]), rng.standard_normal((D, 1)), np.array([-3.5])
+    pos = _points(rng, D, 40)
+    wants = [hp.changeWeights(w), hp.movePoints(delta), rf.refit_host(hp, new_weights=w, delta=delta)]
+    hb, le_h, ess_h = hp.bayes_update(logl)
+    with kdehip.DeviceDensity(hp) as up:
+        dd = _all_dims(up) if source == "built" else up
+        try:
+            if source == "built":
+                rm.same_bits(dd.download(), hp, "the built twin is the host density")
+            gots = [dd.changeWeights(w), dd.movePoints(delta), rf.refit_device(dd, w, rf.WEIGHTS, delta)[0]]
+            db, le, ess = dd.bayes_update(logl)
+            assert abs(le - le_h) <= 1e-12 * max(1.0, abs(le_h)) and abs(ess - 1.0) <= 1e-12 and abs(ess_h - 1.0) <= 1e-12
+            for got, want, what in zip(gots + [db], wants + [hb], ("weights", "delta", "both", "bayes")):
+                if source == "built":
+                    if what == "bayes":
+                        _check_bayes(dd, hp, logl, got, le, ess)
+                    else:
+                        rm.same_bits(got.download(), want, what)
+                    assert got.evaluate(pos).tobytes() == kdehip.evaluateDualTree(got.download(), pos).tobytes(), what
+                else:
+                    _same_consumers(got, want, pos)
+                got.close()
+        finally:
+            if dd is not up:
+                dd.close()
+
+
+# ---- G10: a source with a bandwidth per point ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("D,N", [(2, 129), (6, 1025)])
+def test_g10_a_per_point_bandwidth_source(D, N):
+    """`kde_varbw` as H2 of the host test builds it, uploaded: the leaves keep their own variances through the copy, and the
+    internal nodes' are recomputed from them"""
+    rng = np.random.default_rng(11 * D + N)
+    hp = kdehip.kde_varbw(_points(rng, D, N), rng.uniform(0.1, 0.9, size=(D, N)), rng.uniform(0.1, 1.0, size=N))
+    assert hp.multibandwidth == 1
+    w, delta = _weights(rng, N), rng.standard_normal((D, N)) * 0.2
+    pos = _points(rng, D, 300)
+    with kdehip.DeviceDensity(hp) as dd:
+        with dd.changeWeights(w) as a:
+            _same_consumers(a, hp.changeWeights(w), pos)
+        with dd.movePoints(delta) as b:
+            _same_consumers(b, hp.movePoints(delta), pos)
+        with rf.refit_device(dd, w, rf.WEIGHTS, delta)[0] as ab:
+            _same_consumers(ab, rf.refit_host(hp, new_weights=w, delta=delta), pos)
+
+
+# ---- G11: a tree built with circular operators --------------------------------------------------------------------------------
+TMAN = ["euclid", "circular"]
+
+
+def _across_the_cut(N=200):
+    """H3's data: one cluster of angles on both sides of the cut at +-pi, and moves that carry some of them across it"""
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal(N)
+    th = rm.PI - np.abs(rng.standard_normal(N)) * 0.2
+    th[::2] = -rm.PI + np.abs(rng.standard_normal(N // 2)) * 0.2
+    pts = np.stack([x, th])
+    w0 = rng.uniform(0.1, 1.0, size=N)
+    delta = np.stack([rng.standard_normal(N) * 0.1, rng.uniform(-0.5, 0.5, size=N)])
+    assert (np.abs(th + delta[1]) > rm.PI).any() and (np.abs(th + delta[1]) < rm.PI).any()
+    return pts, w0, delta, _weights(rng, N)
+
+
+def test_g11_a_circular_tree_built_on_the_device():
+    """the `circ_wrap` branch of leaf_kernel and the circular boxes of refit_node, against the host entry bit for bit"""
+    pts, _, delta, w = _across_the_cut()
+    N = pts.shape[1]
+    d_pts = _dev(pts.T)
+    _torch().cuda.synchronize()
+    with kdehip.DeviceDensity.from_device_points(d_pts, 2, N, tree_manifold=TMAN) as dd:
+        hp = dd.download()
+        assert list(hp.tree_manifold) == [0, 1]
+        assert (hp.bt.ranges[:(N - 1) * 2][1::2] < 1.0).all()   # the premise: the boxes of the angle are the short way round
+        moved = dd.movePoints(delta)
+        assert np.array_equal(moved.tree_manifold, dd.tree_manifold)
+        want = hp.movePoints(delta)
+        rm.same_bits(moved.download(), want, "delta")
+        th = kdehip.getPoints(want)[1]
+        assert (th >= -rm.PI).all() and (th < rm.PI).all()
+        rm.same_bits(dd.changeWeights(w).download(), hp.changeWeights(w), "weights")
+        rm.same_bits(rf.refit_device(dd, w, rf.WEIGHTS, delta)[0].download(), rf.refit_host(hp, new_weights=w, delta=delta), "both")
+        rm.same_bits(dd.changeWeights(kdehip.getWeights(hp)).download(), hp, "the circular boxes are recomputed to the same bits")
+        rm.same_bits(moved.movePoints(-delta).changeWeights(w).download(), want.movePoints(-delta).changeWeights(w), "a refit of a refit")
+        # a batch mixes it with a Euclidean item of the same D: circular_mask differs per item
+        flat, hflat = _built(2, 129)
+        rng = np.random.default_rng(77)
+        d2 = rng.standard_normal((2, 129)) * 3.0   # (moves beyond pi, which a Euclidean item must not wrap)
+        out = kdehip.DeviceDensity.refit_batch([dict(density=dd, weights=w, delta=delta), dict(density=flat, delta=d2),
+                                                dict(density=dd, delta=delta)])
+        rm.same_bits(out[0][0].download(), rf.refit_host(hp, new_weights=w, delta=delta), "batch: circular")
+        rm.same_bits(out[1][0].download(), hflat.movePoints(d2), "batch: Euclidean")
+        rm.same_bits(out[2][0].download(), want, "batch: circular again")
+        assert (np.abs(kdehip.getPoints(out[1][0].download())) > rm.PI).any()
+
+
+def test_g11_a_circular_tree_uploaded():
+    pts, w0, delta, w = _across_the_cut()
+    hp = kdehip.kde(pts, [0.3, 0.2], w0, tree_manifold=TMAN)
+    rng = np.random.default_rng(6)
+    pos = np.stack([rng.standard_normal(300), rng.uniform(-rm.PI, rm.PI, size=300)])
+    with kdehip.DeviceDensity(hp) as dd:
+        for man in (None, TMAN):
+            with dd.movePoints(delta) as a:
+                assert np.array_equal(a.tree_manifold, hp.tree_manifold)
+                _same_consumers(a, hp.movePoints(delta), pos, man)
+            with dd.changeWeights(w) as b:
+                _same_consumers(b, hp.changeWeights(w), pos, man)
+            with rf.refit_device(dd, w, rf.WEIGHTS, delta)[0] as ab:
+                _same_consumers(ab, rf.refit_host(hp, new_weights=w, delta=delta), pos, man)
+        flat = _uploaded(2, 200)
+        out = kdehip.DeviceDensity.refit_batch([dict(density=dd, delta=delta), dict(density=flat[0], delta=delta * 8.0)])
+        _same_consumers(out[0][0], hp.movePoints(delta), pos, TMAN)
+        _same_consumers(out[1][0], flat[1].movePoints(delta * 8.0), pos)
+
+
+# ---- G12: more than 1024 chunks ---------------------------------------------------------------------------------------------------
+def test_g12_the_fold_makes_a_second_trip_through_its_tile():
+    """(1, 131201): 1026 chunks of 128 leaves, so fold_kernel stages 1024 chunk partials, adds them, and comes back for two"""
+    D, N = 1, 131201
+    assert (N + 127) // 128 == 1026
+    dd, hp = _built(D, N)
+    rng = np.random.default_rng(131201)
+    logl = rng.uniform(-1000.0, 0.0, size=N) - 2000.0
+    logl[1] = -np.inf
+    res, le, ess = dd.bayes_update(_dev(logl))
+    _check_bayes(dd, hp, logl, res, le, ess)
+    w, delta = _weights(rng, N), rng.standard_normal((D, N)) * 0.3
+    rm.same_bits(dd.changeWeights(w).download(), hp.changeWeights(w), "weights")
+    rm.same_bits(dd.movePoints(delta).download(), hp.movePoints(delta), "delta")

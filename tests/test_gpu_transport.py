@@ -9,7 +9,10 @@ Tolerances, none of them taken from the code under test:
   mean         |sum a T - sum b y|_inf <= err * max |T| + 1e-12 * max |y|: the row error is all that moves the mean
 The sizes: 129 and 257 leave a second chunk / a second query block with one leaf, every fifth weight is 0 on both sides
 (weightless sources and queries), and (2, 8193, 300) is where a group of the second half-step walks two chunks and the
-carried sum is rescaled.  Every case runs in well under a second on the device; the model is computed once per case."""
+carried sum is rescaled; G10 does the same to the first half-step, the map pass and a self item, G11 empties whole chunks
+and groups of sources, G12 takes the scale from the caller, G13 stops on the boundaries of the rounds of eight iterations,
+G14 moves a tree built with circular operators without leaving the device.  Every case runs in well under a second on the
+device; the model is computed once per case (the row-blocked one of G10's self item takes a few seconds)."""
 import math
 
 import numpy as np
@@ -321,6 +324,187 @@ def test_g9_equalize_is_the_ensemble_transform():
             assert drift <= bound
             with dw.equalize(reg=1.0) as dout:
                 rm.same_bits(dout.download(), out, "the resident route")
+
+
+# ---- G10: several chunks a group on side 0 and in the map pass ----------------------------------------------------------------
+def _check_all(info, want):
+    """every output of an item: potentials and scalars (`_check_item`), the map, and the displacement at the map's size (G5)"""
+    _check_item(info, want)
+    _close("map", info["map"], want["map"])
+    _close("delta", info["delta"], want["delta"], np.maximum(1.0, np.abs(want["map"])))
+
+
+@pytest.mark.parametrize("D,N,M", [(3, 130, 8193), (6, 130, 8321)])
+def test_g10_several_chunks_a_group_on_side_0_and_in_the_map_pass(D, N, M):
+    """q is the large side: its 65 (66) chunks are the SOURCES of the first half-step and of the map pass and go to groups of
+    two, so `total` of ot_partial_kernel<SIDE = 0> and the D + 2 carried sums of ot_map_kernel are rescaled between the chunks
+    of a group; p's two chunks on side 1 stay one a group.  8193 leaves a last group of one chunk of one point, 8321 a last
+    group whose second chunk is partial.  Two steps: the second one's first half reads the gamma the first one made."""
+    assert chunks_per_group(M, N) == 2 and chunks_per_group(N, M) == 1
+    c = _case(D, N, M)
+    want = _model(c, False, 1.0, 0.0, 2)
+    info = c["p"].sinkhorn(c["q"], reg=1.0, tol=0.0, maxiter=2, return_info=True)[1]
+    assert info["iters"] == -2
+    _check_all(info, want)
+
+
+def test_g10_a_self_item_with_two_chunks_a_group():
+    """(1, 8193) against itself: 65 chunks in groups of two on the only side there is.  The model is the row-blocked one (the
+    dense one would hold several GB), which tests/test_transport_host.py holds to the dense one; one step keeps it short."""
+    assert chunks_per_group(8193, 8193) == 2
+    (x, a), _ = tm.two_clusters_pair(1, 8193, 129)
+    p = kdehip.kde(x, tm.silverman(x), a)
+    vp = _views(p)
+    want = tm.iterate_blocked(vp, None, tm.default_scale(_variances(p), _variances(p)), 1.0, 0.0, 1)
+    info = p.sinkhorn(p, reg=1.0, tol=0.0, maxiter=1, return_info=True)[1]
+    assert info["iters"] == want["iters"] == -1
+    _check_all(info, want)
+    assert np.array_equal(info["gamma"], info["phi"])
+
+
+# ---- G11: whole chunks and whole groups of weightless sources ----------------------------------------------------------------
+def _weightless(p, runs):
+    """p with the leaf positions [lo, hi) of every run made weightless (through the permutation, as tests/test_gpu_refit.py's
+    `_runs_of_zeros`), the rest renormalised: the same tree"""
+    N = p.bt.num_points
+    w = kdehip.getWeights(p).copy()
+    for lo, hi in runs:
+        w[p.bt.permutation[N + lo:N + hi] - 1] = 0.0
+    out = p.changeWeights(w / w.sum())
+    assert np.array_equal(out.bt.permutation, p.bt.permutation)
+    for lo, hi in runs:
+        assert not out.bt.weights[N + lo:N + hi].any()
+    return out
+
+
+@pytest.mark.parametrize("D,N,M,side,runs", [(2, 130, 300, "q", [(128, 256)]), (2, 300, 130, "p", [(128, 256)]),
+                                             (3, 130, 8193, "q", [(0, 128), (256, 512)])])
+def test_g11_weightless_chunks_and_groups(D, N, M, side, runs):
+    """300 sources are three chunks in three groups: positions 128..255 weightless empty group 1 -- of side 0 and the map pass
+    when they are q's, of side 1 when they are p's -- which leaves (-Inf, 0) and is skipped by `mg > -INFINITY`.  8193 sources
+    go two chunks a group: positions 0..127 empty the FIRST chunk of group 0 (m stays -Inf, and the rescale of the still zero
+    sums by exp_nonpos(-Inf) must give 0 and no NaN), positions 256..511 all of group 1.  The model leaves weightless leaves
+    out by their value; p's weightless leaves still move (section 5s)."""
+    big = max(N, M)
+    assert chunks_per_group(big, min(N, M)) == (2 if big > 8192 else 1)
+    c = _case(D, N, M)
+    p, q = (_weightless(c["p"], runs), c["q"]) if side == "p" else (c["p"], _weightless(c["q"], runs))
+    vp, vq = _views(p), _views(q)
+    leaves = (p if side == "p" else q).bt.permutation[(N if side == "p" else M):] - 1
+    for lo, hi in runs:
+        assert not (vp if side == "p" else vq)[1][leaves[lo:hi]].any()
+    want = tm.iterate(vp, vq, c["s"], 1.0, 0.0, 2)
+    info = p.sinkhorn(q, reg=1.0, tol=0.0, maxiter=2, return_info=True)[1]
+    assert info["iters"] == -2
+    for k in ("phi", "gamma", "map", "delta"):
+        assert np.all(np.isfinite(info[k])), k
+    _check_all(info, want)
+
+
+# ---- G12: a scale from the caller ----------------------------------------------------------------------------------------------
+def test_g12_an_explicit_scale():
+    """`write_scale`: the model at the caller's scale; host, resident and batch give the same bits, the batch with two items
+    on the SAME pair at different scales (and one at the default); a per-point-bandwidth q, which must have a scale"""
+    D, N, M = 3, 300, 257
+    c = _case(D, N, M)
+    p, q = c["p"], c["q"]
+    s1, s2 = np.array([0.7, 1.3, 2.1]), np.array([2.1, 0.7, 1.3])
+    kw = dict(reg=1.0, tol=0.0, maxiter=5)
+    h1 = p.sinkhorn(q, scale=s1, return_info=True, **kw)[1]
+    h2 = p.sinkhorn(q, scale=s2, return_info=True, **kw)[1]
+    h0 = p.sinkhorn(q, return_info=True, **kw)[1]
+    _check_all(h1, tm.iterate(c["vp"], c["vq"], s1, 1.0, 0.0, 5))
+    _check_all(h2, tm.iterate(c["vp"], c["vq"], s2, 1.0, 0.0, 5))
+    assert h1["value"] != h2["value"] != h0["value"]
+    leaf = p.bt.permutation[N:] - 1
+    with kdehip.DeviceDensity(p) as dp, kdehip.DeviceDensity(q) as dq:
+        items = [dict(p=dp, q=dq, scale=s1), dict(p=dp, q=dq, scale=s2), dict(p=dp, q=dq), dict(p=dp, q=dp, scale=s1)]
+        single = [it["p"].sinkhorn(it["q"], scale=it.get("scale"), return_info=True, **kw)[1] for it in items]
+        batch = kdehip.DeviceDensity.sinkhorn_batch(items, vectors=True, **kw)
+        for k, (one, b) in enumerate(zip(single, batch)):
+            _same_item(b, one, f"batch item {k}")
+        for h, one in ((h1, single[0]), (h2, single[1]), (h0, single[2]), (p.sinkhorn(p, scale=s1, return_info=True, **kw)[1], single[3])):
+            for k in _SCALARS:
+                assert np.float64(h[k]).tobytes() == np.float64(one[k]).tobytes(), k
+            for k in ("phi", "gamma", "map"):
+                assert np.array_equal(h[k], one[k].cpu().numpy()), k
+            assert np.array_equal(h["delta"][:, leaf], one["delta_leaf"].cpu().numpy())
+    rng = np.random.default_rng(12)
+    y, b = c["vq"]
+    qv = kdehip.kde_varbw(y, tm.silverman(y)[:, None] * rng.uniform(0.5, 2.0, size=(D, M)), b)
+    assert qv.multibandwidth == 1
+    want = tm.iterate(c["vp"], _views(qv), s1, 1.0, 0.0, 5)   # (the model never reads a bandwidth)
+    hv = p.sinkhorn(qv, scale=s1, return_info=True, **kw)[1]
+    _check_all(hv, want)
+    with kdehip.DeviceDensity(p) as dp, kdehip.DeviceDensity(qv) as dv:
+        rv = dp.sinkhorn(dv, scale=s1, return_info=True, **kw)[1]
+        for k in _SCALARS:
+            assert np.float64(hv[k]).tobytes() == np.float64(rv[k]).tobytes(), k
+        assert np.array_equal(hv["phi"], rv["phi"].cpu().numpy()) and np.array_equal(hv["map"], rv["map"].cpu().numpy())
+
+
+# ---- G13: maxiter on the boundaries of the rounds ------------------------------------------------------------------------------
+ROUND_EDGES = [7, 8, 9, 16]   # rounds() runs maxiter + 1 iterations in rounds of 8: the last of a round, the first and the
+# second of the next one, and the first of the third
+
+
+@pytest.mark.parametrize("self_item", [False, True])
+@pytest.mark.parametrize("maxiter", ROUND_EDGES)
+def test_g13_stopping_by_maxiter_on_a_round_boundary(maxiter, self_item):
+    c = _case(2, 257, 129)
+    p, q = c["p"], (c["p"] if self_item else c["q"])
+    want = _model(c, self_item, 1.0, 0.0, maxiter)
+    info = p.sinkhorn(q, reg=1.0, tol=0.0, maxiter=maxiter, return_info=True)[1]
+    assert want["iters"] == -maxiter and info["iters"] == -maxiter
+    _check_all(info, want)
+
+
+def test_g13_a_batch_of_items_that_stop_in_different_rounds():
+    c = _case(2, 257, 129)
+    with kdehip.DeviceDensity(c["p"]) as dp, kdehip.DeviceDensity(c["q"]) as dq:
+        items = [dict(p=dp, q=dq, maxiter=m) for m in ROUND_EDGES]
+        batch = kdehip.DeviceDensity.sinkhorn_batch(items, reg=1.0, tol=0.0, vectors=True)
+        for it, b in zip(items, batch):
+            one = dp.sinkhorn(dq, reg=1.0, tol=0.0, maxiter=it["maxiter"], return_info=True)[1]
+            assert b["iters"] == -it["maxiter"]
+            _same_item(b, one, f"maxiter {it['maxiter']}")
+            host = c["p"].sinkhorn(c["q"], reg=1.0, tol=0.0, maxiter=it["maxiter"], return_info=True)[1]
+            assert np.array_equal(host["phi"], one["phi"].cpu().numpy()) and host["value"] == one["value"]
+
+
+# ---- G14: a tree built with circular operators, resident ----------------------------------------------------------------------
+def test_g14_a_circular_tree_moves_on_the_device_as_on_the_host():
+    """both densities are built on the device with circular operators in dimension 1 (a moved density can be downloaded only
+    if its source was built by the library); the host route runs on their downloaded arrays"""
+    import torch
+    man = ["euclid", "circular"]
+    (x, a), (y, b) = tm.angle_pair()
+    dx, dy = _dev(x.T), _dev(y.T)
+    torch.cuda.synchronize()
+    kw = dict(reg=1.0, tol=TOL, manifold=man)
+    with kdehip.DeviceDensity.from_device_points(dx, 2, x.shape[1], tree_manifold=man) as dp, \
+            kdehip.DeviceDensity.from_device_points(dy, 2, y.shape[1], tree_manifold=man) as dq:
+        p, q = dp.download(), dq.download()
+        assert list(p.tree_manifold) == [0, 1] and list(dp.tree_manifold) == [0, 1]
+        T, info = p.transport_map(q, return_info=True, **kw)
+        assert info["iters"] > 0
+        moved = p.transport_to(q, **kw)
+        assert np.array_equal(moved.tree_manifold, p.tree_manifold)
+        rm.same_bits(moved, p.movePoints(info["delta"]), "transport_to is movePoints(delta) with the tree's operators")
+        pts = kdehip.getPoints(moved)
+        assert np.array_equal(pts, T)
+        assert np.all(pts[1] >= -math.pi) and np.all(pts[1] < math.pi)
+        assert (np.abs(_views(p)[0][1] + info["delta"][1]) > math.pi).any()   # the premise: some sums left [-pi, pi) and were wrapped
+        even = p.equalize(**kw)
+        assert np.array_equal(kdehip.getWeights(even), np.full(len(a), 1.0 / len(a)))
+        th = kdehip.getPoints(even)[1]
+        assert np.all(th >= -math.pi) and np.all(th < math.pi)
+        with dp.transport_to(dq, **kw) as dm:
+            assert np.array_equal(dm.tree_manifold, dp.tree_manifold)
+            rm.same_bits(dm.download(), moved, "transport_to, the resident route")
+        assert np.array_equal(dp.transport_map(dq, **kw).cpu().numpy(), T)
+        with dp.equalize(**kw) as de:
+            rm.same_bits(de.download(), even, "equalize, the resident route")
 
 
 # ---- the refusals that read a handle ----------------------------------------------------------------------------------------

@@ -111,7 +111,7 @@ def test_h2_per_point_bandwidths_with_their_extremes(D, N):
 
 
 # ---- H3 ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,N", [(1, 2), (2, 5), (3, 129), (8, 200), (2, 1000)])
+@pytest.mark.parametrize("D,N", [(1, 1), (6, 1), (1, 2), (2, 5), (3, 129), (8, 200), (2, 1000)])
 def test_h3_moved_points_equal_the_model(D, N):
     pts, rng = _points(13 * D + N, D, N)
     p = kdehip.kde(pts, rng.uniform(0.2, 0.6, size=D), rng.uniform(0.1, 1.0, size=N))

@@ -285,3 +285,84 @@ def test_model_angle_pair_across_the_cut_of_the_circle():
     assert np.all(circle["map"][1] >= -math.pi) and np.all(circle["map"][1] < math.pi)
     shifted = tm.iterate((x + np.array([[0.0], [2.0 * math.pi]]), a), (y, b), s, 1.0, 1e-6, 5000, [0, 1])
     assert abs(shifted["value"] - circle["value"]) <= 1e-9
+
+
+def _rel13(name, got, want):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    bound = 1e-13 * np.maximum(1.0, np.abs(want))
+    assert np.all(np.abs(got - want) <= bound), (name, float(np.max(np.abs(got - want) / bound)))
+
+
+@pytest.mark.parametrize("rows", [128, 1024])
+@pytest.mark.parametrize("self_item", [False, True])
+def test_model_blocked_iteration_equals_the_dense_one(self_item, rows):
+    """(2, 300, 257): 128 rows a block gives three blocks a side, the last one partial; 1024 is the default (one block).  1e-13
+    relative to max(1, |.|): the blocks add the same numbers, and only the second half-step differs in how it is written
+    (the rows of the transposed cost from diff(y, x) in the place of the columns of the cost from diff(x, y))"""
+    (x, a), (y, b) = tm.two_clusters_pair(2, 300, 257)
+    s = np.array([0.7, 0.9])
+    q = None if self_item else (y, b)
+    for maxiter, tol in ((3, 0.0), (1000, 1e-6)):
+        want = tm.iterate((x, a), q, s, 2.0, tol, maxiter)
+        got = tm.iterate_blocked((x, a), q, s, 2.0, tol, maxiter, rows=rows)
+        assert got["iters"] == want["iters"] and len(got["errs"]) == len(want["errs"])
+        for name in ("phi", "gamma", "delta", "map", "value", "transport_cost", "err", "mass", "errs"):
+            _rel13(name, got[name], want[name])
+    (ax, aa), (ay, ab) = tm.angle_pair()
+    want = tm.iterate((ax, aa), (ay, ab), np.array([0.5, 0.3]), 1.0, 0.0, 4, [0, 1])
+    got = tm.iterate_blocked((ax, aa), (ay, ab), np.array([0.5, 0.3]), 1.0, 0.0, 4, [0, 1], rows=16)
+    for name in ("phi", "gamma", "delta", "map", "value", "transport_cost", "err", "mass"):
+        _rel13("circular " + name, got[name], want[name])
+
+
+_LAW_K = (-80, -30, 30, 80)
+_BITS0 = ("phi", "gamma", "value", "transport_cost", "err", "mass", "iters")
+
+
+def _law_pair(lattice):
+    """(5, 257, 129), every fifth weight 0; lattice: every coordinate a multiple of 2^-20"""
+    (x, a), (y, b) = tm.two_clusters_pair(5, 257, 129)
+    s = np.random.default_rng(12).uniform(0.5, 1.5, size=5)
+    if lattice:
+        x, y = np.round(x * 2.0 ** 20) / 2.0 ** 20, np.round(y * 2.0 ** 20) / 2.0 ** 20
+    return (x, a), (y, b), s
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).tobytes()
+
+
+@pytest.mark.parametrize("self_item", [False, True])
+def test_model_obeys_the_rescaling_laws_of_the_equivariance_table(self_item):
+    """the laws tests/equivariance_cases.py states for the `transport` row, in the model itself -- so that a wrong law is told
+    apart from a wrong kernel: with the points and the scale multiplied by 2^k exactly, every difference, its square and the
+    factor 1 / (2 s^2) scale exactly, the cost keeps its bits, and with it the potentials and every scalar; the displacement
+    and the map are the base's times 2^k"""
+    (x, a), (y, b), s = _law_pair(False)
+    q = None if self_item else (y, b)
+    base = tm.iterate((x, a), q, s, 1.0, 0.0, 8)
+    assert base["iters"] == -8
+    for k in _LAW_K:
+        qk = None if self_item else (np.ldexp(y, k), b)
+        got = tm.iterate((np.ldexp(x, k), a), qk, np.ldexp(s, k), 1.0, 0.0, 8)
+        for name in _BITS0:
+            assert _bits(got[name]) == _bits(base[name]), (k, name)
+        for name in ("delta", "map"):
+            assert _bits(got[name]) == _bits(np.ldexp(base[name], k)), (k, name)
+
+
+@pytest.mark.parametrize("self_item", [False, True])
+def test_model_obeys_the_translation_laws_of_the_equivariance_table(self_item):
+    """inputs on the 2^-20 lattice below 2^6 and offsets of +-2^20, +-3 2^19: x + t is exact, every difference is the
+    untranslated one, so all that is formed from differences keeps its bits; the map is a position -- fl(x + t + m) is within
+    half a spacing of doubles at 2^20 of fl(x + m) + t"""
+    (x, a), (y, b), s = _law_pair(True)
+    assert np.abs(x).max() < 2.0 ** 6 and np.abs(y).max() < 2.0 ** 6
+    t = np.array([2.0 ** 20, -3.0 * 2.0 ** 19, 3.0 * 2.0 ** 19, -2.0 ** 20, 2.0 ** 20])[:, None]
+    assert np.array_equal((x + t) - t, x) and np.array_equal((y + t) - t, y)
+    base = tm.iterate((x, a), None if self_item else (y, b), s, 1.0, 0.0, 8)
+    got = tm.iterate((x + t, a), None if self_item else (y + t, b), s, 1.0, 0.0, 8)
+    for name in _BITS0 + ("delta",):
+        assert _bits(got[name]) == _bits(base[name]), name
+    sp = float(np.spacing(np.abs(got["map"]).max()))
+    assert sp == 2.0 ** -32 and np.abs((got["map"] - t) - base["map"]).max() <= sp

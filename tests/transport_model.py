@@ -106,6 +106,68 @@ def iterate(p, q, s, reg, tol, maxiter, man=None):
                 delta=delta, map=T, errs=np.array(errs))
 
 
+def iterate_blocked(p, q, s, reg, tol, maxiter, man=None, rows=1024):
+    """`iterate`, the same formulas `rows` rows of the cost at a time: no array larger than (rows, max(N, M)) per dimension is
+    ever formed, so a self item of 8193 points costs megabytes where the dense model needs gigabytes.  The second half-step
+    takes the rows of the transposed cost from diff(y_j, x_i) = -diff(x_i, y_j).  Held to `iterate` by
+    tests/test_transport_host.py; `errs` is returned as in `iterate`."""
+    x, a = np.asarray(p[0], dtype=np.float64), np.asarray(p[1], dtype=np.float64)
+    self_item = q is None
+    y, b = (x, a) if self_item else (np.asarray(q[0], dtype=np.float64), np.asarray(q[1], dtype=np.float64))
+    eps = float(reg)
+    N, M = len(a), len(b)
+    la, lb = _logw(a), _logw(b)
+
+    def half(u, v, l):
+        """-LSE_j (l_j - c(u_i, v_j) / eps) for every column i of u"""
+        out = np.empty(u.shape[1])
+        for i0 in range(0, u.shape[1], rows):
+            A = -cost(u[:, i0:i0 + rows], v, s, man) / eps
+            out[i0:i0 + rows] = _neg_lse(A + l[None, :])
+        return out
+
+    phi, gamma = np.zeros(N), np.zeros(M)
+    steps, errs = 0, []
+    while True:
+        tau = half(x, y, lb + gamma)
+        r = np.exp(phi - tau)
+        err = _dot(a, np.abs(r - 1.0))
+        mass = _dot(a, r)
+        errs.append(err)
+        if (steps >= 1 and err <= tol) or steps == maxiter:
+            break
+        if self_item:
+            phi = 0.5 * (phi + tau)
+            gamma = phi
+        else:
+            phi = tau
+            gamma = half(y, x, la + phi)
+        steps += 1
+    value = eps * (_dot(a, phi) + _dot(b, gamma) - (mass - 1.0))
+    delta, m, rowsum = np.empty(x.shape), np.empty(N), np.empty(N)
+    for i0 in range(0, N, rows):
+        xb = x[:, i0:i0 + rows]
+        d = diffs(xb, y, man)
+        c = cost(xb, y, s, man)
+        Z = -c / eps + (lb + gamma)[None, :]
+        mb = Z.max(axis=1)
+        with np.errstate(under="ignore"):
+            e = np.exp(Z - mb[:, None])
+        S0 = e.sum(axis=1)
+        for k in range(d.shape[0]):
+            delta[k, i0:i0 + rows] = -(e * d[k]).sum(axis=1) / S0
+        m[i0:i0 + rows] = mb
+        rowsum[i0:i0 + rows] = (e * c).sum(axis=1)
+    T = x + delta
+    if man is not None:
+        for k in np.flatnonzero(np.asarray(man, dtype=bool)):
+            T[k] = wrap(T[k])
+    use = np.flatnonzero(a > 0)
+    tcost = math.fsum(float(a[i]) * math.exp(float(phi[i] + m[i])) * float(rowsum[i]) for i in use)
+    return dict(value=value, transport_cost=tcost, err=err, mass=mass, iters=steps if err <= tol else -steps, phi=phi, gamma=gamma,
+                delta=delta, map=T, errs=np.array(errs))
+
+
 def plan(p, q, s, reg, phi, gamma, man=None):
     """pi (N, M) = a_i b_j exp(phi_i + gamma_j + A_ij), from potentials alone"""
     A = -cost(p[0], q[0], s, man) / float(reg)
