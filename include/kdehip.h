@@ -1811,6 +1811,77 @@ typedef struct kdehip_sinkhorn_item {
  * results are bit for bit those of kdehip_sinkhorn_device at the same scale.  One bad item fails the whole call. */
 int kdehip_sinkhorn_device_batch(int n, const kdehip_sinkhorn_item *items);
 
+/* ---- (5t) compression: a density cut to M of its own points by kernel herding (csrc/compress.hip) ------------------------
+ * The library's own; the reference has no counterpart.  resample and sample go from N points to M at random and repeat
+ * points; herding picks, one after another, the points of p that best match p's kernel mean embedding, and the MMD of the
+ * equal-weight density on the picks falls like 1/M where random subsets give 1/sqrt(M).
+ *   c_i (i < N) are the leaf points of p in tree order, alpha_i their weights as the density holds them, o(i) their original
+ *     index (0-based; the permutation's leaf row minus 1).
+ *   v_k are the kernel variances: the caller's var (D entries), or with var = NULL twice p's leaf variance -- the quantity
+ *     minimised is then, up to the Gaussian constant, the integrated squared error between p and the equal-weight density on
+ *     the picks at p's own bandwidth (what `ise` measures).  nh_k = -0.5 / v_k.
+ *   Exponent: a(s, j) = sum_k fma(d_k^2, nh_k, acc), k ascending from acc = 0, d_k = c_jk - c_sk, through wrap() in a
+ *     circular dimension (5d): the expression and fma order of the direct kernel, leaf j the query and leaf s the source.
+ *   Kernel mean: z_j = sum_i alpha_i exp(a(i, j)), by the all-pairs sweep in the summation order of 5b: the 128-leaf chunks of
+ *     a group in order, then the groups in ascending order (the split depends on N alone).
+ *   Self sum: self_sum = sum_j alpha_j z_j: 256 partial sums, sum t over j = t, t + 256, .. ascending, combined in the fixed
+ *     256-wide tree of 5b.
+ *   Steps, t = 0 .. M-1, from r_j = 0:
+ *     score_j = z_j - r_j * inv_t, inv_t = 1.0 / (double)(t + 1) (a correctly rounded division); the product and the
+ *       difference are each rounded: NO fused multiply-add, so that a NumPy model has the same bits;
+ *     the pick s_t is the not-yet-chosen j with the largest (score_j, -o(j)): ties go to the lower original index;
+ *     idx[t] = o(s_t) + 1, zpick[t] = z_{s_t}, rpick[t] = r_{s_t} as they stand at the pick;
+ *     then r_j += exp(a(s_t, j)) for every j.
+ *   Points of weight 0 are candidates like any other.  1 <= M <= N.  fp64 only.
+ * From the traces a caller forms the whole curve of the squared MMD (without the Gaussian constant) between p and the
+ * equal-weight density on the first m picks,
+ *   mmd2(m) = self_sum - (2/m) sum_{t<m} zpick[t] + (m + 2 sum_{t<m} rpick[t]) / m^2,
+ * and the run is ANYTIME: the first m picks and traces of a run to M are bit for bit the run to m.
+ * Two routes with the same bits (the pick is the maximum of a total order and every r_j grows in step order, so nothing
+ * depends on how the leaves are dealt to lanes, wavefronts or workgroups; no atomics):
+ *   route A, N <= KDEHIP_COMPRESS_ONE_BLOCK_MAX: ONE workgroup runs all M steps in one launch, a lane's leaves in registers;
+ *   route B, any N: one plain launch per step (M + 1 in all, enqueued back to back); KDEHIP_COMPRESS_STEPWISE in flags forces it.
+ * No grid-wide barrier, no cooperative launch, no spinning on memory.  The z pass is one launch per distinct (D, circular,
+ * route) of a call's items, route A one launch per distinct (D, circular) for the items that fit.
+ * All four entries are BLOCKING and take no stream; the caller's own work on p must be complete when the call is made.
+ * Errors, all checked before any device is touched: KDEHIP_ERR_ARG for a null p, idx or handle, M < 1 or M > N, a var or ks
+ * entry not finite or <= 0, unknown flag bits, a manifold byte above 1 or a mask bit at or above ndims, 2^31 points or more,
+ * densities of a batch on different devices; KDEHIP_ERR_UNSUPPORTED for ndims outside 1..KDEHIP_MAX_DIMS and for per-point
+ * bandwidths without var.
+ * Not here: weights other than 1/M, herding towards another target than p's own kernel mean, fp32, an enqueue-only form. */
+#define KDEHIP_COMPRESS_ONE_BLOCK_MAX 2048 /* route A: 1024 threads x 2 leaves in registers */
+#define KDEHIP_COMPRESS_STEPWISE 1         /* flags: route B whatever N */
+/* A host density, host results.  idx [M] (1-based, by ORIGINAL point); zpick, rpick [M] and self_sum [1]: each optional (NULL). */
+int kdehip_compress(const kdehip_density *p, int64_t M, const double *var /* D, or NULL */, int flags, int64_t *idx,
+                    double *zpick, double *rpick, double *self_sum, int device, const uint8_t *manifold);
+/* A resident density; var is a HOST pointer.  DEVICE results: d_idx [M]; d_points [ndims x M column-major, in pick order],
+ * d_zpick, d_rpick [M], d_self_sum [1]: each optional (NULL).  Complete on return. */
+int kdehip_compress_device(const kdehip_device_density *p, int64_t M, const double *var, int flags, int64_t *d_idx,
+                           double *d_points, double *d_zpick, double *d_rpick, double *d_self_sum, const uint8_t *manifold);
+typedef struct kdehip_compress_item {
+  const kdehip_device_density *p;
+  const double *var;                    /* HOST pointer, D entries, or NULL */
+  int64_t M;
+  int64_t *d_idx;                       /* device, [M] */
+  double *d_points, *d_zpick, *d_rpick, *d_self_sum;   /* device or NULL, as kdehip_compress_device */
+  uint32_t flags;                       /* KDEHIP_COMPRESS_STEPWISE or 0 */
+  uint32_t circular_mask;               /* bit d = dimension d circular; a bit at or above ndims is KDEHIP_ERR_ARG */
+  kdehip_device_density **out;          /* HOST pointer or NULL: also the compressed density, as kdehip_density_compress_device
+                                           builds it (d_idx may then be NULL) */
+  const double *ks;                     /* HOST pointer, D standard deviations, or NULL = p's own; read with out only */
+  const uint8_t *tree_manifold;         /* ndims bytes or NULL; read with out only */
+} kdehip_compress_item;
+/* Many densities (mixed D, N and M, Euclidean and circular, both routes) on one device in one call; every item's results are
+ * bit for bit those of kdehip_compress_device, its density that of kdehip_density_compress_device: the picks of all items come
+ * down in ONE copy.  One bad item fails the whole call and returns no handle. */
+int kdehip_compress_device_batch(int n, const kdehip_compress_item *items);
+/* The compressed density as a NEW resident handle, by the route of kdehip_density_marginal_device (5c): the picks gathered on
+ * the device in pick order, ONE copy down, the host builder with bandwidth ks (D standard deviations; NULL = p's own, which
+ * must then be one vector), weights 1/M and the operators of tree_manifold (5e, or NULL), the block back up:
+ * kde!(getPoints(p)[:, idx], ks, fill(1/M, M)).  On an error *out = NULL. */
+int kdehip_density_compress_device(kdehip_device_density **out, const kdehip_device_density *p, int64_t M, const double *var,
+                                   const double *ks, const uint8_t *manifold, const uint8_t *tree_manifold);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,13 @@ class CSinkhornItem(C.Structure):
                 ("maxiter", C.c_int32), ("circular_mask", C.c_uint32)]
 
 
+class CCompressItem(C.Structure):
+    """struct kdehip_compress_item (`var`, `ks`, `tree_manifold` and `out` are HOST pointers, the five results DEVICE addresses)"""
+    _fields_ = [("p", C.c_void_p), ("var", f64p), ("M", C.c_int64), ("d_idx", C.c_void_p), ("d_points", C.c_void_p),
+                ("d_zpick", C.c_void_p), ("d_rpick", C.c_void_p), ("d_self_sum", C.c_void_p), ("flags", C.c_uint32),
+                ("circular_mask", C.c_uint32), ("out", C.POINTER(C.c_void_p)), ("ks", f64p), ("tree_manifold", u8p)]
+
+
 class CRefitItem(C.Structure):
     """struct kdehip_refit_item (`log_evidence` and `ess` are HOST pointers)"""
     _fields_ = [("p", C.c_void_p), ("d_values", C.c_void_p), ("d_delta", C.c_void_p), ("log_evidence", f64p), ("ess", f64p),
@@ -364,6 +371,12 @@ SIGNATURES = {
     "kdehip_sinkhorn_device": (C.c_int, [C.c_void_p, C.c_void_p, f64p, f64p, f64p, C.c_int, f64p, f64p, f64p, f64p,
                                          i32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u8p]),
     "kdehip_sinkhorn_device_batch": (C.c_int, [C.c_int, C.POINTER(CSinkhornItem)]),
+    # compression by kernel herding (include/kdehip.h section 5t): blocking, no stream
+    "kdehip_compress": (C.c_int, [C.POINTER(CDensity), C.c_int64, f64p, C.c_int, i64p, f64p, f64p, f64p, C.c_int, u8p]),
+    "kdehip_compress_device": (C.c_int, [C.c_void_p, C.c_int64, f64p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, u8p]),
+    "kdehip_compress_device_batch": (C.c_int, [C.c_int, C.POINTER(CCompressItem)]),
+    "kdehip_density_compress_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, f64p, f64p, u8p, u8p]),
     "kdehip_sample_manifold": (C.c_int, [C.POINTER(CDensity), C.c_int64, C.c_uint64, C.c_int64, i64p, f64p, i64p, C.c_int,
                                          u8p]),
     "kdehip_sample_device_manifold": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,

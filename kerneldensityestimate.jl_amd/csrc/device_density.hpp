@@ -149,6 +149,11 @@ bool leaves_share_bandwidth(const kdehip_device_density *h);
 int prod_philox_device_blocking_stream(int Ndens, kdehip_device_density *const *trees, int64_t Np, int Niter, uint64_t seed,
                                        int64_t sample_offset, int addEntropy, const uint8_t *partialDimMask, int precision,
                                        double *d_points, int64_t *d_indices, void *stream, const uint8_t *manifold = nullptr);
+// (pack_device.hip) a resident density from HOST data by the host builder -- pts D x N column-major, ks D standard deviations,
+// N weights, tree_manifold or NULL --, uploaded on `stream` of `device`, which is current: the tail of the marginal, the
+// conditional and the compressed density
+int resident_from_host_points(kdehip_device_density **out, int device, int D, int64_t N, const double *pts, const double *ks,
+                              const double *weights, const uint8_t *tree_manifold, hipStream_t stream);
 // kdehip_prod_philox_batch with a manifold per item (product.hip; manifolds or any of its entries may be NULL)
 int prod_philox_batch_manifold(int nprod, const kdehip_batch_item *items, const uint8_t *const *manifolds, int precision,
                                void *stream);

@@ -566,6 +566,38 @@ extern "C" int kdehip_density_from_device_points_tree(kdehip_device_density **ou
   return KDEHIP_OK;
 }
 
+// A resident density of N points in D dimensions from HOST data, by the host builder: pts (D x N column-major), ks (D standard
+// deviations), weights (N), the operators of tree_manifold (or NULL); the twelve arrays become the handle's mirror and the
+// block goes up on `cs` (kdehip_density_from_device_points without the bandwidth search).  The device is current.
+int kdehip::resident_from_host_points(kdehip_device_density **out, int device, int D, int64_t N, const double *pts, const double *ks,
+                                      const double *weights, const uint8_t *tree_manifold, hipStream_t cs) {
+  struct Cleanup {  // (the handle, until it is the caller's)
+    kdehip_device_density *h = nullptr;
+    ~Cleanup() {
+      if (h && h->d_blob) cached_free(h->d_blob, h->blob_bytes);
+      if (h && h->mirror) cached_host_free(h->mirror, h->mirror_bytes);
+      delete h;
+    }
+  } cl;
+  kdehip_device_density *h = new (std::nothrow) kdehip_device_density();
+  if (!h) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
+  cl.h = h;
+  h->device = device; h->N = N; h->D = D; h->Lown = nlevels_for(N);
+  KDEHIP_CHECK(alloc_mirror(h, mirror_layout(h)));
+  const kdehip_device_density::Mirror &m = h->m;
+  int rc = kdehip_make_density_tree(D, N, pts, ks, D, weights, m.centers, m.ranges, m.weights, m.left, m.right, m.lowest,
+                                    m.highest, m.perm, m.means, m.bandwidth, m.bwmin, m.bwmax, tree_manifold);
+  if (rc != KDEHIP_OK) return rc;
+  for (int s = 0; s < D; ++s) h->bw[s] = ks[s];
+  h->built = true;
+  const kdehip_density host{N, D, m.means, m.bandwidth, m.weights, m.left, m.right, m.perm};
+  rc = upload_common(h, host, cs);
+  if (rc != KDEHIP_OK) return rc;
+  cl.h = nullptr;
+  *out = h;
+  return KDEHIP_OK;
+}
+
 // The density over the dimensions md of a resident p, built by the host builder from ONE copy down: the points gathered in
 // original order, ks = the bandwidth of original point 0 in those dimensions, and the weights of p -- or, with `on`, the
 // conditional weights omega of kdehip_condition_weights_device for the query on->y (then no leaf in S is KDEHIP_ERR_ARG).
@@ -578,14 +610,6 @@ static int subdensity_device(kdehip_device_density **out, const kdehip_device_de
   int rc = guard.enter(p->device);
   if (rc != KDEHIP_OK) return rc;
   hipStream_t cs = hipStreamPerThread;
-  struct Cleanup {  // (the handle, until it is the caller's)
-    kdehip_device_density *h = nullptr;
-    ~Cleanup() {
-      if (h && h->d_blob) cached_free(h->d_blob, h->blob_bytes);
-      if (h && h->mirror) cached_host_free(h->mirror, h->mirror_bytes);
-      delete h;
-    }
-  } cl;
   // [points (N nsel) | weights (N) | the bandwidth of original point 0 (D) | logz (1) | y (D - nsel)]: the last two with `on`
   const size_t o_logz = static_cast<size_t>(N) * nsel + N + D, o_y = o_logz + 1;
   const size_t bytes = sizeof(double) * (on ? o_y + (D - nsel) : o_logz);
@@ -609,23 +633,7 @@ static int subdensity_device(kdehip_device_density **out, const kdehip_device_de
     return set_error(KDEHIP_ERR_ARG, "condition: no point of the density has a positive weight at y (logz = -Inf), or y holds a NaN");
   double ks[KDEHIP_MAX_DIMS];
   for (int s = 0; s < nsel; ++s) ks[s] = std::sqrt(blk[N * nsel + N + md.d[s]]);  // getBW(p, [1])[dims]
-  kdehip_device_density *h = new (std::nothrow) kdehip_device_density();
-  if (!h) return set_error(KDEHIP_ERR_ALLOC, "out of host memory");
-  cl.h = h;
-  h->device = p->device; h->N = N; h->D = nsel; h->Lown = nlevels_for(N);
-  KDEHIP_CHECK(alloc_mirror(h, mirror_layout(h)));
-  const kdehip_device_density::Mirror &m = h->m;
-  rc = kdehip_make_density_tree(nsel, N, blk, ks, nsel, blk + N * nsel, m.centers, m.ranges, m.weights, m.left, m.right,
-                                m.lowest, m.highest, m.perm, m.means, m.bandwidth, m.bwmin, m.bwmax, tree_manifold);
-  if (rc != KDEHIP_OK) return rc;
-  for (int s = 0; s < nsel; ++s) h->bw[s] = ks[s];
-  h->built = true;
-  const kdehip_density host{N, nsel, m.means, m.bandwidth, m.weights, m.left, m.right, m.perm};
-  rc = upload_common(h, host, cs);
-  if (rc != KDEHIP_OK) return rc;
-  cl.h = nullptr;
-  *out = h;
-  return KDEHIP_OK;
+  return resident_from_host_points(out, p->device, nsel, N, blk, ks, blk + N * nsel, tree_manifold, cs);
 }
 
 // marginal(p, dims) (src/KDE01.jl:143-153) of a resident density = kde!(getPoints(p)[dims, :], getBW(p, [1])[dims],

@@ -98,6 +98,20 @@ class BallTreeDensity:
         from .transport import equalize
         return equalize(self, reg, scale, tol, maxiter, manifold, return_info, device)
 
+    # compression by kernel herding (include/kdehip.h section 5t): see compress.py
+    def compress(self, M=None, mmd_tol=None, bw=None, ks=None, manifold=None, return_info=False, tree_manifold=None,
+                 stepwise=False, device=0):
+        """M of this density's own points, picked by kernel herding under the Gaussian kernel of standard deviation `bw`
+        (None: sqrt(2) times the bandwidth), with weights 1 / M and bandwidth `ks` (None: unchanged).  `mmd_tol`: the run
+        goes to M (default N) and the result is the shortest prefix whose MMD is at most mmd_tol."""
+        from .compress import _compress
+        return _compress(self, M, mmd_tol, bw, ks, manifold, return_info, tree_manifold, stepwise, device)
+
+    def herding_order(self, M, bw=None, manifold=None, stepwise=False, device=0):
+        """(idx, info): the first M herding picks (1-based, by original point) and their traces; nothing is built"""
+        from .compress import _herding_order
+        return _herding_order(self, M, bw, manifold, stepwise, device)
+
 
 def _prepare(points, ks, weights):
     pts = np.asarray(points, dtype=np.float64)

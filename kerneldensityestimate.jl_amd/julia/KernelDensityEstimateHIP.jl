@@ -1129,6 +1129,65 @@ function hip_transport_map(p::BallTreeDensity, q::BallTreeDensity; reg::Float64=
 end
 
 """
+    hip_herding_order(p, M; bw=nothing, manifold=nothing, stepwise=false, device=0)
+
+The first `M` kernel-herding picks of `p` (`kdehip_compress`, include/kdehip.h section 5t) under the Gaussian kernel of
+standard deviation `bw` (one entry per dimension; `nothing`: `sqrt(2)` times the bandwidth of `p`).  Returns a named tuple:
+`idx` (1-based, by original point, in pick order), `zpick`, `rpick`, `self_sum` and `mmd2`, the squared MMD (not
+normalised) between `p` and the equal-weight density on the first `1 .. M` picks.  The first `m` picks of a run to `M` are
+the run to `m`.  The library's own: not installed by `enable!()`.
+"""
+function hip_herding_order(p::BallTreeDensity, M::Int; bw::Union{Nothing,AbstractVector{Float64}}=nothing, manifold=nothing,
+                           stepwise::Bool=false, device::Int=0)
+  D = Ndim(p)
+  1 <= M <= p.bt.num_points || error("M must lie in 1..Npts(p)")
+  bw === nothing || length(bw) == D || error("bw needs one entry per dimension")
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  var = bw === nothing ? zeros(0) : Vector{Float64}(bw) .* Vector{Float64}(bw)
+  idx, zpick, rpick, self = zeros(Int64, M), zeros(M), zeros(M), zeros(1)
+  cp = Ref(CDensity(p))
+  GC.@preserve p var man begin
+    check(ccall((:kdehip_compress, libkdehip), Cint,
+                (Ref{CDensity}, Int64, Ptr{Float64}, Cint, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{UInt8}),
+                cp, M, bw === nothing ? Ptr{Float64}(C_NULL) : pointer(var), stepwise ? 1 : 0, idx, zpick, rpick, self, device, man))
+  end
+  m = collect(1.0:M)
+  mmd2 = self[1] .- (2.0 ./ m) .* cumsum(zpick) .+ (m .+ 2.0 .* cumsum(rpick)) ./ (m .* m)
+  return (idx=idx, zpick=zpick, rpick=rpick, self_sum=self[1], mmd2=mmd2)
+end
+
+"""
+    hip_compress(p, M; bw=nothing, ks=nothing, manifold=nothing, device=0)
+
+`p` cut to `M` of its own points by kernel herding: `kde!(getPoints(p)[:, idx], ks, fill(1/M, M))` with `idx` the picks of
+`hip_herding_order` and `ks` the bandwidth of the result (`nothing`: unchanged).
+"""
+function hip_compress(p::BallTreeDensity, M::Int; bw::Union{Nothing,AbstractVector{Float64}}=nothing,
+                      ks::Union{Nothing,AbstractVector{Float64}}=nothing, manifold=nothing, device::Int=0)
+  order = hip_herding_order(p, M; bw=bw, manifold=manifold, device=device)
+  sd = ks === nothing ? sqrt.(leaf_variances(p)) : Vector{Float64}(ks)
+  return kde!(getPoints(p)[:, order.idx], sd, fill(1.0 / M, M))
+end
+
+"`compress` of a resident density as a new handle (`kdehip_density_compress_device`): the picks never leave the device but for the builder's one copy."
+function hip_compress(d::DeviceDensity, M::Int; bw::Union{Nothing,AbstractVector{Float64}}=nothing,
+                      ks::Union{Nothing,AbstractVector{Float64}}=nothing, manifold=nothing, tree_manifold=nothing)
+  D = d.ndim
+  man = manifold === nothing ? zeros(UInt8, D) : manifold_bytes(manifold, D)
+  tman = tree_manifold === nothing ? zeros(UInt8, D) : manifold_bytes(tree_manifold, D)
+  var = bw === nothing ? zeros(0) : Vector{Float64}(bw) .* Vector{Float64}(bw)
+  sd = ks === nothing ? zeros(0) : Vector{Float64}(ks)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve var sd man tman begin
+    check(ccall((:kdehip_density_compress_device, libkdehip), Cint,
+                (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{UInt8}),
+                h, d.handle, M, bw === nothing ? Ptr{Float64}(C_NULL) : pointer(var),
+                ks === nothing ? Ptr{Float64}(C_NULL) : pointer(sd), man, tman))
+  end
+  return DeviceDensity(h[])
+end
+
+"""
     hip_box_mass(bd, lo, hi; dims=nothing, manifold=nothing, device=0)
 
 The probability that `x[dims]` lies in the box `[lo[:, q], hi[:, q]]` under `bd`, one value per column

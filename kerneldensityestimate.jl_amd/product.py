@@ -543,6 +543,25 @@ class DeviceDensity:
         from .transport import sinkhorn_batch
         return sinkhorn_batch(pairs, reg, scale, tol, maxiter, manifold, vectors)
 
+    # compression by kernel herding (include/kdehip.h section 5t): see compress.py
+    def compress(self, M=None, mmd_tol=None, bw=None, ks=None, manifold=None, return_info=False, tree_manifold=None,
+                 stepwise=False) -> "DeviceDensity":
+        """M of this density's own points, picked by kernel herding, as a new resident density with weights 1 / M and
+        bandwidth `ks` (None: unchanged); the points come to the host through the builder's one copy alone"""
+        from .compress import _compress
+        return _compress(self, M, mmd_tol, bw, ks, manifold, return_info, tree_manifold, stepwise)
+
+    def herding_order(self, M, bw=None, manifold=None, stepwise=False):
+        """(idx, info): the first M herding picks (1-based, by original point) and their traces; nothing is built"""
+        from .compress import _herding_order
+        return _herding_order(self, M, bw, manifold, stepwise)
+
+    @staticmethod
+    def compress_batch(densities, M, bw=None, ks=None, manifold=None, return_info=False, tree_manifold=None, stepwise=False):
+        """many densities in one call (kdehip_compress_device_batch): a list of new handles; see `compress._compress_batch`"""
+        from .compress import _compress_batch
+        return _compress_batch(densities, M, bw, ks, manifold, return_info, tree_manifold, stepwise)
+
     def marginal(self, dims, *, manifold=None, tree_manifold=None) -> "DeviceDensity":
         """`marginal(p, dims)` (reference src/KDE01.jl:143-153), dims 0-based, built on this density's device
         (kdehip_density_marginal_device): the same arrays as the host `marginal` of the same density.  `tree_manifold` (one
