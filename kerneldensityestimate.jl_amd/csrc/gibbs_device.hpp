@@ -1014,6 +1014,7 @@ struct LaunchView<true> {
     plan.tab_rows_total = h.tab_rows_total;
     plan.M = h.M; plan.L = h.L; plan.D = h.D; plan.Lt = h.Lt;
     plan.screened = 0;
+    plan.resident = 0;  // (batched launches run the one build that knows every staging mode)
     plan.circ_bits = fl.circ_bits;  // (read by the generic and circular modes of gibbs_product_kernel only)
     a.Np = be.Np; a.Niter = fl.Niter; a.addEntropy = fl.addEntropy; a.use_tables = fl.use_tables;
     a.variant = a_.variant;

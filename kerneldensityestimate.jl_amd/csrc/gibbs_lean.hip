@@ -56,6 +56,15 @@ __device__ __forceinline__ int scalar_copy(int x) {
   return y;
 }
 
+// The same for a pointer (two registers of their own): the first 32 bytes of PlanDev arrive as one 8-dword scalar load.
+template <typename P>
+__device__ __forceinline__ P *scalar_copy(P *p) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = static_cast<uint32_t>(scalar_copy(static_cast<int>(v)));
+  const uint32_t hi = static_cast<uint32_t>(scalar_copy(static_cast<int>(v >> 32)));
+  return reinterpret_cast<P *>((static_cast<uint64_t>(hi) << 32) | lo);
+}
+
 // One density's tile on the current level: what the steps of a level need, as independent scalars.
 template <int D>
 struct LeanTile {
@@ -94,8 +103,26 @@ template <typename P, typename T, bool OK> constexpr bool kCanPreloadImpl = OK &
 // SCHUNK: the build that also knows CHUNKED screen tiles (kStageScreenChunked).  A build of its own, launched only for plans
 // that have such a level: with that code in every build, config 3 -- which never runs it -- was 3.3 % slower (32 more
 // vector registers, 200 more scalar spills; profiles/r05_experiments.md section 10).
-template <typename T, int D, int M, int WAVES, bool BATCH = false, bool SCHUNK = false>
+//
+// STAGED: the build that knows the levels whose tiles come through the pool a tile or a chunk at a time, or are read from
+// global memory (kStageStream, kStageChunked, kStageGlobal, kStageScreenStream).  Without it every level is taken as resident
+// (tabulated or not) or screened from resident screen tiles -- what PlanDev::resident promises the launcher.  The branches a
+// plan never runs shape the register allocation of the ones it does: with them config 3's kernel had 207 vector registers
+// and 384 scalar spills whose reloads stood at the head of every step; without them 194 and 141 (profiles/scalar_spills.md).
+// The kernel's name for the precision alone (gibbs_lean_kernel<double, ...>) is the build for plans that are resident
+// throughout wherever the builds come as a pair (kLeanHasTwin); its staged twin is instantiated for Staged<double>.
+template <typename T> struct Staged {};
+template <typename TT> struct LeanPrec { using type = TT; static constexpr bool kStaged = false; };
+template <typename T> struct LeanPrec<Staged<T>> { using type = T; static constexpr bool kStaged = true; };
+// (fp32, the 4-chain workgroups of small runs, batched launches and the chunked-screen build stay one build, the staged one:
+// each twin is another kernel per density count and width to compile.)
+template <typename T, int WAVES, bool BATCH, bool SCHUNK>
+constexpr bool kLeanHasTwin = sizeof(T) == 8 && WAVES >= 8 && !BATCH && !SCHUNK;
+
+template <typename TT, int D, int M, int WAVES, bool BATCH = false, bool SCHUNK = false>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, RunArgs a_) {
+  using T = typename LeanPrec<TT>::type;
+  constexpr bool STAGED = LeanPrec<TT>::kStaged || !kLeanHasTwin<T, WAVES, BATCH, SCHUNK>;
   const LaunchView<BATCH> view(plan_, a_);
   const PlanDev &plan = view.plan;
   const auto &a = view.a;
@@ -111,6 +138,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   // fp32 screening of the deep levels (screen_device.hpp): the fp64 instantiations of plain launches
   constexpr bool kScreen = sizeof(T) == 8 && !BATCH;
   constexpr bool kPreloadBuild = kKeptRows && kPrefetchRows;
+  constexpr bool kResidentOnly = !STAGED;
+  static_assert(STAGED || !SCHUNK, "chunked screen tiles are staged tiles");
   // LDS: [exp table 2 KiB][normals: 1 KiB per chain][uniforms: WAVES x 1 KiB][tile pool]
   constexpr int kNormOff = 2048;
   constexpr int kUnifOff = kNormOff + WAVES * kLeanMaxNormals * 8;
@@ -144,12 +173,32 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   const bool live = s < a.Np;  // surplus wavefronts of the last workgroup replay the last chain and store nothing
   if (!live) s = a.Np - 1;
   const uint64_t gs = static_cast<uint64_t>(a.sample_offset + s);
-  const void *fb = live ? static_cast<const void *>(plan.levels) : nullptr;  // who counts uniform fallbacks
+  // (the plan's pointers detached from the 8-dword load of PlanDev's head: where one of them is reloaded from a spill lane,
+  // it comes alone and not with the other three -- scalar_copy)
+  const T *__restrict__ data = scalar_copy(static_cast<const T *>(plan.data));
+  const LevelDesc *const plan_levels = scalar_copy(plan.levels);
+  const int32_t *const plan_perm = scalar_copy(plan.perm);
+  const void *fb = live ? static_cast<const void *>(plan_levels) : nullptr;  // who counts uniform fallbacks
 
+  // What the kernel needs only before the level loop, in a refill of the uniforms or after the loop -- the caller's streams and
+  // their lengths, the Philox key, the label trace, the output arrays, the peers -- is read from the kernel-argument segment
+  // WHERE IT IS USED, through a pointer the compiler cannot look through: loaded in the prologue, as kernel arguments are,
+  // these values (and the Philox key schedule formed from the seed) were live across the whole level loop, i.e. spilled, and
+  // reloaded at every use.  A batched workgroup has them in its BatchArgs (registers) as before.
+  auto cold = [&]() -> decltype(auto) {
+    if constexpr (BATCH) {
+      return (view.a);
+    } else {
+      constexpr size_t kOff = (sizeof(PlanDev) + alignof(RunArgs) - 1) / alignof(RunArgs) * alignof(RunArgs);  // (RunArgs follows PlanDev)
+      auto p = (const __attribute__((address_space(4))) RunArgs *)((const __attribute__((address_space(4))) char *)
+                                                                        __builtin_amdgcn_kernarg_segment_ptr() + kOff);
+      asm volatile("" : "+s"(p));
+      return (*p);
+    }
+  };
   const int L = plan.L;
-  const T *__restrict__ data = static_cast<const T *>(plan.data);
-  const LevelTable levels{(const __attribute__((address_space(4))) kdehip_v16i *)(plan.levels)};
-  const StepTable steps{(const __attribute__((address_space(4))) kdehip_v8i *)(plan.levels + 2 * plan.M * (plan.L + 1))};
+  const LevelTable levels{(const __attribute__((address_space(4))) kdehip_v16i *)(plan_levels)};
+  const StepTable steps{(const __attribute__((address_space(4))) kdehip_v8i *)(plan_levels + 2 * plan.M * (plan.L + 1))};
   unsigned char *pool = smem + kPoolOff;
   const int dl = lane < D ? lane : D - 1;  // this lane's dimension in the "lanes = dimensions" phases
   const int vlev = a.variant % 1000;
@@ -167,7 +216,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       if (2 * b + 1 < R) sNorm[2 * b + 1] = n1;
     }
   } else {
-    for (int r = lane; r < R; r += 64) sNorm[r] = a.randN[s * a.R + r];
+    for (int r = lane; r < R; r += 64) { const auto &ca = cold(); sNorm[r] = ca.randN[s * ca.R + r]; }
   }
   __syncthreads();  // (exp table; the strip is only read by its own chain's wavefronts)
 
@@ -240,13 +289,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       ubatch = b;
       double u_even, u_odd;
       if (a.rng_philox) {
-        const Philox4 r = philox_block(a.seed, gs, b * 64u + static_cast<uint32_t>(lane), 0u);
+        const Philox4 r = philox_block(cold().seed, gs, b * 64u + static_cast<uint32_t>(lane), 0u);
         u_even = bits_to_unit(r.v[0], r.v[1]);
         u_odd = bits_to_unit(r.v[2], r.v[3]);
       } else {  // element i of the sample's slice feeds call i+1
-        const int64_t i0 = s * a.K + static_cast<int64_t>(b) * 128 + 2 * lane - 1;
-        u_even = (i0 >= 0 && i0 < a.nU) ? a.randU[i0] : 0.5;
-        u_odd = (i0 + 1 < a.nU) ? a.randU[i0 + 1] : 0.5;
+        const auto &ca = cold();
+        const int64_t i0 = s * ca.K + static_cast<int64_t>(b) * 128 + 2 * lane - 1;
+        u_even = (i0 >= 0 && i0 < ca.nU) ? ca.randU[i0] : 0.5;
+        u_odd = (i0 + 1 < ca.nU) ? ca.randU[i0 + 1] : 0.5;
       }
       wave_sync();
       sUnif[2 * lane] = u_even;
@@ -265,7 +315,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   });
 
   const TabTable tabs{(const __attribute__((address_space(4))) kdehip_v8i *)(plan.tabdesc)};
-  const T *tables = static_cast<const T *>(plan.tables);
+  const T *tables = scalar_copy(static_cast<const T *>(plan.tables));
   const int Lt = (vlev == 1 || vlev == 4 || !a.use_tables) ? 0 : plan.Lt;
 
   // the draw on a tile readable through one pointer
@@ -629,7 +679,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
     const int np = (npairs - p0 < cp) ? (npairs - p0) : cp;
     const int head = p0 == 0 ? kScreenHeaderFloats : 0;
     const int bytes = ((head + np * RS) * 4 + 1023) & ~1023;
-    const unsigned char *src = reinterpret_cast<const unsigned char *>(reinterpret_cast<const float *>(plan.data) + sc.hdr_off +
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(reinterpret_cast<const float *>(data) + sc.hdr_off +
                                                                        (p0 == 0 ? 0 : kScreenHeaderFloats + p0 * RS));
     if (wave < kCopyWaves) stage_tile<kCopyWaves>(src, pool + half * (kLdsPoolBytes / 2), bytes, wave, lane);
   };
@@ -654,7 +704,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       const LdsPtr<double> h64 = (LdsPtr<double>)(pool + (gchunk & 1) * (kLdsPoolBytes / 2));
       const double mu0 = h64[dl], cmin = h64[8 + dl];
       const float mmax = h32[32 + dl], valid = h32[40];
-      const float *grows = reinterpret_cast<const float *>(plan.data) + sc.hdr_off + kScreenHeaderFloats;
+      const float *grows = reinterpret_cast<const float *>(data) + sc.hdr_off + kScreenHeaderFloats;
       const int pos = __builtin_amdgcn_readfirstlane(screen_eval(ds, mu0, cmin, mmax, valid, mean, cov, [&](const auto &ev, bool ok) {
         using Ev = std::decay_t<decltype(ev)>;
         ScreenSums q;
@@ -712,7 +762,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       t.load(tile_raw(j));
       return t;
     };
-    const int mode = vlev == 1 ? int(kStageGlobal) : level_mode;
+    const int mode = kResidentOnly ? int(kStageResident) : vlev == 1 ? int(kStageGlobal) : level_mode;
     const bool tabulated = (l <= Lt);
     const int npass = tabulated ? 1 : a.Niter + 1;  // tabulated levels: only the sampleIndices! pass runs here
 
@@ -721,7 +771,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       if (a.use_screen && vlev != 1) {
         const int smode = scalar_copy(levels[M * (L + 1) + l].stage_mode);
         screened = smode == kStageScreen;
-        screen_streamed = smode == kStageScreenStream;
+        screen_streamed = !kResidentOnly && smode == kStageScreenStream;
         if constexpr (SCHUNK) screen_chunked = smode == kStageScreenChunked;
       }
     }
@@ -738,7 +788,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       staging_barrier();
       static_for<M>([&](auto jc) {
         const LevelDesc sc = screen(decltype(jc)::value);
-        stage_tile<WAVES>(reinterpret_cast<const unsigned char *>(reinterpret_cast<const float *>(plan.data) + sc.hdr_off),
+        stage_tile<WAVES>(reinterpret_cast<const unsigned char *>(reinterpret_cast<const float *>(data) + sc.hdr_off),
                           pool + sc.lds_off, sc.stage_bytes, wave, lane);
       });
       staging_barrier();
@@ -755,7 +805,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
       auto stage_screen = [&](const LevelDesc &sc, int half, auto wc) {
         constexpr int W = decltype(wc)::value;
         if (wave < W)
-          stage_tile<W>(reinterpret_cast<const unsigned char *>(reinterpret_cast<const float *>(plan.data) + sc.hdr_off),
+          stage_tile<W>(reinterpret_cast<const unsigned char *>(reinterpret_cast<const float *>(data) + sc.hdr_off),
                         pool + half * (kLdsPoolBytes / 2), sc.stage_bytes, wave, lane);
       };
       // (A barrier split into "arrive" and "wait" -- an LDS counter; a wavefront that must repeat its step arrives at the next
@@ -955,18 +1005,19 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
         adopt(jc, dk, (LdsPtr<T>)(pool + dk.lds_off), pk);
       });
     }
-    if (a.labels && live && lane == 0) {
+    if (int32_t *const labels = cold().labels; labels && live && lane == 0) {
       static_for<M>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        a.labels[(s * M + j) * L + (l - 1)] = plan.perm[levels[j * (L + 1) + l].perm_off + psel[j]];
+        labels[(s * M + j) * L + (l - 1)] = plan_perm[levels[j * (L + 1) + l].perm_off + psel[j]];
       });
     }
     if (l == L && live && lane == 0) {  // final labels (:612-616)
+      const auto &ca = cold();
       static_for<M>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        const int64_t label = static_cast<int64_t>(plan.perm[levels[j * (L + 1) + l].perm_off + psel[j]]) + 1;
-        a.indices[s * M + j] = label;
-        for (int k = 0; k < a.npeers; ++k) a.peer_indices[k][s * M + j] = label;  // (multi-GPU: the all-gather)
+        const int64_t label = static_cast<int64_t>(plan_perm[levels[j * (L + 1) + l].perm_off + psel[j]]) + 1;
+        ca.indices[s * M + j] = label;
+        for (int k = 0; k < ca.npeers; ++k) ca.peer_indices[k][s * M + j] = label;  // (multi-GPU: the all-gather)
       });
     }
   }
@@ -977,7 +1028,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
 #endif
   if constexpr (kScreen) {  // diagnostic counters in front of the level table: [-3] screened steps, [-2] repeated in fp64
     if (live && lane == 0 && n_screened != 0u) {
-      unsigned long long *cnt = reinterpret_cast<unsigned long long *>(const_cast<LevelDesc *>(plan.levels));
+      unsigned long long *cnt = reinterpret_cast<unsigned long long *>(const_cast<LevelDesc *>(plan_levels));
       atomicAdd(cnt - 3, static_cast<unsigned long long>(n_screened));
       if (n_repeated != 0u) atomicAdd(cnt - 2, static_cast<unsigned long long>(n_repeated));
     }
@@ -985,11 +1036,12 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_lean_kernel(PlanDev plan_, R
   {  // final point (:625)
     T mean, cov;
     product(IC<-1>{}, mean, cov);
+    const auto &ca = cold();
     T xf = mean;
-    if (a.addEntropy) xf = mean + Num<T>::sqrt(cov) * static_cast<T>(sNorm[L * D + dl]);
+    if (ca.addEntropy) xf = mean + Num<T>::sqrt(cov) * static_cast<T>(sNorm[L * D + dl]);
     if (live && lane < D) {
-      a.points[s * D + lane] = static_cast<double>(xf);
-      for (int k = 0; k < a.npeers; ++k) a.peer_points[k][s * D + lane] = static_cast<double>(xf);
+      ca.points[s * D + lane] = static_cast<double>(xf);
+      for (int k = 0; k < ca.npeers; ++k) ca.peer_points[k][s * D + lane] = static_cast<double>(xf);
     }
   }
 }
@@ -1008,9 +1060,19 @@ static void launch_lean_waves(const PlanDev &plan, const RunArgs &args, hipStrea
       return;
     }
   }
-  if constexpr (!(sizeof(T) == 8 && WAVES >= 8 && M == 8))
+  if constexpr (!(sizeof(T) == 8 && WAVES >= 8 && M == 8)) {
+    if constexpr (kLeanHasTwin<T, WAVES, false, false>) {
+      // (PlanDev::resident == 2: resident only while the screen tiles are in use; variant 1 reads every tile from global memory)
+      const bool resident = plan.resident == 1 || (plan.resident == 2 && args.use_screen);
+      if (!resident || args.variant % 1000 == 1) {
+        hipLaunchKernelGGL((gibbs_lean_kernel<Staged<T>, D, M, WAVES>), dim3(static_cast<unsigned>(blocks)), dim3(WAVES * 64), 0,
+                           stream, plan, args);
+        return;
+      }
+    }
     hipLaunchKernelGGL((gibbs_lean_kernel<T, D, M, WAVES>), dim3(static_cast<unsigned>(blocks)), dim3(WAVES * 64), 0,
                        stream, plan, args);
+  }
 }
 
 // wavefronts (= chains) per workgroup of this run

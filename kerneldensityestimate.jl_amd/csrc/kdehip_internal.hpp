@@ -184,7 +184,12 @@ struct PlanDev {
   // the reference's hook points (src/MSGibbs01.jl:290, 183-184 / 210-213, 456) by the general sampler's generic and
   // circular fast modes (kModeGeneric, kModeFastCirc)
   uint32_t circ_bits;
-  int32_t reserved_[2];
+  // What the plan's levels 1..L ask of the sampler's staging: 1: the fp64 tiles of every level sit in the LDS pool together
+  // (kStageResident); 2: ... or the level is screened from resident screen tiles (kStageScreen), so the same holds while the
+  // screen is in use; 0: some level is streamed, chunked or read from global memory.  Non-zero selects the build of the
+  // register-resident sampler without those branches (gibbs_lean.hip, STAGED).
+  int32_t resident;
+  int32_t reserved_;
 };
 
 constexpr int kMaxPeers = 7;  // other GPUs of one node

@@ -330,6 +330,14 @@ void bind_plan(kdehip_product *p, size_t off_lev, size_t off_count, size_t off_t
   if (p->dev.screened)
     for (const LevelDesc &sc : p->host.screens)
       if (sc.stage_mode == kStageScreenChunked) p->dev.screened = 2;  // (selects the sampler build that knows chunked screens)
+  // (selects the sampler build without the streamed, chunked and global-memory branches: PlanDev::resident)
+  int resident = 1;
+  for (size_t i = 0; i < p->host.levels.size(); ++i) {
+    if (i % static_cast<size_t>(p->host.L + 1) == 0 || p->host.levels[i].stage_mode == kStageResident) continue;  // (level 0: the root)
+    const bool screen_resident = p->dev.screened && p->host.screens[i].stage_mode == kStageScreen;
+    resident = (resident && screen_resident) ? 2 : 0;
+  }
+  p->dev.resident = p->mode == kModeFast ? resident : 0;
 }
 
 // A plan on `device` from an image: one device allocation, one DMA transfer (hipMalloc / hipFree cost tens of
